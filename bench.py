@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- V-cycles/s of the MI355X multigrid V-cycle on the reference's own problem.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one V(nu,nu) cycle of the 3D Poisson problem test_mg_3d.c sets up (unit cube, RHS 0,
 Dirichlet u = x^2-2y^2+z^2 on the six faces, zero initial guess), device resident, through the C ABI
@@ -12,6 +12,8 @@ BASELINE.json configs[2].  Prints ONE JSON line (contract in the task statement)
                  8 TB/s HBM3E; the same for every finest-level launch; SURVEY 8(d)'s credit reported separately
   cpu_baseline : the reference CPU path (oracle/_ref, kind "reference") or our CPU restatement
                  (oracle/, kind "port") timed on this box's host cores on a bounded sample
+--dump-outputs DIR: after the timed steps, what the timed call handed its caller is written to DIR (dump_outputs()),
+so that two builds can be compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -24,6 +26,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured copy)
+DUMP_POINTS = 1 << 22  # a larger field is dumped as a sample of this many points: 32 MB in fp64, inside the dump's 64 MB
+
+
+def dump_outputs(d, norms, u):
+    """--dump-outputs: the residual norm of every timed cycle (norms.npy, fp64) and the finest level's u after the last
+    one (u.npy, the solver's precision).  A field of more than DUMP_POINTS points is replaced by its values at a fixed,
+    seeded set of flat indices (ascending; the same in every run of the same size), so two builds compare value for value."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if u.size > DUMP_POINTS:
+        u = u[np.unique(np.random.default_rng(0).integers(0, u.size, DUMP_POINTS))]
+    np.save(os.path.join(d, "norms.npy"), np.asarray(norms, dtype=np.float64))
+    np.save(os.path.join(d, "u.npy"), u)
 
 
 def algorithmic_bytes_per_cycle(c, L, nu, w=8):
@@ -233,6 +248,9 @@ def f32_line(args):
     norms = s.vcycles(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        from multigrid_parallel_amd.binding import MG3D_U
+        dump_outputs(args.dump_outputs, norms, s.download(MG3D_U, L - 1))
     # per-launch roofline of the finest level (single domain): the same cycles once more with the kernel timers on (event
     # pairs on the library's stream; kept out of `value`'s timed region: a marker packet is ~5 us of idle queue)
     launches_tab = []
@@ -331,7 +349,11 @@ def main():
     ap.add_argument("--f32", action="store_true",
                     help="BASELINE configs[4] on one GPU instead of the headline: fp32, damped Jacobi, F-cycle start "
                          "(parity unpinned); default size 9 8 2 = 1025^3")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/norms.npy and DIR/u.npy (one rank only)")
     args = ap.parse_args()
+    if args.dump_outputs and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        ap.error("--dump-outputs: one GPU only (a rank holds only its own slab of u)")
     if args.cpu_child:
         return cpu_child(args)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -390,6 +412,8 @@ def main():
         elapsed = time.perf_counter() - t0
         phase_ms = dict(solver.timing(), rank=rank)
         solver.timing_enable(False)
+        if args.dump_outputs:  # (one rank: it owns every plane)
+            dump_outputs(args.dump_outputs, norms, solver.download(MG3D_U, L - 1))
         per_rank = [phase_ms]
         if dist.is_initialized():
             per_rank = [None] * world
@@ -497,6 +521,8 @@ def main():
     barrier(solver)
     elapsed = time.perf_counter() - t0
     solver.timing_enable(0)
+    if args.dump_outputs:  # before the other schedules below run more cycles on the same solver
+        dump_outputs(args.dump_outputs, norms, solver.download(MG3D_U, L - 1))
 
     tm = solver.timing()
     kt = solver.kernel_times()

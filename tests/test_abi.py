@@ -187,6 +187,29 @@ def test_bench_self_launch_explains_missing_gpus():
     assert r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_budget(tmp_path):
+    """bench.py --dump-outputs: the norms in fp64 and u in the solver's precision; a u too large to dump whole is the same
+    seeded sample in every run, and the dump stays within 64 MB.  More than one rank is refused before anything runs."""
+    import subprocess
+    import sys
+    import bench
+    big = np.arange(3 * bench.DUMP_POINTS, dtype=np.float32)  # value = flat index
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), [3.0, 2.0], big)
+    a, b = (np.load(tmp_path / run / "u.npy") for run in "ab")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert 0.8 * bench.DUMP_POINTS < a.size <= bench.DUMP_POINTS and np.all(np.diff(a) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    norms = np.load(tmp_path / "a" / "norms.npy")
+    assert norms.dtype == np.float64 and list(norms) == [3.0, 2.0]
+    small = np.linspace(0.0, 1.0, 33 ** 3)
+    bench.dump_outputs(str(tmp_path / "c"), [1.0], small)
+    assert np.array_equal(np.load(tmp_path / "c" / "u.npy"), small)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "one GPU only" in r.stderr and not (tmp_path / "d").exists()
+
+
 def test_option_keys_match_the_documented_tables():
     """mg3d_option_name enumerates the launch / schedule options (no GPU needed); the table in include/mg3d.h and the one in
     INTEGRATION.md name exactly these keys, and no product source reads the environment outside context creation."""
