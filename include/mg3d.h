@@ -71,6 +71,19 @@ int mg3d_ctx_set_keep_residual(mg3d_ctx *ctx, int keep);
 int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse);
 int mg3d_ctx_set_lu(mg3d_ctx *ctx, const double *LU);
 
+/* Screened operator.  Every operator of the context -- smoother, residual, the coarsest matrix -- becomes the one of
+ *     Delta_h u - sigma u = d        (sigma >= 0; the residual stays d - (Delta_h u - sigma u), mg_3d.h:819-821)
+ * per level of spacing h:  smoother  v = (1/dg) * (sum of the six neighbours - h^2 d),  dg = 6 + sigma*h^2;
+ * residual  d - (sum - dg*v)/h^2;  coarse matrix diagonal -dg/h^2 (mg3d_coarse_matrix_shift).  The default sigma = 0 is
+ * the reference's operator, bit for bit.  Implicit diffusion (backward Euler, u1 - dt*Delta u1 = u0): sigma = 1/dt with
+ * the right-hand side d = -u0/dt.  A negative, NaN or infinite sigma is MG3D_ERR_ARG and changes nothing.  Otherwise a
+ * cycle that has run ahead is finished first; a new sigma rebuilds a factor of mg3d_ctx_build_coarse (same h_coarse) and
+ * drops one installed by mg3d_ctx_set_lu or mg3d_es_setup (the next cycle returns MG3D_ERR_STATE until a factor is set
+ * again); a call that leaves sigma as it is changes nothing.  mg3d_es_* refuse a context with sigma != 0 (MG3D_ERR_STATE);
+ * the mg3d_host_* forms and include/mg_3d.h always use sigma = 0, as the reference does. */
+int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma);
+int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma);
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -226,6 +239,9 @@ int mg3d_dist_carried_cycles(const mg3d_dist *d); /* cycles since creation that 
 int mg3d_dist_legs_cycles(const mg3d_dist *d);    /* cycles since creation whose up-leg on the finest level ran as ONE launch (options legs, legs_min;
                                                    * plan policy bits 4 / 8 of mg3d_dist_plan): their norm is completed by the next cycle's down-leg */
 int mg3d_dist_build_coarse(mg3d_dist *d, double h_coarse);
+/* as mg3d_ctx_set_shift, for every local rank's levels and the replicated coarse levels.  Every rank of a multi-rank job
+ * must pass the same sigma (not checked). */
+int mg3d_dist_set_shift(mg3d_dist *d, double sigma);
 int mg3d_dist_set_keep_residual(mg3d_dist *d, int keep); /* as mg3d_ctx_set_keep_residual */
 int mg3d_dist_set_option(mg3d_dist *d, const char *key, int value); /* as mg3d_ctx_set_option, for every local rank */
 int mg3d_dist_upload(mg3d_dist *d, int field, int level, const double *host_full);
@@ -303,6 +319,7 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  * mg3d_bc_func            : BCFunc (mg_3d.h:89-90)
  * mg3d_fill_boundary_host : setupBoundaryConditions (mg_3d.h:1147-1239)
  * mg3d_coarse_matrix      : constructCoarseMatrixA (mg_3d.h:147-273), A zeroed by caller
+ * mg3d_coarse_matrix_shift: the same for the screened operator (diagonal -(6 + sigma*h^2)/h^2; sigma = 0: the same bytes)
  * mg3d_lu_factor          : convertToLU_InPlace (gauss_elim.h:9-29)
  * mg3d_lu_solve_host      : NOT provided -- the solve runs on the device only
  * mg3d_l2norm_host        : GetL2NormOfVector (mg_3d.h:783-792)
@@ -311,6 +328,7 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
 double mg3d_bc_func(double x, double y, double z);
 void mg3d_fill_boundary_host(double *v, int N, double h);
 void mg3d_coarse_matrix(double *A, int N, double h);
+void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma);
 void mg3d_lu_factor(double *a, int n);
 double mg3d_l2norm_host(const double *d, long n);
 void mg3d_smooth_edges_host(double *u, int N);

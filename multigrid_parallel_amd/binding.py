@@ -42,6 +42,8 @@ SIGNATURES = {
     "mg3d_ctx_set_keep_residual": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_ctx_build_coarse": (C.c_int, [C.c_void_p, C.c_double]),
     "mg3d_ctx_set_lu": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_ctx_set_shift": (C.c_int, [C.c_void_p, C.c_double]),
+    "mg3d_ctx_get_shift": (C.c_int, [C.c_void_p, dp]),
     "mg3d_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -84,6 +86,7 @@ SIGNATURES = {
     "mg3d32_kernel_name": (C.c_char_p, [C.c_int]),
     "mg3d32_kernel_time_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), dp]),
     "mg3d_dist_build_coarse": (C.c_int, [C.c_void_p, C.c_double]),
+    "mg3d_dist_set_shift": (C.c_int, [C.c_void_p, C.c_double]),
     "mg3d_dist_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_dist_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_dist_vcycles": (C.c_int, [C.c_void_p, C.c_int, dp]),
@@ -107,6 +110,7 @@ SIGNATURES = {
     "mg3d_bc_func": (C.c_double, [C.c_double, C.c_double, C.c_double]),
     "mg3d_fill_boundary_host": (None, [dp, C.c_int, C.c_double]),
     "mg3d_coarse_matrix": (None, [dp, C.c_int, C.c_double]),
+    "mg3d_coarse_matrix_shift": (None, [dp, C.c_int, C.c_double, C.c_double]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
     "mg3d_smooth_edges_host": (None, [dp, C.c_int]),
@@ -270,6 +274,16 @@ class Solver:
 
     def set_lu(self, LU):
         check(self.L.mg3d_ctx_set_lu(self._h, P(LU)))
+
+    def set_shift(self, sigma):
+        """mg3d_ctx_set_shift: solve the screened equation  Laplacian(u) - sigma*u = d  (sigma >= 0; 0 is Poisson).
+        Rebuilds a coarse factor of get_details(); drops one given to set_lu."""
+        check(self.L.mg3d_ctx_set_shift(self._h, float(sigma)))
+
+    def get_shift(self):
+        sigma = C.c_double(0.)
+        check(self.L.mg3d_ctx_get_shift(self._h, C.byref(sigma)))
+        return sigma.value
 
     def setup_boundary_conditions(self, field=MG3D_D, level=None):
         level = self.num_levels - 1 if level is None else level
@@ -466,6 +480,10 @@ class DistSolver:
 
     def set_option(self, key, value):
         check(self.L.mg3d_dist_set_option(self._h, key.encode(), int(value)))
+
+    def set_shift(self, sigma):
+        """mg3d_dist_set_shift: the screened operator on every local rank (every rank of a job passes the same sigma)."""
+        check(self.L.mg3d_dist_set_shift(self._h, float(sigma)))
 
     def setup_test_problem(self):
         """test_mg_3d.c:11-29 on the full grid; every rank takes its slab."""

@@ -28,6 +28,11 @@ struct mg3d_ctx {
     LuBand lu;
     LuBand lu_in; /* the factor without its identity rows (n == 0: not built), see install_lu */
     bool have_lu;
+    /* the screened operator Delta_h u - sigma u (mg3d_ctx_set_shift; 0: the reference's Poisson operator) and where the
+     * factor came from: lu_built -- mg3d_ctx_build_coarse(lu_h), rebuilt for a new sigma; else mg3d_ctx_set_lu, dropped */
+    double sigma;
+    bool lu_built;
+    double lu_h;
     double *lu_work;  /* 2n doubles */
     double *partials; /* MG3D_MAX_PARTIALS doubles */
     double *sumsq;    /* device slots for squared norms */
@@ -71,6 +76,8 @@ struct mg3d_ctx {
     std::vector<hipEvent_t> event_pool;
 };
 
+/* the operator constants of a level of this context (its spacing, the context's sigma) */
+static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
 /* records a failure text for mg3d_last_error() and returns `code` */

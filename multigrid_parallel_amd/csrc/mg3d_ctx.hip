@@ -259,6 +259,9 @@ static mg3d_ctx *ctx_new(int L, int iters)
     ctx->L = L;
     ctx->iters = iters;
     ctx->have_lu = false;
+    ctx->sigma = 0.;
+    ctx->lu_built = false;
+    ctx->lu_h = 0.;
     memset(&ctx->lu, 0, sizeof ctx->lu);
     memset(&ctx->lu_in, 0, sizeof ctx->lu_in);
     ctx->lu_work = nullptr;
@@ -320,7 +323,7 @@ int mg3d_drop_carry_keep(mg3d_ctx *ctx)
     if (!ctx || !ctx->carried)
         return MG3D_OK;
     Level &l = ctx->lv[ctx->L - 1];
-    const int np = k_sweep(ctx->opt, l.g, l.alt, l.f[MG3D_D], l.f[MG3D_U], nullptr, nullptr, MG3D_MAX_PARTIALS, l.h, 2, 0, false,
+    const int np = k_sweep(ctx->opt, l.g, l.alt, l.f[MG3D_D], l.f[MG3D_U], nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(ctx, l), 2, 0, false,
                            ctx->stream);
     /* a failure leaves the context where it was -- u three passes into the next cycle, `carried` still set: the caller
      * returns the error instead of going on with (and handing out) a state nobody asked for; a later call tries again */
@@ -604,6 +607,7 @@ extern "C" int mg3d_ctx_set_lu(mg3d_ctx *ctx, const double *LU)
     if (n * n >= 2147483647LL) /* assert(totalNodes*totalNodes < INT_MAX), mg_3d.h:163 */
         return fail(MG3D_ERR_ARG, "mg3d_ctx_set_lu: coarse grid %d^3 too large for a dense factor", N0);
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->lu_built = false;
     CHK(install_lu(ctx, LU, n, 2 * (size_t)n));
     ctx->have_lu = true;
     ctx->have_es = false; /* whatever factor was loaded before (mg3d_es_setup re-arms it after its own call) */
@@ -622,11 +626,53 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    mg3d_coarse_matrix(A, N0, h_coarse); /* mg_3d.h:288 */
-    mg3d_lu_factor(A, (int)n);           /* mg_3d.h:289 */
+    mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
+    mg3d_lu_factor(A, (int)n);                             /* mg_3d.h:289 */
     const int rc = mg3d_ctx_set_lu(ctx, A);
     free(A);
+    if (rc == MG3D_OK) { /* remembered: mg3d_ctx_set_shift builds it again for another sigma */
+        ctx->lu_built = true;
+        ctx->lu_h = h_coarse;
+    }
     return rc;
+}
+
+/* The screened operator Delta_h u - sigma u = d on every level (LevelOp).  The argument is checked before anything
+ * changes.  Then: a cycle that has run ahead is finished with the operator it started with (mg3d_drop_carry), and a new
+ * sigma rebuilds a factor of mg3d_ctx_build_coarse for the spacing it was built with, or drops one installed by
+ * mg3d_ctx_set_lu (or mg3d_es_setup): the next cycle returns MG3D_ERR_STATE until a factor is set again. */
+extern "C" int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma)
+{
+    if (!ctx || !(sigma >= 0.) || !isfinite(sigma))
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_shift: %s", ctx ? "sigma must be finite and >= 0" : "NULL context");
+    CHK(mg3d_drop_carry(ctx));
+    if (sigma == ctx->sigma)
+        return MG3D_OK;
+    ctx->sigma = sigma == 0. ? 0. : sigma; /* (-0 is stored as +0) */
+    if (!ctx->have_lu)
+        return MG3D_OK;
+    if (ctx->lu_built) {
+        const int rc = mg3d_ctx_build_coarse(ctx, ctx->lu_h);
+        if (rc == MG3D_OK)
+            return MG3D_OK;
+        /* no factor of the old operator may survive next to the new sigma */
+        (void)hipStreamSynchronize(ctx->stream);
+        free_lu(ctx);
+        ctx->lu_built = false;
+        return rc;
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream)); /* a solve still in flight reads the factor */
+    free_lu(ctx);
+    ctx->have_es = false;
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma)
+{
+    if (!ctx || !sigma)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_shift: NULL argument");
+    *sigma = ctx->sigma;
+    return MG3D_OK;
 }
 
 /* ----------------------------------------------------------- data movement */
@@ -776,7 +822,7 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
                 np = k_sweep(ctx->opt, l.g, (zero_in && passes == 2 * iters) ? nullptr : l.f[MG3D_U], l.f[MG3D_D], l.alt,
                              (res && want_res == 2 && !rst) ? l.f[MG3D_R] : nullptr,
                              (res && need_norm) ? ctx->partials : nullptr,
-                             MG3D_MAX_PARTIALS, l.h, S, c1, res, s, 0, -1, rst ? &coarse->g : nullptr,
+                             MG3D_MAX_PARTIALS, mg3d_op(ctx, l), S, c1, res, s, 0, -1, rst ? &coarse->g : nullptr,
                              rst ? coarse->f[MG3D_D] : nullptr, -1, -1, with_pro ? &pro->g : nullptr,
                              with_pro ? pro->f[MG3D_U] : nullptr);
             }
@@ -797,15 +843,14 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
         }
         return MG3D_OK;
     }
-    const double hSq = l.h * l.h; /* mg_3d.h:644 */
+    const LevelOp op = mg3d_op(ctx, l);
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-        k_smooth_color(l.g, l.f[MG3D_U], l.f[MG3D_D], hSq, c1 ^ (it & 1), s);
+        k_smooth_color(l.g, l.f[MG3D_U], l.f[MG3D_D], op, c1 ^ (it & 1), s);
     }
     if (want_res) {
-        const double invHsq = 1. / (l.h * l.h); /* mg_3d.h:797 */
         StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-        k_residual(l.g, l.f[MG3D_U], l.f[MG3D_D], invHsq, want_res == 2 ? l.f[MG3D_R] : nullptr, ctx->partials,
+        k_residual(l.g, l.f[MG3D_U], l.f[MG3D_D], op, want_res == 2 ? l.f[MG3D_R] : nullptr, ctx->partials,
                    ctx->sumsq + slot, s);
     }
     return MG3D_OK;
@@ -1042,7 +1087,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                     StageScope kt(ctx, l, MG3D_K_LEG_DOWN, true);
                     /* behind another cycle: black, red, black (the first red pass is the identity) and the black half of
                      * that cycle's norm, + residual + restriction (:1282 + :1294 + :1310) */
-                    const int np = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_D], lev.h,
+                    const int np = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_D], mg3d_op(ctx, lev),
                                                     3, red_in ? nullptr : part_b, MG3D_MAX_PARTIALS / 2, s);
                     if (np < 0)
                         return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the down-leg");
@@ -1066,7 +1111,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             { /* the one pre-smoothing pass that is left (black) + residual + restriction (:1282 + :1294 + :1310) */
                 StageScope t(ctx, l, MG3D_ST_SMOOTH1);
                 StageScope kt(ctx, l, MG3D_K_SWEEP1_RESTRICT, true);
-                const int np = k_sweep(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, lev.h,
+                const int np = k_sweep(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(ctx, lev),
                                        1, 0, true, s, 0, -1, &ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_D]);
                 if (np < 0)
                     return fail(MG3D_ERR_STATE, "carried cycle: no kernel for one pass + residual + restriction");
@@ -1088,7 +1133,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                 StageScope t(ctx, l, MG3D_ST_SMOOTH1);
                 StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
                 k_tiny_cycle(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], ctx->lv[0].g, ctx->lv[0].f[MG3D_D],
-                             ctx->lv[0].f[MG3D_U], ctx->lu, ctx->lu_in, lev.h, ctx->iters, s); /* :1258 ... :1341 of levels 1, 0 */
+                             ctx->lv[0].f[MG3D_U], ctx->lu, ctx->lu_in, mg3d_op(ctx, lev), ctx->iters, s); /* :1258 ... :1341 of levels 1, 0 */
             }
             { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
             { StageScope t(ctx, l, MG3D_ST_RESTRICT); }
@@ -1099,7 +1144,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             {
                 StageScope t(ctx, l, MG3D_ST_SMOOTH1);
                 StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
-                k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], ctx->lv[0].g, ctx->lv[0].f[MG3D_D], lev.h,
+                k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], ctx->lv[0].g, ctx->lv[0].f[MG3D_D], mg3d_op(ctx, lev),
                             ctx->iters, s); /* :1258 + :1282 + :1294 + :1310 */
             }
             { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
@@ -1163,7 +1208,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             {
                 StageScope t(ctx, l, MG3D_ST_SMOOTH2);
                 StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
-                k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], ctx->lv[0].g, ctx->lv[0].f[MG3D_U], lev.h, ctx->iters,
+                k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], ctx->lv[0].g, ctx->lv[0].f[MG3D_U], mg3d_op(ctx, lev), ctx->iters,
                           s); /* :1331 + :1341 */
             }
             { StageScope t(ctx, l, MG3D_ST_RESIDUAL2); }
@@ -1179,7 +1224,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                     StageScope kt(ctx, l, MG3D_K_LEG_UP, true);
                     /* prolongation + black, red, black, red (:1331 + :1341); with another cycle behind it, the red half of
                      * the norm (:1354) from the last pass's sums */
-                    npa = k_sweep_leg_up(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_U], lev.h,
+                    npa = k_sweep_leg_up(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_U], mg3d_op(ctx, lev),
                                          carry_out ? part_a : nullptr, MG3D_MAX_PARTIALS / 2, s);
                 }
                 if (npa < 0)
@@ -1194,7 +1239,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                 } else if (carry_out == 2) {
                     /* mg3d_vcycle: the next cycle's down-leg now, into the alt buffers (see mg3d_can_legs) */
                     StageScope kt(ctx, l, MG3D_K_LEG_DOWN, true);
-                    const int npb = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.alt, lev.h, 3, part_b,
+                    const int npb = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.alt, mg3d_op(ctx, lev), 3, part_b,
                                                      MG3D_MAX_PARTIALS / 2, s);
                     if (npb < 0)
                         return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the down-leg");
@@ -1222,7 +1267,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                  * being the identity) */
                 StageScope kt(ctx, l, MG3D_K_SWEEP4_NORM, true);
                 const int np = k_sweep_tap(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, ctx->partials, MG3D_MAX_PARTIALS,
-                                           lev.h, 0, s);
+                                           mg3d_op(ctx, lev), 0, s);
                 if (np < 0)
                     return fail(MG3D_ERR_STATE, "carried cycle: no kernel for four passes + norm tap");
                 double *t2 = lev.f[MG3D_U];

@@ -689,6 +689,20 @@ extern "C" int mg3d_dist_build_coarse(mg3d_dist *D, double h_coarse)
     return MG3D_OK;
 }
 
+/* the screened operator (mg3d_ctx_set_shift) on every local rank: its slab levels take sigma from the rank's replicated
+ * context (mg3d_op), whose coarse factor is rebuilt there.  A multi-rank job must agree on sigma (not checked). */
+extern "C" int mg3d_dist_set_shift(mg3d_dist *D, double sigma)
+{
+    if (!D || !(sigma >= 0.) || !isfinite(sigma))
+        return fail(MG3D_ERR_ARG, "mg3d_dist_set_shift: %s", D ? "sigma must be finite and >= 0" : "NULL");
+    if (D->carried || D->legs_pending)
+        return fail(MG3D_ERR_STATE, "mg3d_dist_set_shift: inside a carried cycle");
+    D->red_tail = false;
+    for (auto &R : D->rs)
+        CHK(mg3d_ctx_set_shift(R.coarse, sigma));
+    return MG3D_OK;
+}
+
 /* ------------------------------------------------------------------------------------ data movement */
 static int dist_field_ptr(mg3d_dist *D, RankState &R, int field, int level, double **ptr, Geom *g)
 {
@@ -926,9 +940,9 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
                     Level &lv = sl.lv;
                     mg3d_ctx *cx = D->rs[ri].coarse;
                     if (tap)
-                        return k_sweep_tap(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, part, MG3D_MAX_PARTIALS / 2, lv.h, c1, s, sl.own_lo,
+                        return k_sweep_tap(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, part, MG3D_MAX_PARTIALS / 2, mg3d_op(cx, lv), c1, s, sl.own_lo,
                                            sl.own_hi, lo, hi, edge);
-                    return k_sweep(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, nullptr, part, MG3D_MAX_PARTIALS / 2, lv.h, S, c1, true, s,
+                    return k_sweep(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, nullptr, part, MG3D_MAX_PARTIALS / 2, mg3d_op(cx, lv), S, c1, true, s,
                                    sl.own_lo, sl.own_hi, nullptr, nullptr, -1, -1, (pro && first) ? pro[ri].gc : nullptr,
                                    (pro && first) ? pro[ri].ec : nullptr, lo, hi, edge);
                 };
@@ -986,7 +1000,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
             if (tap && last) {
                 /* output: the owned planes only -- the four passes use up the halo planes the first launch has left, and
                  * the next launch (one pass + residual + restriction) gets three fresh ones by exchange first */
-                const int np = k_sweep_tap(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, cx->partials, MG3D_MAX_PARTIALS, lv.h, c1, s,
+                const int np = k_sweep_tap(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, cx->partials, MG3D_MAX_PARTIALS, mg3d_op(cx, lv), c1, s,
                                            sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
                 if (np < 0)
                     return fail(MG3D_ERR_STATE, "slab sweep: no kernel for four passes + norm tap on level %d", l);
@@ -996,7 +1010,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
             const int np = k_sweep(cx->opt, lv.g, (zero_in && first) ? nullptr : lv.f[MG3D_U], lv.f[MG3D_D], lv.alt,
                                    (res && want_res == 2 && !rst) ? lv.f[MG3D_R] : nullptr,
                                    (res && want_res == 1) ? cx->partials : nullptr, /* the pre-smoothing norm is dropped (:1294) */
-                                   MG3D_MAX_PARTIALS, lv.h, S, c1, res, s, sl.own_lo, sl.own_hi,
+                                   MG3D_MAX_PARTIALS, mg3d_op(cx, lv), S, c1, res, s, sl.own_lo, sl.own_hi,
                                    rst ? tgt[ri].gc : nullptr, rst ? tgt[ri].dc : nullptr, rst ? tgt[ri].lo : -1,
                                    rst ? tgt[ri].hi : -1, (pro && first) ? pro[ri].gc : nullptr,
                                    (pro && first) ? pro[ri].ec : nullptr, w_lo, w_hi);
@@ -1131,7 +1145,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
                 Level &lv = sl.lv;
                 mg3d_ctx *cx = R.coarse;
                 double *part_b = red_in ? nullptr : cx->partials + MG3D_MAX_PARTIALS / 2;
-                const int npb = k_sweep_leg_down(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, *tgt[ri].gc, tgt[ri].dc, lv.h, 3, part_b,
+                const int npb = k_sweep_leg_down(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, *tgt[ri].gc, tgt[ri].dc, mg3d_op(cx, lv), 3, part_b,
                                                  MG3D_MAX_PARTIALS / 2, s, sl.own_lo, sl.own_hi, tgt[ri].lo, tgt[ri].hi, sl.own_lo, sl.own_hi);
                 if (npb <= 0)
                     return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch down-leg on level %d", l);
@@ -1149,7 +1163,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
             for (size_t ri = 0; ri < D->rs.size(); ri++) {
                 SlabLevel &sl = SL(D, D->rs[ri], l);
                 Level &lv = sl.lv;
-                const int np = k_sweep(D->rs[ri].coarse->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, lv.h, 1, 0,
+                const int np = k_sweep(D->rs[ri].coarse->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(D->rs[ri].coarse, lv), 1, 0,
                                        true, s, sl.own_lo, sl.own_hi, tgt[ri].gc, tgt[ri].dc, tgt[ri].lo, tgt[ri].hi, nullptr,
                                        nullptr, sl.own_lo, sl.own_hi);
                 if (np < 0)
@@ -1231,7 +1245,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
             auto up = [&](size_t ri, const double *vin, double *vout, double *part, int maxp, int lo, int hi, int edge) -> int {
                 SlabLevel &sl = SL(D, D->rs[ri], l);
                 Level &lv = sl.lv;
-                return k_sweep_leg_up(D->rs[ri].coarse->opt, lv.g, vin, lv.f[MG3D_D], vout, *pro[ri].gc, pro[ri].ec, lv.h, part, maxp, s,
+                return k_sweep_leg_up(D->rs[ri].coarse->opt, lv.g, vin, lv.f[MG3D_D], vout, *pro[ri].gc, pro[ri].ec, mg3d_op(D->rs[ri].coarse, lv), part, maxp, s,
                                       sl.own_lo, sl.own_hi, lo, hi, edge);
             };
             std::vector<int> n1(D->rs.size(), 0);

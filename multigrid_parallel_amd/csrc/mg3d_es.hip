@@ -171,6 +171,8 @@ extern "C" int mg3d_es_setup(mg3d_ctx *ctx, const mg3d_es_params *p)
     CHK(mg3d_drop_carry(ctx));
     if (!ctx || !p || !(p->length > 0.))
         return fail(MG3D_ERR_ARG, "mg3d_es_setup: bad arguments");
+    if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
+        return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has a screened operator (mg3d_ctx_set_shift); set the shift to 0");
     if (p->length != ctx->length)
         return fail(MG3D_ERR_ARG, "mg3d_es_setup: the context was created with grid length %g, the problem has %g", ctx->length,
                     p->length);
@@ -207,6 +209,8 @@ extern "C" int mg3d_es_smooth(mg3d_ctx *ctx, int level, int post, int iters)
     CHK(mg3d_drop_carry(ctx));
     if (!ctx || !ctx->have_es || level < 0 || level >= ctx->L || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_es_smooth: bad arguments (mg3d_es_setup first)");
+    if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
+        return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has a screened operator (mg3d_ctx_set_shift); set the shift to 0");
     es_smooth(ctx, level, post, iters);
     return launch_ok_es("mg3d_es_smooth");
 }
@@ -221,7 +225,7 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
         if (l < ctx->L - 1)
             HIPCHK(hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), s)); /* mg_3d.h:1258-1259 */
         es_smooth(ctx, l, 0, ctx->iters);                                                            /* :1282 */
-        k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], 1. / (lev.h * lev.h), lev.f[MG3D_R], ctx->partials,
+        k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], mg3d_level_op(lev.h, 0.), lev.f[MG3D_R], ctx->partials,
                    ctx->sumsq + ctx->sumsq_slots - 1, s);                                            /* :1294 */
         k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], s);                                     /* :1310 */
     }
@@ -239,7 +243,7 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
         es_fill(ctx, l, l == ctx->L - 1 ? 1. : 0.);
         es_smooth(ctx, l, 1, ctx->iters);                       /* :1341 */
         if (l == q)
-            k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], 1. / (lev.h * lev.h), nullptr, ctx->partials, ctx->sumsq + slot,
+            k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], mg3d_level_op(lev.h, 0.), nullptr, ctx->partials, ctx->sumsq + slot,
                        s);                                      /* :1354 */
     }
     return launch_ok_es("mg3d_es_vcycles");
@@ -250,6 +254,8 @@ extern "C" int mg3d_es_vcycles(mg3d_ctx *ctx, int count, double *norms)
     CHK(mg3d_drop_carry(ctx));
     if (!ctx || count < 0 || !ctx->have_es)
         return fail(MG3D_ERR_ARG, "mg3d_es_vcycles: bad arguments (mg3d_es_setup first)");
+    if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
+        return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has a screened operator (mg3d_ctx_set_shift); set the shift to 0");
     if (ctx->L < 2)
         return fail(MG3D_ERR_ARG, "mg3d_es_vcycles: needs at least two levels");
     const int batch = ctx->sumsq_slots - 1;

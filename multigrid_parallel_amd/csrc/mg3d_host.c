@@ -35,15 +35,16 @@ void mg3d_fill_boundary_host(double *v, int N, double h)
     }
 }
 
-/* constructCoarseMatrixA, mg_3d.h:147-273.  Row `p` of the dense n x n matrix:
- * identity on boundary nodes (:179-185), (1,1,1,1,1,1,-6)/h^2 on interior
- * nodes (:257-268).  A must be zero on entry (calloc, mg_3d.h:283). */
-void mg3d_coarse_matrix(double *A, int N, double h)
+/* constructCoarseMatrixA, mg_3d.h:147-273, of the screened operator Delta_h - sigma.  Row `p` of the dense n x n
+ * matrix: identity on boundary nodes (:179-185), (1,1,1,1,1,1,-dg)/h^2 on interior nodes (:257-268) with
+ * dg = 6 + sigma*h^2 (sigma = 0: the reference's 6, bit for bit).  A must be zero on entry (calloc, mg_3d.h:283). */
+void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma)
 {
     const long NN = (long)N * N, n = NN * N;
     const double hSq = h * h;
     const double invHsq = 1. / hSq;
-    const double off = 1. * invHsq, diag = 6. * invHsq;
+    const double dg = 6. + sigma * hSq;
+    const double off = 1. * invHsq, diag = dg * invHsq;
     long p = 0;
     for (int i = 0; i < N; i++)
         for (int j = 0; j < N; j++)
@@ -63,6 +64,8 @@ void mg3d_coarse_matrix(double *A, int N, double h)
                 row[p] = -diag;
             }
 }
+
+void mg3d_coarse_matrix(double *A, int N, double h) { mg3d_coarse_matrix_shift(A, N, h, 0.); }
 
 /* The coarsest operator of the mixed-boundary problem (csrc/mg3d_es.hip): constructCoarseMatrixA (identity rows on
  * the boundary, mg_3d.h:179-185) except that a wall point -- a face point with an interior point in front of it that is

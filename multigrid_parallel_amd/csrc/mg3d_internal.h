@@ -22,6 +22,24 @@ struct Geom {
 
 static inline int mg3d_pitch_for(int nk) { return (nk + 15) & ~15; }
 
+/* The constants of one level's operator, the screened 7-point Laplacian  Delta_h u - sigma u = d  (sigma >= 0, set per
+ * context by mg3d_ctx_set_shift; 0 is the reference's Poisson operator):
+ *   smoother  v = sixth * (((((((up + dn) + jm) + jp) + km) + kp) - hSq*d)          (mg_3d.h:438-443)
+ *   residual  diff = d - invHsq * (sum - dg*v)                                       (mg_3d.h:819-821)
+ * With sigma = 0 every constant is the reference's own double: dg = 6 + 0*hSq = 6, sixth = 1./6, invHsq = 1./(h*h). */
+struct LevelOp {
+    double hSq, sixth, invHsq, dg;
+};
+static inline LevelOp mg3d_level_op(double h, double sigma)
+{
+    LevelOp op;
+    op.hSq = h * h;             /* mg_3d.h:644 */
+    op.dg = 6 + sigma * op.hSq; /* the diagonal times h^2 */
+    op.sixth = 1. / op.dg;      /* mg_3d.h:646 */
+    op.invHsq = 1. / op.hSq;    /* mg_3d.h:797 */
+    return op;
+}
+
 struct LuBand {
     int n;        /* unknowns */
     int bw;       /* half bandwidth actually populated (max |i-j| with LU[i][j] != 0) */
@@ -80,9 +98,9 @@ int mg3d_option_index(const char *key);           /* -1: no such key */
 const char *mg3d_option_key(int index);           /* NULL past the end */
 
 /* launchers (mg3d_kernels.hip); all asynchronous on `s` */
-void k_smooth_color(const Geom &g, double *v, const double *d, double hSq, int color, hipStream_t s);
+void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOp &op, int color, hipStream_t s);
 /* writes partials (one per block) then reduces them, in a fixed order, into *sumsq_out */
-void k_residual(const Geom &g, const double *v, const double *d, double invHsq, double *res, double *partials,
+void k_residual(const Geom &g, const double *v, const double *d, const LevelOp &op, double *res, double *partials,
                 double *sumsq_out, hipStream_t s);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
@@ -103,7 +121,7 @@ void k_fold2(const double *pa, int na, const double *pb, int nb, double *out, hi
 void k_sweep_set_tune_default(int on); /* first-use chunk measurement on / off where the option says -1 */
 bool k_sweep_fuse_rst2(const mg3d_options &o, int N); /* two passes + residual + restriction as ONE launch on a level of N points per side */
 int k_sweep(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-            int max_partials, double h, int S, int c1, bool residual, hipStream_t s, int acc_lo = 0,
+            int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo = 0,
             int acc_hi = -1 /* local planes entering the norm; default all */,
             const Geom *gc = nullptr, double *dc = nullptr /* non-NULL: also restrict the residual into the
             interior of the coarse right-hand side dc (S = 0 or 2 with residual only) */,
@@ -118,30 +136,31 @@ int k_sweep(const mg3d_options &o, const Geom &g, const double *vin, const doubl
  * (the launch that ends one V-cycle -- its last two post-smoothing passes and its norm -- and begins the next: mg3d_ctx.hip,
  * "carried cycles").  Returns the number of partials written or -1. */
 int k_sweep_tap(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *partials, int max_partials,
-                double h, int c1, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int i_lo = -1, int i_hi = -1, int edge = 0);
+                const LevelOp &op, int c1, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int i_lo = -1, int i_hi = -1, int edge = 0);
 /* One launch per leg of a V(2,2) cycle on a level (mg3d_sweep.hip, "one launch per leg").  down: S = 4 colour passes red
  * first, or S = 3 black first (behind another cycle), + residual + full-weighting restriction into the interior of dc;
  * partials (S = 3 only): sum of diff^2 of the INCOMING state over the colour the first pass updates.  up: the input is
  * vin + P(ec), four passes black first; partials: sum of diff^2 of the RESULT over the colour the last pass updated.
  * Return value as k_sweep. */
-int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, double h, int S,
+int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, const LevelOp &op, int S,
                      double *partials, int max_partials, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int ic_lo = -1,
                      int ic_hi = -1, int i_lo = -1, int i_hi = -1);
-int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, double h,
+int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, const LevelOp &op,
                    double *partials, int max_partials, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int i_lo = -1,
                    int i_hi = -1, int edge = 0);
 /* mg3d_tiny.hip: the level above the coarsest one in one workgroup (LDS-resident), when it fits (N <= 17) */
 bool k_tiny_fits(const Geom &g, const Geom &gc);
 /* zero guess, `iters` x (red, black), residual, restriction (interior + face injection from r's boundary) into dc */
-void k_tiny_down(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double h, int iters,
-                 hipStream_t s);
+void k_tiny_down(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, const LevelOp &op,
+                 int iters, hipStream_t s);
 /* u += P(ec) at every point, then `iters` x (black, red) */
-void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const double *ec, double h, int iters, hipStream_t s);
+void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const double *ec, const LevelOp &op, int iters,
+               hipStream_t s);
 /* the bottom of the cycle in one launch: tiny_down on level 1, the direct solve of level 0 (reduced factor lin, the full
  * one as its fall-back), tiny_up on level 1; dc / xc receive level 0's right-hand side and solution */
 bool k_tiny_cycle_fits(const Geom &g, const Geom &gc, const LuBand &lu, const LuBand &lin);
 void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double *xc,
-                  const LuBand &lu, const LuBand &lin, double h, int iters, hipStream_t s);
+                  const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

@@ -50,14 +50,14 @@ __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__res
     v[p] = sixth * s;
 }
 
-void k_smooth_color(const Geom &g, double *v, const double *d, double hSq, int color, hipStream_t s)
+void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOp &op, int color, hipStream_t s)
 {
     if (g.ni < 3 || g.nj < 3 || g.nk < 3)
         return;
     dim3 block(64, 4, 1);
     const int pairs = (g.nk + 1) / 2;
     dim3 grid((pairs + 63) / 64, (g.nj - 2 + 3) / 4, g.ni - 2);
-    hipLaunchKernelGGL(smooth_color_kernel, grid, block, 0, s, g, v, d, hSq, 1. / 6, color);
+    hipLaunchKernelGGL(smooth_color_kernel, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color);
 }
 
 /* ------------------------------------------------------------ boundary fill
@@ -118,13 +118,14 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const double *__rest
 
 /* ------------------------------------------------------------------ residual
  * calculateResidual, mg_3d.h:819-821:
- *   diff = d[p] - invHsq * (((((((v[p-NN]+v[p+NN])+v[p-N])+v[p+N])+v[p-1])+v[p+1]) - 6*v[p])
+ *   diff = d[p] - invHsq * (((((((v[p-NN]+v[p+NN])+v[p-N])+v[p+N])+v[p-1])+v[p+1]) - dg*v[p])
+ * (dg = 6 for the reference's operator, 6 + sigma*h^2 for the screened one: LevelOp)
  * res (optional) is written on the interior only (mg_3d.h:824-825).
  * Each thread marches `chunk` planes in i keeping the i-1 / i / i+1 values of its
  * column in registers; diff^2 is reduced lane -> wave (__shfl_down) -> block. */
 __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v,
                                                        const double *__restrict__ d, double invHsq,
-                                                       double *__restrict__ res, double *__restrict__ partials,
+                                                       double dg, double *__restrict__ res, double *__restrict__ partials,
                                                        int chunk)
 {
     __shared__ double lds4[4];
@@ -145,7 +146,7 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
             s = s + v[p + g.pitch];
             s = s + v[p - 1];
             s = s + v[p + 1];
-            s = s - 6 * here;
+            s = s - dg * here;
             const double diff = d[p] - invHsq * s;
             if (res)
                 res[p] = diff;
@@ -186,7 +187,7 @@ void k_fold(const double *partials, int np, double *out, hipStream_t s)
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, np, out);
 }
 
-void k_residual(const Geom &g, const double *v, const double *d, double invHsq, double *res, double *partials,
+void k_residual(const Geom &g, const double *v, const double *d, const LevelOp &op, double *res, double *partials,
                 double *sumsq_out, hipStream_t s)
 {
     if (g.ni < 3 || g.nj < 3 || g.nk < 3) {
@@ -198,8 +199,8 @@ void k_residual(const Geom &g, const double *v, const double *d, double invHsq, 
     while ((long long)gx * gy * ((g.ni - 2 + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
         chunk *= 2;
     const int gz = (g.ni - 2 + chunk - 1) / chunk;
-    hipLaunchKernelGGL(residual_kernel, dim3(gx, gy, gz), dim3(64, 4, 1), 0, s, g, v, d, invHsq, res, partials,
-                       chunk);
+    hipLaunchKernelGGL(residual_kernel, dim3(gx, gy, gz), dim3(64, 4, 1), 0, s, g, v, d, op.invHsq, op.dg, res,
+                       partials, chunk);
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, gx * gy * gz, sumsq_out);
 }
 

@@ -368,7 +368,7 @@ bool k_sweep_fuse_rst2(const mg3d_options &o, int N) /* two passes + residual + 
 }
 
 static int sweep_impl(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-                      int max_partials, double h, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
+                      int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
                       const Geom *gc, double *dc, int ic_lo, int ic_hi, const Geom *gce, const double *ec, int i_lo, int i_hi,
                       bool tap, int edge = 0)
 {
@@ -402,9 +402,10 @@ static int sweep_impl(const mg3d_options &o, const Geom &g, const double *vin, c
         return -1;
     a.r = r;
     a.partials = partials;
-    a.hSq = h * h;           /* mg_3d.h:644 */
-    a.sixth = 1. / 6;        /* mg_3d.h:646 */
-    a.invHsq = 1. / (h * h); /* mg_3d.h:797 */
+    a.hSq = op.hSq;
+    a.sixth = op.sixth;
+    a.invHsq = op.invHsq;
+    a.dg = op.dg;
     a.c1 = c1;
     if (tap) { /* four passes, the residual norm of the state after the second one into partials */
         if (S != 4 || dc || ec || r || !partials || residual)
@@ -505,8 +506,8 @@ static mg3d_options leg_options(const mg3d_options &o)
     return q;
 }
 
-static void leg_args(SweepArgs &a, const Geom &g, const double *vin, const double *d, double *vout, double *partials, double h,
-                     int c1, int i_lo, int i_hi, int acc_lo, int acc_hi)
+static void leg_args(SweepArgs &a, const Geom &g, const double *vin, const double *d, double *vout, double *partials,
+                     const LevelOp &op, int c1, int i_lo, int i_hi, int acc_lo, int acc_hi)
 {
     a.g = g;
     a.vin = vin;
@@ -514,9 +515,10 @@ static void leg_args(SweepArgs &a, const Geom &g, const double *vin, const doubl
     a.vout = vout;
     a.r = nullptr;
     a.partials = partials;
-    a.hSq = h * h;           /* mg_3d.h:644 */
-    a.sixth = 1. / 6;        /* mg_3d.h:646 */
-    a.invHsq = 1. / (h * h); /* mg_3d.h:797 */
+    a.hSq = op.hSq;
+    a.sixth = op.sixth;
+    a.invHsq = op.invHsq;
+    a.dg = op.dg;
     a.c1 = c1;
     a.i_lo = i_lo >= 0 ? i_lo : 0;
     a.i_hi = i_hi >= 0 ? i_hi : g.ni;
@@ -530,13 +532,13 @@ static void leg_args(SweepArgs &a, const Geom &g, const double *vin, const doubl
     a.edge = 0;
 }
 
-int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, double h, int S,
+int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, const LevelOp &op, int S,
                      double *partials, int max_partials, hipStream_t s, int acc_lo, int acc_hi, int ic_lo, int ic_hi, int i_lo,
                      int i_hi)
 {
     const mg3d_options oq = leg_options(o);
     SweepArgs a;
-    leg_args(a, g, vin, d, vout, partials, h, S == 4 ? 1 : 0, i_lo, i_hi, acc_lo, acc_hi);
+    leg_args(a, g, vin, d, vout, partials, op, S == 4 ? 1 : 0, i_lo, i_hi, acc_lo, acc_hi);
     if (a.i_hi <= a.i_lo)
         return 0;
     a.gc = gc;
@@ -557,14 +559,14 @@ int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, co
     return -1;
 }
 
-int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, double h,
+int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, const LevelOp &op,
                    double *partials, int max_partials, hipStream_t s, int acc_lo, int acc_hi, int i_lo, int i_hi, int edge)
 {
     if ((g.nj & 1) == 0)
         return -1;
     const mg3d_options oq = leg_options(o);
     SweepArgs a;
-    leg_args(a, g, vin, d, vout, partials, h, 0, i_lo, i_hi, acc_lo, acc_hi);
+    leg_args(a, g, vin, d, vout, partials, op, 0, i_lo, i_hi, acc_lo, acc_hi);
     if (a.i_hi <= a.i_lo)
         return 0;
     a.ec = ec;
@@ -582,17 +584,17 @@ int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, cons
 }
 
 int k_sweep(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-            int max_partials, double h, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
+            int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
             const Geom *gc, double *dc, int ic_lo, int ic_hi, const Geom *gce, const double *ec, int i_lo, int i_hi, int edge)
 {
-    return sweep_impl(o, g, vin, d, vout, r, partials, max_partials, h, S, c1, residual, s, acc_lo, acc_hi, gc, dc, ic_lo, ic_hi,
+    return sweep_impl(o, g, vin, d, vout, r, partials, max_partials, op, S, c1, residual, s, acc_lo, acc_hi, gc, dc, ic_lo, ic_hi,
                       gce, ec, i_lo, i_hi, false, edge);
 }
 
 int k_sweep_tap(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *partials, int max_partials,
-                double h, int c1, hipStream_t s, int acc_lo, int acc_hi, int i_lo, int i_hi, int edge)
+                const LevelOp &op, int c1, hipStream_t s, int acc_lo, int acc_hi, int i_lo, int i_hi, int edge)
 {
-    return sweep_impl(o, g, vin, d, vout, nullptr, partials, max_partials, h, 4, c1, false, s, acc_lo, acc_hi, nullptr, nullptr,
+    return sweep_impl(o, g, vin, d, vout, nullptr, partials, max_partials, op, 4, c1, false, s, acc_lo, acc_hi, nullptr, nullptr,
                       -1, -1, nullptr, nullptr, i_lo, i_hi, true, edge);
 }
 

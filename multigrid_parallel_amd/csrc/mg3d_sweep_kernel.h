@@ -16,7 +16,7 @@ struct SweepArgs {
     double *vout;     /* may equal nullptr when S == 0 */
     double *r;        /* residual store (interior only) or nullptr */
     double *partials; /* one partial sum of diff^2 per block, or nullptr */
-    double hSq, sixth, invHsq;
+    double hSq, sixth, invHsq, dg; /* LevelOp of the level (screened operator: dg = 6 + sigma*h^2) */
     int c1;         /* colour of the first pass: 1 red, 0 black */
     int ntj, ntk;   /* tiles in j, k */
     int vk, hk;     /* k-tiling: tile tk covers columns [vk*tk, vk*tk + 128) and owns those at least hk from its
@@ -798,13 +798,13 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                                  * residual of the tapped state is made of -- mg_3d.h:819-821 on the sum the update forms anyway.
                                  * TAPQ = S has only the first half, TAPQ = 0 only the second: two launches, one norm. */
                                 if (s == TAPQ || s == TAPQ + 1) {
-                                    const double diff = dd - a.invHsq * (sum - 6 * (s == TAPQ ? nwG[g][s] : center));
+                                    const double diff = dd - a.invHsq * (sum - a.dg * (s == TAPQ ? nwG[g][s] : center));
                                     if ((updu & row_own[rr]) & acc_ok[s])
                                         acc += LM(X ? LM_OWN1 : LM_OWN0) ? diff * diff : 0.;
                                 }
                             }
                             if ((RES == 1 || RES == 2) && s == S) { /* residual of the point just updated: same six neighbours */
-                                const double diff = dd - a.invHsq * (sum - 6 * nwG[g][s]); /* mg_3d.h:819-821 */
+                                const double diff = dd - a.invHsq * (sum - a.dg * nwG[g][s]); /* mg_3d.h:819-821 */
                                 diffsG[g][0] = diff;
                                 /* adding +0 leaves a sum of squares unchanged: a select, not a branch */
                                 if constexpr (RES == 1)
@@ -812,7 +812,7 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                                         acc += LM(X ? LM_OWN1 : LM_OWN0) ? diff * diff : 0.;
                             }
                         } else {
-                            const double diff = dd - a.invHsq * (sum - 6 * center); /* mg_3d.h:819-821 */
+                            const double diff = dd - a.invHsq * (sum - a.dg * center); /* mg_3d.h:819-821 */
                             nwG[g][s] = center;
                             diffsG[g][S > 0 ? 1 : s - 1] = diff;
                             if constexpr (RES == 1)

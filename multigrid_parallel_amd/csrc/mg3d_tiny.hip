@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_down_kernel(Geom g, double 
                                                                 const double *__restrict__ d_in,
                                                                 const double *__restrict__ r_in, Geom gc,
                                                                 double *__restrict__ dc, double hSq, double sixth,
-                                                                double invHsq, int iters)
+                                                                double invHsq, double dg, int iters)
 {
     extern __shared__ double lds[];
     const int N = g.N, n = N * N * N, Nc = gc.N;
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(TINY_THREADS) tiny_down_kernel(Geom g, double 
             s = s + u[p + N];
             s = s + u[p - 1];
             s = s + u[p + 1];
-            s = s - 6 * u[p];
+            s = s - dg * u[p];
             r[p] = d[p] - invHsq * s;
         }
     }
@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(TINY_CYC_THREADS) tiny_cycle_kernel(Geom g, do
                                                                     const double *__restrict__ r_in, Geom gc,
                                                                     double *__restrict__ dc, double *__restrict__ xc,
                                                                     LuBand lu, LuBand lin, double hSq, double sixth,
-                                                                    double invHsq, int iters, int s_doubles)
+                                                                    double invHsq, double dg, int iters, int s_doubles)
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int N = g.N, n = N * N * N, Nc = gc.N, nc = Nc * Nc * Nc, tid = threadIdx.x, lane = tid & 63;
@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(TINY_CYC_THREADS) tiny_cycle_kernel(Geom g, do
             s = s + u[p + N];
             s = s + u[p - 1];
             s = s + u[p + 1];
-            s = s - 6 * u[p];
+            s = s - dg * u[p];
             r[p] = d[p] - invHsq * s;
         }
     __syncthreads();
@@ -491,16 +491,18 @@ bool k_tiny_fits(const Geom &g, const Geom &gc)
            tiny_lds_granted((const void *)tiny_up_kernel, tiny_up_lds(g, gc));
 }
 
-void k_tiny_down(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double h, int iters,
-                 hipStream_t s)
+void k_tiny_down(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, const LevelOp &op,
+                 int iters, hipStream_t s)
 {
-    hipLaunchKernelGGL(tiny_down_kernel, dim3(1), dim3(TINY_THREADS), tiny_down_lds(g), s, g, u, d, r, gc, dc, h * h, 1. / 6,
-                       1. / (h * h), iters);
+    hipLaunchKernelGGL(tiny_down_kernel, dim3(1), dim3(TINY_THREADS), tiny_down_lds(g), s, g, u, d, r, gc, dc, op.hSq, op.sixth,
+                       op.invHsq, op.dg, iters);
 }
 
-void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const double *ec, double h, int iters, hipStream_t s)
+void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const double *ec, const LevelOp &op, int iters,
+               hipStream_t s)
 {
-    hipLaunchKernelGGL(tiny_up_kernel, dim3(1), dim3(TINY_THREADS), tiny_up_lds(g, gc), s, g, u, d, gc, ec, h * h, 1. / 6, iters);
+    hipLaunchKernelGGL(tiny_up_kernel, dim3(1), dim3(TINY_THREADS), tiny_up_lds(g, gc), s, g, u, d, gc, ec, op.hSq, op.sixth,
+                       iters);
 }
 
 /* the S region of tiny_cycle_kernel in doubles: r and the full right-hand side, or the reduced solve's ring and vectors */
@@ -538,16 +540,16 @@ bool k_tiny_cycle_fits(const Geom &g, const Geom &gc, const LuBand &lu, const Lu
 }
 
 void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double *xc,
-                  const LuBand &lu, const LuBand &lin, double h, int iters, hipStream_t s)
+                  const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s)
 {
     const size_t lds = tiny_cycle_lds(g, gc, lu, lin);
     const int sd = tiny_cycle_s_doubles(g, lu, lin);
     if (lu.rot_r == 2)
-        hipLaunchKernelGGL(tiny_cycle_kernel<2>, dim3(1), dim3(TINY_CYC_THREADS), lds, s, g, u, d, r, gc, dc, xc, lu, lin, h * h,
-                           1. / 6, 1. / (h * h), iters, sd);
+        hipLaunchKernelGGL(tiny_cycle_kernel<2>, dim3(1), dim3(TINY_CYC_THREADS), lds, s, g, u, d, r, gc, dc, xc, lu, lin, op.hSq,
+                           op.sixth, op.invHsq, op.dg, iters, sd);
     else
-        hipLaunchKernelGGL(tiny_cycle_kernel<1>, dim3(1), dim3(TINY_CYC_THREADS), lds, s, g, u, d, r, gc, dc, xc, lu, lin, h * h,
-                           1. / 6, 1. / (h * h), iters, sd);
+        hipLaunchKernelGGL(tiny_cycle_kernel<1>, dim3(1), dim3(TINY_CYC_THREADS), lds, s, g, u, d, r, gc, dc, xc, lu, lin, op.hSq,
+                           op.sixth, op.invHsq, op.dg, iters, sd);
 }
 
 extern "C" int mg3d_debug_tiny_stamps(long long *out16)
