@@ -84,6 +84,22 @@ int mg3d_ctx_set_lu(mg3d_ctx *ctx, const double *LU);
 int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma);
 int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma);
 
+/* Variable coefficient.  Every operator of the context becomes the one of
+ *     div(eps grad u) - sigma u = d        (eps > 0 at every grid point, vertex-centred; sigma as mg3d_ctx_set_shift)
+ * with face means a = 0.5*(eps_p + eps_q) over the six neighbours q (order i-, i+, j-, j+, k-, k+):  s = sum of a*v_q,
+ * dg = sum of a + sigma*h^2;  smoother  v = (s - h^2 d)/dg;  residual  d - (s - dg*v)/h^2;  coarse matrix
+ * mg3d_coarse_matrix_coef of level 0's eps.  eps is the finest level's, a dense N^3 host array; a coarser level takes
+ * eps by injection (e_{l-1}[I,J,K] = e_l[2I,2J,2K]).  An entry that is not finite and > 0 is MG3D_ERR_ARG and changes
+ * nothing.  Otherwise, as for mg3d_ctx_set_shift, a cycle that has run ahead is finished first, and a factor of
+ * mg3d_ctx_build_coarse is rebuilt (one of mg3d_ctx_set_lu / mg3d_es_setup dropped).  Another array replaces eps on every
+ * level; NULL returns to the constant-coefficient operator, bit for bit.  With a coefficient every level runs colour
+ * passes and residual of their own kernels: the fused schedules and their options (carry, legs, tiny, tiny_cycle,
+ * fuse_*, sweep_*) keep their values but do not apply.  mg3d_es_* refuse such a context (MG3D_ERR_STATE); the slab
+ * (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms have no coefficient. */
+int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps); /* finest level, dense N^3 host array; NULL: constant operator again */
+int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on);
+int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host); /* the injected eps of a level, dense n^3; MG3D_ERR_STATE without one */
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -163,7 +179,9 @@ int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
  *   sweep_rj/nw/pf  0        MG3D_SWEEP_CFG="rj,nw,pf" another compiled tile shape (unknown ones fall back to the default)
  * mg3d_option_name(i) enumerates the keys (NULL past the end).  mg3d_dist_set_option forwards to every local rank (carry /
  * carry_min of a multi-rank job are agreed at creation and refuse to change); mg3d32_set_option knows "pairs", "fuse",
- * "carry" (MG3D_F32_NO_PAIRS / _NO_FUSE / _NO_CARRY at creation). */
+ * "carry" (MG3D_F32_NO_PAIRS / _NO_FUSE / _NO_CARRY at creation).  A context with a variable coefficient
+ * (mg3d_ctx_set_coefficient) keeps and reports every value, but of these only lu_reduced applies to it: its levels run
+ * the coefficient kernels, never the fused, carried, per-leg or single-workgroup schedules. */
 int mg3d_ctx_set_option(mg3d_ctx *ctx, const char *key, int value);
 int mg3d_ctx_get_option(const mg3d_ctx *ctx, const char *key, int *value);
 const char *mg3d_option_name(int index);
@@ -320,6 +338,7 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  * mg3d_fill_boundary_host : setupBoundaryConditions (mg_3d.h:1147-1239)
  * mg3d_coarse_matrix      : constructCoarseMatrixA (mg_3d.h:147-273), A zeroed by caller
  * mg3d_coarse_matrix_shift: the same for the screened operator (diagonal -(6 + sigma*h^2)/h^2; sigma = 0: the same bytes)
+ * mg3d_coarse_matrix_coef : the same for the variable-coefficient operator (mg3d_ctx_set_coefficient; eps dense N^3)
  * mg3d_lu_factor          : convertToLU_InPlace (gauss_elim.h:9-29)
  * mg3d_lu_solve_host      : NOT provided -- the solve runs on the device only
  * mg3d_l2norm_host        : GetL2NormOfVector (mg_3d.h:783-792)
@@ -329,6 +348,7 @@ double mg3d_bc_func(double x, double y, double z);
 void mg3d_fill_boundary_host(double *v, int N, double h);
 void mg3d_coarse_matrix(double *A, int N, double h);
 void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma);
+void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma); /* host only, A zeroed by caller */
 void mg3d_lu_factor(double *a, int n);
 double mg3d_l2norm_host(const double *d, long n);
 void mg3d_smooth_edges_host(double *u, int N);

@@ -44,6 +44,9 @@ SIGNATURES = {
     "mg3d_ctx_set_lu": (C.c_int, [C.c_void_p, dp]),
     "mg3d_ctx_set_shift": (C.c_int, [C.c_void_p, C.c_double]),
     "mg3d_ctx_get_shift": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_ctx_set_coefficient": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_ctx_has_coefficient": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mg3d_ctx_get_coefficient": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -111,6 +114,7 @@ SIGNATURES = {
     "mg3d_fill_boundary_host": (None, [dp, C.c_int, C.c_double]),
     "mg3d_coarse_matrix": (None, [dp, C.c_int, C.c_double]),
     "mg3d_coarse_matrix_shift": (None, [dp, C.c_int, C.c_double, C.c_double]),
+    "mg3d_coarse_matrix_coef": (None, [dp, C.c_int, C.c_double, dp, C.c_double]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
     "mg3d_smooth_edges_host": (None, [dp, C.c_int]),
@@ -284,6 +288,33 @@ class Solver:
         sigma = C.c_double(0.)
         check(self.L.mg3d_ctx_get_shift(self._h, C.byref(sigma)))
         return sigma.value
+
+    def set_coefficient(self, eps):
+        """mg3d_ctx_set_coefficient: solve  div(eps grad u) - sigma*u = d  with eps > 0 given at every point of the finest
+        level ((N, N, N) or flat float64; coarser levels take it by injection).  None: the constant operator again.
+        Rebuilds a coarse factor of get_details(); drops one given to set_lu."""
+        if eps is None:
+            check(self.L.mg3d_ctx_set_coefficient(self._h, None))
+            return
+        eps = np.asarray(eps)
+        if eps.dtype != np.float64:
+            raise TypeError(f"set_coefficient: need float64, got {eps.dtype}")
+        if eps.size != self.N ** 3 or eps.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"set_coefficient: need shape ({self.N},)*3 or ({self.N ** 3},), got {eps.shape}")
+        check(self.L.mg3d_ctx_set_coefficient(self._h, P(np.ascontiguousarray(eps).reshape(-1))))
+
+    def has_coefficient(self):
+        on = C.c_int(0)
+        check(self.L.mg3d_ctx_has_coefficient(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def coefficient(self, level=None):
+        """eps of a level as the kernels use it, (n, n, n)"""
+        level = self.num_levels - 1 if level is None else level
+        n = self.level_n(level)
+        out = np.empty(n ** 3)
+        check(self.L.mg3d_ctx_get_coefficient(self._h, level, P(out)))
+        return out.reshape(n, n, n)
 
     def setup_boundary_conditions(self, field=MG3D_D, level=None):
         level = self.num_levels - 1 if level is None else level

@@ -33,6 +33,10 @@ struct mg3d_ctx {
     double sigma;
     bool lu_built;
     double lu_h;
+    /* the variable coefficient of div(eps grad u) - sigma u (mg3d_ctx_set_coefficient): eps of every level in the padded
+     * layout (empty: the constant-coefficient operator) and level 0's, dense, for the coarse matrix */
+    std::vector<double *> eps;
+    std::vector<double> eps0;
     double *lu_work;  /* 2n doubles */
     double *partials; /* MG3D_MAX_PARTIALS doubles */
     double *sumsq;    /* device slots for squared norms */
@@ -78,6 +82,9 @@ struct mg3d_ctx {
 
 /* the operator constants of a level of this context (its spacing, the context's sigma) */
 static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
+/* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
+ * passes and residual of mg3d_coef.hip with the plain restriction, prolongation and coarse solve between them */
+static inline bool mg3d_fused(const mg3d_ctx *ctx) { return ctx->fused && ctx->eps.empty(); }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
 /* records a failure text for mg3d_last_error() and returns `code` */

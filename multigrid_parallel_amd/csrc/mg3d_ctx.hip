@@ -172,6 +172,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
             (void)hipFree(l.alt);
     }
     free_lu(ctx);
+    for (double *e : ctx->eps)
+        (void)hipFree(e);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)
@@ -626,7 +628,10 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
+    if (ctx->eps.empty())
+        mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
+    else
+        mg3d_coarse_matrix_coef(A, N0, h_coarse, ctx->eps0.data(), ctx->sigma);
     mg3d_lu_factor(A, (int)n);                             /* mg_3d.h:289 */
     const int rc = mg3d_ctx_set_lu(ctx, A);
     free(A);
@@ -641,6 +646,9 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
  * changes.  Then: a cycle that has run ahead is finished with the operator it started with (mg3d_drop_carry), and a new
  * sigma rebuilds a factor of mg3d_ctx_build_coarse for the spacing it was built with, or drops one installed by
  * mg3d_ctx_set_lu (or mg3d_es_setup): the next cycle returns MG3D_ERR_STATE until a factor is set again. */
+static int operator_changed(mg3d_ctx *ctx);
+static int launch_ok(const char *who);
+static int check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who);
 extern "C" int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma)
 {
     if (!ctx || !(sigma >= 0.) || !isfinite(sigma))
@@ -649,13 +657,20 @@ extern "C" int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma)
     if (sigma == ctx->sigma)
         return MG3D_OK;
     ctx->sigma = sigma == 0. ? 0. : sigma; /* (-0 is stored as +0) */
+    return operator_changed(ctx);
+}
+
+/* the operator of the context changed (sigma, the coefficient): a factor of mg3d_ctx_build_coarse is built again for the
+ * spacing it was built with, one installed by mg3d_ctx_set_lu (or mg3d_es_setup) is dropped */
+static int operator_changed(mg3d_ctx *ctx)
+{
     if (!ctx->have_lu)
         return MG3D_OK;
     if (ctx->lu_built) {
         const int rc = mg3d_ctx_build_coarse(ctx, ctx->lu_h);
         if (rc == MG3D_OK)
             return MG3D_OK;
-        /* no factor of the old operator may survive next to the new sigma */
+        /* no factor of the old operator may survive next to the new one */
         (void)hipStreamSynchronize(ctx->stream);
         free_lu(ctx);
         ctx->lu_built = false;
@@ -672,6 +687,93 @@ extern "C" int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma)
     if (!ctx || !sigma)
         return fail(MG3D_ERR_ARG, "mg3d_ctx_get_shift: NULL argument");
     *sigma = ctx->sigma;
+    return MG3D_OK;
+}
+
+static void free_eps(mg3d_ctx *ctx)
+{
+    for (double *e : ctx->eps)
+        (void)hipFree(e);
+    ctx->eps.clear();
+    ctx->eps0.clear();
+}
+
+/* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_coef.hip) on every level: eps of the finest level
+ * as given, of each coarser one by injection.  The array is checked before anything changes; then, as for a new sigma, a
+ * cycle that has run ahead is finished with the operator it started with and the coarse factor is rebuilt or dropped.
+ * NULL: back to the constant-coefficient operator and its fused schedules. */
+extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
+{
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_coefficient: NULL context");
+    const int L = ctx->L;
+    const Level &top = ctx->lv[L - 1];
+    const int N = top.g.N;
+    const long long n = (long long)N * N * N;
+    if (eps)
+        for (long long p = 0; p < n; p++)
+            if (!(eps[p] > 0.) || !isfinite(eps[p]))
+                return fail(MG3D_ERR_ARG, "mg3d_ctx_set_coefficient: eps[%lld] = %g (every entry must be finite and > 0)", p,
+                            eps[p]);
+    CHK(mg3d_drop_carry(ctx));
+    if (!eps) {
+        if (ctx->eps.empty())
+            return MG3D_OK;
+        HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read eps */
+        free_eps(ctx);
+        return operator_changed(ctx);
+    }
+    if (ctx->eps.empty()) {
+        std::vector<double *> e(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            const hipError_t rc = hipMalloc(&e[l], ctx->lv[l].elems * sizeof(double));
+            if (rc == hipSuccess)
+                continue;
+            for (double *q : e)
+                if (q)
+                    (void)hipFree(q);
+            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_coefficient: hipMalloc: %s",
+                        hipGetErrorString(rc));
+        }
+        ctx->eps = e;
+    }
+    HIPCHK(hipMemcpy2DAsync(ctx->eps[L - 1], top.g.pitch * sizeof(double), eps, N * sizeof(double), N * sizeof(double),
+                            (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
+    for (int l = L - 1; l >= 1; l--)
+        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
+    HIPCHK(hipStreamSynchronize(ctx->stream)); /* (the host array may go once the call returns) */
+    CHK(launch_ok("mg3d_ctx_set_coefficient"));
+    /* level 0's eps on the host for the coarse matrix: the same subsample the injections took */
+    const int N0 = ctx->lv[0].g.N;
+    const long long st = 1LL << (L - 1);
+    ctx->eps0.resize((size_t)N0 * N0 * N0);
+    for (int i = 0; i < N0; i++)
+        for (int j = 0; j < N0; j++)
+            for (int k = 0; k < N0; k++)
+                ctx->eps0[((size_t)i * N0 + j) * N0 + k] = eps[((i * st) * N + j * st) * N + k * st];
+    return operator_changed(ctx);
+}
+
+extern "C" int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on)
+{
+    if (!ctx || !on)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_coefficient: NULL argument");
+    *on = ctx->eps.empty() ? 0 : 1;
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
+{
+    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_coefficient"));
+    if (!host)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_coefficient: NULL host pointer");
+    if (ctx->eps.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_coefficient: no coefficient set");
+    const Level &l = ctx->lv[level];
+    const int N = l.g.N;
+    HIPCHK(hipMemcpy2DAsync(host, N * sizeof(double), ctx->eps[level], l.g.pitch * sizeof(double), N * sizeof(double),
+                            (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return MG3D_OK;
 }
 
@@ -790,7 +892,7 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     Level &l = ctx->lv[level];
     hipStream_t s = ctx->stream;
     const int c1 = post ? 0 : 1; /* pre: red first (mg_3d.h:657); post: black first (mg_3d.h:728) */
-    if (ctx->fused) {
+    if (mg3d_fused(ctx)) {
         int passes = 2 * iters;
         bool done_res = want_res == 0;
         while (passes > 0 || !done_res) {
@@ -844,6 +946,20 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
         return MG3D_OK;
     }
     const LevelOp op = mg3d_op(ctx, l);
+    if (!ctx->eps.empty()) { /* div(eps grad u) - sigma u: the kernels of mg3d_coef.hip, same slots of the kernel timers */
+        const double *e = ctx->eps[level];
+        const double shift = ctx->sigma * op.hSq;
+        for (int it = 0; it < 2 * iters; it++) {
+            StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
+            k_coef_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op.hSq, shift, c1 ^ (it & 1), s);
+        }
+        if (want_res) {
+            StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
+            k_coef_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op.invHsq, shift, want_res == 2 ? l.f[MG3D_R] : nullptr,
+                            ctx->partials, ctx->sumsq + slot, s);
+        }
+        return MG3D_OK;
+    }
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
         k_smooth_color(l.g, l.f[MG3D_U], l.f[MG3D_D], op, c1 ^ (it & 1), s);
@@ -868,7 +984,7 @@ static bool pro_fusable(const mg3d_ctx *ctx, int iters, int want_res, int level)
      * the kernel) that shape has 248 VGPRs and no scratch: the 257^3 level of the 513^3 problem takes 0.12 instead of
      * 0.058 + 0.112 ms, the cycle 2.18 -> 2.13 ms -- fuse_up_max now defaults to every level.  The 2-pass first launch of
      * a split stage takes it almost for free. */
-    if (!ctx->fused || iters < 1)
+    if (!mg3d_fused(ctx) || iters < 1)
         return false;
     const bool sp = split_up_leg(iters, want_res);
     if (!sp && !small)
@@ -925,9 +1041,9 @@ extern "C" int mg3d_smooth_restrict(mg3d_ctx *ctx, int level, int iters)
     if (level < 1 || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_smooth_restrict: bad level/iteration count");
     Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    CHK(enqueue_smooth_residual(ctx, level, 0, iters, 2, ctx->sumsq_slots - 1, ctx->fused ? &lc : nullptr, nullptr, false,
-                                /* need_norm: only without the fused restriction, whose shapes have no norm */ !ctx->fused));
-    k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, ctx->fused);
+    CHK(enqueue_smooth_residual(ctx, level, 0, iters, 2, ctx->sumsq_slots - 1, mg3d_fused(ctx) ? &lc : nullptr, nullptr, false,
+                                /* need_norm: only without the fused restriction, whose shapes have no norm */ !mg3d_fused(ctx)));
+    k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, mg3d_fused(ctx));
     return launch_ok("mg3d_smooth_restrict");
 }
 
@@ -1008,7 +1124,7 @@ bool mg3d_can_legs(const mg3d_ctx *ctx, int q)
         return false;
     const mg3d_ctx *c = ctx;
     /* the conditions of the carried cycles, except their own switch and threshold */
-    return c->fused && !c->keep_r && !c->have_es && c->iters == 2 && q == c->L - 1 && q >= 2 && c->lv[q].g.N >= c->opt.v[MG3D_OPT_LEGS_MIN] &&
+    return mg3d_fused(c) && !c->keep_r && !c->have_es && c->iters == 2 && q == c->L - 1 && q >= 2 && c->lv[q].g.N >= c->opt.v[MG3D_OPT_LEGS_MIN] &&
            c->lv[q].g.N > 65 && (c->lv[q].g.nj & 1) != 0;
 }
 
@@ -1021,7 +1137,7 @@ bool mg3d_can_carry(const mg3d_ctx *ctx, int q)
      * moves the threshold (the tests run 129^3 problems); never at 65^3 and below (the two launches only exist in
      * the four-rows-per-thread shapes) */
     const int n_min = ctx->opt.v[MG3D_OPT_CARRY_MIN];
-    return ctx->fused && !ctx->keep_r && !ctx->have_es && ctx->iters == 2 && q == ctx->L - 1 && q >= 2 &&
+    return mg3d_fused(ctx) && !ctx->keep_r && !ctx->have_es && ctx->iters == 2 && q == ctx->L - 1 && q >= 2 &&
            ctx->lv[q].g.N >= n_min && ctx->lv[q].g.N > 65 && (ctx->lv[q].g.nj & 1) != 0 && split_up_leg(2, 1) &&
            pro_fusable(ctx, 2, 1, q);
 }
@@ -1046,7 +1162,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
     } tick{ctx, q == L - 1};
     /* level 1 below the top of the cycle, small enough for one workgroup's LDS: two launches instead of five */
     const bool no_tiny = !ctx->opt.v[MG3D_OPT_TINY];
-    const bool tiny = !no_tiny && ctx->fused && !ctx->keep_r && q >= 2 && ctx->iters >= 1 && k_tiny_fits(ctx->lv[1].g, ctx->lv[0].g);
+    const bool tiny = !no_tiny && mg3d_fused(ctx) && !ctx->keep_r && q >= 2 && ctx->iters >= 1 && k_tiny_fits(ctx->lv[1].g, ctx->lv[0].g);
     /* ... and the whole bottom of the cycle (level 1 down, the direct solve, level 1 up) as ONE launch when the reduced
      * factor exists (mg3d_tiny.hip, tiny_cycle_kernel); MG3D_NO_TINY_CYCLE=1 keeps the three launches (tests compare) */
     const bool no_cyc = !ctx->opt.v[MG3D_OPT_TINY_CYCLE];
@@ -1154,10 +1270,10 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
         }
         /* :1258-1259: the zero initial guess of a coarser level; with the fused sweep the first launch simply
          * does not read u (and writes every plane of the other buffer), so no memset is needed */
-        const bool zero_in = l < L - 1 && ctx->fused && ctx->iters > 0;
+        const bool zero_in = l < L - 1 && mg3d_fused(ctx) && ctx->iters > 0;
         if (l < L - 1 && !zero_in)
             (void)hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), s);
-        if (ctx->fused) { /* pre-smoother and residual in one pass over the level (:1282 + :1294) */
+        if (mg3d_fused(ctx)) { /* pre-smoother and residual in one pass over the level (:1282 + :1294) */
             {
                 StageScope t(ctx, l, MG3D_ST_SMOOTH1);
                 CHK(enqueue_smooth_residual(ctx, l, 0, ctx->iters, 2, ctx->sumsq_slots - 1,
@@ -1177,7 +1293,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             /* :1310; when the interior was restricted on the fly only the face injection (:879-958) is left, and
              * that only has something new to copy after r of this level or d of the coarser one was written from
              * outside the cycle (faces_dirty) */
-            const bool faces_only = ctx->fused && !ctx->keep_r;
+            const bool faces_only = mg3d_fused(ctx) && !ctx->keep_r;
             if (!faces_only || ctx->faces_dirty[l] || ctx->faces_always[l]) {
                 StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
                 k_restrict(lev.g, lev.f[MG3D_R], ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_D], s, -1, -1, faces_only);
@@ -1288,7 +1404,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                 k_prolong(ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_U], lev.g, lev.f[MG3D_U], s);
             }
         }
-        if (ctx->fused) { /* (prolongation,) post-smoother and residual norm (:1331 + :1341 + :1354) */
+        if (mg3d_fused(ctx)) { /* (prolongation,) post-smoother and residual norm (:1331 + :1341 + :1354) */
             {
                 StageScope t(ctx, l, MG3D_ST_SMOOTH2);
                 /* the norm of a level below the top one is computed and dropped by the reference (:1320
@@ -1308,7 +1424,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
         }
     }
     /* a whole V(2,2) cycle from the top level has ended with its last red pass and nothing runs ahead: see red_in above */
-    if (q == L - 1 && ctx->legs_state == 0 && !ctx->carried && ctx->iters == 2 && ctx->fused)
+    if (q == L - 1 && ctx->legs_state == 0 && !ctx->carried && ctx->iters == 2 && mg3d_fused(ctx))
         ctx->red_tail = true;
     return launch_ok("mg3d_vcycle");
 }

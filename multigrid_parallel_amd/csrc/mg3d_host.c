@@ -67,6 +67,42 @@ void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma)
 
 void mg3d_coarse_matrix(double *A, int N, double h) { mg3d_coarse_matrix_shift(A, N, h, 0.); }
 
+/* The coarsest matrix of the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient): identity
+ * on boundary nodes; on interior node p the face means a = 0.5*(eps[p] + eps[q]) of its six neighbours q (order i-, i+,
+ * j-, j+, k-, k+) divided by h^2 off the diagonal, -dg/h^2 on it, dg = (((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp)
+ * + sigma*h^2 -- the diagonal of the kernels of mg3d_coef.hip.  eps is dense N^3; eps = 1 everywhere gives the bytes of
+ * mg3d_coarse_matrix_shift.  A must be zero on entry. */
+void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma)
+{
+    const long NN = (long)N * N, n = NN * N;
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double shift = sigma * hSq;
+    long p = 0;
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++)
+            for (int k = 0; k < N; k++, p++) {
+                double *row = A + p * n;
+                const int interior = i > 0 && i < N - 1 && j > 0 && j < N - 1 && k > 0 && k < N - 1;
+                if (!interior) {
+                    row[p] = 1.;
+                    continue;
+                }
+                const double e = eps[p];
+                const double a_im = 0.5 * (e + eps[p - NN]), a_ip = 0.5 * (e + eps[p + NN]);
+                const double a_jm = 0.5 * (e + eps[p - N]), a_jp = 0.5 * (e + eps[p + N]);
+                const double a_km = 0.5 * (e + eps[p - 1]), a_kp = 0.5 * (e + eps[p + 1]);
+                const double dg = ((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp + shift;
+                row[p - NN] = a_im * invHsq;
+                row[p + NN] = a_ip * invHsq;
+                row[p - N] = a_jm * invHsq;
+                row[p + N] = a_jp * invHsq;
+                row[p - 1] = a_km * invHsq;
+                row[p + 1] = a_kp * invHsq;
+                row[p] = -(dg * invHsq);
+            }
+}
+
 /* The coarsest operator of the mixed-boundary problem (csrc/mg3d_es.hip): constructCoarseMatrixA (identity rows on
  * the boundary, mg_3d.h:179-185) except that a wall point -- a face point with an interior point in front of it that is
  * not part of a Dirichlet patch -- gets the row  x_wall - x_front = b_wall, the zero-gradient condition the smoother

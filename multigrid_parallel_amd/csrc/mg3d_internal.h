@@ -161,6 +161,14 @@ void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const 
 bool k_tiny_cycle_fits(const Geom &g, const Geom &gc, const LuBand &lu, const LuBand &lin);
 void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double *xc,
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
+/* mg3d_coef.hip: the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient); e is eps of the
+ * level in the padded layout, shift = sigma*hSq.  One colour pass in place; the residual as k_residual (res optional,
+ * partials folded into *sumsq_out); eps of the coarser level by injection at every point */
+void k_coef_color(const Geom &g, double *v, const double *e, const double *d, double hSq, double shift, int color,
+                  hipStream_t s);
+void k_coef_residual(const Geom &g, const double *v, const double *e, const double *d, double invHsq, double shift,
+                     double *res, double *partials, double *sumsq_out, hipStream_t s);
+void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);
