@@ -94,8 +94,9 @@ int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma);
  * mg3d_ctx_build_coarse is rebuilt (one of mg3d_ctx_set_lu / mg3d_es_setup dropped).  Another array replaces eps on every
  * level; NULL returns to the constant-coefficient operator, bit for bit.  With a coefficient every level runs colour
  * passes and residual of their own kernels: the fused schedules and their options (carry, legs, tiny, tiny_cycle,
- * fuse_*, sweep_*) keep their values but do not apply.  mg3d_es_* refuse such a context (MG3D_ERR_STATE); the slab
- * (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms have no coefficient. */
+ * fuse_*, sweep_*) keep their values but do not apply.  mg3d_es_* refuse such a context (MG3D_ERR_STATE).  The slab form
+ * has its own call, mg3d_dist_set_coefficient; the fp32 (mg3d32_*, mg3d32_dist_*), mixed-boundary (mg3d_es_*) and
+ * mg3d_host_* forms and the drop-in mg_3d.h have no coefficient. */
 int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps); /* finest level, dense N^3 host array; NULL: constant operator again */
 int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on);
 int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host); /* the injected eps of a level, dense n^3; MG3D_ERR_STATE without one */
@@ -260,6 +261,18 @@ int mg3d_dist_build_coarse(mg3d_dist *d, double h_coarse);
 /* as mg3d_ctx_set_shift, for every local rank's levels and the replicated coarse levels.  Every rank of a multi-rank job
  * must pass the same sigma (not checked). */
 int mg3d_dist_set_shift(mg3d_dist *d, double sigma);
+/* Variable coefficient on slabs: the semantics of mg3d_ctx_set_coefficient (eps of level l is the injection of the
+ * caller's array, the coarse matrix comes from level 0's, sigma from mg3d_dist_set_shift, the two in either order).  Every
+ * rank passes the FULL finest-level N^3 array and takes its window of every level, halos included.  An entry that is not
+ * finite and > 0 is MG3D_ERR_ARG and changes nothing.  With an RCCL communicator (a multi-rank job, or MG3D_FORCE_COMM=1)
+ * the call runs one all-reduce on it before anything changes: if any rank's array is invalid every rank returns
+ * MG3D_ERR_ARG, if the ranks disagree on whether a coefficient is set every rank returns MG3D_ERR_STATE.  The values of eps
+ * are not compared between ranks, nor is sigma: every rank must pass the same ones.  With a coefficient the cycle walks the
+ * plain exchange plan (policy 0 or 1): no carried cycles, no one-launch legs.  MG3D_ERR_STATE inside a carried cycle.
+ * NULL: the constant operator and its schedules again, as on a fresh handle. */
+int mg3d_dist_set_coefficient(mg3d_dist *d, const double *eps_full); /* finest level, dense N^3 host array; NULL: constant operator again */
+int mg3d_dist_has_coefficient(const mg3d_dist *d, int *on);
+int mg3d_dist_get_coefficient(mg3d_dist *d, int level, double *host_full); /* injected eps of a level; writes the planes each local rank owns, as mg3d_dist_download; MG3D_ERR_STATE without one */
 int mg3d_dist_set_keep_residual(mg3d_dist *d, int keep); /* as mg3d_ctx_set_keep_residual */
 int mg3d_dist_set_option(mg3d_dist *d, const char *key, int value); /* as mg3d_ctx_set_option, for every local rank */
 int mg3d_dist_upload(mg3d_dist *d, int field, int level, const double *host_full);

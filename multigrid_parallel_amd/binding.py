@@ -90,6 +90,9 @@ SIGNATURES = {
     "mg3d32_kernel_time_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), dp]),
     "mg3d_dist_build_coarse": (C.c_int, [C.c_void_p, C.c_double]),
     "mg3d_dist_set_shift": (C.c_int, [C.c_void_p, C.c_double]),
+    "mg3d_dist_set_coefficient": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_dist_has_coefficient": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mg3d_dist_get_coefficient": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_dist_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_dist_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_dist_vcycles": (C.c_int, [C.c_void_p, C.c_int, dp]),
@@ -515,6 +518,34 @@ class DistSolver:
     def set_shift(self, sigma):
         """mg3d_dist_set_shift: the screened operator on every local rank (every rank of a job passes the same sigma)."""
         check(self.L.mg3d_dist_set_shift(self._h, float(sigma)))
+
+    def set_coefficient(self, eps):
+        """mg3d_dist_set_coefficient: div(eps grad u) - sigma*u = d on every local rank.  eps as Solver.set_coefficient:
+        the FULL finest level, (N, N, N) or flat float64; every rank of a job passes the same array.  None: the constant
+        operator and its schedules again."""
+        if eps is None:
+            check(self.L.mg3d_dist_set_coefficient(self._h, None))
+            return
+        eps = np.asarray(eps)
+        if eps.dtype != np.float64:
+            raise TypeError(f"set_coefficient: need float64, got {eps.dtype}")
+        if eps.size != self.N ** 3 or eps.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"set_coefficient: need shape ({self.N},)*3 or ({self.N ** 3},), got {eps.shape}")
+        check(self.L.mg3d_dist_set_coefficient(self._h, P(np.ascontiguousarray(eps).reshape(-1))))
+
+    def has_coefficient(self):
+        on = C.c_int(0)
+        check(self.L.mg3d_dist_has_coefficient(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def coefficient(self, level=None):
+        """eps of a level as the kernels use it, (n, n, n): the planes the local ranks own (every plane of a replicated
+        level, or with the loopback transport); zero elsewhere"""
+        level = self.num_levels - 1 if level is None else level
+        n = self.level_n(level)
+        out = np.zeros(n ** 3)
+        check(self.L.mg3d_dist_get_coefficient(self._h, level, P(out)))
+        return out.reshape(n, n, n)
 
     def setup_test_problem(self):
         """test_mg_3d.c:11-29 on the full grid; every rank takes its slab."""

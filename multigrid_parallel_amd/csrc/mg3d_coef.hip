@@ -15,6 +15,10 @@
  * Layout and colours as mg3d_kernels.hip: idx = plane*i + pitch*j + k; colour (ig0 + i + j + k) & 1, 1 = red.
  * Both stencil kernels give each thread one (j, k) column of `chunk` planes, lanes contiguous in k, and keep the
  * i-1 / i / i+1 values of v and eps of the column in registers (as residual_kernel does for v).
+ *
+ * Windows (the i-slabs of mg3d_dist.hip, conventions of k_sweep): [i_lo, i_hi) are the local planes a launch produces,
+ * clipped to the interior 1 .. ni-2; [acc_lo, acc_hi) the local planes whose diff^2 enters the norm.  -1 / -1: every
+ * plane, the launches of a single-domain level.
  */
 #include "mg3d_internal.h"
 
@@ -57,12 +61,12 @@ __device__ __forceinline__ void coef_stencil(const Geom &g, const double *__rest
  * points are never written. */
 __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ e,
                                                          const double *__restrict__ d, double hSq, double shift,
-                                                         int color, int chunk)
+                                                         int color, int chunk, int i_lo, int i_hi)
 {
     const int k = 1 + blockIdx.x * WAVE + threadIdx.x;
     const int j = 1 + blockIdx.y * 4 + threadIdx.y;
-    const int i0 = 1 + blockIdx.z * chunk;
-    const int i1 = min(i0 + chunk, g.ni - 1);
+    const int i0 = i_lo + blockIdx.z * chunk;
+    const int i1 = min(i0 + chunk, i_hi);
     if (k > g.nk - 2 || j > g.nj - 2)
         return;
     long long p = cidx(g, i0, j, k);
@@ -84,23 +88,34 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
 }
 
 /* chunk of planes per thread: 16 as residual_kernel, doubled until the partial sums fit */
-static int coef_chunk(const Geom &g, int gx, int gy)
+static int coef_chunk(int planes, int gx, int gy)
 {
     int chunk = 16;
-    while ((long long)gx * gy * ((g.ni - 2 + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
+    while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
         chunk *= 2;
     return chunk;
 }
 
-void k_coef_color(const Geom &g, double *v, const double *e, const double *d, double hSq, double shift, int color,
-                  hipStream_t s)
+/* the window [i_lo, i_hi) clipped to the interior planes 1 .. ni-2; false: nothing to produce */
+static bool coef_window(const Geom &g, int &i_lo, int &i_hi)
 {
     if (g.ni < 3 || g.nj < 3 || g.nk < 3)
+        return false;
+    i_lo = i_lo < 1 ? 1 : i_lo;
+    i_hi = (i_hi < 0 || i_hi > g.ni - 1) ? g.ni - 1 : i_hi;
+    return i_hi > i_lo;
+}
+
+void k_coef_color(const Geom &g, double *v, const double *e, const double *d, double hSq, double shift, int color,
+                  hipStream_t s, int i_lo, int i_hi)
+{
+    if (!coef_window(g, i_lo, i_hi))
         return;
     const int gx = (g.nk - 2 + WAVE - 1) / WAVE, gy = (g.nj - 2 + 3) / 4;
-    const int chunk = coef_chunk(g, gx, gy);
-    const int gz = (g.ni - 2 + chunk - 1) / chunk;
-    hipLaunchKernelGGL(coef_color_kernel, dim3(gx, gy, gz), dim3(WAVE, 4, 1), 0, s, g, v, e, d, hSq, shift, color, chunk);
+    const int chunk = coef_chunk(i_hi - i_lo, gx, gy);
+    const int gz = (i_hi - i_lo + chunk - 1) / chunk;
+    hipLaunchKernelGGL(coef_color_kernel, dim3(gx, gy, gz), dim3(WAVE, 4, 1), 0, s, g, v, e, d, hSq, shift, color, chunk,
+                       i_lo, i_hi);
 }
 
 /* ------------------------------------------------------------------ residual
@@ -121,13 +136,14 @@ __device__ __forceinline__ double coef_block_sum(double x, double *lds4)
 __global__ void __launch_bounds__(256) coef_residual_kernel(Geom g, const double *__restrict__ v,
                                                             const double *__restrict__ e, const double *__restrict__ d,
                                                             double invHsq, double shift, double *__restrict__ res,
-                                                            double *__restrict__ partials, int chunk)
+                                                            double *__restrict__ partials, int chunk, int i_lo,
+                                                            int i_hi, int acc_lo, int acc_hi)
 {
     __shared__ double lds4[4];
     const int k = 1 + blockIdx.x * WAVE + threadIdx.x;
     const int j = 1 + blockIdx.y * 4 + threadIdx.y;
-    const int i0 = 1 + blockIdx.z * chunk;
-    const int i1 = min(i0 + chunk, g.ni - 1);
+    const int i0 = i_lo + blockIdx.z * chunk;
+    const int i1 = min(i0 + chunk, i_hi);
     double acc = 0.;
     if (k <= g.nk - 2 && j <= g.nj - 2) {
         long long p = cidx(g, i0, j, k);
@@ -140,7 +156,8 @@ __global__ void __launch_bounds__(256) coef_residual_kernel(Geom g, const double
             const double diff = d[p] - invHsq * (s - dg * vh);
             if (res)
                 res[p] = diff;
-            acc += diff * diff;
+            if (i >= acc_lo && i < acc_hi)
+                acc += diff * diff;
             vb = vh;
             vh = va;
             eb = eh;
@@ -153,17 +170,20 @@ __global__ void __launch_bounds__(256) coef_residual_kernel(Geom g, const double
 }
 
 void k_coef_residual(const Geom &g, const double *v, const double *e, const double *d, double invHsq, double shift,
-                     double *res, double *partials, double *sumsq_out, hipStream_t s)
+                     double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
+                     int acc_hi)
 {
-    if (g.ni < 3 || g.nj < 3 || g.nk < 3) {
+    if (!coef_window(g, i_lo, i_hi)) {
         (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
         return;
     }
+    if (acc_hi < 0)
+        acc_hi = g.ni;
     const int gx = (g.nk - 2 + WAVE - 1) / WAVE, gy = (g.nj - 2 + 3) / 4;
-    const int chunk = coef_chunk(g, gx, gy);
-    const int gz = (g.ni - 2 + chunk - 1) / chunk;
+    const int chunk = coef_chunk(i_hi - i_lo, gx, gy);
+    const int gz = (i_hi - i_lo + chunk - 1) / chunk;
     hipLaunchKernelGGL(coef_residual_kernel, dim3(gx, gy, gz), dim3(WAVE, 4, 1), 0, s, g, v, e, d, invHsq, shift, res,
-                       partials, chunk);
+                       partials, chunk, i_lo, i_hi, acc_lo, acc_hi);
     k_fold(partials, gx * gy * gz, sumsq_out, s);
 }
 

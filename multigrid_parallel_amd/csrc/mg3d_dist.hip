@@ -199,6 +199,7 @@ struct SlabLevel {
     int glo, ghi;         /* owned global planes */
     int own_lo, own_hi;   /* the same in local plane indices */
     int h_lo, h_hi;       /* halo planes below / above (0 at a physical boundary) */
+    double *eps = nullptr; /* mg3d_dist_set_coefficient: eps of this level on every local plane, halos included */
 };
 
 struct RankState {
@@ -254,6 +255,9 @@ struct mg3d_dist {
      * from cycle to cycle (the tests toggle them). */
     bool carry_fixed, carry_on;
     int n_carried;                 /* cycles that ended that way (mg3d_dist_carried_cycles) */
+    /* a variable coefficient is set (mg3d_dist_set_coefficient): eps on every slab level, the replicated contexts have it too;
+     * the cycle is the plain one of mg3d_coef.hip's kernels (dist_enqueue_vcycle, dist_coef_smooth), no carried cycles or legs */
+    bool coef;
     int phase;  /* next phase of the cycle being enqueued */
     int policy; /* bit 0: coarse levels on rank 0 only (MG3D_COARSE_GATHER=1) */
     /* per-phase cost (mg3d_dist_timing_enable): event pairs, resolved at the next synchronisation */
@@ -370,6 +374,8 @@ extern "C" int mg3d_dist_destroy(mg3d_dist *D)
                     (void)hipFree(s.lv.f[k]);
             if (s.lv.alt)
                 (void)hipFree(s.lv.alt);
+            if (s.eps)
+                (void)hipFree(s.eps);
         }
         if (R.gather)
             (void)hipFree(R.gather);
@@ -575,6 +581,7 @@ extern "C" int mg3d_dist_create(int coarse_pts, int num_levels, int smooth_iters
     D->legs_fixed = false;
     D->legs_on = false;
     D->n_legs = 0;
+    D->coef = false;
     if (D->have_comm && nranks > 1) {
         /* every rank must pick the same plan variant: all-reduce MIN of "carried cycles are on here", "one launch per leg is" */
         int mine[2] = {dist_carry_policy(D) ? 1 : 0, dist_legs_policy(D) ? 1 : 0}, *dflag = nullptr;
@@ -700,6 +707,141 @@ extern "C" int mg3d_dist_set_shift(mg3d_dist *D, double sigma)
     D->red_tail = false;
     for (auto &R : D->rs)
         CHK(mg3d_ctx_set_shift(R.coarse, sigma));
+    return MG3D_OK;
+}
+
+static void dist_free_eps(mg3d_dist *D)
+{
+    for (auto &R : D->rs)
+        for (auto &sl : R.dl) {
+            if (sl.eps)
+                (void)hipFree(sl.eps);
+            sl.eps = nullptr;
+        }
+    D->coef = false;
+}
+
+/* The variable-coefficient operator (mg3d_ctx_set_coefficient) on every local rank.  eps_full is the finest level's dense
+ * N^3 array; every level takes its injection, subsampled here on the host, because a coarse slab's halo planes are not
+ * injections of planes the fine slab holds: each rank uploads its window of every distributed level, halos included, and
+ * its replicated context gets level ld-1's (which builds the coarse matrix from level 0's).  With an RCCL communicator the
+ * ranks first agree by one all-reduce: any rank's invalid array fails the call on every rank (MG3D_ERR_ARG), ranks that
+ * disagree on on / off fail it with MG3D_ERR_STATE (a coefficient rank walks the plain plan, a constant one may walk the
+ * legs or carried plan: their exchanges would never match).  The VALUES of eps are not compared between ranks, nor is
+ * sigma.  NULL: the constant operator and its schedules again. */
+extern "C" int mg3d_dist_set_coefficient(mg3d_dist *D, const double *eps)
+{
+    if (!D)
+        return fail(MG3D_ERR_ARG, "mg3d_dist_set_coefficient: NULL handle");
+    if (D->carried || D->legs_pending)
+        return fail(MG3D_ERR_STATE, "mg3d_dist_set_coefficient: inside a carried cycle");
+    D->red_tail = false;
+    const int L = D->L;
+    const long long N = ((long long)(D->c - 1) << (L - 1)) + 1, n = N * N * N;
+    long long bad = -1;
+    if (eps)
+        for (long long p = 0; p < n && bad < 0; p++)
+            if (!(eps[p] > 0.) || !isfinite(eps[p]))
+                bad = p;
+    const int on = eps ? 1 : 0;
+    int all_valid = bad < 0, agree = 1;
+    if (D->have_comm) {
+        /* MIN of {valid here, on here, off here}: every rank valid, every rank on, every rank off */
+        int f[3] = {bad < 0 ? 1 : 0, on, 1 - on}, *dflag = nullptr;
+        bool ok = hipStreamSynchronize(D->comm_stream) == hipSuccess && hipMalloc(&dflag, sizeof(f)) == hipSuccess &&
+                  hipMemcpyAsync(dflag, f, sizeof(f), hipMemcpyHostToDevice, D->stream) == hipSuccess &&
+                  ncclAllReduce(dflag, dflag, 3, ncclInt, ncclMin, D->comm, D->stream) == ncclSuccess &&
+                  hipMemcpyAsync(f, dflag, sizeof(f), hipMemcpyDeviceToHost, D->stream) == hipSuccess &&
+                  hipStreamSynchronize(D->stream) == hipSuccess;
+        if (dflag)
+            (void)hipFree(dflag);
+        if (!ok)
+            return fail(MG3D_ERR_HIP, "mg3d_dist_set_coefficient: the ranks could not agree (all-reduce failed)");
+        all_valid = f[0];
+        agree = f[1] + f[2] == 1;
+    }
+    if (bad >= 0)
+        return fail(MG3D_ERR_ARG, "mg3d_dist_set_coefficient: eps[%lld] = %g (every entry must be finite and > 0)", bad,
+                    eps[bad]);
+    if (!all_valid)
+        return fail(MG3D_ERR_ARG, "mg3d_dist_set_coefficient: another rank's eps has an entry that is not finite and > 0");
+    if (!agree)
+        return fail(MG3D_ERR_STATE, "mg3d_dist_set_coefficient: the ranks disagree on whether a coefficient is set");
+    HIPCHK(hipStreamSynchronize(D->comm_stream));
+    HIPCHK(hipStreamSynchronize(D->stream)); /* launches in flight read eps */
+    if (!eps) {
+        dist_free_eps(D);
+        for (auto &R : D->rs)
+            CHK(mg3d_ctx_set_coefficient(R.coarse, nullptr));
+        return MG3D_OK;
+    }
+    if (!D->coef) {
+        for (auto &R : D->rs)
+            for (auto &sl : R.dl) {
+                const hipError_t rc = hipMalloc(&sl.eps, sl.lv.elems * sizeof(double));
+                if (rc == hipSuccess)
+                    continue;
+                sl.eps = nullptr;
+                dist_free_eps(D);
+                return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP,
+                            "mg3d_dist_set_coefficient: hipMalloc: %s", hipGetErrorString(rc));
+            }
+    }
+    std::vector<double> sub;
+    for (int l = L - 1; l >= D->ld - 1; l--) {
+        const long long Nl = ((long long)(D->c - 1) << l) + 1, st = 1LL << (L - 1 - l);
+        const double *src = eps;
+        if (l < L - 1) { /* the injection: every st-th point of the finest level */
+            sub.resize((size_t)(Nl * Nl * Nl));
+            for (long long i = 0; i < Nl; i++)
+                for (long long j = 0; j < Nl; j++)
+                    for (long long k = 0; k < Nl; k++)
+                        sub[(size_t)((i * Nl + j) * Nl + k)] = eps[((i * st) * N + j * st) * N + k * st];
+            src = sub.data();
+        }
+        if (l < D->ld) {
+            for (auto &R : D->rs)
+                CHK(mg3d_ctx_set_coefficient(R.coarse, src));
+            continue;
+        }
+        for (auto &R : D->rs) {
+            SlabLevel &sl = SL(D, R, l);
+            const Geom &g = sl.lv.g;
+            HIPCHK(hipMemcpy2DAsync(sl.eps, g.pitch * sizeof(double), src + (size_t)g.ig0 * Nl * Nl, Nl * sizeof(double),
+                                    Nl * sizeof(double), (size_t)g.ni * Nl, hipMemcpyHostToDevice, D->stream));
+        }
+        HIPCHK(hipStreamSynchronize(D->stream)); /* before `sub` is rewritten */
+    }
+    D->coef = true;
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_dist_has_coefficient(const mg3d_dist *D, int *on)
+{
+    if (!D || !on)
+        return fail(MG3D_ERR_ARG, "mg3d_dist_has_coefficient: NULL argument");
+    *on = D->coef ? 1 : 0;
+    return MG3D_OK;
+}
+
+/* eps of a level as the kernels use it: the planes each local rank owns into the full host array (replicated levels: all) */
+extern "C" int mg3d_dist_get_coefficient(mg3d_dist *D, int level, double *host)
+{
+    if (!D || !host || level < 0 || level >= D->L)
+        return fail(MG3D_ERR_ARG, "mg3d_dist_get_coefficient: %s", (!D || !host) ? "NULL argument" : "bad level");
+    if (!D->coef)
+        return fail(MG3D_ERR_STATE, "mg3d_dist_get_coefficient: no coefficient set");
+    if (level < D->ld)
+        return mg3d_ctx_get_coefficient(D->rs[0].coarse, level, host);
+    for (auto &R : D->rs) {
+        SlabLevel &sl = SL(D, R, level);
+        const Geom &g = sl.lv.g;
+        const int N = g.N;
+        HIPCHK(hipMemcpy2DAsync(host + (size_t)sl.glo * N * N, N * sizeof(double), sl.eps + g.plane * sl.own_lo,
+                                g.pitch * sizeof(double), N * sizeof(double), (size_t)(sl.own_hi - sl.own_lo) * N,
+                                hipMemcpyDeviceToHost, D->stream));
+    }
+    HIPCHK(hipStreamSynchronize(D->stream));
     return MG3D_OK;
 }
 
@@ -1037,6 +1179,46 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
     return MG3D_OK;
 }
 
+/* One smoothing stage of the variable-coefficient operator (mg3d_coef.hip) on distributed level l for every local rank: the
+ * single-domain schedule (2*nu colour passes in place, then the residual) with windows.  On entry u, d and eps are exact on
+ * every local plane.  Pass t of S = 2*nu produces the owned planes +- (margin + S - t), its dependence cone, and no more:
+ * margin 2 before a stored residual, 1 before the top-level norm.  want_res 2: r on owned +-1, what the restriction reads
+ * (its norm is dropped, :1294); 1: the exchange of planes 2..H of u for the next cycle starts, then the norm of the OWNED
+ * planes into the rank's coarse->sumsq[0] -- it reads u on owned +-1, which the post-smoother made exact and the exchange
+ * does not touch (the halo planes still hold stale values: the norm window keeps them out); 0: passes only. */
+static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
+{
+    hipStream_t s = D->stream;
+    const int S = 2 * D->nu, c1 = post ? 0 : 1, margin = want_res == 2 ? 2 : 1;
+    for (auto &R : D->rs) {
+        SlabLevel &sl = SL(D, R, l);
+        Level &lv = sl.lv;
+        mg3d_ctx *cx = R.coarse;
+        const LevelOp op = mg3d_op(cx, lv);
+        const double shift = cx->sigma * op.hSq;
+        for (int t = 1; t <= S; t++) { /* :1282 / :1341 */
+            const int w = margin + S - t;
+            k_coef_color(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.hSq, shift, c1 ^ ((t - 1) & 1), s, sl.own_lo - w,
+                         sl.own_hi + w);
+        }
+        if (want_res == 2) /* :1294 */
+            k_coef_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.invHsq, shift, lv.f[MG3D_R], cx->partials,
+                            cx->sumsq + cx->sumsq_slots - 1, s, sl.own_lo - 1, sl.own_hi + 1, 0, 0);
+    }
+    if (want_res != 1)
+        return MG3D_OK;
+    CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
+    for (auto &R : D->rs) { /* :1354 */
+        SlabLevel &sl = SL(D, R, l);
+        Level &lv = sl.lv;
+        mg3d_ctx *cx = R.coarse;
+        const LevelOp op = mg3d_op(cx, lv);
+        k_coef_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.invHsq, cx->sigma * op.hSq, nullptr, cx->partials,
+                        cx->sumsq, s, sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
+    }
+    return MG3D_OK;
+}
+
 /* carried cycles on slabs (csrc/mg3d_ctx.hip has the argument): same conditions as the single-domain path */
 static bool dist_carry_policy(mg3d_dist *D) /* what the options say (carry, carry_min), for this level geometry */
 {
@@ -1056,7 +1238,7 @@ static bool dist_legs_policy(mg3d_dist *D)
 
 static bool dist_can_legs(mg3d_dist *D)
 {
-    if (!(D->legs_fixed ? D->legs_on : dist_legs_policy(D)))
+    if (D->coef || !(D->legs_fixed ? D->legs_on : dist_legs_policy(D)))
         return false;
     const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
     return D->nu == 2 && D->H >= 5 && !D->rs[0].coarse->keep_r && g.N > 65 && (g.nj & 1) != 0;
@@ -1064,7 +1246,7 @@ static bool dist_can_legs(mg3d_dist *D)
 
 static bool dist_can_carry(mg3d_dist *D)
 {
-    if (!(D->carry_fixed ? D->carry_on : dist_carry_policy(D)))
+    if (D->coef || !(D->carry_fixed ? D->carry_on : dist_carry_policy(D)))
         return false;
     const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
     return D->nu == 2 && !D->rs[0].coarse->keep_r && g.N > 65 && (g.nj & 1) != 0 && dist_split_up_leg(D, 1, 1);
@@ -1172,12 +1354,18 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
                 lv.f[MG3D_U] = lv.alt;
                 lv.alt = t;
             }
+        } else if (D->coef) {
+            /* variable coefficient: zero guess below the finest level (:1258) on every local plane, passes, r stored */
+            if (l < L - 1)
+                for (auto &R : D->rs)
+                    (void)hipMemsetAsync(SL(D, R, l).lv.f[MG3D_U], 0, SL(D, R, l).lv.elems * sizeof(double), s);
+            CHK(dist_coef_smooth(D, l, 0, 2));
         } else
         /* :1282 + :1294 + :1310 (interior of the coarse rhs on the fly unless r is to be kept) */
         CHK(stage_smooth(D, l, 0, 2, keep ? none.data() : tgt.data(), l < L - 1));
         for (size_t ri = 0; ri < D->rs.size(); ri++) {
             SlabLevel &sl = SL(D, D->rs[ri], l);
-            k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, s, tgt[ri].lo, tgt[ri].hi, !keep);
+            k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, s, tgt[ri].lo, tgt[ri].hi, !keep && !D->coef);
         }
         /* the coarser level starts from its right-hand side at once: only owned planes were produced */
         if (l - 1 < ld)
@@ -1218,8 +1406,8 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
         /* the prolongation rides on the post-smoother's first launch: the top level's split stage, and (option fuse_up_max, as
          * on a single domain) the four-pass launch of a V(2,2) cycle on the levels below it */
         const Geom &gl = SL(D, D->rs[0], l).lv.g;
-        const bool fold = dist_split_up_leg(D, 1, want) ||
-                          (D->nu == 2 && want == 0 && (gl.nj & 1) != 0 && gl.N <= D->rs[0].coarse->opt.v[MG3D_OPT_FUSE_UP_MAX]);
+        const bool fold = !D->coef && (dist_split_up_leg(D, 1, want) ||
+                          (D->nu == 2 && want == 0 && (gl.nj & 1) != 0 && gl.N <= D->rs[0].coarse->opt.v[MG3D_OPT_FUSE_UP_MAX]));
         std::vector<ProlongSource> pro(D->rs.size());
         for (size_t ri = 0; ri < D->rs.size(); ri++) {
             RankState &R = D->rs[ri];
@@ -1277,6 +1465,10 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
             D->n_legs++;
             continue;
         }
+        if (D->coef) {
+            CHK(dist_coef_smooth(D, l, 1, want));
+            continue;
+        }
         CHK(stage_smooth(D, l, 1, want, nullptr, false, l == L - 1, fold ? pro.data() : nullptr, l == L - 1 && carry_out));
         if (l == L - 1 && carry_out) {
             D->carried = true;
@@ -1287,7 +1479,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
         CHK(reduce_norm(D, slot));
     /* a whole V(2,2) cycle has ended the ordinary way: its last pass was red, the exchange behind it leaves all H halo planes
      * of u exact (plain plan: planes 2..H by exchange, plane 1 as the post-smoother made it) */
-    if (!legs_out && !carry_out && D->nu == 2)
+    if (!legs_out && !carry_out && D->nu == 2 && !D->coef)
         D->red_tail = true;
     if (D->phase != (int)(*D->cur)[0].kind.size())
         return fail(MG3D_ERR_STATE, "slab schedule ended after %d of the plan's %d phases", D->phase, (int)(*D->cur)[0].kind.size());

@@ -163,11 +163,13 @@ void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, co
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
 /* mg3d_coef.hip: the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient); e is eps of the
  * level in the padded layout, shift = sigma*hSq.  One colour pass in place; the residual as k_residual (res optional,
- * partials folded into *sumsq_out); eps of the coarser level by injection at every point */
+ * partials folded into *sumsq_out); eps of the coarser level by injection at every point.  Windows as k_sweep's: i_lo /
+ * i_hi the local planes produced, acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
 void k_coef_color(const Geom &g, double *v, const double *e, const double *d, double hSq, double shift, int color,
-                  hipStream_t s);
+                  hipStream_t s, int i_lo = -1, int i_hi = -1);
 void k_coef_residual(const Geom &g, const double *v, const double *e, const double *d, double invHsq, double shift,
-                     double *res, double *partials, double *sumsq_out, hipStream_t s);
+                     double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
+                     int acc_lo = 0, int acc_hi = -1);
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */

@@ -2,6 +2,10 @@
 """The variable-coefficient V-cycle (mg3d_ctx_set_coefficient) against the constant one: python tools/coef_bench.py [c,L ...]
 (default 9,6 and 9,7: 257^3 and 513^3, V(2,2), eps = 1 + 1/2 sin(2 pi x) cos(pi y), sigma = 0).
 
+python tools/coef_bench.py --slabs [--ranks 2,4,8] [c,L ...]: ms per coefficient cycle on i-slabs (mg3d_dist_set_coefficient)
+through the loopback transport -- the single domain, then P virtual ranks on this one GPU.  Loopback serialises every rank
+on one device: the numbers measure the halo planes' extra work and the extra launches, not multi-GPU speed.
+
 Per size: ms per cycle with and without the coefficient (mg3d_vcycles, best of three timed runs); the finest level's
 colour pass and residual as single launches (mg3d_smooth / mg3d_residual, HIP events around them on the library's
 stream); and inside the cycle, the finest level's kernel timers (MG3D_K_COLOUR_PASS, MG3D_K_RESIDUAL).  Bandwidth is
@@ -54,8 +58,40 @@ def tbs(bytes_, secs):
     return bytes_ / secs / 1e12
 
 
+def slab_table(sizes, ranks):
+    """ms per coefficient cycle: single domain, then loopback P ranks; the norms must agree with the single domain's"""
+    print(f"{'size':>6s} {'single':>9s} " + " ".join(f"{'P=' + str(p):>9s}" for p in ranks) + "   (ms per V(2,2) cycle, eps set)")
+    for c, L in sizes:
+        N = (c - 1) * (1 << (L - 1)) + 1
+        eps = smooth_eps(N)
+        with M.Solver(c, L, 2) as s:
+            s.set_coefficient(eps)
+            s.setup_test_problem()
+            row = [cycle_ms(s)]
+            s.setup_test_problem()
+            ref = s.vcycles(4)
+        for P in ranks:
+            with M.DistSolver(c, L, 2, nranks=P) as d:
+                d.set_coefficient(eps)
+                d.setup_test_problem()
+                got = d.vcycles(4)
+                assert np.allclose(got, ref, rtol=1e-11, atol=0), (P, got, ref)
+                row.append(cycle_ms(d))
+        print(f"{N:>4d}^3 " + " ".join(f"{t:9.3f}" for t in row), flush=True)
+
+
 def main():
-    sizes = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]] or [(9, 6), (9, 7)]
+    argv = sys.argv[1:]
+    if "--slabs" in argv:
+        argv.remove("--slabs")
+        ranks = [2, 4, 8]
+        if "--ranks" in argv:
+            i = argv.index("--ranks")
+            ranks = [int(v) for v in argv[i + 1].split(",")]
+            del argv[i:i + 2]
+        slab_table([tuple(int(v) for v in a.split(",")) for a in argv] or [(9, 6), (9, 7)], ranks)
+        return
+    sizes = [tuple(int(v) for v in a.split(",")) for a in argv] or [(9, 6), (9, 7)]
     for c, L in sizes:
         with M.Solver(c, L, 2) as s:
             N, top = s.N, L - 1
