@@ -423,3 +423,158 @@ double orc_run_problem(int c, int L, int iters, int cycles, int coarse_h_mode, d
     free_levels(r, L);
     return t1 - t0;
 }
+
+/* ---- the screened operator  Delta_h u - sigma u = d  (the product's mg3d_ctx_set_shift).  Twins of the functions above
+ * with the diagonal dg = 6 + sigma*hSq in place of the 6: smoother sixth*(sum - hSq*d) with sixth = 1./dg, residual
+ * d - invHsq*(sum - dg*v), coarse matrix diagonal -(dg*invHsq).  At sigma = 0 every constant is the one above (6 + 0*hSq
+ * = 6), so each twin returns the bits of its original; tests/test_screened_oracle.py pins both. */
+
+void orc_smooth_color_shift(double *v, const double *d, int N, double h, double sigma, int color)
+{
+    const double hSq = h * h;
+    const double dg = 6. + sigma * hSq;
+    const double sixth = 1. / dg;
+    const long NN = (long)N * N;
+#pragma omp parallel for schedule(static)
+    for (int i = 1; i < N - 1; i++)
+        for (int j = 1; j < N - 1; j++) {
+            const int k0 = 1 + (i + j + (color ? 0 : 1)) % 2;
+            for (int k = k0; k < N - 1; k += 2) {
+                const long p = IDX(N, i, j, k);
+                v[p] = sixth * (v[p - NN] + v[p + NN] + v[p - N] + v[p + N] + v[p - 1] + v[p + 1] - hSq * d[p]);
+            }
+        }
+}
+
+void orc_pre_smooth_shift(double *v, const double *d, int N, double h, double sigma, int iters)
+{
+    for (int s = 0; s < iters; s++) {
+        orc_smooth_color_shift(v, d, N, h, sigma, 1);
+        orc_smooth_color_shift(v, d, N, h, sigma, 0);
+    }
+}
+
+void orc_post_smooth_shift(double *v, const double *d, int N, double h, double sigma, int iters)
+{
+    for (int s = 0; s < iters; s++) {
+        orc_smooth_color_shift(v, d, N, h, sigma, 0);
+        orc_smooth_color_shift(v, d, N, h, sigma, 1);
+    }
+}
+
+double orc_residual_shift(const double *v, const double *d, int N, double h, double sigma, double *res)
+{
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double dg = 6. + sigma * hSq;
+    const long NN = (long)N * N;
+    const int nt = omp_get_max_threads();
+    double *part = (double *)calloc((size_t)nt, sizeof(double));
+#pragma omp parallel
+    {
+        double ret = 0.;
+#pragma omp for schedule(static)
+        for (int i = 1; i < N - 1; i++)
+            for (int j = 1; j < N - 1; j++)
+                for (int k = 1; k < N - 1; k++) {
+                    const long p = IDX(N, i, j, k);
+                    const double diff =
+                        d[p] - invHsq * (v[p - NN] + v[p + NN] + v[p - N] + v[p + N] + v[p - 1] + v[p + 1] - dg * v[p]);
+                    if (res)
+                        res[p] = diff;
+                    ret += diff * diff;
+                }
+        part[omp_get_thread_num()] = ret;
+    }
+    double tot = 0.;
+    for (int t = 0; t < nt; t++)
+        tot += part[t];
+    free(part);
+    return sqrt(tot);
+}
+
+void orc_coarse_matrix_shift(double *A, int N, double h, double sigma)
+{
+    const long n = (long)N * N * N;
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double dg = 6. + sigma * hSq;
+    orc_coarse_matrix(A, N, h);
+    for (int i = 1; i < N - 1; i++)
+        for (int j = 1; j < N - 1; j++)
+            for (int k = 1; k < N - 1; k++) {
+                const long row = IDX(N, i, j, k);
+                A[row * n + row] = -(dg * invHsq);
+            }
+}
+
+double orc_vcycle_shift(double **u, double **f, double **res, double h, double sigma, int q, int numLevels, int iters,
+                        int N, const double *LU)
+{
+    double *v = u[q];
+    if (q < numLevels - 1)
+        memset(v, 0, sizeof(double) * (size_t)N * N * N);
+    if (q == 0) {
+        orc_lu_solve(LU, N * N * N, f[0], v);
+        return 0.;
+    }
+    orc_pre_smooth_shift(v, f[q], N, h, sigma, iters);
+    orc_residual_shift(v, f[q], N, h, sigma, res[q]);
+    const int Nc = (N + 1) / 2;
+    orc_restrict(res[q], N, f[q - 1], Nc);
+    orc_vcycle_shift(u, f, res, 2 * h, sigma, q - 1, numLevels, iters, Nc, LU);
+    orc_prolong(u[q - 1], Nc, v, N);
+    orc_post_smooth_shift(v, f[q], N, h, sigma, iters);
+    return orc_residual_shift(v, f[q], N, h, sigma, NULL);
+}
+
+void orc_fmg_initialize_shift(double **u, double **d, double **r, int c, int numLevels, int iters, double sigma,
+                              double grid_length, const double *LU)
+{
+    int N = c;
+    double h = grid_length / (c - 1);
+    orc_fill_boundary(u[0], N, h);
+    orc_lu_solve(LU, N * N * N, d[0], u[0]);
+    for (int l = 1; l < numLevels; l++) {
+        const int Nc = N;
+        N = 2 * N - 1;
+        h = h * 0.5;
+        orc_prolong(u[l - 1], Nc, u[l], N);
+        orc_fill_boundary(u[l], N, h);
+        memset(u[l - 1], 0, sizeof(double) * (size_t)Nc * Nc * Nc);
+        orc_vcycle_shift(u, d, r, h, sigma, l, numLevels, iters, N, LU);
+    }
+}
+
+double orc_run_problem_shift(int c, int L, int iters, double sigma, int cycles, double *norms, double *u_out,
+                             double *init_norm)
+{
+    const int N = (c - 1) * (1 << (L - 1)) + 1;
+    const double h = 1.0 / (N - 1);
+    double **u = alloc_levels(c, L), **d = alloc_levels(c, L), **r = alloc_levels(c, L);
+    const size_t n0 = (size_t)c * c * c;
+    double *A = (double *)calloc(n0 * n0, sizeof(double));
+    orc_coarse_matrix_shift(A, c, h * (1 << (L - 1)), sigma);
+    if (c > 9)
+        orc_lu_factor_banded(A, (int)n0);
+    else
+        orc_lu_factor(A, (int)n0);
+    orc_fill_boundary(d[L - 1], N, h);
+    orc_fill_boundary(u[L - 1], N, h);
+    if (init_norm)
+        *init_norm = orc_l2norm(d[L - 1], (long)N * N * N);
+    const double t0 = omp_get_wtime();
+    for (int it = 0; it < cycles; it++) {
+        const double nrm = orc_vcycle_shift(u, d, r, h, sigma, L - 1, L, iters, N, A);
+        if (norms)
+            norms[it] = nrm;
+    }
+    const double t1 = omp_get_wtime();
+    if (u_out)
+        memcpy(u_out, u[L - 1], sizeof(double) * (size_t)N * N * N);
+    free(A);
+    free_levels(u, L);
+    free_levels(d, L);
+    free_levels(r, L);
+    return t1 - t0;
+}

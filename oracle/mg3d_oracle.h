@@ -81,6 +81,23 @@ void orc_fmg_initialize(double **u, double **d, double **r, int c, int numLevels
 double orc_run_problem(int c, int L, int iters, int cycles, int coarse_h_mode,
                        double *norms, double *u_out, double *init_norm);
 
+/* The screened operator  Delta_h u - sigma u = d  (sigma >= 0): twins of the functions above with dg = 6 + sigma*h^2 in
+ * place of the 6 (smoother sixth*(sum - hSq*d), sixth = 1./dg; residual d - invHsq*(sum - dg*v); coarse diagonal
+ * -(dg*invHsq)).  At sigma = 0 they return the bits of their originals.  The product's arithmetic, not the reference's:
+ * the reference has no shift. */
+void orc_smooth_color_shift(double *v, const double *d, int N, double h, double sigma, int color);
+void orc_pre_smooth_shift(double *v, const double *d, int N, double h, double sigma, int iters);
+void orc_post_smooth_shift(double *v, const double *d, int N, double h, double sigma, int iters);
+double orc_residual_shift(const double *v, const double *d, int N, double h, double sigma, double *res);
+void orc_coarse_matrix_shift(double *A, int N, double h, double sigma);
+double orc_vcycle_shift(double **u, double **f, double **res, double h, double sigma, int q, int numLevels, int iters,
+                        int N, const double *LU);
+void orc_fmg_initialize_shift(double **u, double **d, double **r, int c, int numLevels, int iters, double sigma,
+                              double grid_length, const double *LU);
+/* orc_run_problem (coarse_h_mode 0) with the screened operator */
+double orc_run_problem_shift(int c, int L, int iters, double sigma, int cycles, double *norms, double *u_out,
+                             double *init_norm);
+
 int orc_max_threads(void);
 void orc_set_threads(int n);
 

@@ -49,6 +49,18 @@ def lib():
         L.orc_fmg_initialize.argtypes = [C.POINTER(dp)] * 3 + [C.c_int, C.c_int, C.c_int, C.c_double, dp]
         L.orc_run_problem.restype = C.c_double
         L.orc_run_problem.argtypes = [C.c_int] * 5 + [dp, dp, dp]
+        # the screened operator (sigma-taking twins; pinned to _screened_ref and, at sigma = 0, to the functions above)
+        L.orc_smooth_color_shift.argtypes = [dp, dp, C.c_int, C.c_double, C.c_double, C.c_int]
+        L.orc_pre_smooth_shift.argtypes = [dp, dp, C.c_int, C.c_double, C.c_double, C.c_int]
+        L.orc_post_smooth_shift.argtypes = [dp, dp, C.c_int, C.c_double, C.c_double, C.c_int]
+        L.orc_residual_shift.restype = C.c_double
+        L.orc_residual_shift.argtypes = [dp, dp, C.c_int, C.c_double, C.c_double, dp]
+        L.orc_coarse_matrix_shift.argtypes = [dp, C.c_int, C.c_double, C.c_double]
+        L.orc_vcycle_shift.restype = C.c_double
+        L.orc_vcycle_shift.argtypes = [C.POINTER(dp)] * 3 + [C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, dp]
+        L.orc_fmg_initialize_shift.argtypes = [C.POINTER(dp)] * 3 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, dp]
+        L.orc_run_problem_shift.restype = C.c_double
+        L.orc_run_problem_shift.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, dp, dp, dp]
         # single precision / Jacobi / F-cycle variant (oracle/mg3d_oracle_f32.c, parity unpinned)
         L.orc32_fill_boundary.argtypes = [fp, C.c_int, C.c_double]
         L.orc32_jacobi.argtypes = [fp, fp, fp, C.c_int, C.c_float, C.c_float]
@@ -100,6 +112,16 @@ def run_problem(c, L, nu, cycles, mode=0, want_u=True):
     u = np.zeros(N ** 3) if want_u else None
     init = C.c_double(0)
     secs = lib().orc_run_problem(c, L, nu, cycles, mode, P(norms), P(u) if want_u else None, C.byref(init))
+    return norms, u, init.value, secs
+
+
+def run_problem_shift(c, L, nu, sigma, cycles, want_u=True):
+    """orc_run_problem_shift: run_problem (mode 0) with the screened operator"""
+    N = level_sizes(c, L)[-1]
+    norms = np.zeros(cycles)
+    u = np.zeros(N ** 3) if want_u else None
+    init = C.c_double(0)
+    secs = lib().orc_run_problem_shift(c, L, nu, sigma, cycles, P(norms), P(u) if want_u else None, C.byref(init))
     return norms, u, init.value, secs
 
 
