@@ -101,6 +101,26 @@ int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps); /* finest level,
 int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on);
 int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host); /* the injected eps of a level, dense n^3; MG3D_ERR_STATE without one */
 
+/* Periodic boundaries per axis.  axes is a mask of MG3D_PERIODIC_I / _J / _K (any of 0..7); 0 is the Dirichlet operator
+ * of every face, bit for bit and with the fused schedules.  A level keeps its N points per side and its layouts; on a
+ * periodic axis index N-1 is the DUPLICATE of index 0, the unique points are 0 .. N-2 and face points there are unknowns
+ * (non-periodic axes keep their Dirichlet faces).  No kernel reads a duplicate of u, d, r or eps: stencils reach across
+ * the wrap to the unique point, and whatever writes a unique point on a periodic face writes its duplicates too, so a
+ * downloaded u (or r with keep_residual) is periodic-consistent.  The restriction fully weights the periodic faces, the
+ * coarse matrix is mg3d_coarse_matrix_periodic, the residual norm counts every unique point once.  All three axes
+ * periodic with sigma = 0 is singular (constants are in the kernel): the coarse matrix pins unique point (0,0,0) of level
+ * 0 to 0, u is determined up to a constant, and f must have zero mean over the unique points -- the library projects
+ * neither f nor u, and the residual stalls at that mean otherwise.  A mask outside 0..7, or a nonzero one when c - 1 is
+ * odd or below 4, is MG3D_ERR_ARG and changes nothing; otherwise, as for mg3d_ctx_set_shift, a cycle that has run ahead
+ * is finished first and a factor of mg3d_ctx_build_coarse is rebuilt (one of mg3d_ctx_set_lu / mg3d_es_setup dropped);
+ * the same mask again changes nothing.  With a periodic axis the fused schedules and their options do not apply (values
+ * kept), and mg3d_es_*, mg3d_fmg_initialize and mg3d_fill_boundary return MG3D_ERR_STATE.  The slab (mg3d_dist_*), fp32
+ * (mg3d32_*) and mg3d_host_* forms have no periodic mode.  mg3d_ctx_set_coefficient on a periodic context neither checks
+ * nor keeps eps at the duplicates: their sources are copied over them. */
+enum { MG3D_PERIODIC_I = 1, MG3D_PERIODIC_J = 2, MG3D_PERIODIC_K = 4 };
+int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes);
+int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes);
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -352,6 +372,7 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  * mg3d_coarse_matrix      : constructCoarseMatrixA (mg_3d.h:147-273), A zeroed by caller
  * mg3d_coarse_matrix_shift: the same for the screened operator (diagonal -(6 + sigma*h^2)/h^2; sigma = 0: the same bytes)
  * mg3d_coarse_matrix_coef : the same for the variable-coefficient operator (mg3d_ctx_set_coefficient; eps dense N^3)
+ * mg3d_coarse_matrix_periodic: the same with periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
  * mg3d_lu_factor          : convertToLU_InPlace (gauss_elim.h:9-29)
  * mg3d_lu_solve_host      : NOT provided -- the solve runs on the device only
  * mg3d_l2norm_host        : GetL2NormOfVector (mg_3d.h:783-792)
@@ -362,6 +383,8 @@ void mg3d_fill_boundary_host(double *v, int N, double h);
 void mg3d_coarse_matrix(double *A, int N, double h);
 void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma);
 void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma); /* host only, A zeroed by caller */
+void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
+                                 int axes); /* host only, A zeroed by caller; axes = 0: _shift / _coef */
 void mg3d_lu_factor(double *a, int n);
 double mg3d_l2norm_host(const double *d, long n);
 void mg3d_smooth_edges_host(double *u, int N);

@@ -11,6 +11,7 @@ dp = C.POINTER(C.c_double)
 fp = C.POINTER(C.c_float)
 
 MG3D_U, MG3D_D, MG3D_R = 0, 1, 2
+MG3D_PERIODIC_I, MG3D_PERIODIC_J, MG3D_PERIODIC_K = 1, 2, 4
 STAGES = 7
 _ERR = {1: "bad argument", 2: "no device", 3: "HIP error", 4: "allocation failed", 5: "bad state"}
 
@@ -47,6 +48,8 @@ SIGNATURES = {
     "mg3d_ctx_set_coefficient": (C.c_int, [C.c_void_p, dp]),
     "mg3d_ctx_has_coefficient": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mg3d_ctx_get_coefficient": (C.c_int, [C.c_void_p, C.c_int, dp]),
+    "mg3d_ctx_set_periodic": (C.c_int, [C.c_void_p, C.c_int]),
+    "mg3d_ctx_get_periodic": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mg3d_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -118,6 +121,7 @@ SIGNATURES = {
     "mg3d_coarse_matrix": (None, [dp, C.c_int, C.c_double]),
     "mg3d_coarse_matrix_shift": (None, [dp, C.c_int, C.c_double, C.c_double]),
     "mg3d_coarse_matrix_coef": (None, [dp, C.c_int, C.c_double, dp, C.c_double]),
+    "mg3d_coarse_matrix_periodic": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
     "mg3d_smooth_edges_host": (None, [dp, C.c_int]),
@@ -318,6 +322,29 @@ class Solver:
         out = np.empty(n ** 3)
         check(self.L.mg3d_ctx_get_coefficient(self._h, level, P(out)))
         return out.reshape(n, n, n)
+
+    def set_periodic(self, axes):
+        """mg3d_ctx_set_periodic: periodic boundaries on the axes given as a mask (MG3D_PERIODIC_I = 1, _J = 2, _K = 4) or
+        as an iterable of axis indices 0, 1, 2; 0 or () gives Dirichlet faces everywhere again.  On a periodic axis index
+        N-1 duplicates index 0: it is never read and always written as a copy.  With all three axes periodic and sigma = 0
+        the operator is singular: u is fixed only up to a constant (the coarse solve pins point (0,0,0) of level 0) and d
+        must have zero mean over the unique points, else the residual stalls at that mean -- nothing projects d or u.
+        Rebuilds a coarse factor of get_details(); drops one given to set_lu."""
+        if not isinstance(axes, (int, np.integer)):
+            mask = 0
+            for a in axes:
+                if a not in (0, 1, 2):
+                    raise ValueError(f"set_periodic: axis {a!r} (need 0, 1 or 2)")
+                mask |= 1 << int(a)
+            axes = mask
+        check(self.L.mg3d_ctx_set_periodic(self._h, int(axes)))
+
+    @property
+    def periodic(self):
+        """the mask of periodic axes"""
+        v = C.c_int(0)
+        check(self.L.mg3d_ctx_get_periodic(self._h, C.byref(v)))
+        return v.value
 
     def setup_boundary_conditions(self, field=MG3D_D, level=None):
         level = self.num_levels - 1 if level is None else level

@@ -37,6 +37,10 @@ struct mg3d_ctx {
      * layout (empty: the constant-coefficient operator) and level 0's, dense, for the coarse matrix */
     std::vector<double *> eps;
     std::vector<double> eps0;
+    /* periodic axes (mg3d_ctx_set_periodic; MG3D_PERIODIC_* mask, 0: Dirichlet faces everywhere) and the padded level-0
+     * right-hand side of the direct solve that mg3d_periodic.hip builds from d (allocated with the first nonzero mask) */
+    int periodic;
+    double *per_b;
     double *lu_work;  /* 2n doubles */
     double *partials; /* MG3D_MAX_PARTIALS doubles */
     double *sumsq;    /* device slots for squared norms */
@@ -83,8 +87,9 @@ struct mg3d_ctx {
 /* the operator constants of a level of this context (its spacing, the context's sigma) */
 static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
- * passes and residual of mg3d_coef.hip with the plain restriction, prolongation and coarse solve between them */
-static inline bool mg3d_fused(const mg3d_ctx *ctx) { return ctx->fused && ctx->eps.empty(); }
+ * passes and residual of mg3d_coef.hip with the plain restriction, prolongation and coarse solve between them, nor with
+ * a periodic axis, whose levels run the kernels of mg3d_periodic.hip */
+static inline bool mg3d_fused(const mg3d_ctx *ctx) { return ctx->fused && ctx->eps.empty() && ctx->periodic == 0; }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
 /* records a failure text for mg3d_last_error() and returns `code` */

@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 /* ------------------------------------------------------------------ errors */
@@ -174,6 +175,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
     free_lu(ctx);
     for (double *e : ctx->eps)
         (void)hipFree(e);
+    if (ctx->per_b)
+        (void)hipFree(ctx->per_b);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)
@@ -264,6 +267,8 @@ static mg3d_ctx *ctx_new(int L, int iters)
     ctx->sigma = 0.;
     ctx->lu_built = false;
     ctx->lu_h = 0.;
+    ctx->periodic = 0;
+    ctx->per_b = nullptr;
     memset(&ctx->lu, 0, sizeof ctx->lu);
     memset(&ctx->lu_in, 0, sizeof ctx->lu_in);
     ctx->lu_work = nullptr;
@@ -628,7 +633,9 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    if (ctx->eps.empty())
+    if (ctx->periodic)
+        mg3d_coarse_matrix_periodic(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic);
+    else if (ctx->eps.empty())
         mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
     else
         mg3d_coarse_matrix_coef(A, N0, h_coarse, ctx->eps0.data(), ctx->sigma);
@@ -710,9 +717,14 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
     const Level &top = ctx->lv[L - 1];
     const int N = top.g.N;
     const long long n = (long long)N * N * N;
+    /* with periodic axes the duplicates are not read: neither checked nor kept (their sources are copied over them) */
+    const int ax = ctx->periodic;
+    auto dup = [&](long long q) {
+        return ((ax & 1) && q / ((long long)N * N) == N - 1) || ((ax & 2) && (q / N) % N == N - 1) || ((ax & 4) && q % N == N - 1);
+    };
     if (eps)
         for (long long p = 0; p < n; p++)
-            if (!(eps[p] > 0.) || !isfinite(eps[p]))
+            if ((!(eps[p] > 0.) || !isfinite(eps[p])) && !(ax && dup(p)))
                 return fail(MG3D_ERR_ARG, "mg3d_ctx_set_coefficient: eps[%lld] = %g (every entry must be finite and > 0)", p,
                             eps[p]);
     CHK(mg3d_drop_carry(ctx));
@@ -739,6 +751,7 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
     }
     HIPCHK(hipMemcpy2DAsync(ctx->eps[L - 1], top.g.pitch * sizeof(double), eps, N * sizeof(double), N * sizeof(double),
                             (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
+    k_per_refresh(top.g, ctx->eps[L - 1], ax, ctx->stream);
     for (int l = L - 1; l >= 1; l--)
         k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
     HIPCHK(hipStreamSynchronize(ctx->stream)); /* (the host array may go once the call returns) */
@@ -747,10 +760,12 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
     const int N0 = ctx->lv[0].g.N;
     const long long st = 1LL << (L - 1);
     ctx->eps0.resize((size_t)N0 * N0 * N0);
+    auto src = [&](int x, int bit) { return ((ax & bit) && x == N - 1) ? 0 : x; }; /* (a duplicate's source) */
     for (int i = 0; i < N0; i++)
         for (int j = 0; j < N0; j++)
             for (int k = 0; k < N0; k++)
-                ctx->eps0[((size_t)i * N0 + j) * N0 + k] = eps[((i * st) * N + j * st) * N + k * st];
+                ctx->eps0[((size_t)i * N0 + j) * N0 + k] =
+                    eps[((long long)src(i * st, 1) * N + src(j * st, 2)) * N + src(k * st, 4)];
     return operator_changed(ctx);
 }
 
@@ -774,6 +789,46 @@ extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
     HIPCHK(hipMemcpy2DAsync(host, N * sizeof(double), ctx->eps[level], l.g.pitch * sizeof(double), N * sizeof(double),
                             (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MG3D_OK;
+}
+
+/* Periodic axes (mg3d_periodic.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
+ * changes -- a mask outside 0..7, or a nonzero one on a hierarchy whose coarsest level has fewer than 4 or an odd number
+ * of unique points per side, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that has run ahead is finished with the
+ * operator it started with and the coarse factor is rebuilt (mg3d_ctx_build_coarse) or dropped.  0: Dirichlet faces
+ * everywhere again, the fused schedules included. */
+extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
+{
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: NULL context");
+    if (axes < 0 || axes > 7)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: axes = %d (a mask of MG3D_PERIODIC_I | _J | _K, 0..7)", axes);
+    const int N0 = ctx->lv[0].g.N;
+    if (axes && ((N0 - 1) % 2 != 0 || N0 - 1 < 4))
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: the coarsest level has %d points per side (c - 1 must be even and >= 4)",
+                    N0);
+    CHK(mg3d_drop_carry(ctx));
+    if (axes == ctx->periodic)
+        return MG3D_OK;
+    if (axes && !ctx->per_b) {
+        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
+        if (rc != hipSuccess) {
+            ctx->per_b = nullptr;
+            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_periodic: hipMalloc: %s",
+                        hipGetErrorString(rc));
+        }
+    }
+    ctx->periodic = axes;
+    /* the coarse faces that the periodic restriction weighted are injections again (and vice versa): redo them */
+    std::fill(ctx->faces_dirty.begin(), ctx->faces_dirty.end(), 1);
+    return operator_changed(ctx);
+}
+
+extern "C" int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes)
+{
+    if (!ctx || !axes)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_periodic: NULL argument");
+    *axes = ctx->periodic;
     return MG3D_OK;
 }
 
@@ -946,6 +1001,20 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
         return MG3D_OK;
     }
     const LevelOp op = mg3d_op(ctx, l);
+    if (ctx->periodic) { /* periodic axes: the kernels of mg3d_periodic.hip (constant or eps), same timer slots */
+        const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
+        const double shift = ctx->sigma * op.hSq;
+        for (int it = 0; it < 2 * iters; it++) {
+            StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
+            k_per_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, shift, c1 ^ (it & 1), ctx->periodic, s);
+        }
+        if (want_res) {
+            StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
+            k_per_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, shift, ctx->periodic, want_res == 2 ? l.f[MG3D_R] : nullptr,
+                           ctx->partials, ctx->sumsq + slot, s);
+        }
+        return MG3D_OK;
+    }
     if (!ctx->eps.empty()) { /* div(eps grad u) - sigma u: the kernels of mg3d_coef.hip, same slots of the kernel timers */
         const double *e = ctx->eps[level];
         const double shift = ctx->sigma * op.hSq;
@@ -994,6 +1063,40 @@ static bool pro_fusable(const mg3d_ctx *ctx, int iters, int want_res, int level)
     return !first_has_res;
 }
 
+/* the unfused grid transfers and the direct solve: periodic forms when an axis is periodic */
+static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
+{
+    const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
+    if (ctx->periodic)
+        k_per_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->periodic, ctx->stream);
+    else
+        k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, faces_only);
+}
+
+static void enqueue_prolong(mg3d_ctx *ctx, int level)
+{
+    const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
+    if (ctx->periodic)
+        k_per_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], ctx->periodic, ctx->stream);
+    else
+        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], ctx->stream);
+}
+
+/* periodic: the factor of mg3d_coarse_matrix_periodic solves for b = d with 0 in the identity rows of the duplicates and,
+ * all three axes periodic with sigma = 0, of the pinned point (0,0,0); the duplicates of x are then copied from their
+ * sources */
+static void enqueue_coarse_solve(mg3d_ctx *ctx)
+{
+    Level &l0 = ctx->lv[0];
+    if (ctx->periodic) {
+        k_per_coarse_rhs(l0.g, l0.f[MG3D_D], ctx->per_b, ctx->periodic, ctx->periodic == 7 && ctx->sigma == 0., ctx->stream);
+        k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
+        k_per_refresh(l0.g, l0.f[MG3D_U], ctx->periodic, ctx->stream);
+        return;
+    }
+    k_lu_solve(ctx->lu, ctx->lu_in, l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu_work, ctx->stream);
+}
+
 static int enqueue_smooth(mg3d_ctx *ctx, int level, int post, int iters)
 {
     return enqueue_smooth_residual(ctx, level, post, iters, 0, 0);
@@ -1040,10 +1143,10 @@ extern "C" int mg3d_smooth_restrict(mg3d_ctx *ctx, int level, int iters)
     CHK(check_field_level(ctx, 0, level, "mg3d_smooth_restrict"));
     if (level < 1 || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_smooth_restrict: bad level/iteration count");
-    Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
+    Level &lc = ctx->lv[level - 1];
     CHK(enqueue_smooth_residual(ctx, level, 0, iters, 2, ctx->sumsq_slots - 1, mg3d_fused(ctx) ? &lc : nullptr, nullptr, false,
                                 /* need_norm: only without the fused restriction, whose shapes have no norm */ !mg3d_fused(ctx)));
-    k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, mg3d_fused(ctx));
+    enqueue_restrict(ctx, level, mg3d_fused(ctx));
     return launch_ok("mg3d_smooth_restrict");
 }
 
@@ -1053,8 +1156,7 @@ extern "C" int mg3d_restrict(mg3d_ctx *ctx, int level)
     CHK(check_field_level(ctx, 0, level, "mg3d_restrict"));
     if (level < 1)
         return fail(MG3D_ERR_ARG, "mg3d_restrict: level 0 has no coarser level");
-    k_restrict(ctx->lv[level].g, ctx->lv[level].f[MG3D_R], ctx->lv[level - 1].g, ctx->lv[level - 1].f[MG3D_D],
-               ctx->stream);
+    enqueue_restrict(ctx, level);
     return launch_ok("mg3d_restrict");
 }
 
@@ -1064,8 +1166,7 @@ extern "C" int mg3d_prolong(mg3d_ctx *ctx, int level)
     CHK(check_field_level(ctx, 0, level, "mg3d_prolong"));
     if (level < 1)
         return fail(MG3D_ERR_ARG, "mg3d_prolong: level 0 has no coarser level");
-    k_prolong(ctx->lv[level - 1].g, ctx->lv[level - 1].f[MG3D_U], ctx->lv[level].g, ctx->lv[level].f[MG3D_U],
-              ctx->stream);
+    enqueue_prolong(ctx, level);
     return launch_ok("mg3d_prolong");
 }
 
@@ -1078,7 +1179,7 @@ extern "C" int mg3d_coarse_solve(mg3d_ctx *ctx)
         return fail(MG3D_ERR_STATE, "mg3d_coarse_solve: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)");
     if (ctx->have_es)
         return fail(MG3D_ERR_STATE, "mg3d_coarse_solve: the context holds the mixed-boundary factor of mg3d_es_setup");
-    k_lu_solve(ctx->lu, ctx->lu_in, ctx->lv[0].g, ctx->lv[0].f[MG3D_D], ctx->lv[0].f[MG3D_U], ctx->lu_work, ctx->stream);
+    enqueue_coarse_solve(ctx);
     return launch_ok("mg3d_coarse_solve");
 }
 
@@ -1296,7 +1397,8 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             const bool faces_only = mg3d_fused(ctx) && !ctx->keep_r;
             if (!faces_only || ctx->faces_dirty[l] || ctx->faces_always[l]) {
                 StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
-                k_restrict(lev.g, lev.f[MG3D_R], ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_D], s, -1, -1, faces_only);
+                /* (periodic axes: never faces_only -- the periodic faces are fully weighted on every cycle) */
+                enqueue_restrict(ctx, l, faces_only);
                 ctx->faces_dirty[l] = 0;
             }
         }
@@ -1309,7 +1411,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             (void)hipMemsetAsync(l0.f[MG3D_U], 0, l0.elems * sizeof(double), s);
         StageScope t(ctx, 0, MG3D_ST_RECURSE);
         StageScope kt(ctx, 0, MG3D_K_COARSE_SOLVE, true);
-        k_lu_solve(ctx->lu, ctx->lu_in, l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu_work, s); /* :1270 */
+        enqueue_coarse_solve(ctx); /* :1270 */
     }
     for (int l = 1; l <= q; l++) {
         Level &lev = ctx->lv[l];
@@ -1401,7 +1503,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
             StageScope t(ctx, l, MG3D_ST_PROLONG); /* :1331; ~0 s when folded into the smoother's loads */
             if (!pro) {
                 StageScope kt(ctx, l, MG3D_K_PROLONG, true);
-                k_prolong(ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_U], lev.g, lev.f[MG3D_U], s);
+                enqueue_prolong(ctx, l);
             }
         }
         if (mg3d_fused(ctx)) { /* (prolongation,) post-smoother and residual norm (:1331 + :1341 + :1354) */
@@ -1493,6 +1595,8 @@ extern "C" int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level)
 {
     CHK(mg3d_drop_carry(ctx));
     CHK(check_field_level(ctx, field, level, "mg3d_fill_boundary"));
+    if (ctx->periodic) /* BCFunc is defined on all six faces */
+        return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     k_fill_boundary(ctx->lv[level].g, ctx->lv[level].f[field], ctx->lv[level].h, ctx->stream);
     mg3d_ctx_touched(ctx, field, level);
     return launch_ok("mg3d_fill_boundary");
@@ -1504,6 +1608,8 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
     CHK(mg3d_drop_carry(ctx));
     if (!ctx)
         return fail(MG3D_ERR_ARG, "mg3d_fmg_initialize: NULL context");
+    if (ctx->periodic) /* the F-cycle start fills BCFunc into all six faces */
+        return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: no coarse LU set");
     if (ctx->have_es)

@@ -103,6 +103,70 @@ void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, doub
             }
 }
 
+/* The coarsest matrix with periodic axes (mg3d_ctx_set_periodic; axes a MG3D_PERIODIC_* mask, eps dense N^3 or NULL for
+ * the constant operator).  axes = 0: mg3d_coarse_matrix_shift / _coef, the same bytes.  Otherwise identity rows on the
+ * Dirichlet faces (index 0 or N-1 of a non-periodic axis), on the duplicates (index N-1 of a periodic axis) and, all three
+ * axes periodic with sigma = 0 (the operator then annihilates constants), on the pinned point (0,0,0); every other row
+ * is the row of the kernels of mg3d_periodic.hip with its neighbours wrapped (i-1 at 0 is N-2, i+1 at N-2 is 0).  Needs
+ * N - 1 >= 4 on a periodic axis (distinct neighbours).  A must be zero on entry. */
+void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, double sigma, int axes)
+{
+    if (axes == 0) {
+        if (eps)
+            mg3d_coarse_matrix_coef(A, N, h, eps, sigma);
+        else
+            mg3d_coarse_matrix_shift(A, N, h, sigma);
+        return;
+    }
+    const long NN = (long)N * N, n = NN * N;
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double shift = sigma * hSq;
+    const double dg0 = 6. + shift;
+    const double off = 1. * invHsq, diag = dg0 * invHsq;
+    const int pi = axes & 1, pj = (axes >> 1) & 1, pk = (axes >> 2) & 1;
+    const int pin = axes == 7 && sigma == 0.;
+    long p = 0;
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++)
+            for (int k = 0; k < N; k++, p++) {
+                double *row = A + p * n;
+                const int dup = (pi && i == N - 1) || (pj && j == N - 1) || (pk && k == N - 1);
+                const int face = (!pi && (i == 0 || i == N - 1)) || (!pj && (j == 0 || j == N - 1)) ||
+                                 (!pk && (k == 0 || k == N - 1));
+                if (dup || face || (pin && p == 0)) {
+                    row[p] = 1.;
+                    continue;
+                }
+                /* (index 0 occurs on periodic axes only; N-2 wraps only there) */
+                const long im = (i == 0 ? N - 2 : i - 1) * NN + j * N + k, ip = (pi && i == N - 2 ? 0 : i + 1) * NN + j * N + k;
+                const long jm = i * NN + (j == 0 ? N - 2 : j - 1) * N + k, jp = i * NN + (pj && j == N - 2 ? 0 : j + 1) * N + k;
+                const long km = i * NN + j * N + (k == 0 ? N - 2 : k - 1), kp = i * NN + j * N + (pk && k == N - 2 ? 0 : k + 1);
+                if (!eps) {
+                    row[im] = off;
+                    row[ip] = off;
+                    row[jm] = off;
+                    row[jp] = off;
+                    row[km] = off;
+                    row[kp] = off;
+                    row[p] = -diag;
+                    continue;
+                }
+                const double e = eps[p];
+                const double a_im = 0.5 * (e + eps[im]), a_ip = 0.5 * (e + eps[ip]);
+                const double a_jm = 0.5 * (e + eps[jm]), a_jp = 0.5 * (e + eps[jp]);
+                const double a_km = 0.5 * (e + eps[km]), a_kp = 0.5 * (e + eps[kp]);
+                const double dg = ((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp + shift;
+                row[im] = a_im * invHsq;
+                row[ip] = a_ip * invHsq;
+                row[jm] = a_jm * invHsq;
+                row[jp] = a_jp * invHsq;
+                row[km] = a_km * invHsq;
+                row[kp] = a_kp * invHsq;
+                row[p] = -(dg * invHsq);
+            }
+}
+
 /* The coarsest operator of the mixed-boundary problem (csrc/mg3d_es.hip): constructCoarseMatrixA (identity rows on
  * the boundary, mg_3d.h:179-185) except that a wall point -- a face point with an interior point in front of it that is
  * not part of a Dirichlet patch -- gets the row  x_wall - x_front = b_wall, the zero-gradient condition the smoother

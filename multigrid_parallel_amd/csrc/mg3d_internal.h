@@ -171,6 +171,18 @@ void k_coef_residual(const Geom &g, const double *v, const double *e, const doub
                      double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
                      int acc_lo = 0, int acc_hi = -1);
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
+/* mg3d_periodic.hip: periodic axes (mg3d_ctx_set_periodic; axes = MG3D_PERIODIC_* mask, single-domain levels).  Colour
+ * pass and residual over the unique points with wrapped neighbours, e = eps of the level (NULL: the constant operator of
+ * op), shift = sigma*hSq; duplicates written as copies.  Restriction (full weighting on periodic faces), prolongation, the
+ * coarse right-hand side (0 in the duplicates' and the pinned point's identity rows) and a duplicate refresh */
+void k_per_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double shift, int color,
+                 int axes, hipStream_t s);
+void k_per_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double shift,
+                    int axes, double *res, double *partials, double *sumsq_out, hipStream_t s);
+void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int axes, hipStream_t s);
+void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int axes, hipStream_t s);
+void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int axes, int pin, hipStream_t s);
+void k_per_refresh(const Geom &g, double *v, int axes, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);
