@@ -38,7 +38,7 @@ struct mg3d_ctx {
     std::vector<double *> eps;
     std::vector<double> eps0;
     /* periodic axes (mg3d_ctx_set_periodic; MG3D_PERIODIC_* mask, 0: Dirichlet faces everywhere) and the padded level-0
-     * right-hand side of the direct solve that mg3d_periodic.hip builds from d (allocated with the first nonzero mask) */
+     * right-hand side of the direct solve that k_per_coarse_rhs builds from d (allocated with the first nonzero mask) */
     int periodic;
     double *per_b;
     double *lu_work;  /* 2n doubles */
@@ -87,8 +87,8 @@ struct mg3d_ctx {
 /* the operator constants of a level of this context (its spacing, the context's sigma) */
 static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
- * passes and residual of mg3d_coef.hip with the plain restriction, prolongation and coarse solve between them, nor with
- * a periodic axis, whose levels run the kernels of mg3d_periodic.hip */
+ * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
+ * them, nor with a periodic axis, whose levels run those with wrapped neighbours and the k_per_* transfers */
 static inline bool mg3d_fused(const mg3d_ctx *ctx) { return ctx->fused && ctx->eps.empty() && ctx->periodic == 0; }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);

@@ -705,7 +705,7 @@ static void free_eps(mg3d_ctx *ctx)
     ctx->eps0.clear();
 }
 
-/* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_coef.hip) on every level: eps of the finest level
+/* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_kernels.hip) on every level: eps of the finest level
  * as given, of each coarser one by injection.  The array is checked before anything changes; then, as for a new sigma, a
  * cycle that has run ahead is finished with the operator it started with and the coarse factor is rebuilt or dropped.
  * NULL: back to the constant-coefficient operator and its fused schedules. */
@@ -792,7 +792,7 @@ extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
     return MG3D_OK;
 }
 
-/* Periodic axes (mg3d_periodic.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
+/* Periodic axes (mg3d_kernels.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
  * changes -- a mask outside 0..7, or a nonzero one on a hierarchy whose coarsest level has fewer than 4 or an odd number
  * of unique points per side, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that has run ahead is finished with the
  * operator it started with and the coarse factor is rebuilt (mg3d_ctx_build_coarse) or dropped.  0: Dirichlet faces
@@ -1001,42 +1001,15 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
         return MG3D_OK;
     }
     const LevelOp op = mg3d_op(ctx, l);
-    if (ctx->periodic) { /* periodic axes: the kernels of mg3d_periodic.hip (constant or eps), same timer slots */
-        const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
-        const double shift = ctx->sigma * op.hSq;
-        for (int it = 0; it < 2 * iters; it++) {
-            StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-            k_per_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, shift, c1 ^ (it & 1), ctx->periodic, s);
-        }
-        if (want_res) {
-            StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-            k_per_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, shift, ctx->periodic, want_res == 2 ? l.f[MG3D_R] : nullptr,
-                           ctx->partials, ctx->sumsq + slot, s);
-        }
-        return MG3D_OK;
-    }
-    if (!ctx->eps.empty()) { /* div(eps grad u) - sigma u: the kernels of mg3d_coef.hip, same slots of the kernel timers */
-        const double *e = ctx->eps[level];
-        const double shift = ctx->sigma * op.hSq;
-        for (int it = 0; it < 2 * iters; it++) {
-            StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-            k_coef_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op.hSq, shift, c1 ^ (it & 1), s);
-        }
-        if (want_res) {
-            StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-            k_coef_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op.invHsq, shift, want_res == 2 ? l.f[MG3D_R] : nullptr,
-                            ctx->partials, ctx->sumsq + slot, s);
-        }
-        return MG3D_OK;
-    }
+    const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-        k_smooth_color(l.g, l.f[MG3D_U], l.f[MG3D_D], op, c1 ^ (it & 1), s);
+        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, ctx->periodic, c1 ^ (it & 1), s);
     }
     if (want_res) {
         StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-        k_residual(l.g, l.f[MG3D_U], l.f[MG3D_D], op, want_res == 2 ? l.f[MG3D_R] : nullptr, ctx->partials,
-                   ctx->sumsq + slot, s);
+        k_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, ctx->periodic, want_res == 2 ? l.f[MG3D_R] : nullptr,
+                   ctx->partials, ctx->sumsq + slot, s);
     }
     return MG3D_OK;
 }

@@ -256,7 +256,7 @@ struct mg3d_dist {
     bool carry_fixed, carry_on;
     int n_carried;                 /* cycles that ended that way (mg3d_dist_carried_cycles) */
     /* a variable coefficient is set (mg3d_dist_set_coefficient): eps on every slab level, the replicated contexts have it too;
-     * the cycle is the plain one of mg3d_coef.hip's kernels (dist_enqueue_vcycle, dist_coef_smooth), no carried cycles or legs */
+     * the cycle is the plain one of the unfused kernels (dist_enqueue_vcycle, dist_coef_smooth), no carried cycles or legs */
     bool coef;
     int phase;  /* next phase of the cycle being enqueued */
     int policy; /* bit 0: coarse levels on rank 0 only (MG3D_COARSE_GATHER=1) */
@@ -1179,7 +1179,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
     return MG3D_OK;
 }
 
-/* One smoothing stage of the variable-coefficient operator (mg3d_coef.hip) on distributed level l for every local rank: the
+/* One smoothing stage of the variable-coefficient operator (mg3d_kernels.hip) on distributed level l for every local rank: the
  * single-domain schedule (2*nu colour passes in place, then the residual) with windows.  On entry u, d and eps are exact on
  * every local plane.  Pass t of S = 2*nu produces the owned planes +- (margin + S - t), its dependence cone, and no more:
  * margin 2 before a stored residual, 1 before the top-level norm.  want_res 2: r on owned +-1, what the restriction reads
@@ -1195,15 +1195,14 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
         Level &lv = sl.lv;
         mg3d_ctx *cx = R.coarse;
         const LevelOp op = mg3d_op(cx, lv);
-        const double shift = cx->sigma * op.hSq;
         for (int t = 1; t <= S; t++) { /* :1282 / :1341 */
             const int w = margin + S - t;
-            k_coef_color(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.hSq, shift, c1 ^ ((t - 1) & 1), s, sl.own_lo - w,
-                         sl.own_hi + w);
+            k_smooth_color(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, c1 ^ ((t - 1) & 1), s,
+                           sl.own_lo - w, sl.own_hi + w);
         }
         if (want_res == 2) /* :1294 */
-            k_coef_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.invHsq, shift, lv.f[MG3D_R], cx->partials,
-                            cx->sumsq + cx->sumsq_slots - 1, s, sl.own_lo - 1, sl.own_hi + 1, 0, 0);
+            k_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, lv.f[MG3D_R], cx->partials,
+                       cx->sumsq + cx->sumsq_slots - 1, s, sl.own_lo - 1, sl.own_hi + 1, 0, 0);
     }
     if (want_res != 1)
         return MG3D_OK;
@@ -1213,8 +1212,8 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
         Level &lv = sl.lv;
         mg3d_ctx *cx = R.coarse;
         const LevelOp op = mg3d_op(cx, lv);
-        k_coef_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op.invHsq, cx->sigma * op.hSq, nullptr, cx->partials,
-                        cx->sumsq, s, sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
+        k_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, nullptr, cx->partials, cx->sumsq, s,
+                   sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
     }
     return MG3D_OK;
 }

@@ -70,7 +70,7 @@ void mg3d_coarse_matrix(double *A, int N, double h) { mg3d_coarse_matrix_shift(A
 /* The coarsest matrix of the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient): identity
  * on boundary nodes; on interior node p the face means a = 0.5*(eps[p] + eps[q]) of its six neighbours q (order i-, i+,
  * j-, j+, k-, k+) divided by h^2 off the diagonal, -dg/h^2 on it, dg = (((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp)
- * + sigma*h^2 -- the diagonal of the kernels of mg3d_coef.hip.  eps is dense N^3; eps = 1 everywhere gives the bytes of
+ * + sigma*h^2 -- the diagonal of the kernels of mg3d_kernels.hip.  eps is dense N^3; eps = 1 everywhere gives the bytes of
  * mg3d_coarse_matrix_shift.  A must be zero on entry. */
 void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma)
 {
@@ -107,7 +107,7 @@ void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, doub
  * the constant operator).  axes = 0: mg3d_coarse_matrix_shift / _coef, the same bytes.  Otherwise identity rows on the
  * Dirichlet faces (index 0 or N-1 of a non-periodic axis), on the duplicates (index N-1 of a periodic axis) and, all three
  * axes periodic with sigma = 0 (the operator then annihilates constants), on the pinned point (0,0,0); every other row
- * is the row of the kernels of mg3d_periodic.hip with its neighbours wrapped (i-1 at 0 is N-2, i+1 at N-2 is 0).  Needs
+ * is the row of the kernels of mg3d_kernels.hip with its neighbours wrapped (i-1 at 0 is N-2, i+1 at N-2 is 0).  Needs
  * N - 1 >= 4 on a periodic axis (distinct neighbours).  A must be zero on entry. */
 void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, double sigma, int axes)
 {

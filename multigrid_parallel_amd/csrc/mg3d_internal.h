@@ -98,10 +98,17 @@ int mg3d_option_index(const char *key);           /* -1: no such key */
 const char *mg3d_option_key(int index);           /* NULL past the end */
 
 /* launchers (mg3d_kernels.hip); all asynchronous on `s` */
-void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOp &op, int color, hipStream_t s);
-/* writes partials (one per block) then reduces them, in a fixed order, into *sumsq_out */
-void k_residual(const Geom &g, const double *v, const double *d, const LevelOp &op, double *res, double *partials,
-                double *sumsq_out, hipStream_t s);
+/* One colour pass in place and the residual of a level's operator: e = eps of the level in the padded layout for
+ * div(eps grad u) - sigma u (mg3d_ctx_set_coefficient), NULL for the constant operator of op; sigma the context's shift;
+ * axes the MG3D_PERIODIC_* mask of wrapped axes (mg3d_ctx_set_periodic; single-domain levels only, no windows), whose
+ * duplicate points receive copies.  The residual writes res (optional) on the interior and partials (one per block),
+ * then reduces them, in a fixed order, into *sumsq_out.  Windows as k_sweep's: i_lo / i_hi the local planes produced,
+ * acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
+void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
+                    int axes, int color, hipStream_t s, int i_lo = -1, int i_hi = -1);
+void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
+                int axes, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
+                int acc_lo = 0, int acc_hi = -1);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo = -1,
@@ -161,24 +168,11 @@ void k_tiny_up(const Geom &g, double *u, const double *d, const Geom &gc, const 
 bool k_tiny_cycle_fits(const Geom &g, const Geom &gc, const LuBand &lu, const LuBand &lin);
 void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, const Geom &gc, double *dc, double *xc,
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
-/* mg3d_coef.hip: the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient); e is eps of the
- * level in the padded layout, shift = sigma*hSq.  One colour pass in place; the residual as k_residual (res optional,
- * partials folded into *sumsq_out); eps of the coarser level by injection at every point.  Windows as k_sweep's: i_lo /
- * i_hi the local planes produced, acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
-void k_coef_color(const Geom &g, double *v, const double *e, const double *d, double hSq, double shift, int color,
-                  hipStream_t s, int i_lo = -1, int i_hi = -1);
-void k_coef_residual(const Geom &g, const double *v, const double *e, const double *d, double invHsq, double shift,
-                     double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
-                     int acc_lo = 0, int acc_hi = -1);
+/* eps of the coarser level by injection at every point */
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
-/* mg3d_periodic.hip: periodic axes (mg3d_ctx_set_periodic; axes = MG3D_PERIODIC_* mask, single-domain levels).  Colour
- * pass and residual over the unique points with wrapped neighbours, e = eps of the level (NULL: the constant operator of
- * op), shift = sigma*hSq; duplicates written as copies.  Restriction (full weighting on periodic faces), prolongation, the
- * coarse right-hand side (0 in the duplicates' and the pinned point's identity rows) and a duplicate refresh */
-void k_per_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double shift, int color,
-                 int axes, hipStream_t s);
-void k_per_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double shift,
-                    int axes, double *res, double *partials, double *sumsq_out, hipStream_t s);
+/* periodic axes (axes = MG3D_PERIODIC_* mask, single-domain levels): restriction (full weighting on periodic faces),
+ * prolongation, the coarse right-hand side (0 in the duplicates' and the pinned point's identity rows) and a duplicate
+ * refresh */
 void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int axes, hipStream_t s);
 void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int axes, hipStream_t s);
 void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int axes, int pin, hipStream_t s);

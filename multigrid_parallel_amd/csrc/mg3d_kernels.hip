@@ -1,5 +1,5 @@
 /*
- * mg3d_kernels.hip -- gfx950 kernels of the multigrid V-cycle (baseline set).
+ * mg3d_kernels.hip -- gfx950 kernels of the multigrid V-cycle outside the fused sweeps.
  *
  * Arithmetic contract: every expression keeps the reference's association
  * (cited per kernel) and the file is compiled with -ffp-contract=off, so each
@@ -8,6 +8,33 @@
  *
  * Layout: idx = plane*i + pitch*j + k (k contiguous, 128-byte aligned rows).
  * Colour of a point: (ig0 + i + j + k) & 1; 1 = red, 0 = black (mg_3d.h:669,693).
+ *
+ * Operators of the colour pass and the residual (neighbours in the reference's order i-, i+, j-, j+, k-, k+):
+ *   constant (LevelOp: the screened 7-point Laplacian, sigma >= 0):
+ *     s = (((((v[p-NN] + v[p+NN]) + v[p-N]) + v[p+N]) + v[p-1]) + v[p+1])
+ *     smoother : v[p] = sixth * (s - hSq*d[p])                      (smoothenAtIndex, mg_3d.h:438-443)
+ *     residual : diff = d[p] - invHsq * (s - dg*v[p])               (calculateResidual, mg_3d.h:819-821)
+ *   variable coefficient (mg3d_ctx_set_coefficient): div(eps grad u) - sigma u = d, eps > 0 vertex-centred, one value
+ *   per grid point of every level; face coefficients are arithmetic means:
+ *     a_im = 0.5*(e[p] + e[p-NN]), a_ip = 0.5*(e[p] + e[p+NN]), ... a_kp = 0.5*(e[p] + e[p+1])
+ *     s    = (((((a_im*v[p-NN] + a_ip*v[p+NN]) + a_jm*v[p-N]) + a_jp*v[p+N]) + a_km*v[p-1]) + a_kp*v[p+1])
+ *     D    = ((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp;   dg = D + sigma*hSq
+ *     smoother : v[p] = (s - hSq*d[p]) / dg          (IEEE division)
+ *     residual : diff = d[p] - invHsq*(s - dg*v[p])
+ *   Coarse levels take eps by injection, e_{l-1}[I,J,K] = e_l[2I,2J,2K].  tests/_coef_ref.py states the same in numpy.
+ *
+ * Periodic axes (mg3d_ctx_set_periodic; axes is a mask, MG3D_PERIODIC_I = 1, _J = 2, _K = 4; single-domain levels only:
+ * ig0 = 0, ni = nj = nk = N).  A level keeps its N points per side; on a periodic axis index N-1 is the DUPLICATE of
+ * index 0 and the unique points are 0 .. N-2 (an even count, so red-black colours agree across the wrap).  On a
+ * non-periodic axis the faces 0 and N-1 stay Dirichlet points that no kernel here writes.
+ *   - Nothing reads a duplicate: a stencil reaches across the wrap to the unique point (i-1 at i = 0 is N-2, i+1 at N-2
+ *     is 0), and every kernel that writes a unique point on a periodic face also writes its duplicates (edges and
+ *     corners included), so written fields are always periodic-consistent.
+ *   - Colour pass and residual keep the arithmetic above exactly; only neighbour indices change.
+ *   - Restriction: the 27-point full weighting of restrict_kernel (same order) on every coarse point that lies on no
+ *     Dirichlet face, with wrapped fine neighbours on periodic axes; Dirichlet faces are injected as before.
+ *   - Prolongation: the parent order of prolong_kernel, the coarse "high" parent wrapped to 0 on a periodic axis.
+ *   tests/_periodic_ref.py states the same in numpy.
  */
 #include "mg3d_internal.h"
 
@@ -23,41 +50,210 @@ __device__ __forceinline__ long long gidx(const Geom &g, int i, int j, int k)
     return g.plane * i + (long long)g.pitch * j + k;
 }
 
-/* ------------------------------------------------------------------ smoother
- * One colour pass of red-black Gauss-Seidel (smoothenAtIndex, mg_3d.h:438-443):
- *   v[p] = (1/6) * (((((((v[p-NN] + v[p+NN]) + v[p-N]) + v[p+N]) + v[p-1]) + v[p+1]) - hSq*d[p])
- * Each lane owns the k-pair (2m, 2m+1) of one row and updates the member whose
- * colour is being swept; boundary points (k = 0, nk-1) are never written. */
-__global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__restrict__ v,
-                                                           const double *__restrict__ d, double hSq, double sixth,
-                                                           int color)
+/* the offsets to the -1 / +1 neighbour along an axis of stride `st` at index x (unique range), wrapped when periodic */
+__device__ __forceinline__ long long nb_lo(int x, int N, bool per, long long st) { return (per && x == 0) ? (N - 2) * st : -st; }
+__device__ __forceinline__ long long nb_hi(int x, int N, bool per, long long st) { return (per && x == N - 2) ? -(N - 2) * st : st; }
+
+/* x to p and to every duplicate of p: di / dj / dk say whether p lies on the periodic face 0 of that axis */
+__device__ __forceinline__ void store_dup(const Geom &g, double *__restrict__ a, long long p, double x, bool di, bool dj,
+                                          bool dk)
 {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
-    const int i = 1 + blockIdx.z;
-    if (j > g.nj - 2)
+    a[p] = x;
+    if (!(di | dj | dk))
         return;
-    const int k = 2 * m + ((color + g.ig0 + i + j) & 1);
-    if (k < 1 || k > g.nk - 2)
-        return;
-    const long long p = gidx(g, i, j, k);
-    double s = v[p - g.plane] + v[p + g.plane];
-    s = s + v[p - g.pitch];
-    s = s + v[p + g.pitch];
-    s = s + v[p - 1];
-    s = s + v[p + 1];
-    s = s - hSq * d[p];
-    v[p] = sixth * s;
+    const long long si = (long long)(g.N - 1) * g.plane, sj = (long long)(g.N - 1) * g.pitch, sk = g.N - 1;
+    for (int m = 1; m < 8; m++) {
+        if (((m & 1) && !di) || ((m & 2) && !dj) || ((m & 4) && !dk))
+            continue;
+        a[p + ((m & 1) ? si : 0) + ((m & 2) ? sj : 0) + ((m & 4) ? sk : 0)] = x;
+    }
 }
 
-void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOp &op, int color, hipStream_t s)
+/* ------------------------------------------------------------------ stencils
+ * One kernel family for the colour pass and the residual of every operator above, templated on what differs:
+ *   COEF  eps is set: face means and an IEEE division instead of the constant `sixth`
+ *   PER   an axis is periodic: wrapped neighbour offsets and duplicate stores; PER = false folds to the plain offsets
+ * The residual and the colour pass with eps give each thread one (j, k) column of `chunk` planes, lanes contiguous in
+ * k, and keep the i-1 / i / i+1 values of v (and eps) of the column in registers; the constant colour pass gives a lane
+ * one k-pair of a row (measured at 513^3 the column form of that pass took 0.76 ms against 0.64 ms).
+ *
+ * Windows (the i-slabs of mg3d_dist.hip, conventions of k_sweep): [i_lo, i_hi) are the local planes a launch produces,
+ * clipped to the unique interior planes; [acc_lo, acc_hi) the local planes whose diff^2 enters the norm.  -1 / -1: every
+ * plane, the launches of a single-domain level. */
+
+/* neighbour sum s and diagonal dg of point p; vb / va and eb / eh / ea: v and eps of planes i-1, i, i+1 of the column
+ * (v of plane i itself is not part of the sum), oj* / ok*: the column's j and k neighbour offsets */
+template <bool COEF>
+__device__ __forceinline__ void stencil(const double *__restrict__ v, const double *__restrict__ e, long long p,
+                                        long long ojm, long long ojp, long long okm, long long okp, double vb, double va,
+                                        double eb, double eh, double ea, double dg0, double &s, double &dg)
 {
-    if (g.ni < 3 || g.nj < 3 || g.nk < 3)
+    if constexpr (COEF) {
+        const double a_im = 0.5 * (eh + eb);
+        const double a_ip = 0.5 * (eh + ea);
+        const double a_jm = 0.5 * (eh + e[p + ojm]);
+        const double a_jp = 0.5 * (eh + e[p + ojp]);
+        const double a_km = 0.5 * (eh + e[p + okm]);
+        const double a_kp = 0.5 * (eh + e[p + okp]);
+        double t = a_im * vb + a_ip * va;
+        t = t + a_jm * v[p + ojm];
+        t = t + a_jp * v[p + ojp];
+        t = t + a_km * v[p + okm];
+        t = t + a_kp * v[p + okp];
+        s = t;
+        double D = a_im + a_ip;
+        D = D + a_jm;
+        D = D + a_jp;
+        D = D + a_km;
+        D = D + a_kp;
+        dg = D + dg0; /* dg0 = sigma*hSq */
+    } else {
+        double t = vb + va;
+        t = t + v[p + ojm];
+        t = t + v[p + ojp];
+        t = t + v[p + okm];
+        t = t + v[p + okp];
+        s = t;
+        dg = dg0; /* dg0 = 6 + sigma*hSq */
+    }
+}
+
+/* one thread's column: planes [i0, i1) of row j, column k; the first unique j and k are 0 on a periodic axis, 1
+ * otherwise (the launcher clips [i_lo, i_hi) the same way); pi / dj / dk: the axis wraps at i = 0 / this row / this
+ * column has duplicates.  A periodic level is single-domain (nj = nk = N): its last unique j and k are taken from N, as
+ * the wrap is -- from nj / nk the eps kernels compile to 74 - 76 VGPRs, below occupancy 8 */
+struct Column {
+    int j, k, i0, i1;
+    bool pi, dj, dk;
+    long long ojm, ojp, okm, okp;
+};
+
+template <bool PER>
+__device__ __forceinline__ bool column(const Geom &g, int axes, int chunk, int i_lo, int i_hi, Column &c)
+{
+    const bool pj = PER && (axes & 2), pk = PER && (axes & 4);
+    c.pi = PER && (axes & 1);
+    c.k = (pk ? 0 : 1) + blockIdx.x * WAVE + threadIdx.x;
+    c.j = (pj ? 0 : 1) + blockIdx.y * 4 + threadIdx.y;
+    c.i0 = i_lo + blockIdx.z * chunk;
+    c.i1 = min(c.i0 + chunk, i_hi);
+    if (c.k > (PER ? g.N : g.nk) - 2 || c.j > (PER ? g.N : g.nj) - 2)
+        return false;
+    c.dj = pj && c.j == 0;
+    c.dk = pk && c.k == 0;
+    c.ojm = nb_lo(c.j, g.N, pj, g.pitch);
+    c.ojp = nb_hi(c.j, g.N, pj, g.pitch);
+    c.okm = nb_lo(c.k, g.N, pk, 1);
+    c.okp = nb_hi(c.k, g.N, pk, 1);
+    return true;
+}
+
+/* the window [i_lo, i_hi) clipped to the unique interior planes (from 0 on a periodic i axis, else from 1, up to ni-2);
+ * false: nothing to produce */
+static bool stencil_window(const Geom &g, int axes, int &i_lo, int &i_hi)
+{
+    if (g.ni < 3 - (axes & 1) || g.nj < 3 - (axes >> 1 & 1) || g.nk < 3 - (axes >> 2 & 1))
+        return false;
+    const int lo = (axes & 1) ? 0 : 1;
+    i_lo = i_lo < lo ? lo : i_lo;
+    i_hi = (i_hi < 0 || i_hi > g.ni - 1) ? g.ni - 1 : i_hi;
+    return i_hi > i_lo;
+}
+
+/* the column grid: unique j and k of a level over (WAVE, 4) blocks; chunk of planes per thread: 16, doubled until the
+ * partial sums fit */
+static dim3 column_grid(const Geom &g, int axes, int planes, int &chunk)
+{
+    const int gx = (g.nk - 2 + (axes >> 2 & 1) + WAVE - 1) / WAVE, gy = (g.nj - 2 + (axes >> 1 & 1) + 3) / 4;
+    chunk = 16;
+    while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
+        chunk *= 2;
+    return dim3(gx, gy, (planes + chunk - 1) / chunk);
+}
+
+/* ------------------------------------------------------------------ smoother
+ * One red-black colour pass in place over the unique interior points.  Everything a point reads -- the six neighbours
+ * -- has the other colour, which this pass never writes (the wrap joins 0 and N-2, of opposite parity); a duplicate has
+ * its source's colour: it is written in the same pass and read by none.  Boundary points are never written.
+ * Constant operator: each lane owns the k-pair (2m, 2m+1) of one row and updates the member whose colour is being
+ * swept.  A periodic level is single-domain (ig0 = 0, ni = nj = nk = N): with PER its range and colour come from N and
+ * axes alone -- taken from i_lo, ig0, nj and nk the launch ran 3.5 % slower at 257^3. */
+template <bool PER>
+__global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ d,
+                                                           double hSq, double sixth, int color, int axes, int i_lo)
+{
+    const bool pi = PER && (axes & 1), pj = PER && (axes & 2), pk = PER && (axes & 4);
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = (pj ? 0 : 1) + blockIdx.y * blockDim.y + threadIdx.y;
+    const int i = (PER ? (pi ? 0 : 1) : i_lo) + blockIdx.z;
+    if (j > (PER ? g.N : g.nj) - 2)
         return;
-    dim3 block(64, 4, 1);
-    const int pairs = (g.nk + 1) / 2;
-    dim3 grid((pairs + 63) / 64, (g.nj - 2 + 3) / 4, g.ni - 2);
-    hipLaunchKernelGGL(smooth_color_kernel, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color);
+    const int k = 2 * m + ((color + (PER ? 0 : g.ig0) + i + j) & 1);
+    if (k < (pk ? 0 : 1) || k > (PER ? g.N : g.nk) - 2)
+        return;
+    const long long p = gidx(g, i, j, k);
+    double s = v[p + nb_lo(i, g.N, pi, g.plane)] + v[p + nb_hi(i, g.N, pi, g.plane)];
+    s = s + v[p + nb_lo(j, g.N, pj, g.pitch)];
+    s = s + v[p + nb_hi(j, g.N, pj, g.pitch)];
+    s = s + v[p + nb_lo(k, g.N, pk, 1)];
+    s = s + v[p + nb_hi(k, g.N, pk, 1)];
+    s = s - hSq * d[p];
+    store_dup(g, v, p, sixth * s, pi && i == 0, pj && j == 0, pk && k == 0);
+}
+
+/* eps set: a thread updates the points of its column that have colour `color` (every other plane) */
+template <bool PER>
+__global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ e,
+                                                         const double *__restrict__ d, double hSq, double shift,
+                                                         int color, int axes, int chunk, int i_lo, int i_hi)
+{
+    Column c;
+    if (!column<PER>(g, axes, chunk, i_lo, i_hi, c))
+        return;
+    long long p = gidx(g, c.i0, c.j, c.k);
+    const long long pb = p + nb_lo(c.i0, g.N, c.pi, g.plane);
+    double vb = v[pb], vh = v[p];
+    double eb = e[pb], eh = e[p];
+    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+        const long long pa = p + nb_hi(i, g.N, c.pi, g.plane);
+        const double va = v[pa], ea = e[pa];
+        if (((g.ig0 + i + c.j + c.k) & 1) == color) {
+            double s, dg;
+            stencil<true>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, shift, s, dg);
+            store_dup(g, v, p, (s - hSq * d[p]) / dg, c.pi && i == 0, c.dj, c.dk);
+        }
+        /* (a point updated here is the i-1 neighbour of a plane this pass does not update: its old value is never used) */
+        vb = vh;
+        vh = va;
+        eb = eh;
+        eh = ea;
+    }
+}
+
+void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
+                    int axes, int color, hipStream_t s, int i_lo, int i_hi)
+{
+    if (!stencil_window(g, axes, i_lo, i_hi))
+        return;
+    const dim3 block(WAVE, 4, 1);
+    if (!e) {
+        const int pairs = (g.nk + 1) / 2;
+        const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + (axes >> 1 & 1) + 3) / 4, i_hi - i_lo);
+        if (axes)
+            hipLaunchKernelGGL(smooth_color_kernel<true>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, axes, i_lo);
+        else
+            hipLaunchKernelGGL(smooth_color_kernel<false>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, axes, i_lo);
+        return;
+    }
+    int chunk;
+    const dim3 grid = column_grid(g, axes, i_hi - i_lo, chunk);
+    const double shift = sigma * op.hSq;
+    if (axes)
+        hipLaunchKernelGGL(coef_color_kernel<true>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, axes, chunk, i_lo,
+                           i_hi);
+    else
+        hipLaunchKernelGGL(coef_color_kernel<false>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, axes, chunk, i_lo,
+                           i_hi);
 }
 
 /* ------------------------------------------------------------ boundary fill
@@ -117,42 +313,46 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const double *__rest
 }
 
 /* ------------------------------------------------------------------ residual
- * calculateResidual, mg_3d.h:819-821:
- *   diff = d[p] - invHsq * (((((((v[p-NN]+v[p+NN])+v[p-N])+v[p+N])+v[p-1])+v[p+1]) - dg*v[p])
- * (dg = 6 for the reference's operator, 6 + sigma*h^2 for the screened one: LevelOp)
- * res (optional) is written on the interior only (mg_3d.h:824-825).
- * Each thread marches `chunk` planes in i keeping the i-1 / i / i+1 values of its
- * column in registers; diff^2 is reduced lane -> wave (__shfl_down) -> block. */
-__global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v,
-                                                       const double *__restrict__ d, double invHsq,
-                                                       double dg, double *__restrict__ res, double *__restrict__ partials,
-                                                       int chunk)
+ * diff at every unique interior point; res (optional) receives it there and at the duplicates (mg_3d.h:824-825), partials
+ * one sum of diff^2 per block (lanes by shuffle tree, waves 0..3 in order), folded by k_fold: the norm counts every
+ * unknown once. */
+template <bool COEF, bool PER>
+__global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
+                                                       const double *__restrict__ d, double invHsq, double dg0,
+                                                       double *__restrict__ res, double *__restrict__ partials, int axes,
+                                                       int chunk, int i_lo, int i_hi, int acc_lo, int acc_hi)
 {
     __shared__ double lds4[4];
-    const int k = 1 + blockIdx.x * 64 + threadIdx.x;
-    const int j = 1 + blockIdx.y * 4 + threadIdx.y;
-    const int i0 = 1 + blockIdx.z * chunk;
-    int i1 = i0 + chunk;
-    if (i1 > g.ni - 1)
-        i1 = g.ni - 1;
     double acc = 0.;
-    if (k <= g.nk - 2 && j <= g.nj - 2) {
-        long long p = gidx(g, i0, j, k);
-        double below = v[p - g.plane], here = v[p];
-        for (int i = i0; i < i1; i++, p += g.plane) {
-            const double above = v[p + g.plane];
-            double s = below + above;
-            s = s + v[p - g.pitch];
-            s = s + v[p + g.pitch];
-            s = s + v[p - 1];
-            s = s + v[p + 1];
-            s = s - dg * here;
-            const double diff = d[p] - invHsq * s;
+    Column c;
+    if (column<PER>(g, axes, chunk, i_lo, i_hi, c)) {
+        long long p = gidx(g, c.i0, c.j, c.k);
+        const long long pb = p + nb_lo(c.i0, g.N, c.pi, g.plane);
+        double vb = v[pb], vh = v[p];
+        double eb = 0., eh = 0.;
+        if constexpr (COEF) {
+            eb = e[pb];
+            eh = e[p];
+        }
+        for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+            const long long pa = p + nb_hi(i, g.N, c.pi, g.plane);
+            const double va = v[pa];
+            double ea = 0.;
+            if constexpr (COEF)
+                ea = e[pa];
+            double s, dg;
+            stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
+            const double diff = d[p] - invHsq * (s - dg * vh);
             if (res)
-                res[p] = diff;
-            acc += diff * diff;
-            below = here;
-            here = above;
+                store_dup(g, res, p, diff, c.pi && i == 0, c.dj, c.dk);
+            if (PER || (i >= acc_lo && i < acc_hi)) /* periodic levels have no windows */
+                acc += diff * diff;
+            vb = vh;
+            vh = va;
+            if constexpr (COEF) {
+                eb = eh;
+                eh = ea;
+            }
         }
     }
     const double tot = block_sum_256(acc, lds4);
@@ -187,21 +387,32 @@ void k_fold(const double *partials, int np, double *out, hipStream_t s)
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, np, out);
 }
 
-void k_residual(const Geom &g, const double *v, const double *d, const LevelOp &op, double *res, double *partials,
-                double *sumsq_out, hipStream_t s)
+void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
+                int axes, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
+                int acc_hi)
 {
-    if (g.ni < 3 || g.nj < 3 || g.nk < 3) {
+    if (!stencil_window(g, axes, i_lo, i_hi)) {
         (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
         return;
     }
-    const int gx = (g.nk - 2 + 63) / 64, gy = (g.nj - 2 + 3) / 4;
-    int chunk = 16;
-    while ((long long)gx * gy * ((g.ni - 2 + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
-        chunk *= 2;
-    const int gz = (g.ni - 2 + chunk - 1) / chunk;
-    hipLaunchKernelGGL(residual_kernel, dim3(gx, gy, gz), dim3(64, 4, 1), 0, s, g, v, d, op.invHsq, op.dg, res,
-                       partials, chunk);
-    hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, gx * gy * gz, sumsq_out);
+    if (acc_hi < 0)
+        acc_hi = g.ni;
+    int chunk;
+    const dim3 grid = column_grid(g, axes, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const double dg0 = e ? sigma * op.hSq : op.dg;
+    if (e && axes)
+        hipLaunchKernelGGL((residual_kernel<true, true>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
+                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+    else if (e)
+        hipLaunchKernelGGL((residual_kernel<true, false>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
+                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+    else if (axes)
+        hipLaunchKernelGGL((residual_kernel<false, true>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
+                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+    else
+        hipLaunchKernelGGL((residual_kernel<false, false>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
+                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+    k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
 
 /* GetL2NormOfVector (mg_3d.h:783-792) over every point of a level, boundary included */
@@ -322,6 +533,70 @@ void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hip
         return;
     dim3 grid((gc.nk + 63) / 64, (gc.nj + 3) / 4, hi - lo);
     hipLaunchKernelGGL(restrict_kernel, grid, dim3(64, 4, 1), 0, s, gf, r, gc, dc, lo, hi, faces_only ? 1 : 0);
+}
+
+/* Periodic axes: one thread per coarse point.  A point on a Dirichlet face (index 0 or Nc-1 of a non-periodic axis) is
+ * injected, dc = r(2I, 2J, 2K), as restrict_kernel does; every other unique point -- periodic face points included -- takes the
+ * full weighting val = 0; val += r(2I-1+ti, ...) * w in restrict_kernel's order, with fine index -1 wrapped to Nf-2
+ * (2I+1 <= Nf-2 never wraps).  Duplicates are written as copies by the thread of their source. */
+__global__ void __launch_bounds__(256) per_restrict_kernel(Geom gf, const double *__restrict__ r, Geom gc,
+                                                           double *__restrict__ dc, int axes)
+{
+    const int kc = blockIdx.x * WAVE + threadIdx.x;
+    const int jc = blockIdx.y * 4 + threadIdx.y;
+    const int ic = blockIdx.z;
+    const int Nc = gc.N, Nf = gf.N;
+    const bool pi = axes & 1, pj = axes & 2, pk = axes & 4;
+    if (kc >= Nc || jc >= Nc || ic >= Nc)
+        return;
+    if ((pi && ic == Nc - 1) || (pj && jc == Nc - 1) || (pk && kc == Nc - 1))
+        return; /* a duplicate: its source's thread writes it */
+    const long long pf = gidx(gf, 2 * ic, 2 * jc, 2 * kc);
+    const bool face = (!pi && (ic == 0 || ic == Nc - 1)) || (!pj && (jc == 0 || jc == Nc - 1)) ||
+                      (!pk && (kc == 0 || kc == Nc - 1));
+    double val;
+    if (face) {
+        val = r[pf];
+    } else {
+        const long long oi[3] = {ic == 0 ? (Nf - 2) * gf.plane : -gf.plane, 0, gf.plane};
+        const long long oj[3] = {jc == 0 ? (long long)(Nf - 2) * gf.pitch : -(long long)gf.pitch, 0, gf.pitch};
+        const long long ok[3] = {kc == 0 ? (long long)(Nf - 2) : -1, 0, 1};
+        val = 0.;
+#pragma unroll
+        for (int ti = 0; ti < 3; ti++)
+#pragma unroll
+            for (int tj = 0; tj < 3; tj++)
+#pragma unroll
+                for (int tk = 0; tk < 3; tk++) {
+                    const double w = (ti != 1 ? 0.25 : 0.5) * (tj != 1 ? 0.25 : 0.5) * (tk != 1 ? 0.25 : 0.5);
+                    val += r[pf + oi[ti] + oj[tj] + ok[tk]] * w;
+                }
+    }
+    store_dup(gc, dc, gidx(gc, ic, jc, kc), val, pi && ic == 0, pj && jc == 0, pk && kc == 0);
+}
+
+void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int axes, hipStream_t s)
+{
+    dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
+    hipLaunchKernelGGL(per_restrict_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, r, gc, dc, axes);
+}
+
+/* eps of the coarse level at every point, boundary included: ec[I,J,K] = ef[2I,2J,2K] (single-domain levels) */
+__global__ void __launch_bounds__(256) coef_inject_kernel(Geom gf, const double *__restrict__ ef, Geom gc,
+                                                          double *__restrict__ ec)
+{
+    const int kc = blockIdx.x * WAVE + threadIdx.x;
+    const int jc = blockIdx.y * 4 + threadIdx.y;
+    const int ic = blockIdx.z;
+    if (kc >= gc.nk || jc >= gc.nj)
+        return;
+    ec[gidx(gc, ic, jc, kc)] = ef[gidx(gf, 2 * ic, 2 * jc, 2 * kc)];
+}
+
+void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s)
+{
+    dim3 grid((gc.nk + WAVE - 1) / WAVE, (gc.nj + 3) / 4, gc.ni);
+    hipLaunchKernelGGL(coef_inject_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, ef, gc, ec);
 }
 
 /* -------------------------------------------------------------- prolongation
@@ -483,6 +758,124 @@ void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, hip
     }
     dim3 grid((gf.nk + 63) / 64, (gf.nj + 3) / 4, hi - lo);
     hipLaunchKernelGGL(prolong_kernel, grid, dim3(64, 4, 1), 0, s, gc, ec, gf, ef, lo, hi);
+}
+
+/* Periodic axes: ef += P(ec) at every fine point that is not a duplicate (Dirichlet faces included, as prolong_kernel),
+ * in prolong_kernel's parent order; on a periodic axis the high parent il+1 = Nc-1 is read at its source 0.  The thread
+ * of a point writes the sum to its duplicates too, so neither a fine nor a coarse duplicate is ever read. */
+__global__ void __launch_bounds__(256) per_prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
+                                                          double *__restrict__ ef, int axes)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int Nc = gc.N, Nf = gf.N;
+    const bool pi = axes & 1, pj = axes & 2, pk = axes & 4;
+    if (k >= Nf || j >= Nf)
+        return;
+    if ((pi && i == Nf - 1) || (pj && j == Nf - 1) || (pk && k == Nf - 1))
+        return;
+    const int oi = i & 1, oj = j & 1, ok = k & 1;
+    const int il = (i - oi) / 2, jl = (j - oj) / 2, kl = (k - ok) / 2;
+    const long long c0 = gidx(gc, il, jl, kl);
+    const long long sI = (pi && il + 1 == Nc - 1) ? -(long long)il * gc.plane : gc.plane;
+    const long long sJ = (pj && jl + 1 == Nc - 1) ? -(long long)jl * gc.pitch : gc.pitch;
+    const long long sK = (pk && kl + 1 == Nc - 1) ? -(long long)kl : 1;
+    double t = 0.;
+    switch (oi + oj + ok) {
+    case 3:
+        t += ec[c0];
+        t += ec[c0 + sK];
+        t += ec[c0 + sJ];
+        t += ec[c0 + sJ + sK];
+        t += ec[c0 + sI];
+        t += ec[c0 + sI + sK];
+        t += ec[c0 + sI + sJ];
+        t += ec[c0 + sI + sJ + sK];
+        t *= 0.125;
+        break;
+    case 2:
+        if (!oi) {
+            t += ec[c0];
+            t += ec[c0 + sJ];
+            t += ec[c0 + sK];
+            t += ec[c0 + sJ + sK];
+        } else if (!oj) {
+            t += ec[c0];
+            t += ec[c0 + sI];
+            t += ec[c0 + sK];
+            t += ec[c0 + sI + sK];
+        } else {
+            t += ec[c0];
+            t += ec[c0 + sJ];
+            t += ec[c0 + sI];
+            t += ec[c0 + sI + sJ];
+        }
+        t *= 0.25;
+        break;
+    case 1:
+        t += ec[c0];
+        t += ec[c0 + (oi ? sI : 0) + (oj ? sJ : 0) + (ok ? sK : 0)];
+        t *= 0.5;
+        break;
+    default:
+        t = ec[c0];
+    }
+    const long long p = gidx(gf, i, j, k);
+    store_dup(gf, ef, p, ef[p] + t, pi && i == 0, pj && j == 0, pk && k == 0);
+}
+
+void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int axes, hipStream_t s)
+{
+    dim3 grid((gf.N + WAVE - 1) / WAVE, (gf.N + 3) / 4, gf.N);
+    hipLaunchKernelGGL(per_prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, axes);
+}
+
+/* ------------------------------------------------------------- coarsest level
+ * Periodic axes: the right-hand side of the direct solve (mg3d_coarse_matrix_periodic): d at every point, except 0 in the identity
+ * rows of the duplicates and of the pinned point (0,0,0) -- so a duplicate's d is never read, and those rows' solution
+ * is 0 until the refresh below copies the sources over the duplicates. */
+__global__ void __launch_bounds__(256) per_coarse_rhs_kernel(Geom g, const double *__restrict__ d, double *__restrict__ b,
+                                                             int axes, int pin)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    if (k >= N || j >= N)
+        return;
+    const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
+    const long long p = gidx(g, i, j, k);
+    b[p] = (dup || (pin && (i | j | k) == 0)) ? 0. : d[p];
+}
+
+void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int axes, int pin, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(per_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, axes, pin);
+}
+
+/* Every duplicate of a field from its source: blockIdx.z = the axis whose duplicate plane a thread covers; (a, b) the
+ * other two indices.  The source maps every periodic index N-1 to 0, so only unique points are read; an edge or corner
+ * duplicate is written by each plane it lies in, with the same value. */
+__global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, double *__restrict__ v, int axes)
+{
+    const int b = blockIdx.x * WAVE + threadIdx.x, a = blockIdx.y * 4 + threadIdx.y, ax = blockIdx.z;
+    const int N = g.N;
+    if (a >= N || b >= N || !(axes & (1 << ax)))
+        return;
+    int i = ax == 0 ? N - 1 : a, j = ax == 1 ? N - 1 : (ax == 0 ? a : b), k = ax == 2 ? N - 1 : b;
+    const int si = (axes & 1) && i == N - 1 ? 0 : i, sj = (axes & 2) && j == N - 1 ? 0 : j,
+              sk = (axes & 4) && k == N - 1 ? 0 : k;
+    v[gidx(g, i, j, k)] = v[gidx(g, si, sj, sk)];
+}
+
+void k_per_refresh(const Geom &g, double *v, int axes, hipStream_t s)
+{
+    if (!axes)
+        return;
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
+    hipLaunchKernelGGL(per_refresh_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes);
 }
 
 /* ------------------------------------------------------- coarsest direct solve

@@ -25,14 +25,14 @@ from test_dist_gloo import PlanRunner, Slab, free_port, owned
 
 
 def _rows(ni, ig0, N, i_lo, i_hi):
-    """interior local planes [lo, hi] (inclusive) of the window [i_lo, i_hi), as mg3d_coef.hip clips it"""
+    """interior local planes [lo, hi] (inclusive) of the window [i_lo, i_hi), as k_smooth_color / k_residual clip it"""
     lo = max(1, 1 - ig0, i_lo)
     hi = min(ni - 2, N - 2 - ig0, i_hi - 1)
     return lo, hi
 
 
 def colour_pass(u, d, e, h, sigma, colour, ig0, N, i_lo, i_hi):
-    """coef_color_kernel on the local planes [i_lo, i_hi) of a slab (colour 1 = red, by GLOBAL index)"""
+    """coef_color_kernel<false> on the local planes [i_lo, i_hi) of a slab (colour 1 = red, by GLOBAL index)"""
     lo, hi = _rows(u.shape[0], ig0, N, i_lo, i_hi)
     if hi < lo:
         return
@@ -47,7 +47,7 @@ def colour_pass(u, d, e, h, sigma, colour, ig0, N, i_lo, i_hi):
 
 
 def residual(u, d, e, h, sigma, r, ig0, N, i_lo, i_hi, acc_lo, acc_hi):
-    """coef_residual_kernel: r (optional) on the window, returns sum diff^2 over the local planes [acc_lo, acc_hi)"""
+    """residual_kernel<true, false>: r (optional) on the window, returns sum diff^2 over the local planes [acc_lo, acc_hi)"""
     lo, hi = _rows(u.shape[0], ig0, N, i_lo, i_hi)
     if hi < lo:
         return 0.0

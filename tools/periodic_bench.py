@@ -3,8 +3,8 @@
 [c,L ...] (default 9,7: 513^3, V(2,2), sigma = 0, eps = 1 + 1/2 sin(2 pi x) cos(pi y) where a coefficient is set).
 
 Four contexts per size: the constant operator run launch by launch (MG3D_NO_FUSE=1 at creation: k_smooth_color /
-k_residual), the coefficient operator (k_coef_*), and the periodic kernels with all three axes periodic, constant and with
-eps.  Per context: the finest level's colour pass and residual as single launches (mg3d_smooth / mg3d_residual, kernel
+k_residual), the coefficient operator (the same launchers with eps), and the periodic kernels with all three axes
+periodic, constant and with eps.  Per context: the finest level's colour pass and residual as single launches (mg3d_smooth / mg3d_residual, kernel
 timers), ms per cycle (mg3d_vcycles, best of three timed runs), and -- periodic only -- the coarse direct solve inside the
 cycle (kernel timers of level 0; at c = 9 the wide band takes lu_solve_block_kernel).  Bandwidth is compulsory bytes
 over kernel time: a colour pass reads v and d (and eps) and writes v (24 / 32 B per point), the residual reads v and d
