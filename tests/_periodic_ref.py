@@ -142,6 +142,72 @@ def exact_residual_norm(u, d, e, N, h, sigma, axes):
     return math.sqrt(math.fsum((diff * diff).reshape(-1)))
 
 
+def _i_blocks(N, axes, planes):
+    """[a, b) blocks of `planes` unique i-planes each, and for each the i-planes its stencils read: a-1 .. b, wrapped"""
+    lo = 0 if per(axes, 0) else 1
+    for a in range(lo, N - 1, planes):
+        b = min(a + planes, N - 1)
+        yield a, b, np.arange(a - 1, b + 1) % (N - 1) if per(axes, 0) else np.arange(a - 1, b + 1)
+
+
+def _ext_jk(a, axes):
+    """ext on the j and k axes only: a holds a block of i-planes with their halo, the i-axis is not wrapped here"""
+    for ax in (1, 2):
+        if per(axes, ax):
+            N = a.shape[ax]
+            a = np.concatenate([a.take([N - 2], axis=ax), a.take(np.arange(N - 1), axis=ax), a.take([0], axis=ax)],
+                               axis=ax)
+    return a
+
+
+def _block_sum_diag(u, e, h, sigma, axes, rows):
+    """_sum_diag of the unique points of the i-planes rows[1:-1] (rows: those planes with their one-plane halo)"""
+    X = _ext_jk(u[rows], axes)
+    if e is None:
+        return S._nbr_sum(X), 6.0 + sigma * h * h, X[1:-1, 1:-1, 1:-1]
+    s, dg = CR._sum_diag(X, _ext_jk(e[rows], axes), sigma * h * h)
+    return s, dg, X[1:-1, 1:-1, 1:-1]
+
+
+def colour_pass_blocks(u, d, e, h, sigma, axes, colour, planes=16):
+    """colour_pass evaluated over blocks of `planes` i-planes with a one-plane halo, for fields too large for the
+    whole-array temporaries.  A pass writes points of one colour from neighbours of the other only, so the order of the
+    blocks changes no value: the result is colour_pass's bit for bit."""
+    N = u.shape[0]
+    hSq = h * h
+    _, jb, kb = unique_block(N, axes)
+    j, k = np.arange(N)[jb], np.arange(N)[kb]
+    for a, b, rows in _i_blocks(N, axes, planes):
+        s, dg, _ = _block_sum_diag(u, e, h, sigma, axes, rows)
+        blk = (slice(a, b), jb, kb)
+        if e is None:
+            new = (1.0 / dg) * (s - hSq * d[blk])
+        else:
+            new = (s - hSq * d[blk]) / dg
+        vals = u[blk].copy()
+        i = np.arange(a, b)
+        m = ((i[:, None, None] + j[None, :, None] + k[None, None, :]) & 1) == colour
+        vals[m] = new[m]
+        put(u, vals, blk, axes if a == 0 else axes & 6)  # (the i-duplicates are the copies of plane 0)
+
+
+def residual_blocks(u, d, e, h, sigma, axes, r=None, planes=16):
+    """residual over blocks of i-planes: r (optional) receives what residual() stores there, bit for bit; returns the
+    norm as exact_residual_norm computes it (the squares summed in extended precision; rounding ~ 2^-64 per term)"""
+    N = u.shape[0]
+    invHsq = 1.0 / (h * h)
+    _, jb, kb = unique_block(N, axes)
+    total = np.longdouble(0)
+    for a, b, rows in _i_blocks(N, axes, planes):
+        s, dg, c = _block_sum_diag(u, e, h, sigma, axes, rows)
+        blk = (slice(a, b), jb, kb)
+        diff = d[blk] - invHsq * (s - dg * c)
+        if r is not None:
+            put(r, diff, blk, axes if a == 0 else axes & 6)
+        total += np.sum((diff * diff).astype(np.longdouble))
+    return float(np.sqrt(total))
+
+
 def _written(N, axes):
     """the points the grid transfers compute: 0 .. N-2 on a periodic axis, every index otherwise"""
     return tuple(slice(0, N - 1) if per(axes, ax) else slice(0, N) for ax in range(3))

@@ -70,7 +70,7 @@ def test_vcycle_converges_to_a_physical_potential():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("c,L,nu", [(5, 4, 2), (9, 3, 1), (3, 5, 2), (5, 5, 3)])
+@pytest.mark.parametrize("c,L,nu", [(5, 4, 2), (9, 3, 1), (3, 5, 2), (5, 5, 3), (11, 3, 2), (13, 3, 2)])
 def test_gpu_matches_the_statement(c, L, nu):
     import multigrid_parallel_amd as M
     from multigrid_parallel_amd.binding import MG3D_U

@@ -73,6 +73,28 @@ def test_parity(monkeypatch, P, nu, sigma, field, min_planes):
     assert norms[-1] == pytest.approx(exact, rel=EXACT_NORM_RTOL)
 
 
+# coarse grids off the 2^k+1 ladder, every rank at least 8 planes on the levels it splits: 97^3 on 3 ranks, 81^3 on 2,
+# on 4 and on 3 (owned planes 12, 14, 15 on the first split level, 41^3)
+_OFF_LADDER = [(7, 5, 3, "exp"), (11, 4, 2, "ball"), (6, 5, 4, "smooth"), (6, 5, 3, "exp")]
+
+
+@pytest.mark.parametrize("sigma", [0.0, 1e3])
+@pytest.mark.parametrize("nu", [1, 3])
+@pytest.mark.parametrize("c,L,P,field", _OFF_LADDER)
+def test_parity_off_ladder(monkeypatch, c, L, P, field, nu, sigma):
+    monkeypatch.setenv("MG3D_SLAB_MIN_PLANES", "8")
+    eps = R.FIELDS[field](_n(c, L))
+    want_norms, want_u, want_d = _single(c, L, nu, sigma, eps)
+    norms, u, dd, exact, first = _dist(c, L, nu, P, sigma, eps)
+    assert 1 <= first < L, first
+    for l in range(L):
+        assert _same_bits(u[l], want_u[l]), f"u level {l}"
+    for l in range(L - 1):
+        assert _same_bits(dd[l], want_d[l]), f"d level {l}"
+    np.testing.assert_allclose(norms, want_norms, rtol=1e-11, atol=0)
+    assert norms[-1] == pytest.approx(exact, rel=EXACT_NORM_RTOL)
+
+
 @pytest.mark.parametrize("policy", ["coarse_gather", "no_overlap", "keep_residual"])
 @pytest.mark.parametrize("c,L,nu,P,min_planes", [(5, 5, 2, 4, 8), (9, 5, 2, 8, 16), (3, 6, 1, 3, 8), (9, 5, 3, 2, 16)])
 def test_policies_same_bits(monkeypatch, policy, c, L, nu, P, min_planes):
