@@ -121,6 +121,44 @@ enum { MG3D_PERIODIC_I = 1, MG3D_PERIODIC_J = 2, MG3D_PERIODIC_K = 4 };
 int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes);
 int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes);
 
+/* Neumann boundaries per face.  faces is a mask of MG3D_NEUMANN_ILO / _IHI / _JLO / _JHI / _KLO / _KHI (any of 0..63); 0
+ * is the operator without Neumann faces, bit for bit and with the same schedules and launches.  A level keeps its N
+ * points per side and its layouts.  A point on a Neumann face is an UNKNOWN -- an edge or corner point too, unless it
+ * also lies on a Dirichlet face: then it is a Dirichlet point that nothing writes.  There are no duplicates and nothing
+ * outside the array.  The operator imposes the homogeneous condition du/dn = 0 by reflection: at index 0 of a Neumann low
+ * face the -1 neighbour is read at index 1, at index N-1 of a Neumann high face the +1 neighbour at N-2, for u and, with
+ * a coefficient, for eps as well (the face coefficient 0.5*(eps_0 + eps_1) then counts twice); smoother and residual keep
+ * their arithmetic and operand order, and red-black colours stay (i + j + k) & 1 over all unknowns (a reflected
+ * neighbour has the other colour: any c >= 3).  The restriction fully weights every coarse unknown, Neumann face points
+ * included, with reflected fine neighbours; the prolongation corrects the Neumann face points; eps goes down the
+ * hierarchy by injection; the coarse matrix is mg3d_coarse_matrix_bc; the residual norm counts every unknown once.
+ * With periodic axes the masks combine per axis: an axis is periodic, or each of its two faces is Dirichlet or Neumann; a
+ * Neumann bit on a periodic axis is MG3D_ERR_ARG from whichever of the two setters is called second.
+ * Singular case: sigma = 0 and every axis either periodic or Neumann on both faces -- constants are in the kernel.  The
+ * coarse matrix then pins unknown (0,0,0) of level 0 to 0 (identity row, right-hand side taken as 0), as the periodic
+ * case does, and the library projects neither f nor u.  The reflected operator is not symmetric: its left null vector
+ * is the trapezoid weight w = 1/2 per Neumann face a point lies on (1/4 on an edge of two, 1/8 at a corner of three), so
+ * the compatibility condition is WEIGHTED: sum of w*f over the unknowns = 0; the residual stalls at that weighted mean
+ * otherwise.
+ * A prescribed flux g = du/dn (outward normal) keeps the operator homogeneous and is folded into the right-hand side by
+ * mg3d_neumann_fold_flux (below) before the upload.
+ * A mask outside 0..63, or a bit on a periodic axis, is MG3D_ERR_ARG and changes nothing; otherwise, as for
+ * mg3d_ctx_set_periodic, a cycle that has run ahead is finished first with the operator it started with and a factor of
+ * mg3d_ctx_build_coarse is rebuilt (one of mg3d_ctx_set_lu / mg3d_es_setup dropped); the same mask again changes
+ * nothing.  With a nonzero mask the fused schedules and their options do not apply (values kept), and mg3d_es_*,
+ * mg3d_fmg_initialize and mg3d_fill_boundary return MG3D_ERR_STATE.  The slab (mg3d_dist_*), fp32 (mg3d32_*) and
+ * mg3d_host_* forms have no Neumann mode.  mg3d_ctx_set_coefficient checks and keeps eps on Neumann faces: they are read. */
+enum {
+    MG3D_NEUMANN_ILO = 1,
+    MG3D_NEUMANN_IHI = 2,
+    MG3D_NEUMANN_JLO = 4,
+    MG3D_NEUMANN_JHI = 8,
+    MG3D_NEUMANN_KLO = 16,
+    MG3D_NEUMANN_KHI = 32
+};
+int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces);
+int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces);
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -373,6 +411,13 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  * mg3d_coarse_matrix_shift: the same for the screened operator (diagonal -(6 + sigma*h^2)/h^2; sigma = 0: the same bytes)
  * mg3d_coarse_matrix_coef : the same for the variable-coefficient operator (mg3d_ctx_set_coefficient; eps dense N^3)
  * mg3d_coarse_matrix_periodic: the same with periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
+ * mg3d_coarse_matrix_bc   : the same with periodic axes and Neumann faces (mg3d_ctx_set_neumann): reflected rows for the
+ *                           Neumann face unknowns; neumann_faces = 0: mg3d_coarse_matrix_periodic, the same bytes
+ * mg3d_neumann_fold_flux  : a prescribed outward normal derivative g folded into the right-hand side d (dense N^3) of the
+ *                           homogeneous Neumann operator: d -= 2*a*g/h at each point of each Neumann face in `faces`, a = 1
+ *                           (eps NULL) or 0.5*(eps_face + eps_inner), summed over the faces an edge or corner point lies
+ *                           on.  g[f] (f = 0..5: ilo, ihi, jlo, jhi, klo, khi) is a dense N^2 array over the face's other
+ *                           two indices in i, j, k order, NULL = 0; g itself may be NULL.  Returns MG3D_OK or MG3D_ERR_ARG.
  * mg3d_lu_factor          : convertToLU_InPlace (gauss_elim.h:9-29)
  * mg3d_lu_solve_host      : NOT provided -- the solve runs on the device only
  * mg3d_l2norm_host        : GetL2NormOfVector (mg_3d.h:783-792)
@@ -385,6 +430,10 @@ void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma);
 void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma); /* host only, A zeroed by caller */
 void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
                                  int axes); /* host only, A zeroed by caller; axes = 0: _shift / _coef */
+void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
+                           int periodic_axes, int neumann_faces); /* host only, A zeroed by caller */
+int mg3d_neumann_fold_flux(double *d, const double *eps /* NULL: constant */, int N, double h, int faces,
+                           const double *const *g);
 void mg3d_lu_factor(double *a, int n);
 double mg3d_l2norm_host(const double *d, long n);
 void mg3d_smooth_edges_host(double *u, int N);

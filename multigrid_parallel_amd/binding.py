@@ -50,6 +50,8 @@ SIGNATURES = {
     "mg3d_ctx_get_coefficient": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_ctx_set_periodic": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_ctx_get_periodic": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mg3d_ctx_set_neumann": (C.c_int, [C.c_void_p, C.c_int]),
+    "mg3d_ctx_get_neumann": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mg3d_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_zero": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -122,6 +124,8 @@ SIGNATURES = {
     "mg3d_coarse_matrix_shift": (None, [dp, C.c_int, C.c_double, C.c_double]),
     "mg3d_coarse_matrix_coef": (None, [dp, C.c_int, C.c_double, dp, C.c_double]),
     "mg3d_coarse_matrix_periodic": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int]),
+    "mg3d_coarse_matrix_bc": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int]),
+    "mg3d_neumann_fold_flux": (C.c_int, [dp, dp, C.c_int, C.c_double, C.c_int, C.POINTER(dp)]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
     "mg3d_smooth_edges_host": (None, [dp, C.c_int]),
@@ -164,6 +168,9 @@ SIGNATURES = {
     "mg3d32_dist_fmg_initialize": (C.c_int, [C.c_void_p]),
     "mg3d32_dist_sync": (C.c_int, [C.c_void_p]),
 }
+
+
+NEUMANN_FACES = ("ilo", "ihi", "jlo", "jhi", "klo", "khi")  # bit f of the MG3D_NEUMANN_* mask
 
 
 class EsParams(C.Structure):
@@ -345,6 +352,71 @@ class Solver:
         v = C.c_int(0)
         check(self.L.mg3d_ctx_get_periodic(self._h, C.byref(v)))
         return v.value
+
+    def set_neumann(self, faces):
+        """mg3d_ctx_set_neumann: homogeneous Neumann faces (du/dn = 0 by reflection) given as a mask (MG3D_NEUMANN_ILO = 1,
+        _IHI = 2, _JLO = 4, _JHI = 8, _KLO = 16, _KHI = 32) or as an iterable of names "ilo", "ihi", "jlo", "jhi", "klo",
+        "khi"; 0 or () gives none again.  A point on a Neumann face is an unknown unless it also lies on a Dirichlet face.
+        An axis is periodic or has Neumann faces, not both.  With sigma = 0 and every axis periodic or Neumann on both faces
+        the operator is singular: u is fixed only up to a constant (the coarse solve pins point (0,0,0) of level 0) and d
+        must satisfy sum(compatibility_weights() * d) = 0, else the residual stalls -- nothing projects d or u.
+        A prescribed flux goes into d with fold_flux().  Rebuilds a coarse factor of get_details(); drops one given to
+        set_lu."""
+        if not isinstance(faces, (int, np.integer)):
+            mask = 0
+            for f in faces:
+                if f not in NEUMANN_FACES:
+                    raise ValueError(f"set_neumann: face {f!r} (need one of {', '.join(NEUMANN_FACES)})")
+                mask |= 1 << NEUMANN_FACES.index(f)
+            faces = mask
+        check(self.L.mg3d_ctx_set_neumann(self._h, int(faces)))
+
+    @property
+    def neumann(self):
+        """the mask of Neumann faces"""
+        v = C.c_int(0)
+        check(self.L.mg3d_ctx_get_neumann(self._h, C.byref(v)))
+        return v.value
+
+    def compatibility_weights(self):
+        """(N, N, N) weights w of the compatibility condition of the singular case: 1/2 per Neumann face a point of the
+        finest level lies on (1/4 on an edge of two, 1/8 at a corner of three), 1 elsewhere among the unknowns, 0 at
+        Dirichlet points and periodic duplicates.  w is the left null vector of the reflected operator: d is compatible
+        when (w * d).sum() == 0; subtract (w * d).sum() / w.sum() from d otherwise."""
+        N, per, neu = self.N, self.periodic, self.neumann
+        w = np.ones((N, N, N))
+        for ax in range(3):
+            lo, hi = [slice(None)] * 3, [slice(None)] * 3
+            lo[ax], hi[ax] = 0, N - 1
+            if (per >> ax) & 1:
+                w[tuple(hi)] = 0.
+                continue
+            for sl, bit in ((lo, 2 * ax), (hi, 2 * ax + 1)):
+                w[tuple(sl)] *= 0.5 if (neu >> bit) & 1 else 0.
+        return w
+
+    def fold_flux(self, d, flux):
+        """mg3d_neumann_fold_flux: folds a prescribed outward normal derivative g = du/dn into the right-hand side d
+        ((N, N, N) float64, changed in place and returned) of the finest level: d -= 2 a g / h at each point of each
+        Neumann face, a = 1 or, with a coefficient, the mean of eps at the face point and the point inside it.  flux maps
+        face names ("ilo" ... "khi") to (N, N) arrays over the face's other two indices in i, j, k order; faces left out
+        have g = 0.  Every face named must be a Neumann face of the solver."""
+        N = self.N
+        if not (isinstance(d, np.ndarray) and d.dtype == np.float64 and d.shape == (N, N, N) and d.flags.c_contiguous):
+            raise TypeError(f"fold_flux: d must be a C-contiguous float64 array of shape ({N},)*3")
+        faces = self.neumann
+        keep, ptrs = [], (dp * 6)()
+        for name, g in flux.items():
+            if name not in NEUMANN_FACES or not (faces >> NEUMANN_FACES.index(name)) & 1:
+                raise ValueError(f"fold_flux: {name!r} is not a Neumann face of this solver")
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != (N, N):
+                raise ValueError(f"fold_flux: flux[{name!r}] needs shape ({N}, {N}), got {g.shape}")
+            keep.append(g)
+            ptrs[NEUMANN_FACES.index(name)] = P(g)
+        eps = np.ascontiguousarray(self.coefficient()).reshape(-1) if self.has_coefficient() else None
+        check(self.L.mg3d_neumann_fold_flux(P(d.reshape(-1)), None if eps is None else P(eps), N, self.h, faces, ptrs))
+        return d
 
     def setup_boundary_conditions(self, field=MG3D_D, level=None):
         level = self.num_levels - 1 if level is None else level

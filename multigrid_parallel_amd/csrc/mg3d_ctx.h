@@ -41,6 +41,9 @@ struct mg3d_ctx {
      * right-hand side of the direct solve that k_per_coarse_rhs builds from d (allocated with the first nonzero mask) */
     int periodic;
     double *per_b;
+    /* Neumann faces (mg3d_ctx_set_neumann; MG3D_NEUMANN_* mask, no bit on a periodic axis; 0: none).  The kernels take
+     * both masks as one boundary word (mg3d_ctx_bc) */
+    int neumann;
     double *lu_work;  /* 2n doubles */
     double *partials; /* MG3D_MAX_PARTIALS doubles */
     double *sumsq;    /* device slots for squared norms */
@@ -88,8 +91,23 @@ struct mg3d_ctx {
 static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
  * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
- * them, nor with a periodic axis, whose levels run those with wrapped neighbours and the k_per_* transfers */
-static inline bool mg3d_fused(const mg3d_ctx *ctx) { return ctx->fused && ctx->eps.empty() && ctx->periodic == 0; }
+ * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
+ * k_per_* transfers */
+static inline bool mg3d_fused(const mg3d_ctx *ctx)
+{
+    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0;
+}
+/* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */
+static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodic, ctx->neumann); }
+/* sigma = 0 and every axis periodic or Neumann on both faces: constants are in the kernel, unknown (0,0,0) of level 0 is
+ * pinned */
+static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
+{
+    bool closed = true;
+    for (int ax = 0; ax < 3; ax++)
+        closed = closed && ((ctx->periodic >> ax & 1) || (ctx->neumann >> (2 * ax) & 3) == 3);
+    return closed && ctx->sigma == 0.;
+}
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
 /* records a failure text for mg3d_last_error() and returns `code` */

@@ -268,6 +268,7 @@ static mg3d_ctx *ctx_new(int L, int iters)
     ctx->lu_built = false;
     ctx->lu_h = 0.;
     ctx->periodic = 0;
+    ctx->neumann = 0;
     ctx->per_b = nullptr;
     memset(&ctx->lu, 0, sizeof ctx->lu);
     memset(&ctx->lu_in, 0, sizeof ctx->lu_in);
@@ -633,8 +634,9 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    if (ctx->periodic)
-        mg3d_coarse_matrix_periodic(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic);
+    if (ctx->periodic || ctx->neumann)
+        mg3d_coarse_matrix_bc(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
+                              ctx->neumann);
     else if (ctx->eps.empty())
         mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
     else
@@ -792,6 +794,25 @@ extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
     return MG3D_OK;
 }
 
+/* The boundary masks changed from (periodic, neumann) = (per0, neu0): the coarse faces that the restriction weighted are
+ * injections again (and vice versa), so every level's are redone; and on a face that was a face of unknowns and is a
+ * Dirichlet face now, r of every level still holds the residuals of the other operator where a Dirichlet cycle never
+ * writes and the injection reads -- zeroed, as in a context that never had the mask. */
+static void boundary_changed(mg3d_ctx *ctx, int per0, int neu0)
+{
+    auto unknown_faces = [](int per, int neu) {
+        int m = neu;
+        for (int ax = 0; ax < 3; ax++)
+            if (per >> ax & 1)
+                m |= 3 << (2 * ax);
+        return m;
+    };
+    const int back = unknown_faces(per0, neu0) & ~unknown_faces(ctx->periodic, ctx->neumann);
+    for (int l = 0; l < ctx->L; l++)
+        k_zero_faces(ctx->lv[l].g, ctx->lv[l].f[MG3D_R], back, ctx->stream);
+    std::fill(ctx->faces_dirty.begin(), ctx->faces_dirty.end(), 1);
+}
+
 /* Periodic axes (mg3d_kernels.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
  * changes -- a mask outside 0..7, or a nonzero one on a hierarchy whose coarsest level has fewer than 4 or an odd number
  * of unique points per side, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that has run ahead is finished with the
@@ -807,6 +828,10 @@ extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
     if (axes && ((N0 - 1) % 2 != 0 || N0 - 1 < 4))
         return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: the coarsest level has %d points per side (c - 1 must be even and >= 4)",
                     N0);
+    for (int ax = 0; ax < 3; ax++)
+        if ((axes >> ax & 1) && (ctx->neumann >> (2 * ax) & 3))
+            return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: axis %d has a Neumann face (mg3d_ctx_set_neumann: mask %d)", ax,
+                        ctx->neumann);
     CHK(mg3d_drop_carry(ctx));
     if (axes == ctx->periodic)
         return MG3D_OK;
@@ -818,9 +843,9 @@ extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
                         hipGetErrorString(rc));
         }
     }
+    const int per0 = ctx->periodic;
     ctx->periodic = axes;
-    /* the coarse faces that the periodic restriction weighted are injections again (and vice versa): redo them */
-    std::fill(ctx->faces_dirty.begin(), ctx->faces_dirty.end(), 1);
+    boundary_changed(ctx, per0, ctx->neumann);
     return operator_changed(ctx);
 }
 
@@ -829,6 +854,45 @@ extern "C" int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes)
     if (!ctx || !axes)
         return fail(MG3D_ERR_ARG, "mg3d_ctx_get_periodic: NULL argument");
     *axes = ctx->periodic;
+    return MG3D_OK;
+}
+
+/* Neumann faces (mg3d_kernels.hip): a mask of MG3D_NEUMANN_ILO ... _KHI.  The argument is checked before anything changes
+ * -- a mask outside 0..63, or one with a bit on a periodic axis, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that
+ * has run ahead is finished with the operator it started with and the coarse factor is rebuilt (mg3d_ctx_build_coarse) or
+ * dropped.  0: no Neumann face again, the fused schedules included (when no axis is periodic). */
+extern "C" int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces)
+{
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: NULL context");
+    if (faces < 0 || faces > 63)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: faces = %d (a mask of MG3D_NEUMANN_ILO ... _KHI, 0..63)", faces);
+    for (int ax = 0; ax < 3; ax++)
+        if ((ctx->periodic >> ax & 1) && (faces >> (2 * ax) & 3))
+            return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: faces = %d has a bit on periodic axis %d (mg3d_ctx_set_periodic: mask %d)",
+                        faces, ax, ctx->periodic);
+    CHK(mg3d_drop_carry(ctx));
+    if (faces == ctx->neumann)
+        return MG3D_OK;
+    if (faces && !ctx->per_b) { /* the pinned right-hand side of the direct solve (k_per_coarse_rhs) */
+        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
+        if (rc != hipSuccess) {
+            ctx->per_b = nullptr;
+            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_neumann: hipMalloc: %s",
+                        hipGetErrorString(rc));
+        }
+    }
+    const int neu0 = ctx->neumann;
+    ctx->neumann = faces;
+    boundary_changed(ctx, ctx->periodic, neu0);
+    return operator_changed(ctx);
+}
+
+extern "C" int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces)
+{
+    if (!ctx || !faces)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_neumann: NULL argument");
+    *faces = ctx->neumann;
     return MG3D_OK;
 }
 
@@ -1004,11 +1068,11 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, ctx->periodic, c1 ^ (it & 1), s);
+        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), c1 ^ (it & 1), s);
     }
     if (want_res) {
         StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-        k_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, ctx->periodic, want_res == 2 ? l.f[MG3D_R] : nullptr,
+        k_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), want_res == 2 ? l.f[MG3D_R] : nullptr,
                    ctx->partials, ctx->sumsq + slot, s);
     }
     return MG3D_OK;
@@ -1036,12 +1100,12 @@ static bool pro_fusable(const mg3d_ctx *ctx, int iters, int want_res, int level)
     return !first_has_res;
 }
 
-/* the unfused grid transfers and the direct solve: periodic forms when an axis is periodic */
+/* the unfused grid transfers and the direct solve: the k_per_* forms when an axis is periodic or a face is a Neumann face */
 static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    if (ctx->periodic)
-        k_per_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->periodic, ctx->stream);
+    if (mg3d_ctx_bc(ctx))
+        k_per_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], mg3d_ctx_bc(ctx), ctx->stream);
     else
         k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, faces_only);
 }
@@ -1049,22 +1113,22 @@ static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
 static void enqueue_prolong(mg3d_ctx *ctx, int level)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    if (ctx->periodic)
-        k_per_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], ctx->periodic, ctx->stream);
+    if (mg3d_ctx_bc(ctx))
+        k_per_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
     else
         k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], ctx->stream);
 }
 
-/* periodic: the factor of mg3d_coarse_matrix_periodic solves for b = d with 0 in the identity rows of the duplicates and,
- * all three axes periodic with sigma = 0, of the pinned point (0,0,0); the duplicates of x are then copied from their
- * sources */
+/* periodic: the factor of mg3d_coarse_matrix_bc solves for b = d with 0 in the identity rows of the duplicates and, in
+ * the singular case (mg3d_ctx_pinned), of the pinned point (0,0,0); the duplicates of x are then copied from their
+ * sources.  Neumann faces alone have no duplicates: only the pinned case takes the detour over per_b */
 static void enqueue_coarse_solve(mg3d_ctx *ctx)
 {
     Level &l0 = ctx->lv[0];
-    if (ctx->periodic) {
-        k_per_coarse_rhs(l0.g, l0.f[MG3D_D], ctx->per_b, ctx->periodic, ctx->periodic == 7 && ctx->sigma == 0., ctx->stream);
+    if (ctx->periodic || (ctx->neumann && mg3d_ctx_pinned(ctx))) {
+        k_per_coarse_rhs(l0.g, l0.f[MG3D_D], ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->stream);
         k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
-        k_per_refresh(l0.g, l0.f[MG3D_U], ctx->periodic, ctx->stream);
+        k_per_refresh(l0.g, l0.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
         return;
     }
     k_lu_solve(ctx->lu, ctx->lu_in, l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu_work, ctx->stream);
@@ -1570,6 +1634,8 @@ extern "C" int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level)
     CHK(check_field_level(ctx, field, level, "mg3d_fill_boundary"));
     if (ctx->periodic) /* BCFunc is defined on all six faces */
         return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
+    if (ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     k_fill_boundary(ctx->lv[level].g, ctx->lv[level].f[field], ctx->lv[level].h, ctx->stream);
     mg3d_ctx_touched(ctx, field, level);
     return launch_ok("mg3d_fill_boundary");
@@ -1583,6 +1649,8 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         return fail(MG3D_ERR_ARG, "mg3d_fmg_initialize: NULL context");
     if (ctx->periodic) /* the F-cycle start fills BCFunc into all six faces */
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
+    if (ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: no coarse LU set");
     if (ctx->have_es)

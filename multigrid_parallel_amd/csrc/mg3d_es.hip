@@ -173,6 +173,8 @@ extern "C" int mg3d_es_setup(mg3d_ctx *ctx, const mg3d_es_params *p)
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
+    if (ctx && ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (!ctx || !p || !(p->length > 0.))
         return fail(MG3D_ERR_ARG, "mg3d_es_setup: bad arguments");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
@@ -215,6 +217,8 @@ extern "C" int mg3d_es_smooth(mg3d_ctx *ctx, int level, int post, int iters)
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
+    if (ctx && ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (!ctx || !ctx->have_es || level < 0 || level >= ctx->L || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_es_smooth: bad arguments (mg3d_es_setup first)");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
@@ -264,6 +268,8 @@ extern "C" int mg3d_es_vcycles(mg3d_ctx *ctx, int count, double *norms)
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
+    if (ctx && ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (!ctx || count < 0 || !ctx->have_es)
         return fail(MG3D_ERR_ARG, "mg3d_es_vcycles: bad arguments (mg3d_es_setup first)");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */

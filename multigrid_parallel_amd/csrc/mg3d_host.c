@@ -167,6 +167,95 @@ void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, 
             }
 }
 
+/* The coarsest matrix with periodic axes and Neumann faces (mg3d_ctx_set_neumann; faces a MG3D_NEUMANN_* mask with no bit
+ * on a periodic axis).  faces = 0: mg3d_coarse_matrix_periodic, the same bytes.  Otherwise its rows, except that a point
+ * on a Neumann face is an unknown unless it lies on a Dirichlet face, and its row is the row of the kernels of
+ * mg3d_kernels.hip with the neighbour across the face reflected (i-1 at 0 is 1, i+1 at N-1 is N-2): the two coincide, so
+ * that column receives the sum of both entries, added in the kernels' operand order (i-, i+, j-, j+, k-, k+).  The pin
+ * (identity row of point (0,0,0)) applies when sigma = 0 and every axis is periodic or Neumann on both faces.
+ * Reflection does not widen the band.  A must be zero on entry. */
+void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double sigma, int axes, int faces)
+{
+    if (faces == 0) {
+        mg3d_coarse_matrix_periodic(A, N, h, eps, sigma, axes);
+        return;
+    }
+    const long NN = (long)N * N, n = NN * N;
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double shift = sigma * hSq;
+    const double dg0 = 6. + shift;
+    const double off = 1. * invHsq, diag = dg0 * invHsq;
+    int per[3], rlo[3], rhi[3], closed = 1;
+    for (int ax = 0; ax < 3; ax++) {
+        per[ax] = (axes >> ax) & 1;
+        rlo[ax] = (faces >> (2 * ax)) & 1;
+        rhi[ax] = (faces >> (2 * ax + 1)) & 1;
+        closed = closed && (per[ax] || (rlo[ax] && rhi[ax]));
+    }
+    const int pin = closed && sigma == 0.;
+    const long st[3] = {NN, N, 1};
+    long p = 0;
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++)
+            for (int k = 0; k < N; k++, p++) {
+                double *row = A + p * n;
+                const int x[3] = {i, j, k};
+                int fixed = pin && p == 0;
+                long q[6];
+                for (int ax = 0; ax < 3; ax++) {
+                    if (per[ax] ? x[ax] == N - 1 : ((x[ax] == 0 && !rlo[ax]) || (x[ax] == N - 1 && !rhi[ax])))
+                        fixed = 1; /* a duplicate, or on a Dirichlet face */
+                    const int lo = x[ax] == 0 ? (per[ax] ? N - 2 : 1) : x[ax] - 1;
+                    const int hi = (per[ax] && x[ax] == N - 2) ? 0 : (x[ax] == N - 1 ? N - 2 : x[ax] + 1);
+                    q[2 * ax] = p + (lo - x[ax]) * st[ax];
+                    q[2 * ax + 1] = p + (hi - x[ax]) * st[ax];
+                }
+                if (fixed) {
+                    row[p] = 1.;
+                    continue;
+                }
+                if (!eps) {
+                    for (int t = 0; t < 6; t++)
+                        row[q[t]] += off;
+                    row[p] = -diag;
+                    continue;
+                }
+                const double e = eps[p];
+                double a[6];
+                for (int t = 0; t < 6; t++)
+                    a[t] = 0.5 * (e + eps[q[t]]);
+                const double dg = ((((a[0] + a[1]) + a[2]) + a[3]) + a[4]) + a[5] + shift;
+                for (int t = 0; t < 6; t++)
+                    row[q[t]] += a[t] * invHsq;
+                row[p] = -(dg * invHsq);
+            }
+}
+
+/* A prescribed outward normal derivative folded into the right-hand side of the homogeneous Neumann operator (mg3d.h) */
+int mg3d_neumann_fold_flux(double *d, const double *eps, int N, double h, int faces, const double *const *g)
+{
+    if (!d || N < 3 || !(h > 0.) || faces < 0 || faces > 63)
+        return MG3D_ERR_ARG;
+    if (!g)
+        return MG3D_OK;
+    const long st[3] = {(long)N * N, N, 1};
+    for (int f = 0; f < 6; f++) {
+        if (!((faces >> f) & 1) || !g[f])
+            continue;
+        const int ax = f / 2, hi = f & 1;
+        const int a1 = ax == 0 ? 1 : 0, a2 = ax == 2 ? 1 : 2; /* the face's other two axes, in i, j, k order */
+        const long base = hi ? (long)(N - 1) * st[ax] : 0, inner = hi ? -st[ax] : st[ax];
+        for (int s = 0; s < N; s++)
+            for (int t = 0; t < N; t++) {
+                const long p = base + s * st[a1] + t * st[a2];
+                const double a = eps ? 0.5 * (eps[p] + eps[p + inner]) : 1.;
+                d[p] = d[p] - 2. * a * g[f][(long)s * N + t] / h;
+            }
+    }
+    return MG3D_OK;
+}
+
 /* The coarsest operator of the mixed-boundary problem (csrc/mg3d_es.hip): constructCoarseMatrixA (identity rows on
  * the boundary, mg_3d.h:179-185) except that a wall point -- a face point with an interior point in front of it that is
  * not part of a Dirichlet patch -- gets the row  x_wall - x_front = b_wall, the zero-gradient condition the smoother

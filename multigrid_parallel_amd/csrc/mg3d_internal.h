@@ -100,14 +100,16 @@ const char *mg3d_option_key(int index);           /* NULL past the end */
 /* launchers (mg3d_kernels.hip); all asynchronous on `s` */
 /* One colour pass in place and the residual of a level's operator: e = eps of the level in the padded layout for
  * div(eps grad u) - sigma u (mg3d_ctx_set_coefficient), NULL for the constant operator of op; sigma the context's shift;
- * axes the MG3D_PERIODIC_* mask of wrapped axes (mg3d_ctx_set_periodic; single-domain levels only, no windows), whose
- * duplicate points receive copies.  The residual writes res (optional) on the interior and partials (one per block),
+ * bc the boundary word mg3d_bc(periodic, neumann): the MG3D_PERIODIC_* mask of wrapped axes (mg3d_ctx_set_periodic), whose
+ * duplicate points receive copies, and above it the MG3D_NEUMANN_* mask of reflected faces (mg3d_ctx_set_neumann), whose
+ * points are unknowns; nonzero on single-domain levels only, no windows.  The residual writes res (optional) on the interior and partials (one per block),
  * then reduces them, in a fixed order, into *sumsq_out.  Windows as k_sweep's: i_lo / i_hi the local planes produced,
  * acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
+static inline int mg3d_bc(int periodic, int neumann) { return periodic | neumann << 3; }
 void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int axes, int color, hipStream_t s, int i_lo = -1, int i_hi = -1);
+                    int bc, int color, hipStream_t s, int i_lo = -1, int i_hi = -1);
 void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                int axes, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
+                int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
                 int acc_lo = 0, int acc_hi = -1);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
@@ -170,13 +172,15 @@ void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, co
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
 /* eps of the coarser level by injection at every point */
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
-/* periodic axes (axes = MG3D_PERIODIC_* mask, single-domain levels): restriction (full weighting on periodic faces),
- * prolongation, the coarse right-hand side (0 in the duplicates' and the pinned point's identity rows) and a duplicate
- * refresh */
-void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int axes, hipStream_t s);
-void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int axes, hipStream_t s);
-void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int axes, int pin, hipStream_t s);
-void k_per_refresh(const Geom &g, double *v, int axes, hipStream_t s);
+/* periodic axes and Neumann faces (bc = mg3d_bc(periodic, neumann), single-domain levels): restriction (full weighting on
+ * periodic and Neumann faces), prolongation, the coarse right-hand side (0 in the duplicates' and the pinned point's
+ * identity rows) and a duplicate refresh */
+void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s);
+void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s);
+void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s);
+void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
+/* zeros on the faces of a single-domain level given as a MG3D_NEUMANN_* mask */
+void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

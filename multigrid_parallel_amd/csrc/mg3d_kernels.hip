@@ -35,6 +35,21 @@
  *     Dirichlet face, with wrapped fine neighbours on periodic axes; Dirichlet faces are injected as before.
  *   - Prolongation: the parent order of prolong_kernel, the coarse "high" parent wrapped to 0 on a periodic axis.
  *   tests/_periodic_ref.py states the same in numpy.
+ *
+ * Neumann faces (mg3d_ctx_set_neumann; a mask of MG3D_NEUMANN_ILO = 1, _IHI = 2, _JLO = 4, _JHI = 8, _KLO = 16, _KHI = 32
+ * on the non-periodic axes; single-domain levels only).  A point on a Neumann face is an unknown; where it also lies on
+ * a Dirichlet face it is a Dirichlet point.  Nothing is duplicated and nothing lies outside the array: homogeneous
+ * du/dn = 0 is imposed by REFLECTION -- at index 0 of a Neumann low face the -1 neighbour is read at index 1, at N-1 of
+ * a Neumann high face the +1 neighbour at N-2, for v and for eps alike.  The unknowns of an axis are [lo, hi] with lo = 0
+ * on a periodic axis or a Neumann low face, else 1, and hi = N-1 on a Neumann high face, else N-2.
+ *   - Colour pass and residual keep the arithmetic above exactly; a reflected neighbour has the other colour.
+ *   - Restriction: full weighting on every coarse unknown, reflected fine neighbours at Neumann faces.
+ *   - Prolongation: unchanged -- every parent of a fine face point lies on the same face.
+ *   tests/_neumann_ref.py states the same in numpy.
+ *
+ * The launchers take both masks as one boundary word bc = periodic axes | Neumann faces << 3 (mg3d_bc); the stencil
+ * kernels are instantiated per boundary mode: BC_PLAIN (bc = 0), BC_WRAP (periodic axes only), BC_REFLECT (a Neumann
+ * face, with or without periodic axes).
  */
 #include "mg3d_internal.h"
 
@@ -50,9 +65,23 @@ __device__ __forceinline__ long long gidx(const Geom &g, int i, int j, int k)
     return g.plane * i + (long long)g.pitch * j + k;
 }
 
-/* the offsets to the -1 / +1 neighbour along an axis of stride `st` at index x (unique range), wrapped when periodic */
-__device__ __forceinline__ long long nb_lo(int x, int N, bool per, long long st) { return (per && x == 0) ? (N - 2) * st : -st; }
-__device__ __forceinline__ long long nb_hi(int x, int N, bool per, long long st) { return (per && x == N - 2) ? -(N - 2) * st : st; }
+/* boundary modes of the stencil kernels and the bits of the boundary word */
+enum { BC_PLAIN = 0, BC_WRAP = 1, BC_REFLECT = 2 };
+static inline int bc_mode(int bc) { return (bc >> 3) ? BC_REFLECT : (bc ? BC_WRAP : BC_PLAIN); }
+/* is the low / high face of axis ax (0 i, 1 j, 2 k) a Neumann face */
+__host__ __device__ __forceinline__ bool bc_ref_lo(int bc, int ax) { return (bc >> (3 + 2 * ax)) & 1; }
+__host__ __device__ __forceinline__ bool bc_ref_hi(int bc, int ax) { return (bc >> (4 + 2 * ax)) & 1; }
+
+/* the offsets to the -1 / +1 neighbour along an axis of stride `st` at index x (an unknown): plain, wrapped when the axis
+ * is periodic (0 reads N-2, N-2 reads 0), reflected at a Neumann face (rlo: 0 reads 1; rhi: N-1 reads N-2) */
+__device__ __forceinline__ long long nb_lo(int x, int N, bool per, bool rlo, long long st)
+{
+    return (per && x == 0) ? (N - 2) * st : ((rlo && x == 0) ? st : -st);
+}
+__device__ __forceinline__ long long nb_hi(int x, int N, bool per, bool rhi, long long st)
+{
+    return (per && x == N - 2) ? -(N - 2) * st : ((rhi && x == N - 1) ? -st : st);
+}
 
 /* x to p and to every duplicate of p: di / dj / dk say whether p lies on the periodic face 0 of that axis */
 __device__ __forceinline__ void store_dup(const Geom &g, double *__restrict__ a, long long p, double x, bool di, bool dj,
@@ -72,7 +101,9 @@ __device__ __forceinline__ void store_dup(const Geom &g, double *__restrict__ a,
 /* ------------------------------------------------------------------ stencils
  * One kernel family for the colour pass and the residual of every operator above, templated on what differs:
  *   COEF  eps is set: face means and an IEEE division instead of the constant `sixth`
- *   PER   an axis is periodic: wrapped neighbour offsets and duplicate stores; PER = false folds to the plain offsets
+ *   BC    the boundary mode: BC_PLAIN folds to the plain offsets; BC_WRAP an axis is periodic: wrapped neighbour offsets
+ *         and duplicate stores; BC_REFLECT a face is a Neumann face: reflected offsets there, the unknowns of an axis are
+ *         [lo, hi], and whatever axis is periodic beside it wraps as in BC_WRAP
  * The residual and the colour pass with eps give each thread one (j, k) column of `chunk` planes, lanes contiguous in
  * k, and keep the i-1 / i / i+1 values of v (and eps) of the column in registers; the constant colour pass gives a lane
  * one k-pair of a row (measured at 513^3 the column form of that pass took 0.76 ms against 0.64 ms).
@@ -118,53 +149,62 @@ __device__ __forceinline__ void stencil(const double *__restrict__ v, const doub
     }
 }
 
-/* one thread's column: planes [i0, i1) of row j, column k; the first unique j and k are 0 on a periodic axis, 1
- * otherwise (the launcher clips [i_lo, i_hi) the same way); pi / dj / dk: the axis wraps at i = 0 / this row / this
- * column has duplicates.  A periodic level is single-domain (nj = nk = N): its last unique j and k are taken from N, as
+/* one thread's column: planes [i0, i1) of row j, column k; the first unknown j and k are 0 on a periodic axis or a
+ * Neumann low face, 1 otherwise, the last N-1 on a Neumann high face, else N-2 (the launcher clips [i_lo, i_hi) the same
+ * way); pi / dj / dk: the axis wraps at i = 0 / this row / this column has duplicates; ril / rih: the i axis reflects at
+ * 0 / at N-1.  A periodic or Neumann level is single-domain (nj = nk = N): its last unknown j and k are taken from N, as
  * the wrap is -- from nj / nk the eps kernels compile to 74 - 76 VGPRs, below occupancy 8 */
 struct Column {
     int j, k, i0, i1;
-    bool pi, dj, dk;
+    bool pi, dj, dk, ril, rih;
     long long ojm, ojp, okm, okp;
 };
 
-template <bool PER>
-__device__ __forceinline__ bool column(const Geom &g, int axes, int chunk, int i_lo, int i_hi, Column &c)
+template <int BC>
+__device__ __forceinline__ bool column(const Geom &g, int bc, int chunk, int i_lo, int i_hi, Column &c)
 {
-    const bool pj = PER && (axes & 2), pk = PER && (axes & 4);
-    c.pi = PER && (axes & 1);
-    c.k = (pk ? 0 : 1) + blockIdx.x * WAVE + threadIdx.x;
-    c.j = (pj ? 0 : 1) + blockIdx.y * 4 + threadIdx.y;
+    const bool pj = BC && (bc & 2), pk = BC && (bc & 4);
+    const bool rjl = BC == BC_REFLECT && bc_ref_lo(bc, 1), rjh = BC == BC_REFLECT && bc_ref_hi(bc, 1);
+    const bool rkl = BC == BC_REFLECT && bc_ref_lo(bc, 2), rkh = BC == BC_REFLECT && bc_ref_hi(bc, 2);
+    c.pi = BC && (bc & 1);
+    c.ril = BC == BC_REFLECT && bc_ref_lo(bc, 0);
+    c.rih = BC == BC_REFLECT && bc_ref_hi(bc, 0);
+    c.k = ((pk || rkl) ? 0 : 1) + blockIdx.x * WAVE + threadIdx.x;
+    c.j = ((pj || rjl) ? 0 : 1) + blockIdx.y * 4 + threadIdx.y;
     c.i0 = i_lo + blockIdx.z * chunk;
     c.i1 = min(c.i0 + chunk, i_hi);
-    if (c.k > (PER ? g.N : g.nk) - 2 || c.j > (PER ? g.N : g.nj) - 2)
+    if (c.k > (BC ? g.N : g.nk) - (rkh ? 1 : 2) || c.j > (BC ? g.N : g.nj) - (rjh ? 1 : 2))
         return false;
     c.dj = pj && c.j == 0;
     c.dk = pk && c.k == 0;
-    c.ojm = nb_lo(c.j, g.N, pj, g.pitch);
-    c.ojp = nb_hi(c.j, g.N, pj, g.pitch);
-    c.okm = nb_lo(c.k, g.N, pk, 1);
-    c.okp = nb_hi(c.k, g.N, pk, 1);
+    c.ojm = nb_lo(c.j, g.N, pj, rjl, g.pitch);
+    c.ojp = nb_hi(c.j, g.N, pj, rjh, g.pitch);
+    c.okm = nb_lo(c.k, g.N, pk, rkl, 1);
+    c.okp = nb_hi(c.k, g.N, pk, rkh, 1);
     return true;
 }
 
-/* the window [i_lo, i_hi) clipped to the unique interior planes (from 0 on a periodic i axis, else from 1, up to ni-2);
- * false: nothing to produce */
-static bool stencil_window(const Geom &g, int axes, int &i_lo, int &i_hi)
+/* how many unknowns axis ax has beyond the ni-2 / nj-2 / nk-2 interior ones: index 0 (a periodic axis or a Neumann low
+ * face) and index N-1 (a Neumann high face) */
+static int bc_extra(int bc, int ax) { return ((bc >> ax & 1) || bc_ref_lo(bc, ax)) + bc_ref_hi(bc, ax); }
+
+/* the window [i_lo, i_hi) clipped to the planes of unknowns (from 0 on a periodic i axis or a Neumann low face, else from
+ * 1, up to ni-2, or ni-1 on a Neumann high face); false: nothing to produce */
+static bool stencil_window(const Geom &g, int bc, int &i_lo, int &i_hi)
 {
-    if (g.ni < 3 - (axes & 1) || g.nj < 3 - (axes >> 1 & 1) || g.nk < 3 - (axes >> 2 & 1))
+    if (g.ni < 3 - (bc & 1) || g.nj < 3 - (bc >> 1 & 1) || g.nk < 3 - (bc >> 2 & 1))
         return false;
-    const int lo = (axes & 1) ? 0 : 1;
+    const int lo = ((bc & 1) || bc_ref_lo(bc, 0)) ? 0 : 1, hi = g.ni - 1 + bc_ref_hi(bc, 0);
     i_lo = i_lo < lo ? lo : i_lo;
-    i_hi = (i_hi < 0 || i_hi > g.ni - 1) ? g.ni - 1 : i_hi;
+    i_hi = (i_hi < 0 || i_hi > hi) ? hi : i_hi;
     return i_hi > i_lo;
 }
 
-/* the column grid: unique j and k of a level over (WAVE, 4) blocks; chunk of planes per thread: 16, doubled until the
- * partial sums fit */
-static dim3 column_grid(const Geom &g, int axes, int planes, int &chunk)
+/* the column grid: the unknown j and k of a level over (WAVE, 4) blocks; chunk of planes per thread: 16, doubled until
+ * the partial sums fit */
+static dim3 column_grid(const Geom &g, int bc, int planes, int &chunk)
 {
-    const int gx = (g.nk - 2 + (axes >> 2 & 1) + WAVE - 1) / WAVE, gy = (g.nj - 2 + (axes >> 1 & 1) + 3) / 4;
+    const int gx = (g.nk - 2 + bc_extra(bc, 2) + WAVE - 1) / WAVE, gy = (g.nj - 2 + bc_extra(bc, 1) + 3) / 4;
     chunk = 16;
     while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
         chunk *= 2;
@@ -178,44 +218,47 @@ static dim3 column_grid(const Geom &g, int axes, int planes, int &chunk)
  * Constant operator: each lane owns the k-pair (2m, 2m+1) of one row and updates the member whose colour is being
  * swept.  A periodic level is single-domain (ig0 = 0, ni = nj = nk = N): with PER its range and colour come from N and
  * axes alone -- taken from i_lo, ig0, nj and nk the launch ran 3.5 % slower at 257^3. */
-template <bool PER>
+template <int BC>
 __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ d,
-                                                           double hSq, double sixth, int color, int axes, int i_lo)
+                                                           double hSq, double sixth, int color, int bc, int i_lo)
 {
-    const bool pi = PER && (axes & 1), pj = PER && (axes & 2), pk = PER && (axes & 4);
+    constexpr bool REF = BC == BC_REFLECT;
+    const bool pi = BC && (bc & 1), pj = BC && (bc & 2), pk = BC && (bc & 4);
+    const bool ril = REF && bc_ref_lo(bc, 0), rih = REF && bc_ref_hi(bc, 0), rjl = REF && bc_ref_lo(bc, 1),
+               rjh = REF && bc_ref_hi(bc, 1), rkl = REF && bc_ref_lo(bc, 2), rkh = REF && bc_ref_hi(bc, 2);
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    const int j = (pj ? 0 : 1) + blockIdx.y * blockDim.y + threadIdx.y;
-    const int i = (PER ? (pi ? 0 : 1) : i_lo) + blockIdx.z;
-    if (j > (PER ? g.N : g.nj) - 2)
+    const int j = ((pj || rjl) ? 0 : 1) + blockIdx.y * blockDim.y + threadIdx.y;
+    const int i = (BC ? ((pi || ril) ? 0 : 1) : i_lo) + blockIdx.z;
+    if (j > (BC ? g.N : g.nj) - (rjh ? 1 : 2))
         return;
-    const int k = 2 * m + ((color + (PER ? 0 : g.ig0) + i + j) & 1);
-    if (k < (pk ? 0 : 1) || k > (PER ? g.N : g.nk) - 2)
+    const int k = 2 * m + ((color + (BC ? 0 : g.ig0) + i + j) & 1);
+    if (k < ((pk || rkl) ? 0 : 1) || k > (BC ? g.N : g.nk) - (rkh ? 1 : 2))
         return;
     const long long p = gidx(g, i, j, k);
-    double s = v[p + nb_lo(i, g.N, pi, g.plane)] + v[p + nb_hi(i, g.N, pi, g.plane)];
-    s = s + v[p + nb_lo(j, g.N, pj, g.pitch)];
-    s = s + v[p + nb_hi(j, g.N, pj, g.pitch)];
-    s = s + v[p + nb_lo(k, g.N, pk, 1)];
-    s = s + v[p + nb_hi(k, g.N, pk, 1)];
+    double s = v[p + nb_lo(i, g.N, pi, ril, g.plane)] + v[p + nb_hi(i, g.N, pi, rih, g.plane)];
+    s = s + v[p + nb_lo(j, g.N, pj, rjl, g.pitch)];
+    s = s + v[p + nb_hi(j, g.N, pj, rjh, g.pitch)];
+    s = s + v[p + nb_lo(k, g.N, pk, rkl, 1)];
+    s = s + v[p + nb_hi(k, g.N, pk, rkh, 1)];
     s = s - hSq * d[p];
     store_dup(g, v, p, sixth * s, pi && i == 0, pj && j == 0, pk && k == 0);
 }
 
 /* eps set: a thread updates the points of its column that have colour `color` (every other plane) */
-template <bool PER>
+template <int BC>
 __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ e,
                                                          const double *__restrict__ d, double hSq, double shift,
-                                                         int color, int axes, int chunk, int i_lo, int i_hi)
+                                                         int color, int bc, int chunk, int i_lo, int i_hi)
 {
     Column c;
-    if (!column<PER>(g, axes, chunk, i_lo, i_hi, c))
+    if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
     long long p = gidx(g, c.i0, c.j, c.k);
-    const long long pb = p + nb_lo(c.i0, g.N, c.pi, g.plane);
+    const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
     double vb = v[pb], vh = v[p];
     double eb = e[pb], eh = e[p];
     for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-        const long long pa = p + nb_hi(i, g.N, c.pi, g.plane);
+        const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
         const double va = v[pa], ea = e[pa];
         if (((g.ig0 + i + c.j + c.k) & 1) == color) {
             double s, dg;
@@ -231,28 +274,34 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
 }
 
 void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int axes, int color, hipStream_t s, int i_lo, int i_hi)
+                    int bc, int color, hipStream_t s, int i_lo, int i_hi)
 {
-    if (!stencil_window(g, axes, i_lo, i_hi))
+    if (!stencil_window(g, bc, i_lo, i_hi))
         return;
     const dim3 block(WAVE, 4, 1);
+    const int mode = bc_mode(bc);
     if (!e) {
         const int pairs = (g.nk + 1) / 2;
-        const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + (axes >> 1 & 1) + 3) / 4, i_hi - i_lo);
-        if (axes)
-            hipLaunchKernelGGL(smooth_color_kernel<true>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, axes, i_lo);
+        const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(bc, 1) + 3) / 4, i_hi - i_lo);
+        if (mode == BC_REFLECT)
+            hipLaunchKernelGGL(smooth_color_kernel<BC_REFLECT>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
+        else if (mode == BC_WRAP)
+            hipLaunchKernelGGL(smooth_color_kernel<BC_WRAP>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
         else
-            hipLaunchKernelGGL(smooth_color_kernel<false>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, axes, i_lo);
+            hipLaunchKernelGGL(smooth_color_kernel<BC_PLAIN>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
         return;
     }
     int chunk;
-    const dim3 grid = column_grid(g, axes, i_hi - i_lo, chunk);
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk);
     const double shift = sigma * op.hSq;
-    if (axes)
-        hipLaunchKernelGGL(coef_color_kernel<true>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, axes, chunk, i_lo,
+    if (mode == BC_REFLECT)
+        hipLaunchKernelGGL(coef_color_kernel<BC_REFLECT>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk,
+                           i_lo, i_hi);
+    else if (mode == BC_WRAP)
+        hipLaunchKernelGGL(coef_color_kernel<BC_WRAP>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk, i_lo,
                            i_hi);
     else
-        hipLaunchKernelGGL(coef_color_kernel<false>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, axes, chunk, i_lo,
+        hipLaunchKernelGGL(coef_color_kernel<BC_PLAIN>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk, i_lo,
                            i_hi);
 }
 
@@ -316,18 +365,18 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const double *__rest
  * diff at every unique interior point; res (optional) receives it there and at the duplicates (mg_3d.h:824-825), partials
  * one sum of diff^2 per block (lanes by shuffle tree, waves 0..3 in order), folded by k_fold: the norm counts every
  * unknown once. */
-template <bool COEF, bool PER>
+template <bool COEF, int BC>
 __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                        const double *__restrict__ d, double invHsq, double dg0,
-                                                       double *__restrict__ res, double *__restrict__ partials, int axes,
+                                                       double *__restrict__ res, double *__restrict__ partials, int bc,
                                                        int chunk, int i_lo, int i_hi, int acc_lo, int acc_hi)
 {
     __shared__ double lds4[4];
     double acc = 0.;
     Column c;
-    if (column<PER>(g, axes, chunk, i_lo, i_hi, c)) {
+    if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
         long long p = gidx(g, c.i0, c.j, c.k);
-        const long long pb = p + nb_lo(c.i0, g.N, c.pi, g.plane);
+        const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
         double vb = v[pb], vh = v[p];
         double eb = 0., eh = 0.;
         if constexpr (COEF) {
@@ -335,7 +384,7 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
             eh = e[p];
         }
         for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-            const long long pa = p + nb_hi(i, g.N, c.pi, g.plane);
+            const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
             const double va = v[pa];
             double ea = 0.;
             if constexpr (COEF)
@@ -345,7 +394,7 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
             const double diff = d[p] - invHsq * (s - dg * vh);
             if (res)
                 store_dup(g, res, p, diff, c.pi && i == 0, c.dj, c.dk);
-            if (PER || (i >= acc_lo && i < acc_hi)) /* periodic levels have no windows */
+            if (BC || (i >= acc_lo && i < acc_hi)) /* periodic and Neumann levels have no windows */
                 acc += diff * diff;
             vb = vh;
             vh = va;
@@ -388,30 +437,35 @@ void k_fold(const double *partials, int np, double *out, hipStream_t s)
 }
 
 void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                int axes, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
+                int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
                 int acc_hi)
 {
-    if (!stencil_window(g, axes, i_lo, i_hi)) {
+    if (!stencil_window(g, bc, i_lo, i_hi)) {
         (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
         return;
     }
     if (acc_hi < 0)
         acc_hi = g.ni;
     int chunk;
-    const dim3 grid = column_grid(g, axes, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-    if (e && axes)
-        hipLaunchKernelGGL((residual_kernel<true, true>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
-                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+#define MG3D_RESIDUAL(COEF, BC)                                                                                            \
+    hipLaunchKernelGGL((residual_kernel<COEF, BC>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials, bc, chunk, \
+                       i_lo, i_hi, acc_lo, acc_hi)
+    const int mode = bc_mode(bc);
+    if (e && mode == BC_REFLECT)
+        MG3D_RESIDUAL(true, BC_REFLECT);
+    else if (e && mode == BC_WRAP)
+        MG3D_RESIDUAL(true, BC_WRAP);
     else if (e)
-        hipLaunchKernelGGL((residual_kernel<true, false>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
-                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
-    else if (axes)
-        hipLaunchKernelGGL((residual_kernel<false, true>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
-                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+        MG3D_RESIDUAL(true, BC_PLAIN);
+    else if (mode == BC_REFLECT)
+        MG3D_RESIDUAL(false, BC_REFLECT);
+    else if (mode == BC_WRAP)
+        MG3D_RESIDUAL(false, BC_WRAP);
     else
-        hipLaunchKernelGGL((residual_kernel<false, false>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials,
-                           axes, chunk, i_lo, i_hi, acc_lo, acc_hi);
+        MG3D_RESIDUAL(false, BC_PLAIN);
+#undef MG3D_RESIDUAL
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
 
@@ -535,13 +589,16 @@ void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hip
     hipLaunchKernelGGL(restrict_kernel, grid, dim3(64, 4, 1), 0, s, gf, r, gc, dc, lo, hi, faces_only ? 1 : 0);
 }
 
-/* Periodic axes: one thread per coarse point.  A point on a Dirichlet face (index 0 or Nc-1 of a non-periodic axis) is
- * injected, dc = r(2I, 2J, 2K), as restrict_kernel does; every other unique point -- periodic face points included -- takes the
- * full weighting val = 0; val += r(2I-1+ti, ...) * w in restrict_kernel's order, with fine index -1 wrapped to Nf-2
- * (2I+1 <= Nf-2 never wraps).  Duplicates are written as copies by the thread of their source. */
+/* Periodic axes and Neumann faces: one thread per coarse point.  A point on a Dirichlet face (index 0 or Nc-1 of a
+ * non-periodic axis, unless that face is a Neumann face) is injected, dc = r(2I, 2J, 2K), as restrict_kernel does; every
+ * other unique point -- periodic and Neumann face points included -- takes the full weighting val = 0;
+ * val += r(2I-1+ti, ...) * w in restrict_kernel's order, with fine index -1 wrapped to Nf-2 on a periodic axis
+ * (2I+1 <= Nf-2 never wraps) and reflected to 1 at a Neumann low face, fine index Nf reflected to Nf-2 at a Neumann high
+ * face.  Duplicates are written as copies by the thread of their source. */
 __global__ void __launch_bounds__(256) per_restrict_kernel(Geom gf, const double *__restrict__ r, Geom gc,
-                                                           double *__restrict__ dc, int axes)
+                                                           double *__restrict__ dc, int bc)
 {
+    const int axes = bc & 7;
     const int kc = blockIdx.x * WAVE + threadIdx.x;
     const int jc = blockIdx.y * 4 + threadIdx.y;
     const int ic = blockIdx.z;
@@ -552,15 +609,19 @@ __global__ void __launch_bounds__(256) per_restrict_kernel(Geom gf, const double
     if ((pi && ic == Nc - 1) || (pj && jc == Nc - 1) || (pk && kc == Nc - 1))
         return; /* a duplicate: its source's thread writes it */
     const long long pf = gidx(gf, 2 * ic, 2 * jc, 2 * kc);
-    const bool face = (!pi && (ic == 0 || ic == Nc - 1)) || (!pj && (jc == 0 || jc == Nc - 1)) ||
-                      (!pk && (kc == 0 || kc == Nc - 1));
+    const bool face = (!pi && ((ic == 0 && !bc_ref_lo(bc, 0)) || (ic == Nc - 1 && !bc_ref_hi(bc, 0)))) ||
+                      (!pj && ((jc == 0 && !bc_ref_lo(bc, 1)) || (jc == Nc - 1 && !bc_ref_hi(bc, 1)))) ||
+                      (!pk && ((kc == 0 && !bc_ref_lo(bc, 2)) || (kc == Nc - 1 && !bc_ref_hi(bc, 2))));
     double val;
     if (face) {
         val = r[pf];
     } else {
-        const long long oi[3] = {ic == 0 ? (Nf - 2) * gf.plane : -gf.plane, 0, gf.plane};
-        const long long oj[3] = {jc == 0 ? (long long)(Nf - 2) * gf.pitch : -(long long)gf.pitch, 0, gf.pitch};
-        const long long ok[3] = {kc == 0 ? (long long)(Nf - 2) : -1, 0, 1};
+        /* (here index 0 is on a periodic axis or a Neumann low face, index Nc-1 on a Neumann high face) */
+        const long long oi[3] = {ic == 0 ? (pi ? (Nf - 2) * gf.plane : gf.plane) : -gf.plane, 0,
+                                 ic == Nc - 1 ? -gf.plane : gf.plane};
+        const long long oj[3] = {jc == 0 ? (pj ? (long long)(Nf - 2) * gf.pitch : (long long)gf.pitch) : -(long long)gf.pitch, 0,
+                                 jc == Nc - 1 ? -(long long)gf.pitch : (long long)gf.pitch};
+        const long long ok[3] = {kc == 0 ? (pk ? (long long)(Nf - 2) : 1LL) : -1LL, 0, kc == Nc - 1 ? -1LL : 1LL};
         val = 0.;
 #pragma unroll
         for (int ti = 0; ti < 3; ti++)
@@ -575,10 +636,10 @@ __global__ void __launch_bounds__(256) per_restrict_kernel(Geom gf, const double
     store_dup(gc, dc, gidx(gc, ic, jc, kc), val, pi && ic == 0, pj && jc == 0, pk && kc == 0);
 }
 
-void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int axes, hipStream_t s)
+void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s)
 {
     dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
-    hipLaunchKernelGGL(per_restrict_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, r, gc, dc, axes);
+    hipLaunchKernelGGL(per_restrict_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, r, gc, dc, bc);
 }
 
 /* eps of the coarse level at every point, boundary included: ec[I,J,K] = ef[2I,2J,2K] (single-domain levels) */
@@ -760,9 +821,11 @@ void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, hip
     hipLaunchKernelGGL(prolong_kernel, grid, dim3(64, 4, 1), 0, s, gc, ec, gf, ef, lo, hi);
 }
 
-/* Periodic axes: ef += P(ec) at every fine point that is not a duplicate (Dirichlet faces included, as prolong_kernel),
- * in prolong_kernel's parent order; on a periodic axis the high parent il+1 = Nc-1 is read at its source 0.  The thread
- * of a point writes the sum to its duplicates too, so neither a fine nor a coarse duplicate is ever read. */
+/* Periodic axes and Neumann faces: ef += P(ec) at every fine point that is not a duplicate (Dirichlet faces included, as
+ * prolong_kernel: their coarse parents hold zeros), in prolong_kernel's parent order; on a periodic axis the high parent
+ * il+1 = Nc-1 is read at its source 0.  The thread of a point writes the sum to its duplicates too, so neither a fine nor a
+ * coarse duplicate is ever read.  A Neumann face needs nothing of its own: every parent of a fine face point lies on the
+ * same face, and this kernel corrects the face points with the rest (axes: the periodic bits of the boundary word). */
 __global__ void __launch_bounds__(256) per_prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
                                                           double *__restrict__ ef, int axes)
 {
@@ -825,10 +888,10 @@ __global__ void __launch_bounds__(256) per_prolong_kernel(Geom gc, const double 
     store_dup(gf, ef, p, ef[p] + t, pi && i == 0, pj && j == 0, pk && k == 0);
 }
 
-void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int axes, hipStream_t s)
+void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s)
 {
     dim3 grid((gf.N + WAVE - 1) / WAVE, (gf.N + 3) / 4, gf.N);
-    hipLaunchKernelGGL(per_prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, axes);
+    hipLaunchKernelGGL(per_prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
 }
 
 /* ------------------------------------------------------------- coarsest level
@@ -849,10 +912,10 @@ __global__ void __launch_bounds__(256) per_coarse_rhs_kernel(Geom g, const doubl
     b[p] = (dup || (pin && (i | j | k) == 0)) ? 0. : d[p];
 }
 
-void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int axes, int pin, hipStream_t s)
+void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s)
 {
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
-    hipLaunchKernelGGL(per_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, axes, pin);
+    hipLaunchKernelGGL(per_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, bc & 7, pin);
 }
 
 /* Every duplicate of a field from its source: blockIdx.z = the axis whose duplicate plane a thread covers; (a, b) the
@@ -870,12 +933,34 @@ __global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, double *__rest
     v[gidx(g, i, j, k)] = v[gidx(g, si, sj, sk)];
 }
 
-void k_per_refresh(const Geom &g, double *v, int axes, hipStream_t s)
+void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s)
 {
+    const int axes = bc & 7;
     if (!axes)
         return;
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
     hipLaunchKernelGGL(per_refresh_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes);
+}
+
+/* Zeros of a field on the faces of the mask `faces` (MG3D_NEUMANN_* numbering: bit 2*ax low, 2*ax+1 high): blockIdx.z =
+ * the face, (a, b) its other two indices.  For r when faces stop being unknowns: a Dirichlet face of r is never written by
+ * a cycle and is injected into the coarse right-hand side, so what the residual of the other operator left there must go. */
+__global__ void __launch_bounds__(256) zero_faces_kernel(Geom g, double *__restrict__ v, int faces)
+{
+    const int b = blockIdx.x * WAVE + threadIdx.x, a = blockIdx.y * 4 + threadIdx.y, f = blockIdx.z;
+    const int N = g.N;
+    if (a >= N || b >= N || !(faces >> f & 1))
+        return;
+    const int ax = f >> 1, x = (f & 1) ? N - 1 : 0;
+    v[gidx(g, ax == 0 ? x : a, ax == 1 ? x : (ax == 0 ? a : b), ax == 2 ? x : b)] = 0.;
+}
+
+void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s)
+{
+    if (!faces)
+        return;
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 6);
+    hipLaunchKernelGGL(zero_faces_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, v, faces);
 }
 
 /* ------------------------------------------------------- coarsest direct solve
