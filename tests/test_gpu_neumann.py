@@ -7,7 +7,14 @@ Left out on purpose (time on the GPU): the V-cycle parity product is not the ful
 Every single face and mask 63 run with the constant operator (sigma = 0 and sigma > 0) and with eps, nu in {1, 2} and
 c in {3, 5, 9} spread over them (_CASES below lists exactly what runs); the mixed periodic masks run at c in {5, 9}
 only, which a periodic axis requires.  At 513^3 the single operators run (one colour pass of each colour, residual with
-r and norm), not a whole V-cycle: its numpy reference alone takes minutes."""
+r and norm), not a whole V-cycle: its numpy reference alone takes minutes.
+
+What this file does not run, tests/test_gpu_neumann_shapes.py does: the pairs of faces on one axis alone (3, 12, 48) and
+every single face at 65^3 and 129^3, where a face fills or overflows the last lane / row / plane block by one; every mask
+on the coarse grids off the 2^k+1 ladder (c = 6, 7, 10, 11, 13); smooth_residual and smooth_restrict; V-cycles with
+keep_residual (r of every level); 513^3 with the masks that keep or double the chunk of planes, and 577^3; and the
+setters in other orders: the coefficient before the masks, one nonzero mask after another, an axis from periodic to
+Neumann and back, eps given under a periodic mask that is cleared afterwards."""
 import math
 
 import numpy as np

@@ -243,10 +243,17 @@ def _max_partials():
     return int(re.search(r"#define\s+MG3D_MAX_PARTIALS\s+(\d+)", text).group(1))
 
 
-def column_grid(N, axes):
-    """column_grid() of csrc/mg3d_kernels.hip for a single-domain level of N points: (gx, gy, gz, chunk, planes)"""
-    planes = N - 2 + (axes & 1)
-    gx, gy = (N - 2 + (axes >> 2 & 1) + 63) // 64, (N - 2 + (axes >> 1 & 1) + 3) // 4
+def bc_extra(axes, faces, ax):
+    """bc_extra() of csrc/mg3d_kernels.hip: the unknowns axis ax (0 i, 1 j, 2 k) has beyond the N - 2 interior ones --
+    index 0 (a periodic axis or a Neumann low face) and index N-1 (a Neumann high face)"""
+    return int(bool(axes >> ax & 1 or faces >> 2 * ax & 1)) + (faces >> (2 * ax + 1) & 1)
+
+
+def column_grid(N, axes, faces=0):
+    """column_grid() of csrc/mg3d_kernels.hip (with the planes stencil_window() leaves) for a single-domain level of N
+    points, periodic axes `axes` and Neumann faces `faces`: (gx, gy, gz, chunk, planes)"""
+    planes = N - 2 + bc_extra(axes, faces, 0)
+    gx, gy = (N - 2 + bc_extra(axes, faces, 2) + 63) // 64, (N - 2 + bc_extra(axes, faces, 1) + 3) // 4
     chunk = 16
     while gx * gy * -(-planes // chunk) > _max_partials():
         chunk *= 2
