@@ -207,6 +207,46 @@ int mg3d_l2norm(mg3d_ctx *ctx, int field, int level, double *norm);
 int mg3d_vcycle(mg3d_ctx *ctx, int level, double *norm);
 int mg3d_vcycles(mg3d_ctx *ctx, int count, double *norms);
 
+/* Solving to a tolerance: conjugate gradients preconditioned by one V-cycle per iteration, for the finest level's system
+ * A u = d of the context's operator -- constant, sigma, eps, periodic axes.  The cycle is a symmetric preconditioner
+ * (red,black before and black,red behind the coarse correction, the restriction 1/8 of the prolongation's transpose, every
+ * level's operator symmetric with arithmetic face means, a zero guess below the finest level), and where the cycle's own
+ * factor degrades on a jump in eps ("Variable coefficient") the Krylov iteration keeps 0.07 - 0.21 per
+ * iteration.  A is negative definite: CG runs on -A with z = -(one V-cycle from a zero guess with right-hand side r), signs
+ * carried through; beta is Fletcher-Reeves, (r_{k+1}.z_{k+1}) / (r_k.z_k).
+ *   in : u of the finest level as uploaded -- Dirichlet values on its faces, any interior: the guess; d of the finest level:
+ *        the right-hand side; the coarse factor set as for mg3d_vcycle (MG3D_ERR_STATE without one).  A cycle that has run
+ *        ahead is finished first.
+ *   out: u holds the iterate, its Dirichlet faces the caller's values bit for bit, on a periodic context its duplicates
+ *        equal to their sources; d of the finest level is the caller's bit for bit.  u and d of the lower levels and r of
+ *        every level are unspecified.  The context is usable for mg3d_vcycle(s) as before: mg3d_vcycles(1) from the
+ *        returned u gives, bit for bit, what a context gives that had this u and d uploaded.
+ * The V-cycles inside go through the context's own cycle code with whatever schedule its options select (grid values never
+ * depend on them).  Norms are Euclidean over the unknowns: every unique non-Dirichlet point once, the set mg3d_residual
+ * counts; r_0 = d - A u of the guess is computed, the later ones are the recurrence's.  The solve stops when
+ * ||r_k|| <= max(rtol * ||r_0||, atol) (converged = 1; also at once when the guess satisfies it, r_0 = 0 included), after
+ * max_iters iterations, or on breakdown -- p.Ap or r.z not finite or of the wrong sign: the last good iterate stays in u,
+ * converged = 0, MG3D_OK.  norms, if not NULL, has max_iters + 1 entries and receives ||r_0|| .. ||r_iterations||.
+ * rtol, atol >= 0 and finite, max_iters >= 0, not all three 0 -- otherwise MG3D_ERR_ARG and nothing changes.  max_iters = 0
+ * computes r0_norm only and changes nothing.  Sums are per-block partial sums folded in a fixed order: the same call on the
+ * same data gives the same bits.  Four work vectors of the finest level's size are allocated on the first call with
+ * max_iters > 0 and freed with the context (MG3D_ERR_ALLOC, nothing changed, when they do not fit).
+ * Refused with MG3D_ERR_STATE, nothing changed: a context with a Neumann face (the reflected operator is not symmetric in
+ * the Euclidean inner product -- see its left null vector w above: it is self-adjoint only in the w-weighted one); the
+ * singular case, every axis periodic with sigma = 0 (the pinned row of the coarse matrix breaks the symmetry of the
+ * preconditioner); a context after mg3d_es_setup.  The slab, fp32 and mg3d_host_* forms have no such entry point.
+ * Use it with a coefficient that jumps; for the constant operator mg3d_vcycles converges at 0.16 per 2 ms cycle and the
+ * extra passes of an iteration cost more than they save ("Solving to a tolerance"). */
+typedef struct mg3d_pcg_info {
+    int iterations;        /* preconditioned iterations performed (updates of u; on breakdown one V-cycle more was run) */
+    int converged;         /* 1: ||r_k|| <= max(rtol*||r_0||, atol) was reached */
+    double r0_norm;        /* ||d - A u|| of the guess the caller uploaded */
+    double r_norm;         /* recurrence residual norm at return */
+} mg3d_pcg_info;
+int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters,
+                   double *norms /* NULL or max_iters+1 entries: r_0 .. r_k */,
+                   mg3d_pcg_info *info /* may be NULL */);
+
 /* Full-multigrid initialisation, SolverFMGInitialize (mg_dirichlet_analytic.c:771-806; commented copy
  * mg_3d.h:1364-1404): BCs on u[0], direct solve, then for every level prolong the coarser solution, impose the
  * Dirichlet values BCFunc on the six faces (on the device), zero the coarser level, one V-cycle from that level. */

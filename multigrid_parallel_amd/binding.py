@@ -68,6 +68,7 @@ SIGNATURES = {
     "mg3d_l2norm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_vcycle": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_vcycles": (C.c_int, [C.c_void_p, C.c_int, dp]),
+    "mg3d_pcg_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, dp, C.c_void_p]),
     "mg3d_fmg_initialize": (C.c_int, [C.c_void_p]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -171,6 +172,11 @@ SIGNATURES = {
 
 
 NEUMANN_FACES = ("ilo", "ihi", "jlo", "jhi", "klo", "khi")  # bit f of the MG3D_NEUMANN_* mask
+
+
+class PcgInfo(C.Structure):
+    """mg3d_pcg_info: what mg3d_pcg_solve reports"""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("r0_norm", C.c_double), ("r_norm", C.c_double)]
 
 
 class EsParams(C.Structure):
@@ -503,6 +509,17 @@ class Solver:
         norms = np.zeros(count)
         check(self.L.mg3d_vcycles(self._h, count, P(norms)))
         return norms
+
+    def pcg_solve(self, rtol=1e-8, atol=0.0, max_iters=50):
+        """mg3d_pcg_solve: conjugate gradients preconditioned by one V-cycle per iteration, from the uploaded u and d of the
+        finest level until ||r|| <= max(rtol * ||r_0||, atol).  Returns (norms ||r_0|| .. ||r_iterations||, info dict:
+        iterations, converged, r0_norm, r_norm).  For coefficients that jump; not with Neumann faces or the singular
+        all-periodic case (Mg3dError, code 5)."""
+        norms = np.zeros(max(int(max_iters), 0) + 1)
+        info = PcgInfo()
+        check(self.L.mg3d_pcg_solve(self._h, float(rtol), float(atol), int(max_iters), P(norms), C.byref(info)))
+        return norms[:info.iterations + 1].copy(), {"iterations": info.iterations, "converged": bool(info.converged),
+                                                    "r0_norm": info.r0_norm, "r_norm": info.r_norm}
 
     def fmg_initialize(self):
         check(self.L.mg3d_fmg_initialize(self._h))

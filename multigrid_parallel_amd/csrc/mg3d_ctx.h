@@ -71,6 +71,9 @@ struct mg3d_ctx {
      * touched since (mg3d_drop_carry clears it: every entry point that reads or writes level data calls that first): the next
      * cycle's first red pass is the identity also ACROSS calls, its down-leg can be the one launch (mg3d_enqueue_vcycle) */
     bool red_tail = false;
+    /* mg3d_pcg_solve (mg3d_pcg.hip): four work vectors of the finest level in its padded layout -- z, r, p, q -- allocated
+     * on first use, freed with the context.  During a solve the first two stand in for the level's u and d */
+    double *pcg_v[4] = {nullptr, nullptr, nullptr, nullptr};
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */

@@ -177,6 +177,9 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
         (void)hipFree(e);
     if (ctx->per_b)
         (void)hipFree(ctx->per_b);
+    for (double *v : ctx->pcg_v)
+        if (v)
+            (void)hipFree(v);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)

@@ -112,6 +112,22 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
                 int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
                 int acc_lo = 0, int acc_hi = -1);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
+/* The vector passes of mg3d_pcg_solve on a single-domain level, bc a mask of periodic axes only (no Neumann face).  Each
+ * touches the unknowns alone, the set the residual counts; sums are per-block partials folded in a fixed order into one
+ * device double.  Scalars are read from device memory.  Return value: the number of partials (0: none needed), -1 when the
+ * level has no launch shape.
+ *   apply_dot   : q = A p (the operator of k_residual: e, op, sigma), *dot_out = sum of p*q
+ *   update_norm : alpha = *rz / *pap; x += alpha p, r -= alpha q, *rr_out = sum of r*r; writes nothing unless both dots
+ *                 are finite and negative (the operator is negative definite)
+ *   dot         : *dot_out = sum of a*b
+ *   direction   : beta = *rz_new / *rz_old; p = z + beta p */
+int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
+                    double *partials, double *dot_out, hipStream_t s);
+int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
+                      const double *pap, double *partials, double *rr_out, hipStream_t s);
+int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s);
+int k_pcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
+                    hipStream_t s);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo = -1,
                 int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);

@@ -469,6 +469,241 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
 
+/* ------------------------------------------------------- conjugate gradients
+ * The vector passes of mg3d_pcg_solve (mg3d_pcg.hip) on one single-domain level without Neumann faces.  Every pass
+ * touches the unknowns only -- the points the residual counts -- so Dirichlet faces and periodic duplicates of its
+ * operands are neither read as unknowns nor written; every sum is per-block partials folded by one block (k_fold).
+ *
+ * apply + dot: q = A p and sum of p*q.  The residual's column walk, neighbour offsets and operand order:
+ * q = invHsq*(s - dg*p), which is what the residual subtracts from d. */
+template <bool COEF, int BC>
+__global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
+                                                        double invHsq, double dg0, double *__restrict__ q,
+                                                        double *__restrict__ partials, int bc, int chunk, int i_lo,
+                                                        int i_hi)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    Column c;
+    if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
+        long long p = gidx(g, c.i0, c.j, c.k);
+        const long long pb = p + nb_lo(c.i0, g.N, c.pi, false, g.plane);
+        double vb = v[pb], vh = v[p];
+        double eb = 0., eh = 0.;
+        if constexpr (COEF) {
+            eb = e[pb];
+            eh = e[p];
+        }
+        for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+            const long long pa = p + nb_hi(i, g.N, c.pi, false, g.plane);
+            const double va = v[pa];
+            double ea = 0.;
+            if constexpr (COEF)
+                ea = e[pa];
+            double s, dg;
+            stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
+            const double ap = invHsq * (s - dg * vh);
+            q[p] = ap;
+            acc += vh * ap;
+            vb = vh;
+            vh = va;
+            if constexpr (COEF) {
+                eb = eh;
+                eh = ea;
+            }
+        }
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
+                    double *partials, double *dot_out, hipStream_t s)
+{
+    int i_lo = -1, i_hi = -1;
+    if (!stencil_window(g, bc, i_lo, i_hi)) {
+        (void)hipMemsetAsync(dot_out, 0, sizeof(double), s);
+        return 0;
+    }
+    int chunk;
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const double dg0 = e ? sigma * op.hSq : op.dg;
+#define MG3D_PCG_APPLY(COEF, BC) \
+    hipLaunchKernelGGL((pcg_apply_kernel<COEF, BC>), grid, block, 0, s, g, p, e, op.invHsq, dg0, q, partials, bc, chunk, i_lo, i_hi)
+    const bool wrap = bc_mode(bc) == BC_WRAP;
+    if (e && wrap)
+        MG3D_PCG_APPLY(true, BC_WRAP);
+    else if (e)
+        MG3D_PCG_APPLY(true, BC_PLAIN);
+    else if (wrap)
+        MG3D_PCG_APPLY(false, BC_WRAP);
+    else
+        MG3D_PCG_APPLY(false, BC_PLAIN);
+#undef MG3D_PCG_APPLY
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, dot_out, s);
+    return np;
+}
+
+/* The streaming passes.  A lane owns the aligned k-pair (2m, 2m+1) of a row -- one 16-byte access per operand; rows are
+ * 128-byte aligned and a pair never leaves its row's pitch -- over `chunk` planes; the member of a pair that is no
+ * unknown (a Dirichlet face, the duplicate k = N-1) keeps the value that was loaded.  lo: first unknown index of i, j, k
+ * (0 on a periodic axis, else 1); the last one is N-2 on every axis. */
+struct PairWalk {
+    long long p;
+    int n; /* planes */
+    bool m0, m1;
+};
+__device__ __forceinline__ bool pair_walk(const Geom &g, int lo_i, int lo_j, int lo_k, int chunk, PairWalk &w)
+{
+    const int k = 2 * (blockIdx.x * WAVE + threadIdx.x);
+    const int j = lo_j + blockIdx.y * 4 + threadIdx.y;
+    const int i0 = lo_i + blockIdx.z * chunk;
+    if (k > g.N - 2 || j > g.N - 2)
+        return false;
+    w.m0 = k >= lo_k;
+    w.m1 = k + 1 <= g.N - 2;
+    w.n = min(chunk, g.N - 1 - i0);
+    w.p = gidx(g, i0, j, k);
+    return true;
+}
+__device__ __forceinline__ bool pcg_finite_neg(double x) { return x < 0. && x >= -1.7976931348623157e308; }
+
+/* update + norm: alpha = (r.z)/(p.Ap); x += alpha p, r -= alpha q, sum of r*r.  The operator is negative definite: both
+ * dots are negative in a healthy iteration.  Otherwise (breakdown) nothing is written -- x stays the last good iterate --
+ * and the host, which reads the same two numbers, ends the solve. */
+__global__ void __launch_bounds__(256) pcg_update_kernel(Geom g, double *__restrict__ x, double *__restrict__ r,
+                                                         const double *__restrict__ pv, const double *__restrict__ qv,
+                                                         const double *__restrict__ rz, const double *__restrict__ pap,
+                                                         double *__restrict__ partials, int lo_i, int lo_j, int lo_k,
+                                                         int chunk)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    PairWalk w;
+    const double num = *rz, den = *pap;
+    const bool ok = pcg_finite_neg(num) && pcg_finite_neg(den);
+    if (ok && pair_walk(g, lo_i, lo_j, lo_k, chunk, w)) {
+        const double alpha = num / den;
+        for (int t = 0; t < w.n; t++, w.p += g.plane) {
+            double2 xx = *reinterpret_cast<double2 *>(x + w.p), rr = *reinterpret_cast<double2 *>(r + w.p);
+            const double2 pp = *reinterpret_cast<const double2 *>(pv + w.p), qq = *reinterpret_cast<const double2 *>(qv + w.p);
+            if (w.m0) {
+                xx.x = xx.x + alpha * pp.x;
+                rr.x = rr.x - alpha * qq.x;
+                acc += rr.x * rr.x;
+            }
+            if (w.m1) {
+                xx.y = xx.y + alpha * pp.y;
+                rr.y = rr.y - alpha * qq.y;
+                acc += rr.y * rr.y;
+            }
+            *reinterpret_cast<double2 *>(x + w.p) = xx;
+            *reinterpret_cast<double2 *>(r + w.p) = rr;
+        }
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+/* dot: sum of a*b over the unknowns */
+__global__ void __launch_bounds__(256) pcg_dot_kernel(Geom g, const double *__restrict__ a, const double *__restrict__ b,
+                                                      double *__restrict__ partials, int lo_i, int lo_j, int lo_k, int chunk)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    PairWalk w;
+    if (pair_walk(g, lo_i, lo_j, lo_k, chunk, w)) {
+        for (int t = 0; t < w.n; t++, w.p += g.plane) {
+            const double2 aa = *reinterpret_cast<const double2 *>(a + w.p), bb = *reinterpret_cast<const double2 *>(b + w.p);
+            if (w.m0)
+                acc += aa.x * bb.x;
+            if (w.m1)
+                acc += aa.y * bb.y;
+        }
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+/* direction: beta = (r.z)_new / (r.z)_old (Fletcher-Reeves); p = z + beta p */
+__global__ void __launch_bounds__(256) pcg_direction_kernel(Geom g, double *__restrict__ pv, const double *__restrict__ z,
+                                                            const double *__restrict__ rz_new,
+                                                            const double *__restrict__ rz_old, int lo_i, int lo_j, int lo_k,
+                                                            int chunk)
+{
+    PairWalk w;
+    if (!pair_walk(g, lo_i, lo_j, lo_k, chunk, w))
+        return;
+    const double beta = *rz_new / *rz_old;
+    for (int t = 0; t < w.n; t++, w.p += g.plane) {
+        double2 pp = *reinterpret_cast<double2 *>(pv + w.p);
+        const double2 zz = *reinterpret_cast<const double2 *>(z + w.p);
+        if (w.m0)
+            pp.x = zz.x + beta * pp.x;
+        if (w.m1)
+            pp.y = zz.y + beta * pp.y;
+        *reinterpret_cast<double2 *>(pv + w.p) = pp;
+    }
+}
+
+/* the pair grid: the k-pairs and unknown rows of a level over (WAVE, 4) blocks, one plane per block in z; planes per
+ * block doubled from 1 until the partial sums fit */
+static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, int lo[3])
+{
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
+        return false;
+    for (int ax = 0; ax < 3; ax++)
+        lo[ax] = (bc >> ax & 1) ? 0 : 1;
+    const int pairs = (g.N - 2) / 2 + 1, rows = g.N - 1 - lo[1], planes = g.N - 1 - lo[0];
+    const int gx = (pairs + WAVE - 1) / WAVE, gy = (rows + 3) / 4;
+    chunk = 1;
+    while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
+        chunk *= 2;
+    grid = dim3(gx, gy, (planes + chunk - 1) / chunk);
+    return true;
+}
+
+int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
+                      const double *pap, double *partials, double *rr_out, hipStream_t s)
+{
+    dim3 grid;
+    int chunk, lo[3];
+    if (!pair_grid(g, bc, grid, chunk, lo))
+        return -1;
+    hipLaunchKernelGGL(pcg_update_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, x, r, p, q, rz, pap, partials, lo[0], lo[1], lo[2],
+                       chunk);
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, rr_out, s);
+    return np;
+}
+
+int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s)
+{
+    dim3 grid;
+    int chunk, lo[3];
+    if (!pair_grid(g, bc, grid, chunk, lo))
+        return -1;
+    hipLaunchKernelGGL(pcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, lo[0], lo[1], lo[2], chunk);
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, dot_out, s);
+    return np;
+}
+
+int k_pcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
+                    hipStream_t s)
+{
+    dim3 grid;
+    int chunk, lo[3];
+    if (!pair_grid(g, bc, grid, chunk, lo))
+        return -1;
+    hipLaunchKernelGGL(pcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, lo[0], lo[1], lo[2], chunk);
+    return 0;
+}
+
 /* GetL2NormOfVector (mg_3d.h:783-792) over every point of a level, boundary included */
 __global__ void __launch_bounds__(256) sumsq_kernel(Geom g, const double *__restrict__ a,
                                                     double *__restrict__ partials)
