@@ -92,6 +92,24 @@ struct mg3d_ctx {
 
 /* the operator constants of a level of this context (its spacing, the context's sigma) */
 static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
+/* the fused sweep writes out of place: u and its second copy change roles behind every launch with colour passes */
+static inline void swap_u(Level &l)
+{
+    double *t = l.f[MG3D_U];
+    l.f[MG3D_U] = l.alt;
+    l.alt = t;
+}
+/* a sweep launch on a level of this context, u -> alt: the caller adds what the launch does (SweepLaunch) */
+static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
+{
+    SweepLaunch w;
+    w.g = &l.g;
+    w.op = mg3d_op(ctx, l);
+    w.vin = l.f[MG3D_U];
+    w.d = l.f[MG3D_D];
+    w.vout = l.alt;
+    return w;
+}
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
  * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
  * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the

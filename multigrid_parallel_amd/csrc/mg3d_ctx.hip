@@ -324,18 +324,19 @@ int mg3d_drop_carry_keep(mg3d_ctx *ctx)
          * cycle's own u is intact in the top level's alt, the coarser level's right-hand side was never touched -- swap
          * back, no launch.  (State 2 only exists inside mg3d_vcycles: u is final, the norm's second half is abandoned.) */
         if (ctx->legs_state == 3) {
-            Level &l = ctx->lv[ctx->L - 1];
-            double *t = l.f[MG3D_U];
-            l.f[MG3D_U] = l.alt;
-            l.alt = t;
+            swap_u(ctx->lv[ctx->L - 1]);
         }
         ctx->legs_state = 0;
     }
     if (!ctx || !ctx->carried)
         return MG3D_OK;
     Level &l = ctx->lv[ctx->L - 1];
-    const int np = k_sweep(ctx->opt, l.g, l.alt, l.f[MG3D_D], l.f[MG3D_U], nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(ctx, l), 2, 0, false,
-                           ctx->stream);
+    SweepLaunch w = mg3d_level_sweep(ctx, l); /* ... here the other way round: alt -> u, black, red */
+    w.vin = l.alt;
+    w.vout = l.f[MG3D_U];
+    w.S = 2;
+    w.c1 = 0;
+    const int np = k_sweep(ctx->opt, w, ctx->stream);
     /* a failure leaves the context where it was -- u three passes into the next cycle, `carried` still set: the caller
      * returns the error instead of going on with (and handing out) a state nobody asked for; a later call tries again */
     if (np < 0)
@@ -992,12 +993,57 @@ static int read_norm(mg3d_ctx *ctx, int slot, double *norm)
     return MG3D_OK;
 }
 
-/* post-smoothing of 4 passes + norm as 2 + 2 passes (see enqueue_smooth_residual) */
-static bool split_up_leg(int iters, int want_res) { return 2 * iters == 4 && want_res == 1; }
+/* what mg3d_stage_plan is asked about a stage on a level of this context */
+static StageAsk stage_ask(const mg3d_ctx *ctx, int level, int post, int iters, int want_res, bool has_coarse, bool need_norm,
+                          bool pro_offered)
+{
+    const Geom &g = ctx->lv[level].g;
+    return StageAsk{g.N, g.nj, post != 0, iters, want_res, has_coarse, need_norm, pro_offered, /* leg4_form */ true};
+}
+
+/* One launch of a stage's list on a single-domain level (fused sweep): u -> alt, swapped behind a launch with passes; the
+ * residual's partial sums folded into sumsq[slot].  first: the stage's first launch (zero_in applies to it). */
+static int enqueue_stage_step(mg3d_ctx *ctx, int level, int post, const StageStep &st, bool first, int want_res, int slot,
+                              Level *coarse, const Level *pro, bool zero_in, bool need_norm)
+{
+    Level &l = ctx->lv[level];
+    SweepLaunch w = mg3d_level_sweep(ctx, l);
+    w.kind = st.res ? SWEEP_PASSES_RES : SWEEP_PASSES;
+    w.S = st.S;
+    w.c1 = post ? 0 : 1; /* pre: red first (mg_3d.h:657); post: black first (mg_3d.h:728) */
+    if (zero_in && first)
+        w.vin = nullptr;
+    if (st.res && want_res == 2 && !st.rst)
+        w.r = l.f[MG3D_R];
+    if (st.res && need_norm)
+        w.partials = ctx->partials;
+    if (st.rst) {
+        w.gc = &coarse->g;
+        w.dc = coarse->f[MG3D_D];
+    }
+    if (st.pro) {
+        w.gce = &pro->g;
+        w.ec = pro->f[MG3D_U];
+    }
+    int np;
+    {
+        StageScope kt(ctx, level, st.S == 4 ? MG3D_K_SWEEP4 : st.S == 2 ? (st.res ? MG3D_K_SWEEP2_RES : MG3D_K_SWEEP2)
+                                                                        : MG3D_K_RESIDUAL, true);
+        np = k_sweep(ctx->opt, w, ctx->stream);
+    }
+    if (np < 0) /* nothing was launched: no buffer swap, no fold of partial sums that were never written */
+        return fail(MG3D_ERR_STATE, "fused sweep: no kernel for %d colour passes%s on level %d", st.S,
+                    st.res ? " + residual" : "", level);
+    if (st.S > 0)
+        swap_u(l);
+    if (st.res && need_norm)
+        k_fold(ctx->partials, np, ctx->sumsq + slot, ctx->stream);
+    return MG3D_OK;
+}
 
 /* iters x (two colour passes), optionally followed by the residual of the result.
- * Fused path: chunks of 4 (or 2) passes per launch, each launch reading u and writing the
- * alternate buffer; the residual rides on the last launch.  want_res: 0 none, 1 norm only,
+ * Fused path: the launches of mg3d_stage_plan, each reading u and writing the alternate buffer; the
+ * residual rides on the last launch.  want_res: 0 none, 1 norm only,
  * 2 store r (+ norm).  The squared norm goes to sumsq[slot]. */
 static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters, int want_res, int slot,
                                     Level *coarse = nullptr, const Level *pro = nullptr, bool zero_in = false,
@@ -1008,65 +1054,19 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     /* zero_in: u of this level is to be taken as identically zero (the memset of mg_3d.h:1258-1259 folded
      * into the first launch: it neither reads u nor needs it zeroed); only valid when a launch with S > 0 follows */
     /* pro != NULL: the smoother's input is u + P(pro->u) (prolongateAndCorrectError, mg_3d.h:1331, folded
-     * into the first launch's loads); the caller must have checked pro_fusable() */
+     * into the first launch's loads) where the stage's list says so: the caller asks pro_fusable() first */
     /* coarse != NULL (with want_res != 0): the residual is restricted on the fly into the interior of
      * coarse->d and never stored; the caller adds the face injection (k_restrict, faces_only) */
     Level &l = ctx->lv[level];
     hipStream_t s = ctx->stream;
-    const int c1 = post ? 0 : 1; /* pre: red first (mg_3d.h:657); post: black first (mg_3d.h:728) */
     if (mg3d_fused(ctx)) {
-        int passes = 2 * iters;
-        bool done_res = want_res == 0;
-        while (passes > 0 || !done_res) {
-            /* Where the norm is wanted behind FOUR post-smoothing passes (the top level of a V(2,2) cycle) the stage
-             * runs as 2 + 2 passes: the first launch takes the prolongation into its loads (the 2-pass shape has the
-             * registers for it: 0.77 ms against 0.74 ms without), the second one the residual norm (0.90 ms) --
-             * 1.67 ms instead of 0.56 (prolongation) + 0.82 (4 passes) + 0.47 (norm).  Below the top level no norm
-             * is formed and prolongation + 4 passes in two launches stays cheaper. */
-            const bool sp = split_up_leg(iters, want_res);
-            const int S = (sp && post && passes >= 2) ? 2 : passes >= 4 ? 4 : passes; /* 4, 2 or 0 */
-            const bool last = passes - S == 0;
-            /* the residual rides on a 2-pass launch; behind 4 passes it gets its own launch (the 5-stage
-             * window leaves too few registers for a tile with a useful interior: measured 1.9 ms fused
-             * against 0.85 + 0.76 ms split on a 513^3 level) */
-            /* two passes + residual + restriction (the down-leg of V(1,1), the tail of V(3,3)'s): one launch from 130
-             * points per side up, two below (k_sweep_fuse_rst2) */
-            /* small levels (<= MG3D_FUSE_LEG_MAX points per side): the whole down-leg -- four passes, residual,
-             * restriction -- as one launch of the two-rows-per-thread shape: it wastes three quarters of its rows
-             * and saves a launch where launches are paid in latency, not in bytes */
-            const bool leg4 = S == 4 && coarse != nullptr && !need_norm && want_res != 0 && l.g.N <= ctx->opt.v[MG3D_OPT_FUSE_LEG_MAX];
-            const bool res = last && want_res != 0 && (S != 4 || leg4) &&
-                             !(S == 2 && coarse != nullptr && !k_sweep_fuse_rst2(ctx->opt, l.g.N));
-            const bool rst = res && coarse != nullptr;
-            const bool with_pro = pro != nullptr && passes == 2 * iters; /* first launch only */
-            int np;
-            {
-                StageScope kt(ctx, level, S == 4 ? MG3D_K_SWEEP4 : S == 2 ? (res ? MG3D_K_SWEEP2_RES : MG3D_K_SWEEP2)
-                                                                          : MG3D_K_RESIDUAL, true);
-                np = k_sweep(ctx->opt, l.g, (zero_in && passes == 2 * iters) ? nullptr : l.f[MG3D_U], l.f[MG3D_D], l.alt,
-                             (res && want_res == 2 && !rst) ? l.f[MG3D_R] : nullptr,
-                             (res && need_norm) ? ctx->partials : nullptr,
-                             MG3D_MAX_PARTIALS, mg3d_op(ctx, l), S, c1, res, s, 0, -1, rst ? &coarse->g : nullptr,
-                             rst ? coarse->f[MG3D_D] : nullptr, -1, -1, with_pro ? &pro->g : nullptr,
-                             with_pro ? pro->f[MG3D_U] : nullptr);
-            }
-            if (np < 0) /* nothing was launched: no buffer swap, no fold of partial sums that were never written */
-                return fail(MG3D_ERR_STATE, "fused sweep: no kernel for %d colour passes%s on level %d", S,
-                            res ? " + residual" : "", level);
-            if (S > 0) {
-                double *t = l.f[MG3D_U];
-                l.f[MG3D_U] = l.alt;
-                l.alt = t;
-            }
-            if (res) {
-                if (need_norm)
-                    k_fold(ctx->partials, np, ctx->sumsq + slot, s);
-                done_res = true;
-            }
-            passes -= S;
-        }
+        const StagePlan plan = mg3d_stage_plan(ctx->opt, stage_ask(ctx, level, post, iters, want_res, coarse != nullptr, need_norm,
+                                                                   pro != nullptr));
+        for (int k = 0; mg3d_stage_launch(plan, k); k++)
+            CHK(enqueue_stage_step(ctx, level, post, *mg3d_stage_launch(plan, k), k == 0, want_res, slot, coarse, pro, zero_in, need_norm));
         return MG3D_OK;
     }
+    const int c1 = post ? 0 : 1;
     const LevelOp op = mg3d_op(ctx, l);
     const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
     for (int it = 0; it < 2 * iters; it++) {
@@ -1081,26 +1081,11 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     return MG3D_OK;
 }
 
-/* can the prolongation ride on the first smoothing launch?  (needs a smoothing-only first launch) */
+/* can the prolongation ride on the first smoothing launch?  (asked of the stage's own list: it needs a smoothing-only first
+ * launch of a shape with the registers for it) */
 static bool pro_fusable(const mg3d_ctx *ctx, int iters, int want_res, int level)
 {
-    /* small levels: the two-rows-per-thread four-pass shape has the registers for the prolongation (k_sweep) */
-    const int up_max = ctx->opt.v[MG3D_OPT_FUSE_UP_MAX] > ctx->opt.v[MG3D_OPT_FUSE_LEG_MAX] ? ctx->opt.v[MG3D_OPT_FUSE_UP_MAX]
-                                                                                             : ctx->opt.v[MG3D_OPT_FUSE_LEG_MAX];
-    const bool small = ctx->lv[level].g.N <= up_max && 2 * iters == 4 && want_res == 0;
-    /* On a 4-pass first launch of a level above small_max it used to be SLOWER (the four-row shape spilt; round 2 measured
-     * 1.48 ms against 0.85 + 0.56 at 513^3).  Since the prolongation is applied at the end of the step before (MG3D_PRO_LATE in
-     * the kernel) that shape has 248 VGPRs and no scratch: the 257^3 level of the 513^3 problem takes 0.12 instead of
-     * 0.058 + 0.112 ms, the cycle 2.18 -> 2.13 ms -- fuse_up_max now defaults to every level.  The 2-pass first launch of
-     * a split stage takes it almost for free. */
-    if (!mg3d_fused(ctx) || iters < 1)
-        return false;
-    const bool sp = split_up_leg(iters, want_res);
-    if (!sp && !small)
-        return false;
-    const int first = (2 * iters >= 4 && !sp) ? 4 : 2;
-    const bool first_has_res = want_res != 0 && first == 2 && 2 * iters == 2;
-    return !first_has_res;
+    return mg3d_fused(ctx) && mg3d_stage_plan(ctx->opt, stage_ask(ctx, level, 1, iters, want_res, false, true, true)).step[0].pro;
 }
 
 /* the unfused grid transfers and the direct solve: the k_per_* forms when an axis is periodic or a face is a Neumann face */
@@ -1241,15 +1226,15 @@ extern "C" int mg3d_l2norm(mg3d_ctx *ctx, int field, int level, double *norm)
  * same operands in the same expression, the same bits -- it is the identity.  What is left is ONE alternating run
  *      [prolongation] B R | B R <norm of cycle n> B R | B [residual, restriction]
  * which three launches cover instead of four: prolongation + 2 passes (as before), four passes with the norm tapped
- * after the second (k_sweep_tap: no stage of its own), one pass + residual + restriction -- 9 n w + 2 n_c w instead of
+ * after the second (SWEEP_TAP: no stage of its own), one pass + residual + restriction -- 9 n w + 2 n_c w instead of
  * 11 n w + 2 n_c w compulsory bytes per cycle on the top level.  The tap launch reads u of cycle n and writes the other
  * buffer; cycle n's own u (the tapped state) is never written -- mg3d_drop_carry makes it from that input when it is
  * wanted.  mg3d_vcycles never ends a call in the carried state (its last cycle ends the ordinary way); mg3d_vcycle does.  Only V(2,2) from the finest level of a context with
  * at least three levels, fused sweeps, r not kept; MG3D_NO_CARRY=1 switches it off (tests compare both). */
 /* One launch per leg ("two launches per level", round 4).  The alternating run of colour passes between two cycles
  *      [prolongation] B R B R <norm of cycle n> (R = identity) B R B [residual, restriction]
- * is cut at the norm instead: the up-leg is ONE launch (prolongation + four passes, k_sweep_leg_up) and the down-leg is ONE
- * launch (three passes + residual + restriction, k_sweep_leg_down) -- 6 n w + 2 n_c w compulsory bytes per cycle on the top
+ * is cut at the norm instead: the up-leg is ONE launch (prolongation + four passes, SWEEP_LEG_UP) and the down-leg is ONE
+ * launch (three passes + residual + restriction, SWEEP_LEG_DOWN) -- 6 n w + 2 n_c w compulsory bytes per cycle on the top
  * level instead of 9 n w + 2 n_c w.  No launch has a stage for the norm: the residual of the points the up-leg's last pass
  * (red) has just updated falls out of that pass's neighbour sums, the residual of the black points out of the sums the
  * next down-leg's first pass (black) forms before it updates them -- two runs of partial sums, folded into one norm.  The
@@ -1261,26 +1246,312 @@ extern "C" int mg3d_l2norm(mg3d_ctx *ctx, int field, int level, double *norm)
  * 769^3 11.31 / 10.76, 1025^3 20.65 / 16.79 (profiles/r04_legs_by_size.txt); option legs = 0 keeps the carried cycles. */
 bool mg3d_can_legs(const mg3d_ctx *ctx, int q)
 {
-    if (!ctx->opt.v[MG3D_OPT_LEGS])
-        return false;
-    const mg3d_ctx *c = ctx;
     /* the conditions of the carried cycles, except their own switch and threshold */
-    return mg3d_fused(c) && !c->keep_r && !c->have_es && c->iters == 2 && q == c->L - 1 && q >= 2 && c->lv[q].g.N >= c->opt.v[MG3D_OPT_LEGS_MIN] &&
-           c->lv[q].g.N > 65 && (c->lv[q].g.nj & 1) != 0;
+    const Geom &g = ctx->lv[q].g;
+    return mg3d_fused(ctx) && !ctx->have_es && q == ctx->L - 1 && q >= 2 &&
+           mg3d_can_run_ahead(ctx->opt, true, -1, ctx->iters, ctx->keep_r, g.N, g.nj);
 }
 
 bool mg3d_can_carry(const mg3d_ctx *ctx, int q)
 {
-    if (!ctx->opt.v[MG3D_OPT_CARRY])
-        return false;
     /* from 257^3 up: there the launch saved is bytes (257^3: +5 %, 513^3: +17 %, 1025^3: +16 % V-cycles/s); at 129^3 a
      * launch is pipeline fill and the plain schedule's lighter launches are 1 % ahead.  MG3D_CARRY_MIN=<points per side>
      * moves the threshold (the tests run 129^3 problems); never at 65^3 and below (the two launches only exist in
      * the four-rows-per-thread shapes) */
-    const int n_min = ctx->opt.v[MG3D_OPT_CARRY_MIN];
-    return mg3d_fused(ctx) && !ctx->keep_r && !ctx->have_es && ctx->iters == 2 && q == ctx->L - 1 && q >= 2 &&
-           ctx->lv[q].g.N >= n_min && ctx->lv[q].g.N > 65 && (ctx->lv[q].g.nj & 1) != 0 && split_up_leg(2, 1) &&
-           pro_fusable(ctx, 2, 1, q);
+    const Geom &g = ctx->lv[q].g;
+    return mg3d_fused(ctx) && !ctx->have_es && q == ctx->L - 1 && q >= 2 &&
+           mg3d_can_run_ahead(ctx->opt, false, -1, ctx->iters, ctx->keep_r, g.N, g.nj) &&
+           pro_fusable(ctx, 2, 1, q); /* the split up-leg whose first launch the carried cycle keeps */
+}
+
+/* What one cycle does on which level, settled before its first launch (mg3d_enqueue_vcycle). */
+struct CycleState {
+    int q, slot, carry_out;
+    bool tiny;      /* level 1 below the top of the cycle, small enough for one workgroup's LDS: two launches instead of five */
+    bool tiny_cyc;  /* ... and the whole bottom of the cycle (level 1 down, the direct solve, level 1 up) as ONE launch when the
+                       reduced factor exists (mg3d_tiny.hip, tiny_cycle_kernel); MG3D_NO_TINY_CYCLE=1 keeps the three launches
+                       (tests compare) */
+    bool can_legs, can_carry;
+    bool carry_in;  /* the previous cycle carried into this one */
+    int legs_in;    /* legs_state the previous cycle left */
+    /* red_tail: the last thing that happened to u of the top level was the red pass that ends a cycle, and nothing has touched
+     * u or d since (every entry point that could clears the flag through mg3d_drop_carry; not once a raw pointer is out) --
+     * this cycle's first red pass is the identity then, ACROSS calls as inside one: its down-leg is the one launch of three
+     * passes + residual + restriction (no norm half: the finished cycle formed its norm itself) instead of four passes, then
+     * residual + restriction (0.84 against 0.67 + 0.50 ms at 513^3) */
+    bool red_in;
+};
+
+static double *part_a(mg3d_ctx *ctx) { return ctx->partials; } /* the two halves of a norm that two leg launches form */
+static double *part_b(mg3d_ctx *ctx) { return ctx->partials + MG3D_MAX_PARTIALS / 2; }
+
+/* The face injection of the restriction l -> l-1 (:879-958), inside the caller's MG3D_ST_RESTRICT scope.  faces_only: the
+ * interior was restricted on the fly, and the faces only have something new to copy after r of this level or d of the
+ * coarser one was written from outside the cycle (faces_dirty), or always once a raw pointer to one of them is out. */
+static void restrict_stage(mg3d_ctx *ctx, int l, bool faces_only)
+{
+    if (faces_only && !ctx->faces_dirty[l] && !ctx->faces_always[l])
+        return;
+    StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
+    /* (periodic axes: never faces_only -- the periodic faces are fully weighted on every cycle) */
+    enqueue_restrict(ctx, l, faces_only);
+    ctx->faces_dirty[l] = 0;
+}
+
+/* behind a down-leg whose one launch held the residual and the restriction: both stages counted (~0 s), the faces injected */
+static void down_leg_tail(mg3d_ctx *ctx, int l)
+{
+    { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); }
+    StageScope t(ctx, l, MG3D_ST_RESTRICT);
+    restrict_stage(ctx, l, true);
+}
+
+/* the three-pass down-leg launch of the one-launch-per-leg schedule: black, red, black (the first red pass is the identity
+ * behind a finished cycle) + residual + restriction into dc (:1282 + :1294 + :1310).  norm_half: on its way the black half
+ * of the norm of the cycle in front of it, folded with that cycle's red half (npa partial sums) into sumsq[slot]. */
+static int launch_leg_down(mg3d_ctx *ctx, int l, double *dc, bool norm_half, int npa, int slot)
+{
+    Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
+    SweepLaunch w = mg3d_level_sweep(ctx, lev);
+    w.kind = SWEEP_LEG_DOWN;
+    w.S = 3;
+    w.gc = &lc.g;
+    w.dc = dc;
+    w.partials = norm_half ? part_b(ctx) : nullptr;
+    w.max_partials = MG3D_MAX_PARTIALS / 2;
+    StageScope kt(ctx, l, MG3D_K_LEG_DOWN, true);
+    const int np = k_sweep(ctx->opt, w, ctx->stream);
+    if (np < 0)
+        return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the down-leg");
+    swap_u(lev);
+    if (norm_half)
+        k_fold2(part_a(ctx), npa, part_b(ctx), np, ctx->sumsq + slot, ctx->stream);
+    return MG3D_OK;
+}
+
+/* down-leg of the top level, one launch per leg, behind another cycle (legs_in) or a finished one (red_in).
+ * (a cycle with no cycle in front of it takes the ordinary down-leg -- four passes, then residual +
+ * restriction: the one-launch form of THAT leg needs a six-plane window, spills 180 bytes at eight rows per thread
+ * and took 2.1 ms against 0.66 + 0.49: profiles/r04_bench_kernel_stats_note.txt) */
+static int down_leg_ahead(mg3d_ctx *ctx, const CycleState &c, int l)
+{
+    Level &lc = ctx->lv[l - 1];
+    {
+        StageScope t(ctx, l, MG3D_ST_SMOOTH1);
+        if (c.legs_in == 3) {
+            /* this cycle's down-leg ran behind the previous mg3d_vcycle call: its u is the top level's u already,
+             * its restricted residual sits in the coarser level's alt buffer */
+            double *t2 = lc.f[MG3D_D];
+            lc.f[MG3D_D] = lc.alt;
+            lc.alt = t2;
+            ctx->faces_dirty[l] = 1; /* the two buffers take turns as d: inject the faces into this one */
+        } else {
+            /* (behind a cycle of this call: the black half of its norm; behind a finished one: none) */
+            CHK(launch_leg_down(ctx, l, lc.f[MG3D_D], !c.red_in, ctx->legs_npa, ctx->legs_slot));
+        }
+    }
+    down_leg_tail(ctx, l);
+    return MG3D_OK;
+}
+
+/* down-leg of the top level behind a carried cycle: the one pre-smoothing pass that is left (black) + residual +
+ * restriction (:1282 + :1294 + :1310) */
+static int down_leg_carried(mg3d_ctx *ctx, int l)
+{
+    Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
+    {
+        StageScope t(ctx, l, MG3D_ST_SMOOTH1);
+        StageScope kt(ctx, l, MG3D_K_SWEEP1_RESTRICT, true);
+        SweepLaunch w = mg3d_level_sweep(ctx, lev);
+        w.kind = SWEEP_PASSES_RES;
+        w.S = 1;
+        w.c1 = 0;
+        w.gc = &lc.g;
+        w.dc = lc.f[MG3D_D];
+        if (k_sweep(ctx->opt, w, ctx->stream) < 0)
+            return fail(MG3D_ERR_STATE, "carried cycle: no kernel for one pass + residual + restriction");
+        swap_u(lev);
+    }
+    down_leg_tail(ctx, l);
+    return MG3D_OK;
+}
+
+/* level 1 in one workgroup: the whole bottom of the cycle (:1258 ... :1341 of levels 1, 0) or its down-leg
+ * (:1258 + :1282 + :1294 + :1310) as one launch, which injects the faces itself */
+static void down_leg_tiny(mg3d_ctx *ctx, const CycleState &c)
+{
+    Level &lev = ctx->lv[1], &l0 = ctx->lv[0];
+    {
+        StageScope t(ctx, 1, MG3D_ST_SMOOTH1);
+        StageScope kt(ctx, 1, MG3D_K_SWEEP4, true);
+        if (c.tiny_cyc)
+            k_tiny_cycle(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu, ctx->lu_in,
+                         mg3d_op(ctx, lev), ctx->iters, ctx->stream);
+        else
+            k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], l0.g, l0.f[MG3D_D], mg3d_op(ctx, lev), ctx->iters,
+                        ctx->stream);
+    }
+    { StageScope t(ctx, 1, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
+    { StageScope t(ctx, 1, MG3D_ST_RESTRICT); }
+    ctx->faces_dirty[1] = 0;
+}
+
+/* the down-leg of every other level: zero guess, pre-smoother, residual, restriction */
+static int down_leg_ordinary(mg3d_ctx *ctx, int l)
+{
+    Level &lev = ctx->lv[l];
+    /* :1258-1259: the zero initial guess of a coarser level; with the fused sweep the first launch simply
+     * does not read u (and writes every plane of the other buffer), so no memset is needed */
+    const bool zero_in = l < ctx->L - 1 && mg3d_fused(ctx) && ctx->iters > 0;
+    if (l < ctx->L - 1 && !zero_in)
+        (void)hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), ctx->stream);
+    if (mg3d_fused(ctx)) { /* pre-smoother and residual in one pass over the level (:1282 + :1294) */
+        {
+            StageScope t(ctx, l, MG3D_ST_SMOOTH1);
+            CHK(enqueue_smooth_residual(ctx, l, 0, ctx->iters, 2, ctx->sumsq_slots - 1,
+                                        ctx->keep_r ? nullptr : &ctx->lv[l - 1], nullptr, zero_in, false));
+        }
+        StageScope t(ctx, l, MG3D_ST_RESIDUAL1); /* fused into the launch above: counted, ~0 s */
+    } else {
+        {
+            StageScope t(ctx, l, MG3D_ST_SMOOTH1);
+            CHK(enqueue_smooth(ctx, l, 0, ctx->iters)); /* :1282 */
+        }
+        StageScope t(ctx, l, MG3D_ST_RESIDUAL1);
+        CHK(enqueue_residual(ctx, l, 1, ctx->sumsq_slots - 1)); /* :1294 (norm discarded) */
+    }
+    StageScope t(ctx, l, MG3D_ST_RESTRICT);
+    /* :1310; when the interior was restricted on the fly only the face injection is left */
+    restrict_stage(ctx, l, mg3d_fused(ctx) && !ctx->keep_r);
+    return MG3D_OK;
+}
+
+/* level 0: the direct solve (:1270), unless the single-workgroup launch of level 1 held it */
+static void bottom(mg3d_ctx *ctx, const CycleState &c)
+{
+    if (c.tiny_cyc) {
+        StageScope t(ctx, 0, MG3D_ST_RECURSE); /* inside the launch above */
+        return;
+    }
+    Level &l0 = ctx->lv[0];
+    if (0 < ctx->L - 1)
+        (void)hipMemsetAsync(l0.f[MG3D_U], 0, l0.elems * sizeof(double), ctx->stream);
+    StageScope t(ctx, 0, MG3D_ST_RECURSE);
+    StageScope kt(ctx, 0, MG3D_K_COARSE_SOLVE, true);
+    enqueue_coarse_solve(ctx);
+}
+
+/* level 1 in one workgroup: prolongation + post-smoother as one launch (:1331 + :1341), or nothing left to do */
+static void up_leg_tiny(mg3d_ctx *ctx, const CycleState &c)
+{
+    Level &lev = ctx->lv[1], &l0 = ctx->lv[0];
+    { StageScope t(ctx, 1, MG3D_ST_PROLONG); } /* inside the launch below (tiny_cyc: the one on the way down) */
+    {
+        StageScope t(ctx, 1, MG3D_ST_SMOOTH2);
+        if (!c.tiny_cyc) {
+            StageScope kt(ctx, 1, MG3D_K_SWEEP4, true);
+            k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], l0.g, l0.f[MG3D_U], mg3d_op(ctx, lev), ctx->iters, ctx->stream);
+        }
+    }
+    { StageScope t(ctx, 1, MG3D_ST_RESIDUAL2); }
+}
+
+/* up-leg of the top level as ONE launch: prolongation + black, red, black, red (:1331 + :1341); with another cycle behind it,
+ * the red half of the norm (:1354) from the last pass's sums */
+static int up_leg_legs(mg3d_ctx *ctx, const CycleState &c, int l)
+{
+    Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
+    { StageScope t(ctx, l, MG3D_ST_PROLONG); } /* :1331, folded into the launch below */
+    {
+        StageScope t(ctx, l, MG3D_ST_SMOOTH2);
+        SweepLaunch w = mg3d_level_sweep(ctx, lev);
+        w.kind = SWEEP_LEG_UP;
+        w.gce = &lc.g;
+        w.ec = lc.f[MG3D_U];
+        w.partials = c.carry_out ? part_a(ctx) : nullptr;
+        w.max_partials = MG3D_MAX_PARTIALS / 2;
+        int npa;
+        {
+            StageScope kt(ctx, l, MG3D_K_LEG_UP, true);
+            npa = k_sweep(ctx->opt, w, ctx->stream);
+        }
+        if (npa < 0)
+            return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the up-leg");
+        swap_u(lev);
+        if (c.carry_out == 1) { /* the next cycle of this mg3d_vcycles call completes the norm */
+            ctx->legs_state = 2;
+            ctx->legs_slot = c.slot;
+            ctx->legs_npa = npa;
+        } else if (c.carry_out == 2) {
+            /* mg3d_vcycle: the next cycle's down-leg now, into the alt buffers (see mg3d_can_legs) */
+            CHK(launch_leg_down(ctx, l, lc.alt, true, npa, c.slot));
+            ctx->legs_state = 3;
+        }
+    }
+    StageScope t(ctx, l, MG3D_ST_RESIDUAL2);
+    if (!c.carry_out)
+        CHK(enqueue_residual(ctx, l, 0, c.slot)); /* :1354, the last cycle of a call: a launch of its own */
+    return MG3D_OK;
+}
+
+/* up-leg of the top level of a cycle that carries into the next one */
+static int up_leg_carried(mg3d_ctx *ctx, const CycleState &c, int l)
+{
+    Level &lev = ctx->lv[l];
+    { StageScope t(ctx, l, MG3D_ST_PROLONG); } /* :1331, folded into the launch below */
+    {
+        StageScope t(ctx, l, MG3D_ST_SMOOTH2);
+        /* prolongation + the first two post-smoothing passes: the launch the ordinary cycle starts its up-leg with */
+        const StagePlan split = mg3d_stage_plan(ctx->opt, stage_ask(ctx, l, 1, 2, 1, false, true, true));
+        CHK(enqueue_stage_step(ctx, l, 1, split.step[0], true, 0, c.slot, nullptr, &ctx->lv[l - 1], false, true));
+        /* black, red (:1341, second half) <norm, :1354> black, red (:1282 of the next cycle, its first red pass
+         * being the identity) */
+        StageScope kt(ctx, l, MG3D_K_SWEEP4_NORM, true);
+        SweepLaunch w = mg3d_level_sweep(ctx, lev);
+        w.kind = SWEEP_TAP;
+        w.c1 = 0;
+        w.partials = ctx->partials;
+        const int np = k_sweep(ctx->opt, w, ctx->stream);
+        if (np < 0)
+            return fail(MG3D_ERR_STATE, "carried cycle: no kernel for four passes + norm tap");
+        swap_u(lev);
+        k_fold(ctx->partials, np, ctx->sumsq + c.slot, ctx->stream);
+        ctx->carried = true;
+    }
+    { StageScope t(ctx, l, MG3D_ST_RESIDUAL2); }
+    return MG3D_OK;
+}
+
+/* the up-leg of every other level: prolongation, post-smoother and, on the top level, the residual norm */
+static int up_leg_ordinary(mg3d_ctx *ctx, const CycleState &c, int l)
+{
+    const int want_norm = l == c.q ? 1 : 0;
+    const bool pro = pro_fusable(ctx, ctx->iters, want_norm, l);
+    {
+        StageScope t(ctx, l, MG3D_ST_PROLONG); /* :1331; ~0 s when folded into the smoother's loads */
+        if (!pro) {
+            StageScope kt(ctx, l, MG3D_K_PROLONG, true);
+            enqueue_prolong(ctx, l);
+        }
+    }
+    if (mg3d_fused(ctx)) { /* (prolongation,) post-smoother and residual norm (:1331 + :1341 + :1354) */
+        {
+            StageScope t(ctx, l, MG3D_ST_SMOOTH2);
+            /* the norm of a level below the top one is computed and dropped by the reference (:1320
+             * ignores the recursive call's value): skip it, nothing observable changes */
+            CHK(enqueue_smooth_residual(ctx, l, 1, ctx->iters, want_norm, c.slot, nullptr, pro ? &ctx->lv[l - 1] : nullptr));
+        }
+        StageScope t(ctx, l, MG3D_ST_RESIDUAL2); /* fused into the launch above: counted, ~0 s */
+        return MG3D_OK;
+    }
+    {
+        StageScope t(ctx, l, MG3D_ST_SMOOTH2);
+        CHK(enqueue_smooth(ctx, l, 1, ctx->iters)); /* :1341 */
+    }
+    StageScope t(ctx, l, MG3D_ST_RESIDUAL2);
+    if (l == c.q)
+        CHK(enqueue_residual(ctx, l, 0, c.slot)); /* :1354; below the top level the value is dropped (:1320) */
+    return MG3D_OK;
 }
 
 int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
@@ -1290,7 +1561,6 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
     if (ctx->have_es)
         return fail(MG3D_ERR_STATE, "mg3d_vcycle: the context holds the mixed-boundary factor of mg3d_es_setup "
                                     "(mg3d_es_vcycles, or load the Dirichlet factor again)");
-    hipStream_t s = ctx->stream;
     const int L = ctx->L;
     struct PhaseTick { /* sampled kernel timers (timing >= 4): full cycles are counted off, also on an early return */
         mg3d_ctx *c;
@@ -1301,271 +1571,48 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
                 c->timing_phase = (c->timing_phase + 1) % (c->timing - 2);
         }
     } tick{ctx, q == L - 1};
-    /* level 1 below the top of the cycle, small enough for one workgroup's LDS: two launches instead of five */
-    const bool no_tiny = !ctx->opt.v[MG3D_OPT_TINY];
-    const bool tiny = !no_tiny && mg3d_fused(ctx) && !ctx->keep_r && q >= 2 && ctx->iters >= 1 && k_tiny_fits(ctx->lv[1].g, ctx->lv[0].g);
-    /* ... and the whole bottom of the cycle (level 1 down, the direct solve, level 1 up) as ONE launch when the reduced
-     * factor exists (mg3d_tiny.hip, tiny_cycle_kernel); MG3D_NO_TINY_CYCLE=1 keeps the three launches (tests compare) */
-    const bool no_cyc = !ctx->opt.v[MG3D_OPT_TINY_CYCLE];
-    const bool tiny_cyc = tiny && !no_cyc && k_tiny_cycle_fits(ctx->lv[1].g, ctx->lv[0].g, ctx->lu, ctx->lu_in);
-    const bool can_legs = mg3d_can_legs(ctx, q);
-    const bool can_carry = !can_legs && mg3d_can_carry(ctx, q);
-    if ((ctx->carried && !can_carry) || (ctx->legs_state != 0 && !can_legs)) /* e.g. MG3D_NO_CARRY set between two calls: finish the carried cycle, go on plainly */
+    /* ---- what this cycle is, and what the one before left behind */
+    CycleState c;
+    c.q = q;
+    c.slot = slot;
+    c.carry_out = carry_out;
+    c.tiny = ctx->opt.v[MG3D_OPT_TINY] && mg3d_fused(ctx) && !ctx->keep_r && q >= 2 && ctx->iters >= 1 &&
+             k_tiny_fits(ctx->lv[1].g, ctx->lv[0].g);
+    c.tiny_cyc = c.tiny && ctx->opt.v[MG3D_OPT_TINY_CYCLE] && k_tiny_cycle_fits(ctx->lv[1].g, ctx->lv[0].g, ctx->lu, ctx->lu_in);
+    c.can_legs = mg3d_can_legs(ctx, q);
+    c.can_carry = !c.can_legs && mg3d_can_carry(ctx, q);
+    if ((ctx->carried && !c.can_carry) || (ctx->legs_state != 0 && !c.can_legs)) /* e.g. MG3D_NO_CARRY set between two calls: finish the carried cycle, go on plainly */
         CHK(mg3d_drop_carry_keep(ctx));
-    const bool carry_in = ctx->carried;
+    c.carry_in = ctx->carried;
     ctx->carried = false;
-    const int legs_in = ctx->legs_state;
+    c.legs_in = ctx->legs_state;
     ctx->legs_state = 0;
-    /* red_tail: the last thing that happened to u of the top level was the red pass that ends a cycle, and nothing has touched
-     * u or d since (every entry point that could clears the flag through mg3d_drop_carry; not once a raw pointer is out) --
-     * this cycle's first red pass is the identity then, ACROSS calls as inside one: its down-leg is the one launch of three
-     * passes + residual + restriction (no norm half: the finished cycle formed its norm itself) instead of four passes, then
-     * residual + restriction (0.84 against 0.67 + 0.50 ms at 513^3) */
-    const bool red_in = q == L - 1 && legs_in == 0 && !carry_in && ctx->red_tail && can_legs && !ctx->raw_top;
+    c.red_in = q == L - 1 && c.legs_in == 0 && !c.carry_in && ctx->red_tail && c.can_legs && !ctx->raw_top;
     ctx->red_tail = false;
-    double *const part_a = ctx->partials, *const part_b = ctx->partials + MG3D_MAX_PARTIALS / 2;
+    /* ---- down: the top level continues what ran ahead of it, level 1 fits one workgroup, the rest is ordinary */
     for (int l = q; l >= 1; l--) {
-        Level &lev = ctx->lv[l];
-        /* (a cycle with no cycle in front of it takes the ordinary down-leg below -- four passes, then residual +
-         * restriction: the one-launch form of THAT leg needs a six-plane window, spills 180 bytes at eight rows per thread
-         * and took 2.1 ms against 0.66 + 0.49: profiles/r04_bench_kernel_stats_note.txt) */
-        if (l == q && can_legs && (legs_in != 0 || red_in)) {
-            Level &lc = ctx->lv[l - 1];
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                if (legs_in == 3) {
-                    /* this cycle's down-leg ran behind the previous mg3d_vcycle call: its u is the top level's u already,
-                     * its restricted residual sits in the coarser level's alt buffer */
-                    double *t2 = lc.f[MG3D_D];
-                    lc.f[MG3D_D] = lc.alt;
-                    lc.alt = t2;
-                    ctx->faces_dirty[l] = 1; /* the two buffers take turns as d: inject the faces into this one */
-                } else {
-                    StageScope kt(ctx, l, MG3D_K_LEG_DOWN, true);
-                    /* behind another cycle: black, red, black (the first red pass is the identity) and the black half of
-                     * that cycle's norm, + residual + restriction (:1282 + :1294 + :1310) */
-                    const int np = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_D], mg3d_op(ctx, lev),
-                                                    3, red_in ? nullptr : part_b, MG3D_MAX_PARTIALS / 2, s);
-                    if (np < 0)
-                        return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the down-leg");
-                    double *t2 = lev.f[MG3D_U];
-                    lev.f[MG3D_U] = lev.alt;
-                    lev.alt = t2;
-                    if (!red_in) /* (behind a cycle of this call: the black half of its norm) */
-                        k_fold2(part_a, ctx->legs_npa, part_b, np, ctx->sumsq + ctx->legs_slot, s);
-                }
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); }
-            StageScope t(ctx, l, MG3D_ST_RESTRICT);
-            if (ctx->faces_dirty[l] || ctx->faces_always[l]) {
-                StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
-                k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], s, -1, -1, true);
-                ctx->faces_dirty[l] = 0;
-            }
-            continue;
-        }
-        if (l == q && carry_in) {
-            { /* the one pre-smoothing pass that is left (black) + residual + restriction (:1282 + :1294 + :1310) */
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                StageScope kt(ctx, l, MG3D_K_SWEEP1_RESTRICT, true);
-                const int np = k_sweep(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(ctx, lev),
-                                       1, 0, true, s, 0, -1, &ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_D]);
-                if (np < 0)
-                    return fail(MG3D_ERR_STATE, "carried cycle: no kernel for one pass + residual + restriction");
-                double *t2 = lev.f[MG3D_U];
-                lev.f[MG3D_U] = lev.alt;
-                lev.alt = t2;
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); }
-            StageScope t(ctx, l, MG3D_ST_RESTRICT);
-            if (ctx->faces_dirty[l] || ctx->faces_always[l]) {
-                StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
-                k_restrict(lev.g, lev.f[MG3D_R], ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_D], s, -1, -1, true);
-                ctx->faces_dirty[l] = 0;
-            }
-            continue;
-        }
-        if (l == 1 && tiny_cyc) {
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
-                k_tiny_cycle(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], ctx->lv[0].g, ctx->lv[0].f[MG3D_D],
-                             ctx->lv[0].f[MG3D_U], ctx->lu, ctx->lu_in, mg3d_op(ctx, lev), ctx->iters, s); /* :1258 ... :1341 of levels 1, 0 */
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
-            { StageScope t(ctx, l, MG3D_ST_RESTRICT); }
-            ctx->faces_dirty[l] = 0;
-            continue;
-        }
-        if (l == 1 && tiny) {
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
-                k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], ctx->lv[0].g, ctx->lv[0].f[MG3D_D], mg3d_op(ctx, lev),
-                            ctx->iters, s); /* :1258 + :1282 + :1294 + :1310 */
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
-            { StageScope t(ctx, l, MG3D_ST_RESTRICT); }
-            ctx->faces_dirty[l] = 0; /* the launch injects the faces itself */
-            continue;
-        }
-        /* :1258-1259: the zero initial guess of a coarser level; with the fused sweep the first launch simply
-         * does not read u (and writes every plane of the other buffer), so no memset is needed */
-        const bool zero_in = l < L - 1 && mg3d_fused(ctx) && ctx->iters > 0;
-        if (l < L - 1 && !zero_in)
-            (void)hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), s);
-        if (mg3d_fused(ctx)) { /* pre-smoother and residual in one pass over the level (:1282 + :1294) */
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                CHK(enqueue_smooth_residual(ctx, l, 0, ctx->iters, 2, ctx->sumsq_slots - 1,
-                                            ctx->keep_r ? nullptr : &ctx->lv[l - 1], nullptr, zero_in, false));
-            }
-            StageScope t(ctx, l, MG3D_ST_RESIDUAL1); /* fused into the launch above: counted, ~0 s */
-        } else {
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH1);
-                CHK(enqueue_smooth(ctx, l, 0, ctx->iters)); /* :1282 */
-            }
-            StageScope t(ctx, l, MG3D_ST_RESIDUAL1);
-            CHK(enqueue_residual(ctx, l, 1, ctx->sumsq_slots - 1)); /* :1294 (norm discarded) */
-        }
-        {
-            StageScope t(ctx, l, MG3D_ST_RESTRICT);
-            /* :1310; when the interior was restricted on the fly only the face injection (:879-958) is left, and
-             * that only has something new to copy after r of this level or d of the coarser one was written from
-             * outside the cycle (faces_dirty) */
-            const bool faces_only = mg3d_fused(ctx) && !ctx->keep_r;
-            if (!faces_only || ctx->faces_dirty[l] || ctx->faces_always[l]) {
-                StageScope kt(ctx, l, MG3D_K_RESTRICT, true);
-                /* (periodic axes: never faces_only -- the periodic faces are fully weighted on every cycle) */
-                enqueue_restrict(ctx, l, faces_only);
-                ctx->faces_dirty[l] = 0;
-            }
-        }
+        if (l == q && c.can_legs && (c.legs_in != 0 || c.red_in))
+            CHK(down_leg_ahead(ctx, c, l));
+        else if (l == q && c.carry_in)
+            CHK(down_leg_carried(ctx, l));
+        else if (l == 1 && c.tiny)
+            down_leg_tiny(ctx, c);
+        else
+            CHK(down_leg_ordinary(ctx, l));
     }
-    if (tiny_cyc) {
-        StageScope t(ctx, 0, MG3D_ST_RECURSE); /* inside the launch above */
-    } else {
-        Level &l0 = ctx->lv[0];
-        if (0 < L - 1)
-            (void)hipMemsetAsync(l0.f[MG3D_U], 0, l0.elems * sizeof(double), s);
-        StageScope t(ctx, 0, MG3D_ST_RECURSE);
-        StageScope kt(ctx, 0, MG3D_K_COARSE_SOLVE, true);
-        enqueue_coarse_solve(ctx); /* :1270 */
-    }
+    bottom(ctx, c);
+    /* ---- up: level 1 as on the way down; the top level in the schedule that lets the next cycle run ahead */
     for (int l = 1; l <= q; l++) {
-        Level &lev = ctx->lv[l];
-        if (l == 1 && tiny_cyc) {
-            { StageScope t(ctx, l, MG3D_ST_PROLONG); }
-            { StageScope t(ctx, l, MG3D_ST_SMOOTH2); }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL2); }
-            continue;
-        }
-        if (l == 1 && tiny) {
-            { StageScope t(ctx, l, MG3D_ST_PROLONG); } /* inside the launch below */
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH2);
-                StageScope kt(ctx, l, MG3D_K_SWEEP4, true);
-                k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], ctx->lv[0].g, ctx->lv[0].f[MG3D_U], mg3d_op(ctx, lev), ctx->iters,
-                          s); /* :1331 + :1341 */
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL2); }
-            continue;
-        }
-        if (l == q && can_legs) {
-            Level &lc = ctx->lv[l - 1];
-            { StageScope t(ctx, l, MG3D_ST_PROLONG); } /* :1331, folded into the launch below */
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH2);
-                int npa;
-                {
-                    StageScope kt(ctx, l, MG3D_K_LEG_UP, true);
-                    /* prolongation + black, red, black, red (:1331 + :1341); with another cycle behind it, the red half of
-                     * the norm (:1354) from the last pass's sums */
-                    npa = k_sweep_leg_up(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.f[MG3D_U], mg3d_op(ctx, lev),
-                                         carry_out ? part_a : nullptr, MG3D_MAX_PARTIALS / 2, s);
-                }
-                if (npa < 0)
-                    return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the up-leg");
-                double *t2 = lev.f[MG3D_U];
-                lev.f[MG3D_U] = lev.alt;
-                lev.alt = t2;
-                if (carry_out == 1) { /* the next cycle of this mg3d_vcycles call completes the norm */
-                    ctx->legs_state = 2;
-                    ctx->legs_slot = slot;
-                    ctx->legs_npa = npa;
-                } else if (carry_out == 2) {
-                    /* mg3d_vcycle: the next cycle's down-leg now, into the alt buffers (see mg3d_can_legs) */
-                    StageScope kt(ctx, l, MG3D_K_LEG_DOWN, true);
-                    const int npb = k_sweep_leg_down(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, lc.g, lc.alt, mg3d_op(ctx, lev), 3, part_b,
-                                                     MG3D_MAX_PARTIALS / 2, s);
-                    if (npb < 0)
-                        return fail(MG3D_ERR_STATE, "one launch per leg: no kernel for the down-leg");
-                    double *t3 = lev.f[MG3D_U];
-                    lev.f[MG3D_U] = lev.alt;
-                    lev.alt = t3;
-                    k_fold2(part_a, npa, part_b, npb, ctx->sumsq + slot, s);
-                    ctx->legs_state = 3;
-                }
-            }
-            {
-                StageScope t(ctx, l, MG3D_ST_RESIDUAL2);
-                if (!carry_out)
-                    CHK(enqueue_residual(ctx, l, 0, slot)); /* :1354, the last cycle of a call: a launch of its own */
-            }
-            continue;
-        }
-        if (l == q && carry_out && can_carry) {
-            { StageScope t(ctx, l, MG3D_ST_PROLONG); } /* :1331, folded into the launch below */
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH2);
-                /* prolongation + the first two post-smoothing passes: the launch the ordinary cycle starts its up-leg with */
-                CHK(enqueue_smooth_residual(ctx, l, 1, 1, 0, slot, nullptr, &ctx->lv[l - 1]));
-                /* black, red (:1341, second half) <norm, :1354> black, red (:1282 of the next cycle, its first red pass
-                 * being the identity) */
-                StageScope kt(ctx, l, MG3D_K_SWEEP4_NORM, true);
-                const int np = k_sweep_tap(ctx->opt, lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.alt, ctx->partials, MG3D_MAX_PARTIALS,
-                                           mg3d_op(ctx, lev), 0, s);
-                if (np < 0)
-                    return fail(MG3D_ERR_STATE, "carried cycle: no kernel for four passes + norm tap");
-                double *t2 = lev.f[MG3D_U];
-                lev.f[MG3D_U] = lev.alt;
-                lev.alt = t2;
-                k_fold(ctx->partials, np, ctx->sumsq + slot, s);
-                ctx->carried = true;
-            }
-            { StageScope t(ctx, l, MG3D_ST_RESIDUAL2); }
-            continue;
-        }
-        const int want_norm = l == q ? 1 : 0;
-        const bool pro = pro_fusable(ctx, ctx->iters, want_norm, l);
-        {
-            StageScope t(ctx, l, MG3D_ST_PROLONG); /* :1331; ~0 s when folded into the smoother's loads */
-            if (!pro) {
-                StageScope kt(ctx, l, MG3D_K_PROLONG, true);
-                enqueue_prolong(ctx, l);
-            }
-        }
-        if (mg3d_fused(ctx)) { /* (prolongation,) post-smoother and residual norm (:1331 + :1341 + :1354) */
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH2);
-                /* the norm of a level below the top one is computed and dropped by the reference (:1320
-                 * ignores the recursive call's value): skip it, nothing observable changes */
-                CHK(enqueue_smooth_residual(ctx, l, 1, ctx->iters, want_norm, slot, nullptr,
-                                            pro ? &ctx->lv[l - 1] : nullptr));
-            }
-            StageScope t(ctx, l, MG3D_ST_RESIDUAL2); /* fused into the launch above: counted, ~0 s */
-        } else {
-            {
-                StageScope t(ctx, l, MG3D_ST_SMOOTH2);
-                CHK(enqueue_smooth(ctx, l, 1, ctx->iters)); /* :1341 */
-            }
-            StageScope t(ctx, l, MG3D_ST_RESIDUAL2);
-            if (l == q)
-                CHK(enqueue_residual(ctx, l, 0, slot)); /* :1354; below the top level the value is dropped (:1320) */
-        }
+        if (l == 1 && c.tiny)
+            up_leg_tiny(ctx, c);
+        else if (l == q && c.can_legs)
+            CHK(up_leg_legs(ctx, c, l));
+        else if (l == q && carry_out && c.can_carry)
+            CHK(up_leg_carried(ctx, c, l));
+        else
+            CHK(up_leg_ordinary(ctx, c, l));
     }
-    /* a whole V(2,2) cycle from the top level has ended with its last red pass and nothing runs ahead: see red_in above */
+    /* a whole V(2,2) cycle from the top level has ended with its last red pass and nothing runs ahead: see red_in */
     if (q == L - 1 && ctx->legs_state == 0 && !ctx->carried && ctx->iters == 2 && mg3d_fused(ctx))
         ctx->red_tail = true;
     return launch_ok("mg3d_vcycle");

@@ -1026,11 +1026,31 @@ struct RestrictTarget { /* where a rank's restricted residual goes: coarse geome
  * residual (want_res 2: r stored or restricted on the fly into tgt[], 1: norm only, over OWNED planes, into
  * the rank's coarse->sumsq[0]).  Same launch policy as the single-domain path.  On entry the halos of u and
  * d on this level are exact (H planes); nothing is exchanged in here. */
-/* the top level's post-smoothing of a V(2,2) cycle runs as 2 + 2 passes: prolongation folded into the first launch,
- * the norm into the second (same policy and reasons as the single-domain path, csrc/mg3d_ctx.hip) */
-static bool dist_split_up_leg(const mg3d_dist *D, int post, int want_res)
+/* The launches of a smoothing stage on distributed level l: the single domain's list (mg3d_stage_plan) with the slab path's
+ * two differences as inputs -- it has no one-launch form of the whole down-leg (leg4_form), and the norm is wanted exactly
+ * where want_res == 1 (the pre-smoothing norm is dropped, :1294).  has_coarse: a list of restriction targets was passed
+ * (with keep_r the down-leg passes a list of empty ones: the stage still splits as if it restricted). */
+static StagePlan dist_stage_plan(mg3d_dist *D, int l, int post, int want_res, bool has_coarse, bool pro_offered)
 {
-    return post && 2 * D->nu == 4 && want_res == 1;
+    const Geom &g = SL(D, D->rs[0], l).lv.g;
+    return mg3d_stage_plan(D->rs[0].coarse->opt,
+                           StageAsk{g.N, g.nj, post != 0, D->nu, want_res, has_coarse, want_res == 1, pro_offered, /* leg4_form */ false});
+}
+
+/* a sweep launch on rank ri's slab of level l, u -> alt; the norm counts the owned planes */
+static SweepLaunch slab_sweep(mg3d_dist *D, size_t ri, int l)
+{
+    SlabLevel &sl = SL(D, D->rs[ri], l);
+    SweepLaunch w = mg3d_level_sweep(D->rs[ri].coarse, sl.lv);
+    w.acc_lo = sl.own_lo;
+    w.acc_hi = sl.own_hi;
+    return w;
+}
+
+static void swap_u_all(mg3d_dist *D, int l) /* every local rank's u and alt of level l change roles */
+{
+    for (auto &R : D->rs)
+        swap_u(SL(D, R, l).lv);
 }
 
 struct ProlongSource { /* per local rank: the coarse correction a split up-leg folds into its first launch */
@@ -1047,15 +1067,12 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
 {
     hipStream_t s = D->stream;
     const int c1 = post ? 0 : 1;
-    int passes = 2 * D->nu;
-    bool done_res = want_res == 0, first = true;
-    const bool sp = dist_split_up_leg(D, post, want_res);
-    while (passes > 0 || !done_res) {
-        const int S = (sp && passes >= 2) ? 2 : passes >= 4 ? 4 : passes;
-        const bool last = passes - S == 0;
-        /* two passes + residual + restriction: one launch from 130 points per side up, two below (k_sweep_fuse_rst2) */
-        const bool res = last && want_res != 0 && S != 4 &&
-                         !(S == 2 && tgt != nullptr && !k_sweep_fuse_rst2(D->rs[0].coarse->opt, SL(D, D->rs[0], l).lv.g.N));
+    const StagePlan plan = dist_stage_plan(D, l, post, want_res, tgt != nullptr, pro != nullptr);
+    for (int k = 0; mg3d_stage_launch(plan, k); k++) {
+        const StageStep &st = *mg3d_stage_launch(plan, k);
+        const bool first = k == 0;
+        const int S = st.S;
+        const bool last = st.last, res = st.res;
         if (S == 0 && refresh_u) { /* u is final; the pure residual launch below reads owned +-1 only */
             CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
             refresh_u = false;
@@ -1078,15 +1095,22 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
             }
             if (ok) {
                 auto launch = [&](size_t ri, const double *vin, double *vout, double *part, int lo, int hi, int edge) -> int {
-                    SlabLevel &sl = SL(D, D->rs[ri], l);
-                    Level &lv = sl.lv;
-                    mg3d_ctx *cx = D->rs[ri].coarse;
-                    if (tap)
-                        return k_sweep_tap(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, part, MG3D_MAX_PARTIALS / 2, mg3d_op(cx, lv), c1, s, sl.own_lo,
-                                           sl.own_hi, lo, hi, edge);
-                    return k_sweep(cx->opt, lv.g, vin, lv.f[MG3D_D], vout, nullptr, part, MG3D_MAX_PARTIALS / 2, mg3d_op(cx, lv), S, c1, true, s,
-                                   sl.own_lo, sl.own_hi, nullptr, nullptr, -1, -1, (pro && first) ? pro[ri].gc : nullptr,
-                                   (pro && first) ? pro[ri].ec : nullptr, lo, hi, edge);
+                    SweepLaunch w = slab_sweep(D, ri, l);
+                    w.vin = vin;
+                    w.vout = vout;
+                    w.kind = tap ? SWEEP_TAP : SWEEP_PASSES_RES;
+                    w.S = S;
+                    w.c1 = c1;
+                    w.partials = part;
+                    w.max_partials = MG3D_MAX_PARTIALS / 2;
+                    if (st.pro) {
+                        w.gce = pro[ri].gc;
+                        w.ec = pro[ri].ec;
+                    }
+                    w.i_lo = lo;
+                    w.i_hi = hi;
+                    w.edge = edge;
+                    return k_sweep(D->rs[ri].coarse->opt, w, s);
                 };
                 for (size_t ri = 0; ri < D->rs.size(); ri++) {
                     Level &lv = SL(D, D->rs[ri], l).lv;
@@ -1094,12 +1118,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
                     if (npa[ri] < 0)
                         return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the edge windows on level %d", l);
                 }
-                for (auto &R : D->rs) { /* the exchange sends from (and lands in) the NEW buffer */
-                    Level &lv = SL(D, R, l).lv;
-                    double *t = lv.f[MG3D_U];
-                    lv.f[MG3D_U] = lv.alt;
-                    lv.alt = t;
-                }
+                swap_u_all(D, l); /* the exchange sends from (and lands in) the NEW buffer */
                 CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
                 refresh_u = false;
                 for (size_t ri = 0; ri < D->rs.size(); ri++) {
@@ -1110,9 +1129,6 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
                         return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior window on level %d", l);
                     k_fold2(cx->partials, npa[ri], cx->partials + MG3D_MAX_PARTIALS / 2, npb, cx->sumsq, s);
                 }
-                done_res = true;
-                passes -= S;
-                first = false;
                 continue;
             }
         }
@@ -1121,7 +1137,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
             SlabLevel &sl = SL(D, R, l);
             Level &lv = sl.lv;
             mg3d_ctx *cx = R.coarse;
-            const bool rst = res && tgt != nullptr && tgt[ri].dc != nullptr;
+            const bool rst = st.rst && tgt[ri].dc != nullptr;
             /* output planes of a smoothing launch: the owned planes plus what the next consumer reads beyond
              * them -- the residual/restriction behind a pre-smoother needs u on owned +-2, the top-level norm
              * owned +-1; the remaining halo planes are refreshed by an exchange before anything reads them
@@ -1142,20 +1158,41 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
             if (tap && last) {
                 /* output: the owned planes only -- the four passes use up the halo planes the first launch has left, and
                  * the next launch (one pass + residual + restriction) gets three fresh ones by exchange first */
-                const int np = k_sweep_tap(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, cx->partials, MG3D_MAX_PARTIALS, mg3d_op(cx, lv), c1, s,
-                                           sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
+                SweepLaunch w = slab_sweep(D, ri, l);
+                w.kind = SWEEP_TAP;
+                w.c1 = c1;
+                w.partials = cx->partials;
+                w.i_lo = sl.own_lo;
+                w.i_hi = sl.own_hi;
+                const int np = k_sweep(cx->opt, w, s);
                 if (np < 0)
                     return fail(MG3D_ERR_STATE, "slab sweep: no kernel for four passes + norm tap on level %d", l);
                 k_fold(cx->partials, np, cx->sumsq, s);
                 continue;
             }
-            const int np = k_sweep(cx->opt, lv.g, (zero_in && first) ? nullptr : lv.f[MG3D_U], lv.f[MG3D_D], lv.alt,
-                                   (res && want_res == 2 && !rst) ? lv.f[MG3D_R] : nullptr,
-                                   (res && want_res == 1) ? cx->partials : nullptr, /* the pre-smoothing norm is dropped (:1294) */
-                                   MG3D_MAX_PARTIALS, mg3d_op(cx, lv), S, c1, res, s, sl.own_lo, sl.own_hi,
-                                   rst ? tgt[ri].gc : nullptr, rst ? tgt[ri].dc : nullptr, rst ? tgt[ri].lo : -1,
-                                   rst ? tgt[ri].hi : -1, (pro && first) ? pro[ri].gc : nullptr,
-                                   (pro && first) ? pro[ri].ec : nullptr, w_lo, w_hi);
+            SweepLaunch w = slab_sweep(D, ri, l);
+            w.kind = res ? SWEEP_PASSES_RES : SWEEP_PASSES;
+            w.S = S;
+            w.c1 = c1;
+            if (zero_in && first)
+                w.vin = nullptr;
+            if (res && want_res == 2 && !rst)
+                w.r = lv.f[MG3D_R];
+            if (res && want_res == 1) /* the pre-smoothing norm is dropped (:1294) */
+                w.partials = cx->partials;
+            if (rst) {
+                w.gc = tgt[ri].gc;
+                w.dc = tgt[ri].dc;
+                w.ic_lo = tgt[ri].lo;
+                w.ic_hi = tgt[ri].hi;
+            }
+            if (st.pro) {
+                w.gce = pro[ri].gc;
+                w.ec = pro[ri].ec;
+            }
+            w.i_lo = w_lo;
+            w.i_hi = w_hi;
+            const int np = k_sweep(cx->opt, w, s);
             if (np < 0) /* nothing was launched: no buffer swap, no fold */
                 return fail(MG3D_ERR_STATE, "slab sweep: no kernel for %d colour passes%s on level %d", S,
                             res ? " + residual" : "", l);
@@ -1163,16 +1200,7 @@ static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const Restr
                 k_fold(cx->partials, np, cx->sumsq, s);
         }
         if (S > 0)
-            for (auto &R : D->rs) {
-                Level &lv = SL(D, R, l).lv;
-                double *t = lv.f[MG3D_U];
-                lv.f[MG3D_U] = lv.alt;
-                lv.alt = t;
-            }
-        if (res)
-            done_res = true;
-        passes -= S;
-        first = false;
+            swap_u_all(D, l);
     }
     if (refresh_u) /* the last launch smoothed and took the norm in one go */
         CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
@@ -1221,34 +1249,139 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
 /* carried cycles on slabs (csrc/mg3d_ctx.hip has the argument): same conditions as the single-domain path */
 static bool dist_carry_policy(mg3d_dist *D) /* what the options say (carry, carry_min), for this level geometry */
 {
-    const mg3d_options &o = D->rs[0].coarse->opt;
-    const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
-    return o.v[MG3D_OPT_CARRY] != 0 && g.N >= o.v[MG3D_OPT_CARRY_MIN];
+    return mg3d_run_ahead_policy(D->rs[0].coarse->opt, false, SL(D, D->rs[0], D->L - 1).lv.g.N);
 }
 
 /* one launch per leg on slabs (csrc/mg3d_ctx.hip "one launch per leg"; options legs, legs_min): same conditions as the carried
  * cycles, which it replaces where both apply */
 static bool dist_legs_policy(mg3d_dist *D)
 {
-    const mg3d_options &o = D->rs[0].coarse->opt;
-    const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
-    return o.v[MG3D_OPT_LEGS] != 0 && g.N >= o.v[MG3D_OPT_LEGS_MIN];
+    return mg3d_run_ahead_policy(D->rs[0].coarse->opt, true, SL(D, D->rs[0], D->L - 1).lv.g.N);
 }
 
 static bool dist_can_legs(mg3d_dist *D)
 {
-    if (D->coef || !(D->legs_fixed ? D->legs_on : dist_legs_policy(D)))
-        return false;
+    /* (legs_fixed: the ranks of a multi-process job agreed on the schedule at creation) */
+    const mg3d_ctx *cx = D->rs[0].coarse;
     const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
-    return D->nu == 2 && D->H >= 5 && !D->rs[0].coarse->keep_r && g.N > 65 && (g.nj & 1) != 0;
+    return !D->coef && D->H >= 5 && mg3d_can_run_ahead(cx->opt, true, D->legs_fixed ? D->legs_on : -1, D->nu, cx->keep_r, g.N, g.nj);
 }
 
 static bool dist_can_carry(mg3d_dist *D)
 {
-    if (D->coef || !(D->carry_fixed ? D->carry_on : dist_carry_policy(D)))
-        return false;
+    const mg3d_ctx *cx = D->rs[0].coarse;
     const Geom &g = SL(D, D->rs[0], D->L - 1).lv.g;
-    return D->nu == 2 && !D->rs[0].coarse->keep_r && g.N > 65 && (g.nj & 1) != 0 && dist_split_up_leg(D, 1, 1);
+    return !D->coef && mg3d_can_run_ahead(cx->opt, false, D->carry_fixed ? D->carry_on : -1, D->nu, cx->keep_r, g.N, g.nj) &&
+           dist_stage_plan(D, D->L - 1, 1, 1, false, true).step[0].pro; /* the split up-leg whose first launch the carried cycle keeps */
+}
+
+/* Down-leg of the finest level behind another cycle (its norm's black half rides along) or a finished one (red_in).
+ * The down-leg as ONE launch over the owned planes: three passes (black first -- the cycle's first red pass is the
+ * identity behind the previous cycle's last one), residual, restriction; it reads five planes either side, which
+ * the previous cycle's last exchange refreshed.  On its way it forms the black half of the previous cycle's
+ * residual norm, whose red half the one-launch up-leg left in partials[0 .. legs_npa): folded and reduced here. */
+static int dist_down_leg_ahead(mg3d_dist *D, int l, const RestrictTarget *tgt, bool red_in, int slot)
+{
+    hipStream_t s = D->stream;
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        RankState &R = D->rs[ri];
+        SlabLevel &sl = SL(D, R, l);
+        mg3d_ctx *cx = R.coarse;
+        double *part_b = red_in ? nullptr : cx->partials + MG3D_MAX_PARTIALS / 2;
+        SweepLaunch w = slab_sweep(D, ri, l);
+        w.kind = SWEEP_LEG_DOWN;
+        w.S = 3;
+        w.partials = part_b;
+        w.max_partials = MG3D_MAX_PARTIALS / 2;
+        w.gc = tgt[ri].gc;
+        w.dc = tgt[ri].dc;
+        w.ic_lo = tgt[ri].lo;
+        w.ic_hi = tgt[ri].hi;
+        w.i_lo = sl.own_lo;
+        w.i_hi = sl.own_hi;
+        const int npb = k_sweep(cx->opt, w, s);
+        if (npb <= 0)
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch down-leg on level %d", l);
+        if (!red_in)
+            k_fold2(cx->partials, R.legs_npa, part_b, npb, cx->sumsq, s);
+        swap_u(sl.lv);
+    }
+    if (!red_in)
+        CHK(reduce_norm(D, slot - 1));
+    return MG3D_OK;
+}
+
+/* Down-leg of the finest level behind a carried cycle: the one pre-smoothing pass that is left (black) + residual +
+ * restriction in one launch over the owned planes: it reads three planes either side, which the previous cycle's last
+ * exchange refreshed */
+static int dist_down_leg_carried(mg3d_dist *D, int l, const RestrictTarget *tgt)
+{
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SlabLevel &sl = SL(D, D->rs[ri], l);
+        SweepLaunch w = slab_sweep(D, ri, l);
+        w.kind = SWEEP_PASSES_RES;
+        w.S = 1;
+        w.c1 = 0;
+        w.gc = tgt[ri].gc;
+        w.dc = tgt[ri].dc;
+        w.ic_lo = tgt[ri].lo;
+        w.ic_hi = tgt[ri].hi;
+        w.i_lo = sl.own_lo;
+        w.i_hi = sl.own_hi;
+        if (k_sweep(D->rs[ri].coarse->opt, w, D->stream) < 0)
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for one pass + residual + restriction on level %d", l);
+        swap_u(sl.lv);
+    }
+    return MG3D_OK;
+}
+
+/* Up-leg of the finest level as ONE launch: prolongation + four passes over the owned planes (it uses up four of the H halo
+ * planes of u and of the correction), the red half of the norm from the last pass's own sums.  With a communication stream the
+ * first and last five planes -- what the exchange for the next down-leg sends -- are made first, as one launch of two
+ * chunks per rank; the exchange then runs underneath the launch that makes the interior. */
+static int dist_up_leg_legs(mg3d_dist *D, int l, const ProlongSource *pro)
+{
+    const int E = 5;
+    bool edge_first = D->overlap && D->P > 1;
+    for (auto &R : D->rs)
+        edge_first = edge_first && SL(D, R, l).own_hi - SL(D, R, l).own_lo >= 2 * E + 2;
+    auto up = [&](size_t ri, const double *vin, double *vout, double *part, int maxp, int lo, int hi, int edge) -> int {
+        SweepLaunch w = slab_sweep(D, ri, l);
+        w.kind = SWEEP_LEG_UP;
+        w.vin = vin;
+        w.vout = vout;
+        w.partials = part;
+        w.max_partials = maxp;
+        w.gce = pro[ri].gc;
+        w.ec = pro[ri].ec;
+        w.i_lo = lo;
+        w.i_hi = hi;
+        w.edge = edge;
+        return k_sweep(D->rs[ri].coarse->opt, w, D->stream);
+    };
+    std::vector<int> n1(D->rs.size(), 0);
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SlabLevel &sl = SL(D, D->rs[ri], l);
+        n1[ri] = up(ri, sl.lv.f[MG3D_U], sl.lv.alt, D->rs[ri].coarse->partials, MG3D_MAX_PARTIALS / 4, sl.own_lo, sl.own_hi, edge_first ? E : 0);
+        if (n1[ri] <= 0)
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch up-leg on level %d", l);
+    }
+    swap_u_all(D, l); /* the exchange sends from (and lands in) the NEW buffer */
+    CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SlabLevel &sl = SL(D, D->rs[ri], l);
+        int n2 = 0;
+        if (edge_first) {
+            n2 = up(ri, sl.lv.alt, sl.lv.f[MG3D_U], D->rs[ri].coarse->partials + n1[ri], MG3D_MAX_PARTIALS / 2 - n1[ri], sl.own_lo + E,
+                    sl.own_hi - E, 0);
+            if (n2 <= 0)
+                return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior of the one-launch up-leg on level %d", l);
+        }
+        D->rs[ri].legs_npa = n1[ri] + n2;
+    }
+    D->legs_pending = true;
+    D->n_legs++;
+    return MG3D_OK;
 }
 
 static int dist_refuse_poisoned(const mg3d_dist *D, const char *who)
@@ -1257,6 +1390,31 @@ static int dist_refuse_poisoned(const mg3d_dist *D, const char *who)
         return fail(MG3D_ERR_STATE, "%s: an earlier mg3d_dist_vcycles call failed after one of its cycles had run ahead into the "
                                     "next: u of the finest level is mid-cycle; upload it again first", who);
     return MG3D_OK;
+}
+
+/* where each local rank's residual of distributed level l is restricted to: its slab of level l-1 or, below the last
+ * distributed level, the rank's replicated context -- the owned coarse planes (plus the physical boundary planes at the ends
+ * of the domain) */
+static void restrict_targets(mg3d_dist *D, int l, RestrictTarget *tgt)
+{
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        RankState &R = D->rs[ri];
+        SlabLevel &sl = SL(D, R, l);
+        RestrictTarget &t = tgt[ri];
+        if (l - 1 >= D->ld) {
+            SlabLevel &sc = SL(D, R, l - 1);
+            t.gc = &sc.lv.g;
+            t.dc = sc.lv.f[MG3D_D];
+            t.lo = sc.own_lo;
+            t.hi = sc.own_hi;
+        } else {
+            Level &lc = R.coarse->lv[D->ld - 1];
+            t.gc = &lc.g;
+            t.dc = lc.f[MG3D_D];
+            t.lo = R.rank == 0 ? 0 : sl.glo / 2;
+            t.hi = R.rank == D->P - 1 ? lc.g.N : sl.ghi / 2;
+        }
+    }
 }
 
 /* carry_out: another cycle of this call follows (it may be enqueued ahead into); legs_out: it follows in the same batch of norm
@@ -1292,76 +1450,23 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
      * that follows each restriction below) and those of the finest u have been refreshed since it last
      * changed (upload, or the exchange started at the end of the previous cycle). */
     for (int l = L - 1; l >= ld; l--) {
-        for (size_t ri = 0; ri < D->rs.size(); ri++) {
-            RankState &R = D->rs[ri];
-            SlabLevel &sl = SL(D, R, l);
-            /* mg_3d.h:1258: zero guess below the finest level -- folded into the first sweep launch */
-            /* owned coarse planes (plus the physical boundary planes at the ends of the domain) */
-            RestrictTarget &t = tgt[ri];
-            if (l - 1 >= ld) {
-                SlabLevel &sc = SL(D, R, l - 1);
-                t.gc = &sc.lv.g;
-                t.dc = sc.lv.f[MG3D_D];
-                t.lo = sc.own_lo;
-                t.hi = sc.own_hi;
-            } else {
-                Level &lc = R.coarse->lv[ld - 1];
-                t.gc = &lc.g;
-                t.dc = lc.f[MG3D_D];
-                t.lo = R.rank == 0 ? 0 : sl.glo / 2;
-                t.hi = R.rank == D->P - 1 ? lc.g.N : sl.ghi / 2;
-            }
-        }
+        /* mg_3d.h:1258: zero guess below the finest level -- folded into the first sweep launch */
+        restrict_targets(D, l, tgt.data());
         const bool keep = D->rs[0].coarse->keep_r;
         std::vector<RestrictTarget> none(D->rs.size(), RestrictTarget{nullptr, nullptr, -1, -1});
         CHK(await_u(D, l));
-        if (l == L - 1 && (legs_in || red_in)) {
-            /* the down-leg as ONE launch over the owned planes: three passes (black first -- the cycle's first red pass is the
-             * identity behind the previous cycle's last one), residual, restriction; it reads five planes either side, which
-             * the previous cycle's last exchange refreshed.  On its way it forms the black half of the previous cycle's
-             * residual norm, whose red half the one-launch up-leg left in partials[0 .. legs_npa): folded and reduced here. */
-            for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                RankState &R = D->rs[ri];
-                SlabLevel &sl = SL(D, R, l);
-                Level &lv = sl.lv;
-                mg3d_ctx *cx = R.coarse;
-                double *part_b = red_in ? nullptr : cx->partials + MG3D_MAX_PARTIALS / 2;
-                const int npb = k_sweep_leg_down(cx->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, *tgt[ri].gc, tgt[ri].dc, mg3d_op(cx, lv), 3, part_b,
-                                                 MG3D_MAX_PARTIALS / 2, s, sl.own_lo, sl.own_hi, tgt[ri].lo, tgt[ri].hi, sl.own_lo, sl.own_hi);
-                if (npb <= 0)
-                    return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch down-leg on level %d", l);
-                if (!red_in)
-                    k_fold2(cx->partials, R.legs_npa, part_b, npb, cx->sumsq, s);
-                double *t = lv.f[MG3D_U];
-                lv.f[MG3D_U] = lv.alt;
-                lv.alt = t;
-            }
-            if (!red_in)
-                CHK(reduce_norm(D, slot - 1));
-        } else if (l == L - 1 && carry_in) {
-            /* the one pre-smoothing pass that is left (black) + residual + restriction in one launch over the owned planes:
-             * it reads three planes either side, which the previous cycle's last exchange refreshed */
-            for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                SlabLevel &sl = SL(D, D->rs[ri], l);
-                Level &lv = sl.lv;
-                const int np = k_sweep(D->rs[ri].coarse->opt, lv.g, lv.f[MG3D_U], lv.f[MG3D_D], lv.alt, nullptr, nullptr, MG3D_MAX_PARTIALS, mg3d_op(D->rs[ri].coarse, lv), 1, 0,
-                                       true, s, sl.own_lo, sl.own_hi, tgt[ri].gc, tgt[ri].dc, tgt[ri].lo, tgt[ri].hi, nullptr,
-                                       nullptr, sl.own_lo, sl.own_hi);
-                if (np < 0)
-                    return fail(MG3D_ERR_STATE, "slab sweep: no kernel for one pass + residual + restriction on level %d", l);
-                double *t = lv.f[MG3D_U];
-                lv.f[MG3D_U] = lv.alt;
-                lv.alt = t;
-            }
-        } else if (D->coef) {
+        if (l == L - 1 && (legs_in || red_in))
+            CHK(dist_down_leg_ahead(D, l, tgt.data(), red_in, slot));
+        else if (l == L - 1 && carry_in)
+            CHK(dist_down_leg_carried(D, l, tgt.data()));
+        else if (D->coef) {
             /* variable coefficient: zero guess below the finest level (:1258) on every local plane, passes, r stored */
             if (l < L - 1)
                 for (auto &R : D->rs)
                     (void)hipMemsetAsync(SL(D, R, l).lv.f[MG3D_U], 0, SL(D, R, l).lv.elems * sizeof(double), s);
             CHK(dist_coef_smooth(D, l, 0, 2));
-        } else
-        /* :1282 + :1294 + :1310 (interior of the coarse rhs on the fly unless r is to be kept) */
-        CHK(stage_smooth(D, l, 0, 2, keep ? none.data() : tgt.data(), l < L - 1));
+        } else /* :1282 + :1294 + :1310 (interior of the coarse rhs on the fly unless r is to be kept) */
+            CHK(stage_smooth(D, l, 0, 2, keep ? none.data() : tgt.data(), l < L - 1));
         for (size_t ri = 0; ri < D->rs.size(); ri++) {
             SlabLevel &sl = SL(D, D->rs[ri], l);
             k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, s, tgt[ri].lo, tgt[ri].hi, !keep && !D->coef);
@@ -1404,9 +1509,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
         const int want = l == L - 1 ? 1 : 0;
         /* the prolongation rides on the post-smoother's first launch: the top level's split stage, and (option fuse_up_max, as
          * on a single domain) the four-pass launch of a V(2,2) cycle on the levels below it */
-        const Geom &gl = SL(D, D->rs[0], l).lv.g;
-        const bool fold = !D->coef && (dist_split_up_leg(D, 1, want) ||
-                          (D->nu == 2 && want == 0 && (gl.nj & 1) != 0 && gl.N <= D->rs[0].coarse->opt.v[MG3D_OPT_FUSE_UP_MAX]));
+        const bool fold = !D->coef && dist_stage_plan(D, l, 1, want, false, true).step[0].pro;
         std::vector<ProlongSource> pro(D->rs.size());
         for (size_t ri = 0; ri < D->rs.size(); ri++) {
             RankState &R = D->rs[ri];
@@ -1421,47 +1524,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
          * underneath the norm kernel, which reads the first halo plane on either side -- just produced
          * exactly by the post-smoother, so the exchange leaves that plane alone. */
         if (l == L - 1 && legs_out) {
-            /* the up-leg as ONE launch: prolongation + four passes over the owned planes (it uses up four of the H halo planes of
-             * u and of the correction), the red half of the norm from the last pass's own sums.  With a communication stream the
-             * first and last five planes -- what the exchange for the next down-leg sends -- are made first, as one launch of two
-             * chunks per rank; the exchange then runs underneath the launch that makes the interior. */
-            const int E = 5;
-            bool edge_first = D->overlap && D->P > 1;
-            for (auto &R : D->rs)
-                edge_first = edge_first && SL(D, R, l).own_hi - SL(D, R, l).own_lo >= 2 * E + 2;
-            auto up = [&](size_t ri, const double *vin, double *vout, double *part, int maxp, int lo, int hi, int edge) -> int {
-                SlabLevel &sl = SL(D, D->rs[ri], l);
-                Level &lv = sl.lv;
-                return k_sweep_leg_up(D->rs[ri].coarse->opt, lv.g, vin, lv.f[MG3D_D], vout, *pro[ri].gc, pro[ri].ec, mg3d_op(D->rs[ri].coarse, lv), part, maxp, s,
-                                      sl.own_lo, sl.own_hi, lo, hi, edge);
-            };
-            std::vector<int> n1(D->rs.size(), 0);
-            for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                SlabLevel &sl = SL(D, D->rs[ri], l);
-                n1[ri] = up(ri, sl.lv.f[MG3D_U], sl.lv.alt, D->rs[ri].coarse->partials, MG3D_MAX_PARTIALS / 4, sl.own_lo, sl.own_hi, edge_first ? E : 0);
-                if (n1[ri] <= 0)
-                    return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch up-leg on level %d", l);
-            }
-            for (auto &R : D->rs) { /* the exchange sends from (and lands in) the NEW buffer */
-                Level &lv = SL(D, R, l).lv;
-                double *t = lv.f[MG3D_U];
-                lv.f[MG3D_U] = lv.alt;
-                lv.alt = t;
-            }
-            CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
-            for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                SlabLevel &sl = SL(D, D->rs[ri], l);
-                int n2 = 0;
-                if (edge_first) {
-                    n2 = up(ri, sl.lv.alt, sl.lv.f[MG3D_U], D->rs[ri].coarse->partials + n1[ri], MG3D_MAX_PARTIALS / 2 - n1[ri], sl.own_lo + E,
-                            sl.own_hi - E, 0);
-                    if (n2 <= 0)
-                        return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior of the one-launch up-leg on level %d", l);
-                }
-                D->rs[ri].legs_npa = n1[ri] + n2;
-            }
-            D->legs_pending = true;
-            D->n_legs++;
+            CHK(dist_up_leg_legs(D, l, pro.data()));
             continue;
         }
         if (D->coef) {

@@ -139,40 +139,150 @@ void k_fill_boundary(const Geom &g, double *v, double h, hipStream_t s);
 void k_fold(const double *partials, int np, double *out, hipStream_t s);
 /* the same over two runs of partial sums (a norm whose halves two launches formed): *out = fold(pa) + fold(pb) */
 void k_fold2(const double *pa, int na, const double *pb, int nb, double *out, hipStream_t s);
-/* fused sweep (mg3d_sweep.hip): S colour passes starting with colour c1 (1 red, 0 black) from vin into
- * vout (vout != vin; ignored when S == 0), then optionally the residual of the result: r (may be NULL)
- * receives it on the interior, partials (may be NULL) one sum of diff^2 per block.  Returns the number
- * of partials written (>= 0) or -1 when the (S, residual) shape has no instantiation. */
+/* fused sweep (mg3d_sweep.hip).  Everything ONE launch can be asked to do is a field of SweepLaunch: a call site sets the
+ * fields it uses, the rest keep their defaults, and k_sweep alone resolves "-1 = all". */
 void k_sweep_set_tune_default(int on); /* first-use chunk measurement on / off where the option says -1 */
 bool k_sweep_fuse_rst2(const mg3d_options &o, int N); /* two passes + residual + restriction as ONE launch on a level of N points per side */
-int k_sweep(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-            int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo = 0,
-            int acc_hi = -1 /* local planes entering the norm; default all */,
-            const Geom *gc = nullptr, double *dc = nullptr /* non-NULL: also restrict the residual into the
-            interior of the coarse right-hand side dc (S = 0 or 2 with residual only) */,
-            int ic_lo = -1, int ic_hi = -1 /* local coarse planes to write; default all */,
-            const Geom *gce = nullptr, const double *ec = nullptr /* non-NULL: the input is vin + P(ec), the
-            trilinear prolongation of the coarse field ec (smoothing-only launches, S = 2 or 4) */,
-            int i_lo = -1, int i_hi = -1 /* local output planes of this launch; default all.  Several launches
-            with disjoint windows and the same vin/vout make up one sweep (overlap with halo exchange) */,
-            int edge = 0 /* > 0: only the first and the last `edge` planes of [i_lo, i_hi), as one launch of two chunks (-1 when
-            the range is shorter than 2 * edge): the planes a halo exchange sends first, the interior in a second launch */);
-/* FOUR colour passes starting with colour c1 and, into partials, the residual norm of the state after the SECOND one
- * (the launch that ends one V-cycle -- its last two post-smoothing passes and its norm -- and begins the next: mg3d_ctx.hip,
- * "carried cycles").  Returns the number of partials written or -1. */
-int k_sweep_tap(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *partials, int max_partials,
-                const LevelOp &op, int c1, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int i_lo = -1, int i_hi = -1, int edge = 0);
-/* One launch per leg of a V(2,2) cycle on a level (mg3d_sweep.hip, "one launch per leg").  down: S = 4 colour passes red
- * first, or S = 3 black first (behind another cycle), + residual + full-weighting restriction into the interior of dc;
- * partials (S = 3 only): sum of diff^2 of the INCOMING state over the colour the first pass updates.  up: the input is
- * vin + P(ec), four passes black first; partials: sum of diff^2 of the RESULT over the colour the last pass updated.
- * Return value as k_sweep. */
-int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, const LevelOp &op, int S,
-                     double *partials, int max_partials, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int ic_lo = -1,
-                     int ic_hi = -1, int i_lo = -1, int i_hi = -1);
-int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, const LevelOp &op,
-                   double *partials, int max_partials, hipStream_t s, int acc_lo = 0, int acc_hi = -1, int i_lo = -1,
-                   int i_hi = -1, int edge = 0);
+enum SweepKind {
+    SWEEP_PASSES,     /* S colour passes starting with colour c1, from vin into vout (vout != vin) */
+    SWEEP_PASSES_RES, /* ... then the residual of the result (S = 0: the residual alone, vout ignored): r receives it on the
+                         interior, partials one sum of diff^2 per block; with a restriction target (S = 0, 1, 2 or 4) neither */
+    SWEEP_TAP,        /* FOUR passes starting with colour c1 and, into partials, the residual norm of the state after the
+                         SECOND one: the launch that ends one V-cycle -- its last two post-smoothing passes and its norm --
+                         and begins the next (mg3d_ctx.hip, "carried cycles") */
+    SWEEP_LEG_DOWN,   /* one launch per leg of a V(2,2) cycle (mg3d_sweep.hip, "one launch per leg"): S = 3 passes black first
+                         (behind another cycle) + residual + restriction into dc; partials: the sum of diff^2 of the INCOMING
+                         state over the colour the first pass updates */
+    SWEEP_LEG_UP      /* ... the input is vin + P(ec), four passes black first; partials: the sum of diff^2 of the RESULT over
+                         the colour the last pass updated.  (The legs set c1 themselves and never measure chunk lengths.) */
+};
+struct SweepLaunch {
+    /* the level: its local geometry, operator constants and arrays */
+    const Geom *g = nullptr;
+    LevelOp op = {};
+    const double *vin = nullptr; /* NULL: identically zero, not read (the zero guess of a coarser level) */
+    const double *d = nullptr;
+    double *vout = nullptr;
+    /* what the launch does */
+    SweepKind kind = SWEEP_PASSES;
+    int S = 0;  /* colour passes (SWEEP_TAP and SWEEP_LEG_UP: always four) */
+    int c1 = 1; /* colour of the first pass: 1 red, 0 black */
+    double *r = nullptr;
+    double *partials = nullptr;
+    int max_partials = MG3D_MAX_PARTIALS; /* room in partials */
+    /* optional: also restrict the residual (full weighting) into the interior of the coarse right-hand side dc, local
+     * coarse planes [ic_lo, ic_hi), -1 / -1 all of them; r then never travels to memory */
+    const Geom *gc = nullptr;
+    double *dc = nullptr;
+    int ic_lo = -1, ic_hi = -1;
+    /* optional: the input is vin + P(ec), the trilinear prolongation of the coarse field ec (smoothing-only launches black
+     * first, S = 2 or 4; SWEEP_LEG_UP) */
+    const Geom *gce = nullptr;
+    const double *ec = nullptr;
+    /* window: [i_lo, i_hi) the local output planes of this launch, -1 / -1 all -- several launches with disjoint windows
+     * and the same vin / vout make up one sweep (overlap with halo exchange); [acc_lo, acc_hi) the local planes entering
+     * the norm, 0 / -1 all; edge > 0: only the first and the last `edge` planes of [i_lo, i_hi), as one launch of two chunks
+     * (-1 when the range is shorter than 2 * edge): the planes a halo exchange sends first, the interior in a second launch */
+    int i_lo = -1, i_hi = -1, acc_lo = 0, acc_hi = -1, edge = 0;
+};
+/* Returns the number of partials written (>= 0; 0 also for an empty window: nothing launched) or -1 when the request has no
+ * instantiation: nothing was launched. */
+int k_sweep(const mg3d_options &o, const SweepLaunch &w, hipStream_t s);
+
+/* ---- the launches of ONE smoothing stage with the fused sweep: `iters` x two colour passes, optionally followed by the
+ * residual of the result.  The single-domain path (mg3d_ctx.hip) and the slab path (mg3d_dist.hip) both run the list this
+ * returns; questions about a stage ("does its first launch take the prolongation?") are asked of the same list. */
+struct StageAsk {
+    int N, nj;        /* of the level: global points per side, local rows */
+    bool post;        /* post-smoother (black first) or pre-smoother */
+    int iters;
+    int want_res;     /* 0 none, 1 norm only, 2 r stored or restricted (+ norm) */
+    bool has_coarse;  /* a restriction target exists: the residual may be restricted on the fly */
+    bool need_norm;   /* the norm of the residual is wanted */
+    bool pro_offered; /* a prolongation source is offered: the first launch may take u + P(e) as its input */
+    bool leg4_form;   /* the single domain has the whole down-leg as one two-row launch (option fuse_leg_max); the slab path does not */
+};
+struct StageStep {
+    int S;      /* colour passes of the launch: 4, 2 or 0 (the residual alone) */
+    int times;  /* how often the launch repeats (the leading four-pass launches of a long stage) */
+    bool res;   /* carries the residual */
+    bool rst;   /* ... restricted on the fly */
+    bool pro;   /* takes the prolongation into its loads (the stage's first launch only) */
+    bool last;  /* no colour pass follows it in this stage */
+};
+struct StagePlan {
+    int n;
+    StageStep step[3];
+};
+static inline StagePlan mg3d_stage_plan(const mg3d_options &o, const StageAsk &q)
+{
+    StagePlan p = {0, {}};
+    /* Where the norm is wanted behind FOUR post-smoothing passes (the top level of a V(2,2) cycle) the stage
+     * runs as 2 + 2 passes: the first launch takes the prolongation into its loads (the 2-pass shape has the
+     * registers for it: 0.77 ms against 0.74 ms without), the second one the residual norm (0.90 ms) --
+     * 1.67 ms instead of 0.56 (prolongation) + 0.82 (4 passes) + 0.47 (norm).  Below the top level no norm
+     * is formed and prolongation + 4 passes in two launches stays cheaper. */
+    const bool sp = q.post && 2 * q.iters == 4 && q.want_res == 1;
+    /* The prolongation rides on a smoothing-only first launch: the 2-pass first launch of a split stage takes it almost for
+     * free.  On a 4-pass first launch of a level above small_max it used to be SLOWER (the four-row shape spilt; round 2 measured
+     * 1.48 ms against 0.85 + 0.56 at 513^3).  Since the prolongation is applied at the end of the step before (MG3D_PRO_LATE in
+     * the kernel) that shape has 248 VGPRs and no scratch: the 257^3 level of the 513^3 problem takes 0.12 instead of
+     * 0.058 + 0.112 ms, the cycle 2.18 -> 2.13 ms -- fuse_up_max now defaults to every level.  Small levels: the
+     * two-rows-per-thread four-pass shape has the registers for it (k_sweep). */
+    const int up_max = q.leg4_form && o.v[MG3D_OPT_FUSE_LEG_MAX] > o.v[MG3D_OPT_FUSE_UP_MAX] ? o.v[MG3D_OPT_FUSE_LEG_MAX]
+                                                                                              : o.v[MG3D_OPT_FUSE_UP_MAX];
+    const bool pro = q.pro_offered && q.post &&
+                     (sp || (2 * q.iters == 4 && q.want_res == 0 && (q.nj & 1) != 0 && q.N <= up_max));
+    int passes = 2 * q.iters;
+    bool done_res = q.want_res == 0;
+    while (passes > 0 || !done_res) {
+        const int S = (sp && passes >= 2) ? 2 : passes >= 4 ? 4 : passes; /* 4, 2 or 0 */
+        const bool last = passes - S == 0;
+        /* small levels (<= fuse_leg_max points per side): the whole down-leg -- four passes, residual,
+         * restriction -- as one launch of the two-rows-per-thread shape: it wastes three quarters of its rows
+         * and saves a launch where launches are paid in latency, not in bytes */
+        const bool leg4 = q.leg4_form && S == 4 && q.has_coarse && !q.need_norm && q.want_res != 0 && q.N <= o.v[MG3D_OPT_FUSE_LEG_MAX];
+        /* the residual rides on a 2-pass launch; behind 4 passes it gets its own launch (the 5-stage
+         * window leaves too few registers for a tile with a useful interior: measured 1.9 ms fused
+         * against 0.85 + 0.76 ms split on a 513^3 level) */
+        /* two passes + residual + restriction (the down-leg of V(1,1), the tail of V(3,3)'s): one launch from 130
+         * points per side up, two below (k_sweep_fuse_rst2) */
+        const bool res = last && q.want_res != 0 && (S != 4 || leg4) && !(S == 2 && q.has_coarse && !k_sweep_fuse_rst2(o, q.N));
+        const StageStep st = {S, 1, res, res && q.has_coarse, pro && passes == 2 * q.iters, last};
+        StageStep *prev = p.n ? &p.step[p.n - 1] : nullptr;
+        if (prev && prev->S == S && !prev->res && !res && !prev->pro && prev->last == last)
+            prev->times++; /* (the leading four-pass launches of a stage of more than two sweeps) */
+        else if (p.n < 3)
+            p.step[p.n++] = st;
+        done_res = done_res || res;
+        passes -= S;
+    }
+    return p;
+}
+
+/* the k-th launch of a stage (k = 0, 1, ...: a step counts `times` times), NULL behind the last one */
+static inline const StageStep *mg3d_stage_launch(const StagePlan &p, int k)
+{
+    for (int i = 0; i < p.n; k -= p.step[i++].times)
+        if (k < p.step[i].times)
+            return &p.step[i];
+    return nullptr;
+}
+
+/* what the options say about one launch per leg (legs, legs_min) or the carried cycles (carry, carry_min) on a finest level
+ * of N points per side */
+static inline bool mg3d_run_ahead_policy(const mg3d_options &o, bool legs, int N)
+{
+    return o.v[legs ? MG3D_OPT_LEGS : MG3D_OPT_CARRY] != 0 && N >= o.v[legs ? MG3D_OPT_LEGS_MIN : MG3D_OPT_CARRY_MIN];
+}
+/* The conditions the one-launch legs and the carried cycles share, single domain and slabs: the schedule's own switch and
+ * threshold unless the caller fixed it (forced = 0 / 1; -1: by the options), V(2,2), r not kept, a level the
+ * four-rows-per-thread shapes exist for (never at 65^3 and below) with an odd number of rows. */
+static inline bool mg3d_can_run_ahead(const mg3d_options &o, bool legs, int forced, int iters, bool keep_r, int N, int nj)
+{
+    const bool on = forced >= 0 ? forced != 0 : mg3d_run_ahead_policy(o, legs, N);
+    return on && iters == 2 && !keep_r && N > 65 && (nj & 1) != 0;
+}
 /* mg3d_tiny.hip: the level above the coarsest one in one workgroup (LDS-resident), when it fits (N <= 17) */
 bool k_tiny_fits(const Geom &g, const Geom &gc);
 /* zero guess, `iters` x (red, black), residual, restriction (interior + face injection from r's boundary) into dc */

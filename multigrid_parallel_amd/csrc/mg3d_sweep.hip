@@ -346,7 +346,7 @@ template <> int dispatch<2, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, 
 template <> int dispatch<1, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
 {
     /* the LAST pre-smoothing pass + residual + restriction: the down-leg's only launch on the top level of a cycle whose
-     * first three pre-smoothing passes rode on the previous cycle's last launch (k_sweep_tap) */
+     * first three pre-smoothing passes rode on the previous cycle's last launch (SWEEP_TAP) */
     TRY(1, 2, 4, 8, 1) TRY(1, 2, 4, 8, 2)
     DFLT(1, 2, 4, 8, 1)
 }
@@ -367,46 +367,54 @@ bool k_sweep_fuse_rst2(const mg3d_options &o, int N) /* two passes + residual + 
     return N >= 130;
 }
 
-static int sweep_impl(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-                      int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
-                      const Geom *gc, double *dc, int ic_lo, int ic_hi, const Geom *gce, const double *ec, int i_lo, int i_hi,
-                      bool tap, int edge = 0)
+/* The descriptor as the kernel's argument block.  The ONE place where the "-1 means all" conventions of SweepLaunch are
+ * resolved: windows to plane ranges, absent grids to the level's own geometry.  false: the window is empty, nothing to launch. */
+static bool fill_args(SweepArgs &a, const SweepLaunch &w)
 {
-    SweepArgs a;
-    a.edge = edge;
-    a.i_lo = i_lo >= 0 ? i_lo : 0;
-    a.i_hi = i_hi >= 0 ? i_hi : g.ni;
-    if (a.i_hi <= a.i_lo)
-        return 0;
-    a.ec = ec;
-    a.gce = gce ? *gce : g;
-    a.dc = dc;
-    if (dc) {
-        a.gc = *gc;
-        a.ic_lo = ic_lo >= 0 ? ic_lo : 0;
-        a.ic_hi = ic_hi >= 0 ? ic_hi : gc->ni;
+    const Geom &g = *w.g;
+    a.g = g;
+    a.vin = w.vin;
+    a.d = w.d;
+    a.vout = w.vout;
+    a.r = w.r;
+    a.partials = w.partials;
+    a.hSq = w.op.hSq;
+    a.sixth = w.op.sixth;
+    a.invHsq = w.op.invHsq;
+    a.dg = w.op.dg;
+    a.c1 = w.c1;
+    a.edge = w.edge;
+    a.i_lo = w.i_lo >= 0 ? w.i_lo : 0;
+    a.i_hi = w.i_hi >= 0 ? w.i_hi : g.ni;
+    a.acc_lo = w.acc_lo;
+    a.acc_hi = w.acc_hi < 0 ? g.ni : w.acc_hi;
+    a.ec = w.ec;
+    a.gce = w.gce ? *w.gce : g;
+    a.dc = w.dc;
+    if (w.dc) {
+        a.gc = *w.gc;
+        a.ic_lo = w.ic_lo >= 0 ? w.ic_lo : 0;
+        a.ic_hi = w.ic_hi >= 0 ? w.ic_hi : w.gc->ni;
     } else {
         a.gc = g;
         a.ic_lo = a.ic_hi = 0;
     }
-    a.acc_lo = acc_lo;
-    a.acc_hi = acc_hi < 0 ? g.ni : acc_hi;
-    a.g = g;
-    a.vin = vin;
-    a.d = d;
-    a.vout = vout;
+    return a.i_hi > a.i_lo;
+}
+
+/* SWEEP_PASSES, SWEEP_PASSES_RES, SWEEP_TAP: the compiled shape by (S, residual, restriction, prolongation) and level size */
+static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
+{
+    const Geom &g = *w.g;
+    const bool tap = w.kind == SWEEP_TAP, residual = w.kind == SWEEP_PASSES_RES;
+    const int S = tap ? 4 : w.S, c1 = w.c1, max_partials = w.max_partials;
+    const double *const vin = w.vin, *const ec = w.ec;
+    double *const dc = w.dc, *const r = w.r, *const partials = w.partials;
     /* the restricting shapes (RES == 2) produce neither a stored r nor the norm: their callers never ask for either,
      * and without that code the residual + restriction launch has 60 fewer scalar instructions and 10 fewer branches a
      * step */
     if (dc && (r || partials))
         return -1;
-    a.r = r;
-    a.partials = partials;
-    a.hSq = op.hSq;
-    a.sixth = op.sixth;
-    a.invHsq = op.invHsq;
-    a.dg = op.dg;
-    a.c1 = c1;
     if (tap) { /* four passes, the residual norm of the state after the second one into partials */
         if (S != 4 || dc || ec || r || !partials || residual)
             return -1;
@@ -473,7 +481,7 @@ static int sweep_impl(const mg3d_options &o, const Geom &g, const double *vin, c
  *         coarse right-hand side (:1310).  (S = 4, the leg of a cycle with none in front of it, needs a six-plane window:
  *         124 bytes of scratch at two waves per SIMD, 2.1 ms at one -- against 0.66 + 0.49 as two launches: not instantiated.)  partials != NULL: the sum of
  *         diff^2 of the INCOMING state over the colour the first pass updates -- the second half of the previous cycle's
- *         residual norm (:1354), see k_sweep_leg_up.
+ *         residual norm (:1354), see the up-leg.
  *   up:   prolongation (:1331) folded into the loads, four post-smoothing passes black, red, black, red (:1341).
  *         partials != NULL: the sum of diff^2 of the RESULT over the colour the last pass has updated (red) -- the first
  *         half of the cycle's residual norm; the other half is formed by the next down-leg (or by a norm-only launch). */
@@ -506,52 +514,20 @@ static mg3d_options leg_options(const mg3d_options &o)
     return q;
 }
 
-static void leg_args(SweepArgs &a, const Geom &g, const double *vin, const double *d, double *vout, double *partials,
-                     const LevelOp &op, int c1, int i_lo, int i_hi, int acc_lo, int acc_hi)
+static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
 {
-    a.g = g;
-    a.vin = vin;
-    a.d = d;
-    a.vout = vout;
-    a.r = nullptr;
-    a.partials = partials;
-    a.hSq = op.hSq;
-    a.sixth = op.sixth;
-    a.invHsq = op.invHsq;
-    a.dg = op.dg;
-    a.c1 = c1;
-    a.i_lo = i_lo >= 0 ? i_lo : 0;
-    a.i_hi = i_hi >= 0 ? i_hi : g.ni;
-    a.acc_lo = acc_lo;
-    a.acc_hi = acc_hi < 0 ? g.ni : acc_hi;
-    a.ec = nullptr;
-    a.gce = g;
-    a.gc = g;
-    a.dc = nullptr;
-    a.ic_lo = a.ic_hi = 0;
-    a.edge = 0;
-}
-
-int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gc, double *dc, const LevelOp &op, int S,
-                     double *partials, int max_partials, hipStream_t s, int acc_lo, int acc_hi, int ic_lo, int ic_hi, int i_lo,
-                     int i_hi)
-{
+    if (!w.dc || w.ec || w.r || w.edge)
+        return -1;
     const mg3d_options oq = leg_options(o);
-    SweepArgs a;
-    leg_args(a, g, vin, d, vout, partials, op, S == 4 ? 1 : 0, i_lo, i_hi, acc_lo, acc_hi);
-    if (a.i_hi <= a.i_lo)
-        return 0;
-    a.gc = gc;
-    a.dc = dc;
-    a.ic_lo = ic_lo >= 0 ? ic_lo : 0;
-    a.ic_hi = ic_hi >= 0 ? ic_hi : gc.ni;
+    const int S = w.S, max_partials = w.max_partials;
+    a.c1 = S == 4 ? 1 : 0;
 #if MG3D_LEG_DOWN_RJ == 4
-    if (S == 3 && partials)
+    if (S == 3 && w.partials)
         return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s);
     if (S == 3)
         return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s);
 #else
-    if (S == 3 && partials)
+    if (S == 3 && w.partials)
         return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s);
     if (S == 3)
         return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s);
@@ -559,43 +535,39 @@ int k_sweep_leg_down(const mg3d_options &o, const Geom &g, const double *vin, co
     return -1;
 }
 
-int k_sweep_leg_up(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, const Geom &gce, const double *ec, const LevelOp &op,
-                   double *partials, int max_partials, hipStream_t s, int acc_lo, int acc_hi, int i_lo, int i_hi, int edge)
+static int sweep_leg_up(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
 {
-    if ((g.nj & 1) == 0)
+    if (!w.ec || w.dc || w.r)
         return -1;
     const mg3d_options oq = leg_options(o);
-    SweepArgs a;
-    leg_args(a, g, vin, d, vout, partials, op, 0, i_lo, i_hi, acc_lo, acc_hi);
-    if (a.i_hi <= a.i_lo)
-        return 0;
-    a.ec = ec;
-    a.gce = gce;
-    a.edge = edge;
+    const int max_partials = w.max_partials;
+    a.c1 = 0;
 #if MG3D_LEG_UP_RJ == 4
-    if (partials)
+    if (w.partials)
         return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s);
     return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s);
 #else
-    if (partials)
+    if (w.partials)
         return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s);
     return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s);
 #endif
 }
 
-int k_sweep(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *r, double *partials,
-            int max_partials, const LevelOp &op, int S, int c1, bool residual, hipStream_t s, int acc_lo, int acc_hi,
-            const Geom *gc, double *dc, int ic_lo, int ic_hi, const Geom *gce, const double *ec, int i_lo, int i_hi, int edge)
+int k_sweep(const mg3d_options &o, const SweepLaunch &w, hipStream_t s)
 {
-    return sweep_impl(o, g, vin, d, vout, r, partials, max_partials, op, S, c1, residual, s, acc_lo, acc_hi, gc, dc, ic_lo, ic_hi,
-                      gce, ec, i_lo, i_hi, false, edge);
-}
-
-int k_sweep_tap(const mg3d_options &o, const Geom &g, const double *vin, const double *d, double *vout, double *partials, int max_partials,
-                const LevelOp &op, int c1, hipStream_t s, int acc_lo, int acc_hi, int i_lo, int i_hi, int edge)
-{
-    return sweep_impl(o, g, vin, d, vout, nullptr, partials, max_partials, op, 4, c1, false, s, acc_lo, acc_hi, nullptr, nullptr,
-                      -1, -1, nullptr, nullptr, i_lo, i_hi, true, edge);
+    if (w.kind == SWEEP_LEG_UP && (w.g->nj & 1) == 0)
+        return -1;
+    SweepArgs a;
+    if (!fill_args(a, w))
+        return 0;
+    switch (w.kind) {
+    case SWEEP_LEG_DOWN:
+        return sweep_leg_down(o, a, w, s);
+    case SWEEP_LEG_UP:
+        return sweep_leg_up(o, a, w, s);
+    default:
+        return sweep_passes(o, a, w, s);
+    }
 }
 
 #ifdef MG3D_DEBUG_BLOCKTIMES

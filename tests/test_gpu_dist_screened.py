@@ -1,5 +1,5 @@
 """The screened operator on i-slabs (mg3d_dist_set_shift) through the loopback transport: every plan of tests/test_gpu_dist.py
--- plain, carried (k_sweep_tap), one launch per leg with edge windows, red_tail across calls, coarse gather, no overlap,
+-- plain, carried (SWEEP_TAP), one launch per leg with edge windows, red_tail across calls, coarse gather, no overlap,
 keep-residual -- at P = 2, 3, 4, 8 and nu = 1, 2, 3 with sigma > 0, bit for bit against the single-domain Solver with the
 same sigma and against the numpy reference of tests/_screened_ref.py on every distributed level; and 513^3 on 8, 4 and 2
 slabs against the C oracle's screened twin."""

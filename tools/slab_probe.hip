@@ -89,11 +89,32 @@ int main(int argc, char **argv)
         printf("copy    %5zu MB x 4 launches: %8.3f ms  %7.1f GB/s (r+w)\n", mb, ms, 2.0 * mb * 1048576.0 * 4 / ms / 1e6);
     }
     /* ---- (2) sweep kernels on windows */
-    const double h = 1.0 / (N - 1);
-    auto A = [&](int lo, int hi) { k_sweep(g, u, d, alt, nullptr, nullptr, MG3D_MAX_PARTIALS, h, 4, 1, false, s, 0, -1, nullptr, nullptr, -1, -1, nullptr, nullptr, lo, hi); };
-    auto B = [&](int lo, int hi) { k_sweep(g, alt, d, nullptr, nullptr, nullptr, MG3D_MAX_PARTIALS, h, 0, 1, true, s, 0, -1, &gc, dc, -1, -1, nullptr, nullptr, lo, hi); };
-    auto C2 = [&](int lo, int hi) { k_sweep(g, u, d, alt, nullptr, nullptr, MG3D_MAX_PARTIALS, h, 2, 0, false, s, 0, -1, nullptr, nullptr, -1, -1, nullptr, nullptr, lo, hi); };
-    auto D2 = [&](int lo, int hi) { k_sweep(g, alt, d, u, nullptr, partials, MG3D_MAX_PARTIALS, h, 2, 0, true, s, 0, -1, nullptr, nullptr, -1, -1, nullptr, nullptr, lo, hi); };
+    mg3d_options opt;
+    mg3d_options_init(&opt);
+    /* one launch on the window [lo, hi): S passes from vin into vout, optionally + residual (restricted into dc or its norm) */
+    auto sweep = [&](const double *vin, double *vout, int S, int c1, bool res, double *dc_, double *part, int lo, int hi) {
+        SweepLaunch w;
+        w.g = &g;
+        w.op = mg3d_level_op(1.0 / (N - 1), 0.);
+        w.vin = vin;
+        w.d = d;
+        w.vout = vout;
+        w.kind = res ? SWEEP_PASSES_RES : SWEEP_PASSES;
+        w.S = S;
+        w.c1 = c1;
+        w.partials = part;
+        if (dc_) {
+            w.gc = &gc;
+            w.dc = dc_;
+        }
+        w.i_lo = lo;
+        w.i_hi = hi;
+        k_sweep(opt, w, s);
+    };
+    auto A = [&](int lo, int hi) { sweep(u, alt, 4, 1, false, nullptr, nullptr, lo, hi); };
+    auto B = [&](int lo, int hi) { sweep(alt, nullptr, 0, 1, true, dc, nullptr, lo, hi); };
+    auto C2 = [&](int lo, int hi) { sweep(u, alt, 2, 0, false, nullptr, nullptr, lo, hi); };
+    auto D2 = [&](int lo, int hi) { sweep(alt, u, 2, 0, true, nullptr, partials, lo, hi); };
     float tA = timed([&] { A(0, N); }, 5), tB = timed([&] { B(0, N); }, 5);
     float tC = timed([&] { C2(0, N); }, 5), tD = timed([&] { D2(0, N); }, 5);
     printf("full: A(4 passes) %.3f ms  B(res+restr) %.3f ms  C(2 passes) %.3f ms  D(2 passes+norm) %.3f ms  A+B %.3f  C+D %.3f  all %.3f\n",
@@ -102,7 +123,7 @@ int main(int argc, char **argv)
         for (const char *ci : {"0", "8", "16", "32"}) {
             if (atoi(ci) > W)
                 continue;
-            setenv("MG3D_SWEEP_CI", ci, 1);
+            opt.v[MG3D_OPT_SWEEP_CI] = atoi(ci);
             auto clampw = [&](int x) { return x < 0 ? 0 : x > N ? N : x; };
             float tAw = timed([&] { for (int lo = 0; lo < N; lo += W) A(lo, clampw(lo + W)); }, 3);
             float tAB = timed([&] { /* B covers what A has finished minus 3 planes */
@@ -140,6 +161,5 @@ int main(int argc, char **argv)
             fflush(stdout);
         }
     }
-    unsetenv("MG3D_SWEEP_CI");
     return 0;
 }
