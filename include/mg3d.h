@@ -139,7 +139,7 @@ int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes);
  * case does, and the library projects neither f nor u.  The reflected operator is not symmetric: its left null vector
  * is the trapezoid weight w = 1/2 per Neumann face a point lies on (1/4 on an edge of two, 1/8 at a corner of three), so
  * the compatibility condition is WEIGHTED: sum of w*f over the unknowns = 0; the residual stalls at that weighted mean
- * otherwise.
+ * otherwise.  mg3d_wpcg_solve solves to a tolerance in that weighted inner product and does project, on its own vectors.
  * A prescribed flux g = du/dn (outward normal) keeps the operator homogeneous and is folded into the right-hand side by
  * mg3d_neumann_fold_flux (below) before the upload.
  * A mask outside 0..63, or a bit on a periodic axis, is MG3D_ERR_ARG and changes nothing; otherwise, as for
@@ -236,7 +236,8 @@ int mg3d_vcycles(mg3d_ctx *ctx, int count, double *norms);
  * singular case, every axis periodic with sigma = 0 (the pinned row of the coarse matrix breaks the symmetry of the
  * preconditioner); a context after mg3d_es_setup.  The slab, fp32 and mg3d_host_* forms have no such entry point.
  * Use it with a coefficient that jumps; for the constant operator mg3d_vcycles converges at 0.16 per 2 ms cycle and the
- * extra passes of an iteration cost more than they save ("Solving to a tolerance"). */
+ * extra passes of an iteration cost more than they save ("Solving to a tolerance").  mg3d_wpcg_solve below
+ * solves the two refused cases, Neumann faces and the singular operator, in the weighted inner product. */
 typedef struct mg3d_pcg_info {
     int iterations;        /* preconditioned iterations performed (updates of u; on breakdown one V-cycle more was run) */
     int converged;         /* 1: ||r_k|| <= max(rtol*||r_0||, atol) was reached */
@@ -246,6 +247,37 @@ typedef struct mg3d_pcg_info {
 int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters,
                    double *norms /* NULL or max_iters+1 entries: r_0 .. r_k */,
                    mg3d_pcg_info *info /* may be NULL */);
+
+/* The same iteration in the weighted inner product <a, b>_w = sum of w*a*b over the unknowns, w = 1/2 per Neumann face a
+ * point lies on and 1 otherwise (the weights of mg3d_ctx_set_neumann's compatibility condition; computed from the point's
+ * index inside the kernels, a power of two: the products are exact).  The reflected operator is self-adjoint in it and so
+ * is the cycle, so conjugate gradients apply where mg3d_pcg_solve refuses, and where plain cycles on a jumping eps between
+ * Neumann faces do not merely slow down but grow ("Weighted PCG").
+ * Everything mg3d_pcg_solve states about in, out, state, arguments, breakdown, determinism and work vectors holds, except:
+ *   accepted : every context mg3d_pcg_solve accepts -- the call is then that one, the same u and norms bit for bit; any
+ *              mask of Neumann faces beside periodic axes, sigma and eps; the singular case (every axis periodic or Neumann
+ *              on both faces, sigma = 0) with or without a Neumann face.  Refused with MG3D_ERR_STATE, nothing changed: a
+ *              context after mg3d_es_setup, one without a coarse factor.
+ *   dots     : r.z and p.Ap are weighted; alpha, beta and the sign tests are mg3d_pcg_solve's (A stays negative
+ *              (semi)definite).  Norms, r0_norm, r_norm and the stopping test stay Euclidean over the unknowns, the
+ *              quantity mg3d_residual returns.
+ *   singular : the system is solved on the subspace of w-mean zero.  With W = sum of w: r_0 = (d - A u) - sum(w (d - A u))/W,
+ *              every z has sum(w z)/W taken out as it enters the direction, r is not projected again.  d is never written;
+ *              rhs_mean reports sum(w d)/W, the part of d that was projected out -- not 0 (to rounding) means the caller's
+ *              right-hand side is incompatible and the solution returned is that of d - rhs_mean.  u keeps the w-mean of the
+ *              guess up to rounding.  The norms are those of the projected residual: mg3d_residual of the returned u agrees
+ *              with r_norm when d is compatible, and after its w-mean is taken out otherwise.  The work vectors are
+ *              allocated also with max_iters = 0.
+ * Points of u on a Neumann face that also lie on a Dirichlet face are Dirichlet points: untouched. */
+typedef struct mg3d_wpcg_info {
+    int iterations, converged;
+    double r0_norm, r_norm; /* as mg3d_pcg_info */
+    int singular;           /* 1: the projected system was solved */
+    double rhs_mean;        /* singular: sum(w*d)/sum(w) over the unknowns, the part of d that was projected out; else 0 */
+} mg3d_wpcg_info;
+int mg3d_wpcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters,
+                    double *norms /* NULL or max_iters+1 entries: r_0 .. r_k */,
+                    mg3d_wpcg_info *info /* may be NULL */);
 
 /* Full-multigrid initialisation, SolverFMGInitialize (mg_dirichlet_analytic.c:771-806; commented copy
  * mg_3d.h:1364-1404): BCs on u[0], direct solve, then for every level prolong the coarser solution, impose the

@@ -69,6 +69,7 @@ SIGNATURES = {
     "mg3d_vcycle": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_vcycles": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_pcg_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, dp, C.c_void_p]),
+    "mg3d_wpcg_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, dp, C.c_void_p]),
     "mg3d_fmg_initialize": (C.c_int, [C.c_void_p]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
@@ -177,6 +178,12 @@ NEUMANN_FACES = ("ilo", "ihi", "jlo", "jhi", "klo", "khi")  # bit f of the MG3D_
 class PcgInfo(C.Structure):
     """mg3d_pcg_info: what mg3d_pcg_solve reports"""
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("r0_norm", C.c_double), ("r_norm", C.c_double)]
+
+
+class WpcgInfo(C.Structure):
+    """mg3d_wpcg_info: what mg3d_wpcg_solve reports"""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("r0_norm", C.c_double), ("r_norm", C.c_double),
+                ("singular", C.c_int), ("rhs_mean", C.c_double)]
 
 
 class EsParams(C.Structure):
@@ -514,12 +521,24 @@ class Solver:
         """mg3d_pcg_solve: conjugate gradients preconditioned by one V-cycle per iteration, from the uploaded u and d of the
         finest level until ||r|| <= max(rtol * ||r_0||, atol).  Returns (norms ||r_0|| .. ||r_iterations||, info dict:
         iterations, converged, r0_norm, r_norm).  For coefficients that jump; not with Neumann faces or the singular
-        all-periodic case (Mg3dError, code 5)."""
+        all-periodic case (Mg3dError, code 5): wpcg_solve."""
         norms = np.zeros(max(int(max_iters), 0) + 1)
         info = PcgInfo()
         check(self.L.mg3d_pcg_solve(self._h, float(rtol), float(atol), int(max_iters), P(norms), C.byref(info)))
         return norms[:info.iterations + 1].copy(), {"iterations": info.iterations, "converged": bool(info.converged),
                                                     "r0_norm": info.r0_norm, "r_norm": info.r_norm}
+
+    def wpcg_solve(self, rtol=1e-8, atol=0.0, max_iters=50):
+        """mg3d_wpcg_solve: pcg_solve in the inner product weighted by compatibility_weights(), for contexts with Neumann
+        faces and for the singular operator (every axis periodic or Neumann on both faces, sigma = 0), which is solved on
+        the subspace of w-mean zero; on any other context it is pcg_solve, bit for bit.  Returns (norms, info dict:
+        iterations, converged, r0_norm, r_norm, singular, rhs_mean -- the w-mean of d that was projected out)."""
+        norms = np.zeros(max(int(max_iters), 0) + 1)
+        info = WpcgInfo()
+        check(self.L.mg3d_wpcg_solve(self._h, float(rtol), float(atol), int(max_iters), P(norms), C.byref(info)))
+        return norms[:info.iterations + 1].copy(), {"iterations": info.iterations, "converged": bool(info.converged),
+                                                    "r0_norm": info.r0_norm, "r_norm": info.r_norm,
+                                                    "singular": bool(info.singular), "rhs_mean": info.rhs_mean}
 
     def fmg_initialize(self):
         check(self.L.mg3d_fmg_initialize(self._h))

@@ -112,11 +112,12 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
                 int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
                 int acc_lo = 0, int acc_hi = -1);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
-/* The vector passes of mg3d_pcg_solve on a single-domain level, bc a mask of periodic axes only (no Neumann face).  Each
+/* The vector passes of mg3d_pcg_solve and mg3d_wpcg_solve on a single-domain level, bc the boundary word.  Each
  * touches the unknowns alone, the set the residual counts; sums are per-block partials folded in a fixed order into one
  * device double.  Scalars are read from device memory.  Return value: the number of partials (0: none needed), -1 when the
- * level has no launch shape.
- *   apply_dot   : q = A p (the operator of k_residual: e, op, sigma), *dot_out = sum of p*q
+ * level has no launch shape.  k_pcg_dot and k_pcg_direction take periodic axes only (no Neumann face).
+ *   apply_dot   : q = A p (the operator of k_residual: e, op, sigma), *dot_out = sum of w*p*q, w = 1/2 per Neumann face
+ *                 the point lies on (1 everywhere without one)
  *   update_norm : alpha = *rz / *pap; x += alpha p, r -= alpha q, *rr_out = sum of r*r; writes nothing unless both dots
  *                 are finite and negative (the operator is negative definite)
  *   dot         : *dot_out = sum of a*b
@@ -128,6 +129,18 @@ int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double 
 int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s);
 int k_pcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
                     hipStream_t s);
+/* mg3d_wpcg_solve's own passes, with the weight w above:
+ *   wpcg_dot       : *dot_out = sum of w*a*b, *sum_out = sum of w*b, from one read; two runs of partials, half the cap each
+ *   wpcg_direction : m = W > 0 ? *wsum / W : 0; beta = *rz_new / *rz_old; p = (z - m) + beta p; first: p = z - m
+ *   wpcg_center    : r -= *wsum / W, *rr_out = sum of r*r
+ *   weight_sum     : W = sum of w over the unknowns (a multiple of 1/8: exact) */
+int k_wpcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, double *sum_out,
+               hipStream_t s);
+int k_wpcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
+                     const double *wsum, double W, bool first, hipStream_t s);
+int k_wpcg_center(const Geom &g, int bc, double *r, const double *wsum, double W, double *partials, double *rr_out,
+                  hipStream_t s);
+double k_wpcg_weight_sum(const Geom &g, int bc);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo = -1,
                 int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);

@@ -470,12 +470,20 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
 }
 
 /* ------------------------------------------------------- conjugate gradients
- * The vector passes of mg3d_pcg_solve (mg3d_pcg.hip) on one single-domain level without Neumann faces.  Every pass
+ * The vector passes of mg3d_pcg_solve and mg3d_wpcg_solve (mg3d_pcg.hip) on one single-domain level.  Every pass
  * touches the unknowns only -- the points the residual counts -- so Dirichlet faces and periodic duplicates of its
  * operands are neither read as unknowns nor written; every sum is per-block partials folded by one block (k_fold).
+ * With a Neumann face (BC_REFLECT, mg3d_wpcg_solve) the dots are taken in the inner product the reflected operator is
+ * self-adjoint in: sum of w*a*b, w = 1/2 per Neumann face the point lies on -- computed from the point's index and the
+ * boundary word, a power of two, so w*(a*b) is the rounded product scaled exactly.
  *
- * apply + dot: q = A p and sum of p*q.  The residual's column walk, neighbour offsets and operand order:
+ * apply + dot: q = A p and sum of w*p*q.  The residual's column walk, neighbour offsets and operand order:
  * q = invHsq*(s - dg*p), which is what the residual subtracts from d. */
+/* 1/2 when index x of axis ax lies on a Neumann face, else 1 */
+__device__ __forceinline__ double bc_weight(int bc, int ax, int x, int N)
+{
+    return ((x == 0 && bc_ref_lo(bc, ax)) || (x == N - 1 && bc_ref_hi(bc, ax))) ? 0.5 : 1.;
+}
 template <bool COEF, int BC>
 __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                         double invHsq, double dg0, double *__restrict__ q,
@@ -487,15 +495,18 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
     Column c;
     if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
         long long p = gidx(g, c.i0, c.j, c.k);
-        const long long pb = p + nb_lo(c.i0, g.N, c.pi, false, g.plane);
+        const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
         double vb = v[pb], vh = v[p];
         double eb = 0., eh = 0.;
         if constexpr (COEF) {
             eb = e[pb];
             eh = e[p];
         }
+        double wjk = 1.;
+        if constexpr (BC == BC_REFLECT)
+            wjk = bc_weight(bc, 1, c.j, g.N) * bc_weight(bc, 2, c.k, g.N);
         for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-            const long long pa = p + nb_hi(i, g.N, c.pi, false, g.plane);
+            const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
             const double va = v[pa];
             double ea = 0.;
             if constexpr (COEF)
@@ -504,7 +515,10 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
             stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
             const double ap = invHsq * (s - dg * vh);
             q[p] = ap;
-            acc += vh * ap;
+            if constexpr (BC == BC_REFLECT)
+                acc += (wjk * bc_weight(bc, 0, i, g.N)) * (vh * ap);
+            else
+                acc += vh * ap;
             vb = vh;
             vh = va;
             if constexpr (COEF) {
@@ -531,12 +545,16 @@ int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const Level
     const double dg0 = e ? sigma * op.hSq : op.dg;
 #define MG3D_PCG_APPLY(COEF, BC) \
     hipLaunchKernelGGL((pcg_apply_kernel<COEF, BC>), grid, block, 0, s, g, p, e, op.invHsq, dg0, q, partials, bc, chunk, i_lo, i_hi)
-    const bool wrap = bc_mode(bc) == BC_WRAP;
-    if (e && wrap)
+    const int mode = bc_mode(bc);
+    if (e && mode == BC_REFLECT)
+        MG3D_PCG_APPLY(true, BC_REFLECT);
+    else if (e && mode == BC_WRAP)
         MG3D_PCG_APPLY(true, BC_WRAP);
     else if (e)
         MG3D_PCG_APPLY(true, BC_PLAIN);
-    else if (wrap)
+    else if (mode == BC_REFLECT)
+        MG3D_PCG_APPLY(false, BC_REFLECT);
+    else if (mode == BC_WRAP)
         MG3D_PCG_APPLY(false, BC_WRAP);
     else
         MG3D_PCG_APPLY(false, BC_PLAIN);
@@ -548,24 +566,29 @@ int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const Level
 
 /* The streaming passes.  A lane owns the aligned k-pair (2m, 2m+1) of a row -- one 16-byte access per operand; rows are
  * 128-byte aligned and a pair never leaves its row's pitch -- over `chunk` planes; the member of a pair that is no
- * unknown (a Dirichlet face, the duplicate k = N-1) keeps the value that was loaded.  lo: first unknown index of i, j, k
- * (0 on a periodic axis, else 1); the last one is N-2 on every axis. */
+ * unknown (a Dirichlet face, the duplicate k = N-1) keeps the value that was loaded.  The unknowns of an axis are
+ * [lo, hi]: lo 0 on a periodic axis or a Neumann low face, else 1; hi N-1 on a Neumann high face, else N-2 (N is odd
+ * and rows are padded to a multiple of 16 doubles: the pair (N-1, N) stays inside its row's pitch). */
+struct PairRange {
+    int lo[3], hi[3];
+};
 struct PairWalk {
     long long p;
+    int i0, j, k;
     int n; /* planes */
     bool m0, m1;
 };
-__device__ __forceinline__ bool pair_walk(const Geom &g, int lo_i, int lo_j, int lo_k, int chunk, PairWalk &w)
+__device__ __forceinline__ bool pair_walk(const Geom &g, const PairRange &u, int chunk, PairWalk &w)
 {
-    const int k = 2 * (blockIdx.x * WAVE + threadIdx.x);
-    const int j = lo_j + blockIdx.y * 4 + threadIdx.y;
-    const int i0 = lo_i + blockIdx.z * chunk;
-    if (k > g.N - 2 || j > g.N - 2)
+    w.k = 2 * (blockIdx.x * WAVE + threadIdx.x);
+    w.j = u.lo[1] + blockIdx.y * 4 + threadIdx.y;
+    w.i0 = u.lo[0] + blockIdx.z * chunk;
+    if (w.k > u.hi[2] || w.j > u.hi[1])
         return false;
-    w.m0 = k >= lo_k;
-    w.m1 = k + 1 <= g.N - 2;
-    w.n = min(chunk, g.N - 1 - i0);
-    w.p = gidx(g, i0, j, k);
+    w.m0 = w.k >= u.lo[2];
+    w.m1 = w.k + 1 <= u.hi[2];
+    w.n = min(chunk, u.hi[0] + 1 - w.i0);
+    w.p = gidx(g, w.i0, w.j, w.k);
     return true;
 }
 __device__ __forceinline__ bool pcg_finite_neg(double x) { return x < 0. && x >= -1.7976931348623157e308; }
@@ -576,15 +599,14 @@ __device__ __forceinline__ bool pcg_finite_neg(double x) { return x < 0. && x >=
 __global__ void __launch_bounds__(256) pcg_update_kernel(Geom g, double *__restrict__ x, double *__restrict__ r,
                                                          const double *__restrict__ pv, const double *__restrict__ qv,
                                                          const double *__restrict__ rz, const double *__restrict__ pap,
-                                                         double *__restrict__ partials, int lo_i, int lo_j, int lo_k,
-                                                         int chunk)
+                                                         double *__restrict__ partials, PairRange u, int chunk)
 {
     __shared__ double lds4[4];
     double acc = 0.;
     PairWalk w;
     const double num = *rz, den = *pap;
     const bool ok = pcg_finite_neg(num) && pcg_finite_neg(den);
-    if (ok && pair_walk(g, lo_i, lo_j, lo_k, chunk, w)) {
+    if (ok && pair_walk(g, u, chunk, w)) {
         const double alpha = num / den;
         for (int t = 0; t < w.n; t++, w.p += g.plane) {
             double2 xx = *reinterpret_cast<double2 *>(x + w.p), rr = *reinterpret_cast<double2 *>(r + w.p);
@@ -610,12 +632,12 @@ __global__ void __launch_bounds__(256) pcg_update_kernel(Geom g, double *__restr
 
 /* dot: sum of a*b over the unknowns */
 __global__ void __launch_bounds__(256) pcg_dot_kernel(Geom g, const double *__restrict__ a, const double *__restrict__ b,
-                                                      double *__restrict__ partials, int lo_i, int lo_j, int lo_k, int chunk)
+                                                      double *__restrict__ partials, PairRange u, int chunk)
 {
     __shared__ double lds4[4];
     double acc = 0.;
     PairWalk w;
-    if (pair_walk(g, lo_i, lo_j, lo_k, chunk, w)) {
+    if (pair_walk(g, u, chunk, w)) {
         for (int t = 0; t < w.n; t++, w.p += g.plane) {
             const double2 aa = *reinterpret_cast<const double2 *>(a + w.p), bb = *reinterpret_cast<const double2 *>(b + w.p);
             if (w.m0)
@@ -632,11 +654,10 @@ __global__ void __launch_bounds__(256) pcg_dot_kernel(Geom g, const double *__re
 /* direction: beta = (r.z)_new / (r.z)_old (Fletcher-Reeves); p = z + beta p */
 __global__ void __launch_bounds__(256) pcg_direction_kernel(Geom g, double *__restrict__ pv, const double *__restrict__ z,
                                                             const double *__restrict__ rz_new,
-                                                            const double *__restrict__ rz_old, int lo_i, int lo_j, int lo_k,
-                                                            int chunk)
+                                                            const double *__restrict__ rz_old, PairRange u, int chunk)
 {
     PairWalk w;
-    if (!pair_walk(g, lo_i, lo_j, lo_k, chunk, w))
+    if (!pair_walk(g, u, chunk, w))
         return;
     const double beta = *rz_new / *rz_old;
     for (int t = 0; t < w.n; t++, w.p += g.plane) {
@@ -650,18 +671,111 @@ __global__ void __launch_bounds__(256) pcg_direction_kernel(Geom g, double *__re
     }
 }
 
-/* the pair grid: the k-pairs and unknown rows of a level over (WAVE, 4) blocks, one plane per block in z; planes per
- * block doubled from 1 until the partial sums fit */
-static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, int lo[3])
+/* The weighted passes of mg3d_wpcg_solve.  wdot: sum of w*a*b and sum of w*b over the unknowns from one read of a and b
+ * (r.z and, for the projection of the singular case, the w-sum of z), into two runs of partials. */
+__device__ __forceinline__ double pair_weight(int bc, int N, int j, int k)
+{
+    return bc_weight(bc, 1, j, N) * bc_weight(bc, 2, k, N);
+}
+__global__ void __launch_bounds__(256) wpcg_dot_kernel(Geom g, const double *__restrict__ a, const double *__restrict__ b,
+                                                       double *__restrict__ pab, double *__restrict__ pb, int bc,
+                                                       PairRange u, int chunk)
+{
+    __shared__ double lds4[4];
+    double acc = 0., sum = 0.;
+    PairWalk w;
+    if (pair_walk(g, u, chunk, w)) {
+        const double w0 = pair_weight(bc, g.N, w.j, w.k), w1 = pair_weight(bc, g.N, w.j, w.k + 1);
+        for (int t = 0; t < w.n; t++, w.p += g.plane) {
+            const double2 aa = *reinterpret_cast<const double2 *>(a + w.p), bb = *reinterpret_cast<const double2 *>(b + w.p);
+            const double wi = bc_weight(bc, 0, w.i0 + t, g.N);
+            if (w.m0) {
+                acc += (wi * w0) * (aa.x * bb.x);
+                sum += (wi * w0) * bb.x;
+            }
+            if (w.m1) {
+                acc += (wi * w1) * (aa.y * bb.y);
+                sum += (wi * w1) * bb.y;
+            }
+        }
+    }
+    const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        pab[blk] = tot;
+    __syncthreads();
+    const double tot_b = block_sum_256(sum, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        pb[blk] = tot_b;
+}
+
+/* direction: p = (z - m) + beta p; m = *wsum / W, the w-mean of z (W = 0: no projection, m = 0), beta Fletcher-Reeves;
+ * first: the direction of iteration 0, p = z - m, p is not read */
+__global__ void __launch_bounds__(256) wpcg_direction_kernel(Geom g, double *__restrict__ pv, const double *__restrict__ z,
+                                                             const double *__restrict__ rz_new,
+                                                             const double *__restrict__ rz_old,
+                                                             const double *__restrict__ wsum, double W, int first,
+                                                             PairRange u, int chunk)
+{
+    PairWalk w;
+    if (!pair_walk(g, u, chunk, w))
+        return;
+    const double m = W > 0. ? *wsum / W : 0.;
+    const double beta = first ? 0. : *rz_new / *rz_old;
+    for (int t = 0; t < w.n; t++, w.p += g.plane) {
+        double2 pp = make_double2(0., 0.);
+        if (!first)
+            pp = *reinterpret_cast<double2 *>(pv + w.p);
+        const double2 zz = *reinterpret_cast<const double2 *>(z + w.p);
+        if (w.m0)
+            pp.x = first ? zz.x - m : (zz.x - m) + beta * pp.x;
+        if (w.m1)
+            pp.y = first ? zz.y - m : (zz.y - m) + beta * pp.y;
+        *reinterpret_cast<double2 *>(pv + w.p) = pp;
+    }
+}
+
+/* the projection of the first residual in the singular case: r -= *wsum / W, sum of r*r */
+__global__ void __launch_bounds__(256) wpcg_center_kernel(Geom g, double *__restrict__ r, const double *__restrict__ wsum,
+                                                          double W, double *__restrict__ partials, PairRange u, int chunk)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    PairWalk w;
+    if (pair_walk(g, u, chunk, w)) {
+        const double m = *wsum / W;
+        for (int t = 0; t < w.n; t++, w.p += g.plane) {
+            double2 rr = *reinterpret_cast<double2 *>(r + w.p);
+            if (w.m0) {
+                rr.x = rr.x - m;
+                acc += rr.x * rr.x;
+            }
+            if (w.m1) {
+                rr.y = rr.y - m;
+                acc += rr.y * rr.y;
+            }
+            *reinterpret_cast<double2 *>(r + w.p) = rr;
+        }
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+/* the pair grid: the k-pairs (from 0 up to the last unknown k) and unknown rows of a level over (WAVE, 4) blocks, one
+ * plane per block in z; planes per block doubled from 1 until the partial sums fit in `cap` */
+static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, PairRange &u, int cap = MG3D_MAX_PARTIALS)
 {
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
         return false;
-    for (int ax = 0; ax < 3; ax++)
-        lo[ax] = (bc >> ax & 1) ? 0 : 1;
-    const int pairs = (g.N - 2) / 2 + 1, rows = g.N - 1 - lo[1], planes = g.N - 1 - lo[0];
+    for (int ax = 0; ax < 3; ax++) {
+        u.lo[ax] = ((bc >> ax & 1) || bc_ref_lo(bc, ax)) ? 0 : 1;
+        u.hi[ax] = bc_ref_hi(bc, ax) ? g.N - 1 : g.N - 2;
+    }
+    const int pairs = u.hi[2] / 2 + 1, rows = u.hi[1] + 1 - u.lo[1], planes = u.hi[0] + 1 - u.lo[0];
     const int gx = (pairs + WAVE - 1) / WAVE, gy = (rows + 3) / 4;
     chunk = 1;
-    while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
+    while ((long long)gx * gy * ((planes + chunk - 1) / chunk) > cap)
         chunk *= 2;
     grid = dim3(gx, gy, (planes + chunk - 1) / chunk);
     return true;
@@ -671,11 +785,11 @@ int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double 
                       const double *pap, double *partials, double *rr_out, hipStream_t s)
 {
     dim3 grid;
-    int chunk, lo[3];
-    if (!pair_grid(g, bc, grid, chunk, lo))
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u))
         return -1;
-    hipLaunchKernelGGL(pcg_update_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, x, r, p, q, rz, pap, partials, lo[0], lo[1], lo[2],
-                       chunk);
+    hipLaunchKernelGGL(pcg_update_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, x, r, p, q, rz, pap, partials, u, chunk);
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, rr_out, s);
     return np;
@@ -684,10 +798,11 @@ int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double 
 int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s)
 {
     dim3 grid;
-    int chunk, lo[3];
-    if (!pair_grid(g, bc, grid, chunk, lo))
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u))
         return -1;
-    hipLaunchKernelGGL(pcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, lo[0], lo[1], lo[2], chunk);
+    hipLaunchKernelGGL(pcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, u, chunk);
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, dot_out, s);
     return np;
@@ -697,11 +812,65 @@ int k_pcg_direction(const Geom &g, int bc, double *p, const double *z, const dou
                     hipStream_t s)
 {
     dim3 grid;
-    int chunk, lo[3];
-    if (!pair_grid(g, bc, grid, chunk, lo))
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u))
         return -1;
-    hipLaunchKernelGGL(pcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, lo[0], lo[1], lo[2], chunk);
+    hipLaunchKernelGGL(pcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, u, chunk);
     return 0;
+}
+
+int k_wpcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, double *sum_out,
+               hipStream_t s)
+{
+    dim3 grid;
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u, MG3D_MAX_PARTIALS / 2))
+        return -1;
+    double *const pb = partials + MG3D_MAX_PARTIALS / 2;
+    hipLaunchKernelGGL(wpcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, pb, bc, u, chunk);
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, dot_out, s);
+    k_fold(pb, np, sum_out, s);
+    return np;
+}
+
+int k_wpcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
+                     const double *wsum, double W, bool first, hipStream_t s)
+{
+    dim3 grid;
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u))
+        return -1;
+    hipLaunchKernelGGL(wpcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, wsum, W, first ? 1 : 0,
+                       u, chunk);
+    return 0;
+}
+
+int k_wpcg_center(const Geom &g, int bc, double *r, const double *wsum, double W, double *partials, double *rr_out,
+                  hipStream_t s)
+{
+    dim3 grid;
+    int chunk;
+    PairRange u;
+    if (!pair_grid(g, bc, grid, chunk, u))
+        return -1;
+    hipLaunchKernelGGL(wpcg_center_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, r, wsum, W, partials, u, chunk);
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, rr_out, s);
+    return np;
+}
+
+double k_wpcg_weight_sum(const Geom &g, int bc)
+{
+    double W = 1.;
+    for (int ax = 0; ax < 3; ax++) {
+        const int lo = ((bc >> ax & 1) || bc_ref_lo(bc, ax)) ? 0 : 1, hi = bc_ref_hi(bc, ax) ? g.N - 1 : g.N - 2;
+        W *= (hi + 1 - lo) - 0.5 * (bc_ref_lo(bc, ax) + bc_ref_hi(bc, ax));
+    }
+    return W;
 }
 
 /* GetL2NormOfVector (mg_3d.h:783-792) over every point of a level, boundary included */

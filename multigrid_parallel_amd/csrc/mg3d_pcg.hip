@@ -1,5 +1,6 @@
 /*
- * mg3d_pcg.hip -- conjugate gradients preconditioned by the context's own V-cycle (mg3d_pcg_solve, include/mg3d.h).
+ * mg3d_pcg.hip -- conjugate gradients preconditioned by the context's own V-cycle (mg3d_pcg_solve and mg3d_wpcg_solve,
+ * include/mg3d.h).
  *
  * The cycle is a symmetric preconditioner: red,black before and black,red behind the coarse correction, the restriction
  * 1/8 of the prolongation's transpose, every level's operator symmetric (arithmetic face means), a zero guess below the
@@ -24,6 +25,15 @@
  *     dot              r.z                             light pass
  *     direction        p = z + beta p                  light pass; beta from the two device scalars
  * The scalars are slots of the context's sumsq array; nothing but the one copy per iteration crosses to the host.
+ *
+ * mg3d_wpcg_solve (Neumann faces, the singular case) is the same iteration in the inner product sum of w*a*b, w = 1/2 per
+ * Neumann face a point lies on: the reflected operator is self-adjoint in it, and so is the cycle -- red-black Gauss-Seidel
+ * does not see a scaling of rows, and the reflected full weighting is W_c^-1 P^T W_f / 8.  r.z and p.Ap are weighted; the
+ * norms stay Euclidean.  In the singular case (mg3d_ctx_pinned; W = sum of w) the system is solved on the subspace of
+ * w-mean zero: r_0 has its w-mean taken out once, every z loses sum(w z)/W as it enters the direction -- the pinned coarse
+ * solve differs from a symmetric pseudo-inverse by a constant only -- and r.z is that of the z the cycle returned, since
+ * <r, 1>_w = 0.  Per iteration the passes are the four above: the dot returns sum(w z) from the same read of z, the
+ * direction pass subtracts the mean and also forms the first direction (no copy).
  */
 #include "mg3d_ctx.h"
 
@@ -46,9 +56,17 @@
 
 /* slots of ctx->sumsq: 0 the initial residual, 1 the norm the cycle computes of its own system (dropped) */
 enum { S_R0 = 0, S_CYCLE = 1, S_RZ = 2 /* and 3: this iteration's and the next one's */, S_PAP = 4, S_RR = 5, S_END = 6 };
+/* the weighted solve's own, never copied inside an iteration: sum(w z); sum(w r_0), sum(w d); a sum nobody reads */
+enum { S_WZ = S_END, S_WR, S_WD, S_DROP };
 enum { V_Z = 0, V_R, V_P, V_Q };
 
-static int pcg_alloc(mg3d_ctx *ctx)
+/* the inner product of a solve: Euclidean (mg3d_pcg_solve), or weighted, with the projection of the singular case */
+struct InnerProduct {
+    bool weighted, singular;
+    double W; /* sum of w over the unknowns */
+};
+
+static int pcg_alloc(mg3d_ctx *ctx, const char *name)
 {
     const Level &top = ctx->lv[ctx->L - 1];
     if (ctx->pcg_v[0])
@@ -63,7 +81,7 @@ static int pcg_alloc(mg3d_ctx *ctx)
             for (double *w : v)
                 if (w)
                     (void)hipFree(w);
-            return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_pcg_solve: work vectors: %s",
+            return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: work vectors: %s", name,
                         hipGetErrorString(e));
         }
     }
@@ -72,17 +90,17 @@ static int pcg_alloc(mg3d_ctx *ctx)
     return MG3D_OK;
 }
 
-static int pcg_launch_ok(const char *what)
+static int pcg_launch_ok(const char *name, const char *what)
 {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return fail(MG3D_ERR_HIP, "mg3d_pcg_solve: %s: kernel launch failed: %s", what, hipGetErrorString(e));
+        return fail(MG3D_ERR_HIP, "%s: %s: kernel launch failed: %s", name, what, hipGetErrorString(e));
     return MG3D_OK;
 }
 
 /* the iterations, with z and r standing in for u and d of the top level (the caller exchanges and restores the pointers) */
-static int pcg_iterate(mg3d_ctx *ctx, double *x, double target, int max_iters, double *norms, int &iters, int &converged,
-                       double &r_norm)
+static int pcg_iterate(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, double *x, double target, int max_iters,
+                       double *norms, int &iters, int &converged, double &r_norm)
 {
     Level &top = ctx->lv[ctx->L - 1];
     const int q = ctx->L - 1, bc = mg3d_ctx_bc(ctx);
@@ -97,15 +115,20 @@ static int pcg_iterate(mg3d_ctx *ctx, double *x, double target, int max_iters, d
         ctx->red_tail = false; /* u and d of the top level change under the next cycle */
         const double *z = top.f[MG3D_U];
         double *const rz = sc + S_RZ + (k & 1), *const rz_old = sc + S_RZ + ((k + 1) & 1);
-        if (k_pcg_dot(top.g, bc, r, z, ctx->partials, rz, s) < 0)
-            return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: the level has no launch shape");
-        if (k == 0)
+        if ((ip.weighted ? k_wpcg_dot(top.g, bc, r, z, ctx->partials, rz, sc + S_WZ, s)
+                         : k_pcg_dot(top.g, bc, r, z, ctx->partials, rz, s)) < 0)
+            return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", name);
+        if (ip.weighted) {
+            if (k == 0) /* whatever an earlier solve left where this context has no unknowns */
+                HIPCHK(hipMemsetAsync(p, 0, top.elems * sizeof(double), s));
+            k_wpcg_direction(top.g, bc, p, z, rz, rz_old, sc + S_WZ, ip.singular ? ip.W : 0., k == 0, s);
+        } else if (k == 0)
             HIPCHK(hipMemcpyAsync(p, z, top.elems * sizeof(double), hipMemcpyDeviceToDevice, s)); /* p = z */
         else
             k_pcg_direction(top.g, bc, p, z, rz, rz_old, s);
         k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s);
         k_pcg_update_norm(top.g, bc, x, r, p, qv, rz, sc + S_PAP, ctx->partials, sc + S_RR, s);
-        CHK(pcg_launch_ok("iteration"));
+        CHK(pcg_launch_ok(name, "iteration"));
         HIPCHK(hipMemcpyAsync(ctx->h_sumsq + S_RZ, sc + S_RZ, (S_END - S_RZ) * sizeof(double), hipMemcpyDeviceToHost, s));
         CHK(mg3d_sync(ctx));
         const double h_rz = ctx->h_sumsq[S_RZ + (k & 1)], h_pap = ctx->h_sumsq[S_PAP];
@@ -124,36 +147,52 @@ static int pcg_iterate(mg3d_ctx *ctx, double *x, double target, int max_iters, d
     }
 }
 
-extern "C" int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters, double *norms, mg3d_pcg_info *info)
+static int pcg_check_args(const char *name, const mg3d_ctx *ctx, double rtol, double atol, int max_iters)
 {
     if (!ctx)
-        return fail(MG3D_ERR_ARG, "mg3d_pcg_solve: NULL context");
+        return fail(MG3D_ERR_ARG, "%s: NULL context", name);
     if (!(rtol >= 0.) || !(atol >= 0.) || !isfinite(rtol) || !isfinite(atol) || max_iters < 0)
-        return fail(MG3D_ERR_ARG, "mg3d_pcg_solve: rtol and atol must be finite and >= 0, max_iters >= 0 (%g, %g, %d)", rtol,
-                    atol, max_iters);
+        return fail(MG3D_ERR_ARG, "%s: rtol and atol must be finite and >= 0, max_iters >= 0 (%g, %g, %d)", name, rtol, atol,
+                    max_iters);
     if (rtol == 0. && atol == 0. && max_iters == 0)
-        return fail(MG3D_ERR_ARG, "mg3d_pcg_solve: rtol = atol = 0 needs max_iters > 0");
-    if (ctx->neumann)
-        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: the context has Neumann faces (mg3d_ctx_set_neumann): the reflected "
-                                    "operator is not symmetric in the Euclidean inner product");
-    if (ctx->periodic && mg3d_ctx_pinned(ctx))
-        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: every axis periodic with sigma = 0 is singular: the pinned row of the "
-                                    "coarse matrix makes the cycle an unsymmetric preconditioner");
+        return fail(MG3D_ERR_ARG, "%s: rtol = atol = 0 needs max_iters > 0", name);
+    return MG3D_OK;
+}
+
+static int pcg_check_state(const char *name, const mg3d_ctx *ctx)
+{
     if (ctx->have_es)
-        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: the context holds the mixed-boundary factor of mg3d_es_setup");
+        return fail(MG3D_ERR_STATE, "%s: the context holds the mixed-boundary factor of mg3d_es_setup", name);
     if (!ctx->have_lu)
-        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)");
+        return fail(MG3D_ERR_STATE, "%s: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)", name);
+    return MG3D_OK;
+}
+
+/* the solve of a checked call in the inner product ip */
+static int pcg_run(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, double rtol, double atol, int max_iters,
+                   double *norms, mg3d_wpcg_info *info)
+{
     CHK(mg3d_drop_carry(ctx)); /* a cycle that has run ahead is finished first */
     const int q = ctx->L - 1, bc = mg3d_ctx_bc(ctx);
     Level &top = ctx->lv[q];
     const double *e = ctx->eps.empty() ? nullptr : ctx->eps[q];
     hipStream_t s = ctx->stream;
-    if (max_iters > 0)
-        CHK(pcg_alloc(ctx));
+    const bool stored = max_iters > 0 || ip.singular; /* the projection works on the stored residual */
+    if (stored)
+        CHK(pcg_alloc(ctx, name));
     /* r_0 = d - A x; with iterations to come it is stored as the first right-hand side of the cycle */
     k_residual(top.g, top.f[MG3D_U], e, top.f[MG3D_D], mg3d_op(ctx, top), ctx->sigma, bc,
-               max_iters > 0 ? ctx->pcg_v[V_R] : nullptr, ctx->partials, ctx->sumsq + S_R0, s);
-    CHK(pcg_launch_ok("initial residual"));
+               stored ? ctx->pcg_v[V_R] : nullptr, ctx->partials, ctx->sumsq + S_R0, s);
+    if (ip.singular) {
+        /* sum(w r_0) and sum(w d), then r_0 -= sum(w r_0)/W and its norm */
+        double *const sc = ctx->sumsq, *const r = ctx->pcg_v[V_R];
+        if (k_wpcg_dot(top.g, bc, top.f[MG3D_D], r, ctx->partials, sc + S_DROP, sc + S_WR, s) < 0)
+            return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", name);
+        k_wpcg_dot(top.g, bc, r, top.f[MG3D_D], ctx->partials, sc + S_DROP, sc + S_WD, s);
+        k_wpcg_center(top.g, bc, r, sc + S_WR, ip.W, ctx->partials, sc + S_R0, s);
+        HIPCHK(hipMemcpyAsync(ctx->h_sumsq + S_WD, sc + S_WD, sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    CHK(pcg_launch_ok(name, "initial residual"));
     HIPCHK(hipMemcpyAsync(ctx->h_sumsq + S_R0, ctx->sumsq + S_R0, sizeof(double), hipMemcpyDeviceToHost, s));
     CHK(mg3d_sync(ctx));
     const double r0 = sqrt(ctx->h_sumsq[S_R0]);
@@ -175,7 +214,7 @@ extern "C" int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_i
         double *const x = top.f[MG3D_U], *const d = top.f[MG3D_D];
         top.f[MG3D_U] = ctx->pcg_v[V_Z];
         top.f[MG3D_D] = ctx->pcg_v[V_R];
-        rc = pcg_iterate(ctx, x, target, max_iters, norms, iters, converged, r_norm);
+        rc = pcg_iterate(ctx, name, ip, x, target, max_iters, norms, iters, converged, r_norm);
         if (rc != MG3D_OK)
             (void)hipStreamSynchronize(s);
         (void)mg3d_drop_carry(ctx);
@@ -184,7 +223,7 @@ extern "C" int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_i
         top.f[MG3D_D] = d;
         if (rc == MG3D_OK && ctx->periodic) {
             k_per_refresh(top.g, x, bc, s); /* the passes write unique points only */
-            rc = pcg_launch_ok("duplicate refresh");
+            rc = pcg_launch_ok(name, "duplicate refresh");
         }
         if (rc == MG3D_OK)
             rc = mg3d_sync(ctx);
@@ -194,6 +233,43 @@ extern "C" int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_i
         info->converged = converged;
         info->r0_norm = r0;
         info->r_norm = r_norm;
+        info->singular = ip.singular;
+        info->rhs_mean = ip.singular ? ctx->h_sumsq[S_WD] / ip.W : 0.;
     }
     return rc;
+}
+
+extern "C" int mg3d_pcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters, double *norms, mg3d_pcg_info *info)
+{
+    const char *const name = "mg3d_pcg_solve";
+    CHK(pcg_check_args(name, ctx, rtol, atol, max_iters));
+    if (ctx->neumann)
+        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: the context has Neumann faces (mg3d_ctx_set_neumann): the reflected "
+                                    "operator is not symmetric in the Euclidean inner product (mg3d_wpcg_solve)");
+    if (ctx->periodic && mg3d_ctx_pinned(ctx))
+        return fail(MG3D_ERR_STATE, "mg3d_pcg_solve: every axis periodic with sigma = 0 is singular: the pinned row of the "
+                                    "coarse matrix makes the cycle an unsymmetric preconditioner (mg3d_wpcg_solve)");
+    CHK(pcg_check_state(name, ctx));
+    mg3d_wpcg_info w;
+    const int rc = pcg_run(ctx, name, InnerProduct{false, false, 0.}, rtol, atol, max_iters, norms, info ? &w : nullptr);
+    if (info) {
+        info->iterations = w.iterations;
+        info->converged = w.converged;
+        info->r0_norm = w.r0_norm;
+        info->r_norm = w.r_norm;
+    }
+    return rc;
+}
+
+extern "C" int mg3d_wpcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters, double *norms, mg3d_wpcg_info *info)
+{
+    const char *const name = "mg3d_wpcg_solve";
+    CHK(pcg_check_args(name, ctx, rtol, atol, max_iters));
+    CHK(pcg_check_state(name, ctx));
+    /* without a Neumann face w = 1 and, unless the operator is singular, this is mg3d_pcg_solve's iteration: its passes */
+    InnerProduct ip;
+    ip.singular = mg3d_ctx_pinned(ctx);
+    ip.weighted = ctx->neumann != 0 || ip.singular;
+    ip.W = k_wpcg_weight_sum(ctx->lv[ctx->L - 1].g, mg3d_ctx_bc(ctx));
+    return pcg_run(ctx, name, ip, rtol, atol, max_iters, norms, info);
 }
