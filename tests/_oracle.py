@@ -70,6 +70,8 @@ def lib():
         L.orc32_restrict.argtypes = [fp, C.c_int, fp, C.c_int]
         L.orc32_prolong.argtypes = [fp, C.c_int, fp, C.c_int]
         L.orc32_coarse_solve.argtypes = [dp, C.c_int, fp, fp]
+        L.orc32_vcycle.restype = C.c_double
+        L.orc32_vcycle.argtypes = [C.POINTER(fp)] * 4 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_int, dp]
         L.orc32_run_problem.restype = C.c_double
         L.orc32_run_problem.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, dp, fp]
         # the mixed-boundary ("electrospray") problem (oracle/mg3d_oracle_es.c, parity unpinned)

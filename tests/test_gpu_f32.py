@@ -8,9 +8,10 @@ accuracy."""
 import numpy as np
 import pytest
 
+import _f32_ref as R
 import _oracle as O
 import multigrid_parallel_amd as M
-from multigrid_parallel_amd.binding import MG3D_D, MG3D_R, MG3D_U
+from multigrid_parallel_amd.binding import MG3D_D, MG3D_U
 
 pytestmark = pytest.mark.gpu
 OMEGA = 6.0 / 7.0
@@ -22,57 +23,8 @@ def rnd(n, seed):
 
 @pytest.mark.parametrize("c,L", [(3, 3), (5, 3), (9, 3), (3, 5), (5, 4)])
 def test_operators_match_the_restatement(c, L):
-    lib = O.lib()
-    with M.Solver32(c, L, 2, OMEGA) as s:
-        top = L - 1
-        N, Nc = s.level_n(top), s.level_n(top - 1)
-        h = np.float32(1.0 / (N - 1))
-        u, d = rnd(N, 1), rnd(N, 2)
-        s.upload(MG3D_U, top, u)
-        s.upload(MG3D_D, top, d)
-        # smoother: 1, 2 and 3 sweeps (buffer parity)
-        for iters in (1, 2, 3):
-            s.upload(MG3D_U, top, u)
-            s.smooth(top, iters)
-            want, scratch = u.copy(), np.zeros_like(u)
-            lib.orc32_smooth(O.PF(want), O.PF(d), O.PF(scratch), N, h, np.float32(OMEGA), iters)
-            assert np.array_equal(s.download(MG3D_U, top), want), f"{iters} sweeps"
-        # residual + norm
-        r0 = rnd(N, 3)
-        s.upload(MG3D_R, top, r0)
-        got_norm = s.residual(top, store=True)
-        want_r = r0.copy()
-        want_norm = lib.orc32_residual(O.PF(want), O.PF(d), N, h, O.PF(want_r))
-        assert np.array_equal(s.download(MG3D_R, top), want_r)  # boundary of r untouched
-        assert got_norm == pytest.approx(want_norm, rel=1e-12)
-        # restriction
-        s.restrict(top)
-        want_dc = np.zeros(Nc ** 3, dtype=np.float32)
-        lib.orc32_restrict(O.PF(want_r), N, O.PF(want_dc), Nc)
-        assert np.array_equal(s.download(MG3D_D, top - 1), want_dc)
-        # prolongation
-        ec = rnd(Nc, 4)
-        s.upload(MG3D_U, top - 1, ec)
-        s.prolong(top)
-        lib.orc32_prolong(O.PF(ec), Nc, O.PF(want), N)
-        assert np.array_equal(s.download(MG3D_U, top), want)
-        # boundary fill
-        s.zero(MG3D_U, top)
-        s.fill_boundary(MG3D_U, top)
-        want_b = np.zeros(N ** 3, dtype=np.float32)
-        lib.orc32_fill_boundary(O.PF(want_b), N, 1.0 / (N - 1))
-        assert np.array_equal(s.download(MG3D_U, top), want_b)
-        # coarsest solve through double
-        n0 = c ** 3
-        b0 = rnd(c, 5)
-        s.upload(MG3D_D, 0, b0)
-        s.coarse_solve()
-        LU = np.zeros(n0 * n0)
-        lib.orc_coarse_matrix(O.P(LU), c, (1.0 / (N - 1)) * (1 << (L - 1)))
-        lib.orc_lu_factor(O.P(LU), n0)
-        want_x = np.zeros(n0, dtype=np.float32)
-        lib.orc32_coarse_solve(O.P(LU), n0, O.PF(b0), O.PF(want_x))
-        assert np.array_equal(s.download(MG3D_U, 0), want_x)
+    """The body is shared with tests/test_gpu_f32_random.py, which takes it past one block in k."""
+    R.check_operators(c, L, sweeps=(1, 2, 3), sequential_norm=True)
 
 
 @pytest.mark.parametrize("c,L,nu,fmg", [(5, 4, 2, False), (5, 4, 2, True), (3, 5, 1, False), (9, 3, 3, True), (9, 4, 2, False)])

@@ -68,3 +68,42 @@ def test_fp32_slabs_random_rhs(monkeypatch):
         norms = d.vcycles(3)
         assert np.array_equal(d.download(MG3D_U, L - 1), want_u)
     np.testing.assert_allclose(norms, want_n, rtol=1e-12, atol=0)
+
+
+_single_random = {}
+
+
+def single_random(c, L, nu, cycles, seed):
+    """Solver32 from seeded uniform(-1, 1) u and d; one run per case, shared by the rank counts.  Solver32 is itself held
+    to the CPU restatement on random data at these shapes and sweep counts by tests/test_gpu_f32_random.py."""
+    key = (c, L, nu, cycles, seed)
+    if key not in _single_random:
+        N = (c - 1) * (1 << (L - 1)) + 1
+        rng = np.random.default_rng(seed)
+        u0 = rng.uniform(-1, 1, N ** 3).astype(np.float32)
+        d0 = rng.uniform(-1, 1, N ** 3).astype(np.float32)
+        with M.Solver32(c, L, nu) as s:
+            s.upload(MG3D_U, L - 1, u0)
+            s.upload(MG3D_D, L - 1, d0)
+            norms = s.vcycles(cycles)
+            _single_random[key] = (u0, d0, norms, s.download(MG3D_U, L - 1))
+    return _single_random[key]
+
+
+@pytest.mark.parametrize("nu", [2, 3])
+@pytest.mark.parametrize("c,L,P", [(9, 6, 3), (9, 6, 8), (10, 5, 4)])
+def test_fp32_slabs_random_data_across_tiles(monkeypatch, c, L, P, nu):
+    """Random u and d at 257^3 (two k-tiles of the fused launches; 3 uneven and 8 thin slabs) and at 145^3 (off the
+    2^k + 1 ladder, 4 slabs), V(2,2) with carried cycles and V(3,3) with pair + single sweep, three cycles: every bit of
+    the single domain, norms to the summation order."""
+    monkeypatch.setenv("MG3D_SLAB_MIN_PLANES", "8")
+    u0, d0, want_n, want_u = single_random(c, L, nu, 3, 7)
+    with M.DistSolver32(c, L, nu, nranks=P) as d:
+        assert 1 <= d.first_level < L and d.halo == nu + 2
+        d.upload(MG3D_U, L - 1, u0)
+        d.upload(MG3D_D, L - 1, d0)
+        norms = d.vcycles(3)
+        u = d.download(MG3D_U, L - 1)
+    assert np.array_equal(u, want_u) and np.array_equal(np.signbit(u), np.signbit(want_u))
+    print(f"({c},{L}) P = {P} nu = {nu}: norm / single domain - 1 =", " ".join(f"{x:+.3e}" for x in norms / want_n - 1))
+    np.testing.assert_allclose(norms, want_n, rtol=1e-12, atol=0)
