@@ -283,6 +283,40 @@ int mg3d_wpcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_iters,
  * mg_3d.h:1364-1404): BCs on u[0], direct solve, then for every level prolong the coarser solution, impose the
  * Dirichlet values BCFunc on the six faces (on the device), zero the coarser level, one V-cycle from that level. */
 int mg3d_fmg_initialize(mg3d_ctx *ctx);
+/* Full multigrid for the CALLER's problem: the finest level's d and Dirichlet values, on every operator the context
+ * supports (constant, sigma, eps, any periodic mask, any Neumann mask).  mg3d_fmg_initialize above stays what the reference
+ * is -- one analytic test problem, Dirichlet faces only, and its interpolated guess is discarded below the finest level.
+ *   in : u of the finest level as uploaded -- only its Dirichlet points are read, whatever else it holds is ignored; d of
+ *        the finest level; the coarse factor set as for mg3d_vcycle; cycles >= 1, otherwise MG3D_ERR_ARG and nothing
+ *        changes.  A cycle that has run ahead is finished first.
+ *   1. for l = L-1 .. 1: d[l-1] = the context's own restriction of d[l] (full weighting of the unknowns; Dirichlet points
+ *      are injected and never enter a weighted sum, so the caller need not define d there), u[l-1] = injection of u[l]
+ *      (u[l-1][I,J,K] = u[l][2I,2J,2K]: the Dirichlet values); then d[0] = u[0] at every Dirichlet point of level 0, the
+ *      right-hand side of the direct solve's identity rows
+ *   2. level 0: the direct solve, duplicates and the pinned row as in a cycle
+ *   3. for l = 1 .. L-1: mg3d_fmg_interpolate(l), then `cycles` V-cycles from level l that keep u[l] as their guess (the
+ *      levels below l start from zero as in every cycle); on l = L-1 they are mg3d_vcycles(cycles), schedules included
+ *   out: u of the finest level holds the result, its Dirichlet points the caller's bit for bit, its periodic duplicates
+ *        equal to their sources; d of the finest level is the caller's bit for bit; *norm (may be NULL) is the residual
+ *        norm after the last finest-level cycle, the value mg3d_vcycles returns.  u and d of the lower levels and r are
+ *        unspecified.  The context is usable as before: mg3d_vcycles(1) from the returned u gives, bit for bit, what a
+ *        context gives that had this u and d uploaded.
+ * With V(2,2) and cycles = 1 the algebraic error of the result is below the discretisation error ("Full
+ * multigrid start"): what six or seven cycles from a zero guess do.  The singular case has mg3d_vcycle's caveat: nothing
+ * is projected, d must be compatible, u is fixed by the pin.
+ * mg3d_fmg_interpolate: u[level] at every unknown (and its periodic duplicates) is OVERWRITTEN with the interpolant of
+ * u[level-1]; Dirichlet points of u[level] are never written, those of u[level-1] are read like any other point.  Per
+ * axis (coarse side Nc): an even fine index 2I copies coarse I; an odd one, 2I+1, takes coarse I-1, I, I+1, I+2 with
+ * -1/16, 9/16, 9/16, -1/16 -- an index outside the unique range wrapped modulo Nc-1 on a periodic axis, reflected at a
+ * Neumann face (-1 -> 1, Nc -> Nc-2); next to a Dirichlet face the one-sided cubic over the four points nearest the face
+ * (low: coarse 0, 1, 2, 3 with 5/16, 15/16, -5/16, 1/16; high: coarse Nc-4 .. Nc-1 with 1/16, -5/16, 15/16, 5/16); with
+ * Nc < 4 coarse I, I+1 with 1/2, 1/2.  The value is the tensor product sum_i(wi * sum_j(wj * sum_k(wk * u))), each sum
+ * left to right in the order given, uncontracted (tests/_fmg_ref.py restates it bit for bit).  1 <= level < L, otherwise
+ * MG3D_ERR_ARG.
+ * Both return MG3D_ERR_STATE, nothing changed, on a context without a coarse factor or after mg3d_es_setup.  The slab,
+ * fp32 and mg3d_host_* forms have no such entry points. */
+int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level);
+int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm /* may be NULL */);
 /* setupBoundaryConditions (mg_3d.h:1147-1239) on a device-resident field */
 int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
 

@@ -71,6 +71,8 @@ SIGNATURES = {
     "mg3d_pcg_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, dp, C.c_void_p]),
     "mg3d_wpcg_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, dp, C.c_void_p]),
     "mg3d_fmg_initialize": (C.c_int, [C.c_void_p]),
+    "mg3d_fmg_interpolate": (C.c_int, [C.c_void_p, C.c_int]),
+    "mg3d_fmg_solve": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -542,6 +544,20 @@ class Solver:
 
     def fmg_initialize(self):
         check(self.L.mg3d_fmg_initialize(self._h))
+
+    def fmg_interpolate(self, level):
+        """mg3d_fmg_interpolate: every unknown of u[level] overwritten with the cubic interpolant of u[level - 1]
+        (1 <= level < num_levels); Dirichlet points stay."""
+        check(self.L.mg3d_fmg_interpolate(self._h, int(level)))
+
+    def fmg_solve(self, cycles=1):
+        """mg3d_fmg_solve: full multigrid from the uploaded d and the Dirichlet points of the uploaded u of the finest
+        level (its interior is ignored) -- d restricted down the hierarchy, a direct solve, then per level the cubic
+        interpolant as the guess of `cycles` V-cycles that keep it.  With V(2,2) one cycle per level leaves an algebraic
+        error below the discretisation error.  Returns the residual norm after the last finest-level cycle."""
+        nrm = C.c_double(0)
+        check(self.L.mg3d_fmg_solve(self._h, int(cycles), C.byref(nrm)))
+        return nrm.value
 
     # -- the mixed-boundary ("electrospray") problem, csrc/mg3d_es.hip
     def es_setup(self, params=None):

@@ -138,7 +138,9 @@ int mg3d_fail(int code, const char *fmt, ...);
  * last cycle of a call); ignored where mg3d_can_carry() says no */
 /* carry_out: 0 the cycle ends the ordinary way; 1 another cycle of the same call follows; 2 the call ends here and runs
  * ahead speculatively (mg3d_vcycle) */
-int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out = 0);
+/* keep_guess: below the finest level, u of level q is the initial guess instead of being zeroed (mg3d_fmg_solve); the
+ * levels below q start from zero as always */
+int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out = 0, bool keep_guess = false);
 bool mg3d_can_carry(const mg3d_ctx *ctx, int q);
 bool mg3d_can_legs(const mg3d_ctx *ctx, int q);
 /* carried state -> the finished cycle's own u; a no-op (MG3D_OK) otherwise.  An error leaves the carried state in place. */

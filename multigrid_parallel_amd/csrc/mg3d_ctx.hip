@@ -1110,16 +1110,18 @@ static void enqueue_prolong(mg3d_ctx *ctx, int level)
 /* periodic: the factor of mg3d_coarse_matrix_bc solves for b = d with 0 in the identity rows of the duplicates and, in
  * the singular case (mg3d_ctx_pinned), of the pinned point (0,0,0); the duplicates of x are then copied from their
  * sources.  Neumann faces alone have no duplicates: only the pinned case takes the detour over per_b */
-static void enqueue_coarse_solve(mg3d_ctx *ctx)
+static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* NULL: d of level 0 */)
 {
     Level &l0 = ctx->lv[0];
+    if (!rhs)
+        rhs = l0.f[MG3D_D];
     if (ctx->periodic || (ctx->neumann && mg3d_ctx_pinned(ctx))) {
-        k_per_coarse_rhs(l0.g, l0.f[MG3D_D], ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->stream);
+        k_per_coarse_rhs(l0.g, rhs, ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->stream);
         k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
         k_per_refresh(l0.g, l0.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
         return;
     }
-    k_lu_solve(ctx->lu, ctx->lu_in, l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu_work, ctx->stream);
+    k_lu_solve(ctx->lu, ctx->lu_in, l0.g, rhs, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
 }
 
 static int enqueue_smooth(mg3d_ctx *ctx, int level, int post, int iters)
@@ -1396,14 +1398,15 @@ static void down_leg_tiny(mg3d_ctx *ctx, const CycleState &c)
     ctx->faces_dirty[1] = 0;
 }
 
-/* the down-leg of every other level: zero guess, pre-smoother, residual, restriction */
-static int down_leg_ordinary(mg3d_ctx *ctx, int l)
+/* the down-leg of every other level: zero guess (keep_guess: the level's u as it is), pre-smoother, residual, restriction */
+static int down_leg_ordinary(mg3d_ctx *ctx, int l, bool keep_guess)
 {
     Level &lev = ctx->lv[l];
     /* :1258-1259: the zero initial guess of a coarser level; with the fused sweep the first launch simply
      * does not read u (and writes every plane of the other buffer), so no memset is needed */
-    const bool zero_in = l < ctx->L - 1 && mg3d_fused(ctx) && ctx->iters > 0;
-    if (l < ctx->L - 1 && !zero_in)
+    const bool zero = l < ctx->L - 1 && !keep_guess;
+    const bool zero_in = zero && mg3d_fused(ctx) && ctx->iters > 0;
+    if (zero && !zero_in)
         (void)hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), ctx->stream);
     if (mg3d_fused(ctx)) { /* pre-smoother and residual in one pass over the level (:1282 + :1294) */
         {
@@ -1554,7 +1557,7 @@ static int up_leg_ordinary(mg3d_ctx *ctx, const CycleState &c, int l)
     return MG3D_OK;
 }
 
-int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
+int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out, bool keep_guess)
 {
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_vcycle: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)");
@@ -1598,7 +1601,7 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out)
         else if (l == 1 && c.tiny)
             down_leg_tiny(ctx, c);
         else
-            CHK(down_leg_ordinary(ctx, l));
+            CHK(down_leg_ordinary(ctx, l, keep_guess && l == q));
     }
     bottom(ctx, c);
     /* ---- up: level 1 as on the way down; the top level in the schedule that lets the next cycle run ahead */
@@ -1716,6 +1719,79 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1));                                              /* :804 */
     }
     return launch_ok("mg3d_fmg_initialize");
+}
+
+/* Full multigrid for the caller's problem (include/mg3d.h): what mg3d_fmg_initialize cannot be while it is pinned to the
+ * reference -- the caller's d and Dirichlet values, every operator of the context, a cubic interpolation, and V-cycles
+ * that keep the interpolated guess (keep_guess of mg3d_enqueue_vcycle). */
+static int fmg_check(mg3d_ctx *ctx, const char *who)
+{
+    if (!ctx->have_lu)
+        return fail(MG3D_ERR_STATE, "%s: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)", who);
+    if (ctx->have_es)
+        return fail(MG3D_ERR_STATE, "%s: the context holds the mixed-boundary factor of mg3d_es_setup", who);
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level)
+{
+    if (!ctx || level < 1 || level >= ctx->L)
+        return fail(MG3D_ERR_ARG, "mg3d_fmg_interpolate: %s", ctx ? "level outside 1 .. L-1" : "NULL context");
+    CHK(fmg_check(ctx, "mg3d_fmg_interpolate"));
+    CHK(mg3d_drop_carry(ctx));
+    const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
+    k_fmg_interp(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
+    return launch_ok("mg3d_fmg_interpolate");
+}
+
+extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
+{
+    if (!ctx || cycles < 1)
+        return fail(MG3D_ERR_ARG, "mg3d_fmg_solve: %s", ctx ? "cycles must be >= 1" : "NULL context");
+    CHK(fmg_check(ctx, "mg3d_fmg_solve"));
+    CHK(mg3d_drop_carry(ctx));
+    const int L = ctx->L, bc = mg3d_ctx_bc(ctx);
+    hipStream_t s = ctx->stream;
+    /* 1. the right-hand side down the hierarchy by the context's own restriction, u by injection: the Dirichlet values */
+    for (int l = L - 1; l >= 1; l--) {
+        const Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
+        if (bc)
+            k_per_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], bc, s);
+        else
+            k_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], s);
+        k_coef_inject(lev.g, lev.f[MG3D_U], lc.g, lc.f[MG3D_U], s);
+        mg3d_ctx_touched(ctx, MG3D_D, l - 1); /* its faces are no injection of r any more: the cycles inject them again */
+    }
+    /* 2. the direct solve, its identity rows taking the Dirichlet values (a one-level context keeps its d: the
+     * right-hand side is put together in r) */
+    Level &l0 = ctx->lv[0];
+    double *rhs = l0.f[MG3D_D];
+    if (L == 1) {
+        rhs = l0.f[MG3D_R];
+        HIPCHK(hipMemcpyAsync(rhs, l0.f[MG3D_D], l0.elems * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    k_dirichlet_rhs(l0.g, l0.f[MG3D_U], rhs, bc, s);
+    enqueue_coarse_solve(ctx, rhs);
+    CHK(launch_ok("mg3d_fmg_solve"));
+    if (L == 1) {
+        if (norm)
+            *norm = 0.;
+        return mg3d_sync(ctx);
+    }
+    /* 3. up: the cubic interpolant as the guess, `cycles` V-cycles that keep it; d of level l and the Dirichlet points of
+     * u of level l are still those of step 1 -- a cycle from below writes d below l and u at or below l - 1 only */
+    for (int l = 1; l < L - 1; l++) {
+        k_fmg_interp(ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_U], ctx->lv[l].g, ctx->lv[l].f[MG3D_U], bc, s);
+        for (int c = 0; c < cycles; c++)
+            CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1, 0, true));
+    }
+    k_fmg_interp(ctx->lv[L - 2].g, ctx->lv[L - 2].f[MG3D_U], ctx->lv[L - 1].g, ctx->lv[L - 1].f[MG3D_U], bc, s);
+    CHK(launch_ok("mg3d_fmg_solve"));
+    std::vector<double> norms((size_t)cycles);
+    CHK(mg3d_vcycles(ctx, cycles, norms.data())); /* the finest level: its schedules, its guard */
+    if (norm)
+        *norm = norms.back();
+    return MG3D_OK;
 }
 
 /* ------------------------------------------------------------------- timing */

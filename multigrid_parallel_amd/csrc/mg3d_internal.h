@@ -318,6 +318,11 @@ void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc,
 void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s);
 void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s);
 void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
+/* full multigrid (mg3d_fmg_solve): every unknown of the fine level (and its periodic duplicates) overwritten with the
+ * tensor-product cubic interpolant of the coarse u -- never a Dirichlet point; and d = u at the Dirichlet points of a level,
+ * the right-hand side of the direct solve's identity rows.  Single-domain levels, bc the boundary word */
+void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s);
+void k_dirichlet_rhs(const Geom &g, const double *u, double *d, int bc, hipStream_t s);
 /* zeros on the faces of a single-domain level given as a MG3D_NEUMANN_* mask */
 void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */

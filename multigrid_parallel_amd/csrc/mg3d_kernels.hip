@@ -1298,6 +1298,245 @@ void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef,
     hipLaunchKernelGGL(per_prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
 }
 
+/* --------------------------------------------------------- FMG interpolation
+ * mg3d_fmg_interpolate / mg3d_fmg_solve: every unknown of the fine level is OVERWRITTEN with the tensor-product cubic
+ * interpolant of the coarse u (nothing is added; Dirichlet points are never written; periodic duplicates as store_dup).
+ * Per axis, coarse side Nc, fine index x:
+ *   x = 2I              one term: coarse I, weight 1
+ *   x = 2I+1, Nc >= 4   four terms over coarse I-1, I, I+1, I+2 with -1/16, 9/16, 9/16, -1/16; an index outside the unique
+ *                       range wraps modulo Nc-1 on a periodic axis and reflects at a Neumann face (-1 -> 1, Nc -> Nc-2);
+ *                       next to a Dirichlet face the one-sided cubic over the four points nearest that face: low side
+ *                       (x = 1) coarse 0, 1, 2, 3 with 5/16, 15/16, -5/16, 1/16, high side (x = Nf-2) coarse Nc-4 .. Nc-1
+ *                       with 1/16, -5/16, 15/16, 5/16
+ *   x = 2I+1, Nc < 4    two terms: coarse I, I+1 with 1/2, 1/2
+ * value = sum_a wi[a] * (sum_b wj[b] * (sum_c wk[c] * uc[i_a, j_b, k_c])), every sum left to right in the order listed
+ * (the first term starts the sum), no contraction; all weights are binary fractions.  tests/_fmg_ref.py states the same in
+ * numpy.
+ *
+ * A term list is held as window slots: slot s stands for the logical coarse index I-1+s, which fmg_phys maps to the point
+ * that is read (wrapped, reflected; at a Dirichlet face -1 maps to 3 and Nc to Nc-4, the fourth point of the one-sided
+ * form, so the four slots always hold the four points of every form and only their order differs).
+ *
+ * A block produces the fine tile 8 rows x 64 columns (rows and columns counted from 0: 512-byte aligned row stores) of
+ * the fine planes 2I, 2I+1 of a chunk of coarse planes I, marching along i.  Per coarse plane: the k pass from global
+ * memory (seven coarse rows x 64 fine columns, into LDS), one barrier, the j pass from LDS into registers; a thread owns
+ * two (row, column) pairs and keeps their j-passed values of the four coarse planes of the i window in registers. */
+enum { FMG_EVEN = 0, FMG_LIN, FMG_CEN, FMG_LOW, FMG_HIGH };
+
+struct FmgAxis {
+    int Nc;
+    bool per, rlo, rhi;
+};
+
+__device__ __forceinline__ FmgAxis fmg_axis(int Nc, int bc, int ax)
+{
+    return FmgAxis{Nc, (bc >> ax & 1) != 0, bc_ref_lo(bc, ax), bc_ref_hi(bc, ax)};
+}
+
+/* the coarse point read for logical index l (-1 .. Nc+1; what no form uses is clamped into the array) */
+__device__ __forceinline__ int fmg_phys(const FmgAxis &a, int l)
+{
+    int p;
+    if (a.per)
+        p = l < 0 ? l + a.Nc - 1 : (l >= a.Nc - 1 ? l - (a.Nc - 1) : l);
+    else if (l < 0)
+        p = a.rlo ? 1 : 3;
+    else if (l >= a.Nc)
+        p = a.rhi ? a.Nc - 2 : a.Nc - 4;
+    else
+        p = l;
+    return min(max(p, 0), a.Nc - 1);
+}
+
+/* the form of fine index x = 2I + odd */
+__device__ __forceinline__ int fmg_form(const FmgAxis &a, int I, int odd)
+{
+    if (!odd)
+        return FMG_EVEN;
+    if (a.Nc < 4)
+        return FMG_LIN;
+    if (!a.per && !a.rlo && I == 0)
+        return FMG_LOW;
+    if (!a.per && !a.rhi && I + 2 == a.Nc)
+        return FMG_HIGH;
+    return FMG_CEN;
+}
+
+/* a form as n terms in summation order: window slots s and weights w (unused entries: slot 1, weight 0) */
+struct FmgTaps {
+    int n, s[4];
+    double w[4];
+};
+
+__device__ __forceinline__ FmgTaps fmg_taps(int form)
+{
+    switch (form) {
+    case FMG_EVEN:
+        return FmgTaps{1, {1, 1, 1, 1}, {1., 0., 0., 0.}};
+    case FMG_LIN:
+        return FmgTaps{2, {1, 2, 1, 1}, {0.5, 0.5, 0., 0.}};
+    case FMG_LOW:
+        return FmgTaps{4, {1, 2, 3, 0}, {0.3125, 0.9375, -0.3125, 0.0625}};
+    case FMG_HIGH:
+        return FmgTaps{4, {3, 0, 1, 2}, {0.0625, -0.3125, 0.9375, 0.3125}};
+    default:
+        return FmgTaps{4, {0, 1, 2, 3}, {-0.0625, 0.5625, 0.5625, -0.0625}};
+    }
+}
+
+/* the sum of a form over its terms x0 .. x3 (already in summation order) */
+__device__ __forceinline__ double fmg_sum(const FmgTaps &t, double x0, double x1, double x2, double x3)
+{
+    double acc = t.w[0] * x0;
+    const double a2 = acc + t.w[1] * x1;
+    const double a4 = (a2 + t.w[2] * x2) + t.w[3] * x3;
+    return t.n == 1 ? acc : (t.n == 2 ? a2 : a4);
+}
+
+#define FMG_TJ 8  /* fine rows of a tile */
+#define FMG_CJ 7  /* coarse rows its j pass reads: logical Jc0-1 .. Jc0+5 */
+
+template <int BC>
+__global__ void __launch_bounds__(256) fmg_interp_kernel(Geom gc, const double *__restrict__ uc, Geom gf,
+                                                         double *__restrict__ uf, int bc, int chunk)
+{
+    __shared__ double T1[2][FMG_CJ][WAVE];
+    const int Nc = gc.N, Nf = gf.N;
+    const int cbc = BC ? bc : 0;
+    const FmgAxis ai = fmg_axis(Nc, cbc, 0), aj = fmg_axis(Nc, cbc, 1), ak = fmg_axis(Nc, cbc, 2);
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    /* unknown ranges of the fine level (column<BC> / stencil_window) */
+    const int ilo = (ai.per || ai.rlo) ? 0 : 1, ihi = Nf - (ai.rhi ? 1 : 2);
+    const int jlo = (aj.per || aj.rlo) ? 0 : 1, jhi = Nf - (aj.rhi ? 1 : 2);
+    const int klo = (ak.per || ak.rlo) ? 0 : 1, khi = Nf - (ak.rhi ? 1 : 2);
+    /* k pass: this thread's fine column and the coarse columns of its terms */
+    const int k = blockIdx.x * WAVE + tx;
+    const int kx = min(k, Nf - 1);
+    const FmgTaps tk = fmg_taps(fmg_form(ak, kx >> 1, kx & 1));
+    int kc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+        kc[t] = fmg_phys(ak, (kx >> 1) - 1 + tk.s[t]);
+    /* ... and its (up to) two coarse rows: tile rows ty and ty + 4 */
+    const int Jc0 = blockIdx.y * (FMG_TJ / 2);
+    const long long rowa = (long long)gc.pitch * fmg_phys(aj, Jc0 - 1 + ty);
+    const long long rowb = (long long)gc.pitch * fmg_phys(aj, Jc0 - 1 + min(ty + 4, FMG_CJ - 1));
+    const bool has_b = ty + 4 < FMG_CJ;
+    /* j pass: this thread's two fine rows ty and ty + 4 of the tile, column tx */
+    int j[2], r[2][4];
+    FmgTaps tj[2];
+    bool ok[2];
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        j[m] = blockIdx.y * FMG_TJ + ty + 4 * m;
+        const int jx = min(j[m], Nf - 1);
+        tj[m] = fmg_taps(fmg_form(aj, jx >> 1, jx & 1));
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            r[m][t] = min((jx >> 1) - Jc0 + tj[m].s[t], FMG_CJ - 1);
+        ok[m] = j[m] >= jlo && j[m] <= jhi && k >= klo && k <= khi;
+    }
+    const bool dk = ak.per && k == 0;
+
+    /* the j-passed values of this thread's two points on coarse plane `l` (logical); every thread of the block calls it */
+    int step = 0;
+    auto plane = [&](int l, double &o0, double &o1) {
+        const double *pl = uc + gc.plane * fmg_phys(ai, l);
+        double(*T)[WAVE] = T1[step & 1];
+        step++;
+        T[ty][tx] = fmg_sum(tk, pl[rowa + kc[0]], pl[rowa + kc[1]], pl[rowa + kc[2]], pl[rowa + kc[3]]);
+        if (has_b)
+            T[ty + 4][tx] = fmg_sum(tk, pl[rowb + kc[0]], pl[rowb + kc[1]], pl[rowb + kc[2]], pl[rowb + kc[3]]);
+        __syncthreads(); /* two buffers: the readers of this one are two barriers ahead of its next writers */
+        o0 = fmg_sum(tj[0], T[r[0][0]][tx], T[r[0][1]][tx], T[r[0][2]][tx], T[r[0][3]][tx]);
+        o1 = fmg_sum(tj[1], T[r[1][0]][tx], T[r[1][1]][tx], T[r[1][2]][tx], T[r[1][3]][tx]);
+    };
+    auto store = [&](int i, int m, double x) {
+        if (ok[m])
+            store_dup(gf, uf, gidx(gf, i, j[m], k), x, ai.per && i == 0, aj.per && j[m] == 0, dk);
+    };
+
+    const int I0 = blockIdx.z * chunk, I1 = min(I0 + chunk, Nc);
+    double W[4][2]; /* window slots 0 .. 3 = logical coarse planes I-1 .. I+2 */
+    plane(I0 - 1, W[0][0], W[0][1]);
+    plane(I0, W[1][0], W[1][1]);
+    plane(I0 + 1, W[2][0], W[2][1]);
+    for (int I = I0; I < I1; I++) {
+        plane(I + 2, W[3][0], W[3][1]);
+        const int i = 2 * I;
+        if (i >= ilo && i <= ihi) {
+            store(i, 0, W[1][0]);
+            store(i, 1, W[1][1]);
+        }
+        if (i + 1 <= ihi) {
+            const int form = fmg_form(ai, I, 1);
+            const FmgTaps ti = fmg_taps(form);
+#pragma unroll
+            for (int m = 0; m < 2; m++) {
+                double x;
+                if (form == FMG_LOW)
+                    x = fmg_sum(ti, W[1][m], W[2][m], W[3][m], W[0][m]);
+                else if (form == FMG_HIGH)
+                    x = fmg_sum(ti, W[3][m], W[0][m], W[1][m], W[2][m]);
+                else if (form == FMG_LIN)
+                    x = fmg_sum(ti, W[1][m], W[2][m], W[1][m], W[1][m]);
+                else
+                    x = fmg_sum(ti, W[0][m], W[1][m], W[2][m], W[3][m]);
+                store(i + 1, m, x);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < 2; m++) {
+            W[0][m] = W[1][m];
+            W[1][m] = W[2][m];
+            W[2][m] = W[3][m];
+        }
+    }
+}
+
+void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s)
+{
+    if (gf.N != 2 * gc.N - 1 || gc.N < 3)
+        return;
+    const int gx = (gf.N + WAVE - 1) / WAVE, gy = (gf.N + FMG_TJ - 1) / FMG_TJ;
+    int chunk = 16; /* three coarse planes of lead-in per chunk; shorter chunks while the grid is small */
+    while (chunk > 2 && (long long)gx * gy * ((gc.N + chunk - 1) / chunk) < 1024)
+        chunk /= 2;
+    const dim3 grid(gx, gy, (gc.N + chunk - 1) / chunk), block(WAVE, 4, 1);
+    const int mode = bc_mode(bc);
+    if (mode == BC_REFLECT)
+        hipLaunchKernelGGL(fmg_interp_kernel<BC_REFLECT>, grid, block, 0, s, gc, uc, gf, uf, bc, chunk);
+    else if (mode == BC_WRAP)
+        hipLaunchKernelGGL(fmg_interp_kernel<BC_WRAP>, grid, block, 0, s, gc, uc, gf, uf, bc, chunk);
+    else
+        hipLaunchKernelGGL(fmg_interp_kernel<BC_PLAIN>, grid, block, 0, s, gc, uc, gf, uf, bc, chunk);
+}
+
+/* d = u at every Dirichlet point of a (single-domain) level -- a face point of a non-periodic axis whose face is not a
+ * Neumann face: the right-hand side of the identity rows of the direct solve (mg3d_fmg_solve) */
+__global__ void __launch_bounds__(256) dirichlet_rhs_kernel(Geom g, const double *__restrict__ u, double *__restrict__ d,
+                                                            int bc)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    if (k >= N || j >= N)
+        return;
+    const int x[3] = {i, j, k};
+    bool dir = false;
+    for (int ax = 0; ax < 3; ax++)
+        dir = dir || (!(bc >> ax & 1) && ((x[ax] == 0 && !bc_ref_lo(bc, ax)) || (x[ax] == N - 1 && !bc_ref_hi(bc, ax))));
+    if (dir)
+        d[gidx(g, i, j, k)] = u[gidx(g, i, j, k)];
+}
+
+void k_dirichlet_rhs(const Geom &g, const double *u, double *d, int bc, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(dirichlet_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, u, d, bc);
+}
+
 /* ------------------------------------------------------------- coarsest level
  * Periodic axes: the right-hand side of the direct solve (mg3d_coarse_matrix_periodic): d at every point, except 0 in the identity
  * rows of the duplicates and of the pinned point (0,0,0) -- so a duplicate's d is never read, and those rows' solution
