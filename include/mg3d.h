@@ -76,7 +76,8 @@ int mg3d_ctx_set_lu(mg3d_ctx *ctx, const double *LU);
  * per level of spacing h:  smoother  v = (1/dg) * (sum of the six neighbours - h^2 d),  dg = 6 + sigma*h^2;
  * residual  d - (sum - dg*v)/h^2;  coarse matrix diagonal -dg/h^2 (mg3d_coarse_matrix_shift).  The default sigma = 0 is
  * the reference's operator, bit for bit.  Implicit diffusion (backward Euler, u1 - dt*Delta u1 = u0): sigma = 1/dt with
- * the right-hand side d = -u0/dt.  A negative, NaN or infinite sigma is MG3D_ERR_ARG and changes nothing.  Otherwise a
+ * the right-hand side d = -u0/dt -- mg3d_step_advance below does it, and the theta-scheme, on the device.
+ * A negative, NaN or infinite sigma is MG3D_ERR_ARG and changes nothing.  Otherwise a
  * cycle that has run ahead is finished first; a new sigma rebuilds a factor of mg3d_ctx_build_coarse (same h_coarse) and
  * drops one installed by mg3d_ctx_set_lu or mg3d_es_setup (the next cycle returns MG3D_ERR_STATE until a factor is set
  * again); a call that leaves sigma as it is changes nothing.  mg3d_es_* refuse a context with sigma != 0 (MG3D_ERR_STATE);
@@ -317,6 +318,60 @@ int mg3d_fmg_initialize(mg3d_ctx *ctx);
  * fp32 and mg3d_host_* forms have no such entry points. */
 int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level);
 int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm /* may be NULL */);
+
+/* Implicit time stepping on the device: the theta-scheme for
+ *     u_t = div(eps grad u) - kappa u + s        (kappa >= 0 constant; s an optional source held on the device)
+ * with the context's operator (constant or eps) and boundaries: Dirichlet values are whatever the Dirichlet points of u
+ * hold -- fixed in time, never written --, periodic axes as set, Neumann faces homogeneous.  A prescribed flux is folded
+ * into the source by the caller: s = -fold_flux(-s) (mg3d_neumann_fold_flux subtracts 2 a g / h from what it is given).
+ * With L the operator at sigma = 0, one step of length dt, 1/2 <= theta <= 1 (1: backward Euler, 1/2: Crank-Nicolson), is
+ *     (u1 - u0)/dt = theta (L - kappa) u1 + (1 - theta)(L - kappa) u0 + s
+ * and, divided by theta, the system  A_sigma u1 = d  of the context's operator at sigma = kappa + 1/(theta*dt), where
+ *     q    = A_sigma u0 = invHsq*(S - dg*u0)     the expression, operand order and neighbour order of mg3d_pcg_solve's A p
+ *     d[p] = -((a*u0[p] + c1*q[p]) + b*s[p])     at every unknown (the set mg3d_residual counts)
+ *     c0 = 1.0/(theta*dt);  a = c0/theta;  c1 = (1.0 - theta)/theta;  b = 1.0/theta      (host, double, in this order)
+ * (L u0 - kappa u0 = q + c0 u0 and 1 + c1 = 1/theta).  Without a source the b*s term is absent, d = -(a*u0 + c1*q); with
+ * theta == 1.0 exactly c1 = 0 and q is not computed, d = -(a*u0 + b*s), or -(a*u0).  Uncontracted: tests/_step_ref.py
+ * restates d bit for bit.  d is written at the unknowns only: its Dirichlet points and periodic duplicates keep what they
+ * hold.  Nothing but the norms crosses to the host.
+ * mg3d_step_setup: dt > 0, 0.5 <= theta <= 1, kappa >= 0, all finite (and their sigma finite), otherwise MG3D_ERR_ARG and
+ *   nothing changes.  Sets the context's shift to kappa + 1/(theta*dt) as mg3d_ctx_set_shift does -- a cycle that has run
+ *   ahead is finished first, a factor of mg3d_ctx_build_coarse is rebuilt, one of mg3d_ctx_set_lu dropped -- and stores
+ *   dt, theta, kappa.  Call it again for another dt.
+ * mg3d_step_set_source: s of the finest level, a dense N^3 host array, uploaded into a field of the library's own that is
+ *   allocated on the first call and freed with the context (MG3D_ERR_ALLOC, nothing changed, when it does not fit); NULL
+ *   drops the source.  May be called between mg3d_step_advance calls, for a source that changes in time.  Values of s at
+ *   Dirichlet points and duplicates are never used.
+ * mg3d_step_advance: nsteps steps from u of the finest level.  Per step: a cycle that has run ahead is finished; d is
+ *   formed in one launch; the system is solved with u as it stands as the guess --
+ *     MG3D_STEP_VCYCLES  cycles >= 1 V-cycles, exactly mg3d_vcycles(cycles), schedules included; the step's norm is the last
+ *                        cycle's; rtol is ignored; iterations and converged stay 0
+ *     MG3D_STEP_WPCG     mg3d_wpcg_solve(rtol, 0, cycles): at most `cycles` iterations; the step's norm is its r_norm;
+ *                        iterations accumulates over the steps, converged is 1 only if every step converged (sigma > 0:
+ *                        the operator is never singular)
+ *   norms, if not NULL, receives one norm per step; time is steps*dt of this call.
+ *   out: u of the finest level holds u at the new time, its Dirichlet points the caller's bit for bit, its periodic
+ *        duplicates equal to their sources; d of the finest level holds the last step's right-hand side; the lower levels
+ *        and r are unspecified.  The context is usable as before: mg3d_vcycles(1) afterwards gives, bit for bit, what a
+ *        context gives that had this u, d and sigma set.
+ *   MG3D_ERR_ARG, nothing changed: nsteps < 0, a method that is neither, cycles < 1, MG3D_STEP_WPCG with an rtol that is
+ *   negative or not finite.  MG3D_ERR_STATE, nothing changed: mg3d_step_setup was never called; the context's sigma is no
+ *   longer the one it set (mg3d_ctx_set_shift since); no coarse factor.  A context after mg3d_es_setup is refused through
+ *   these three: mg3d_es_setup needs sigma = 0, and the shift of mg3d_step_setup, which is > 0, drops its factor.
+ *   nsteps = 0 changes nothing.  A HIP error (or MG3D_ERR_ALLOC from the first MG3D_STEP_WPCG step's work vectors) is returned as it is;
+ *   info->steps says how many steps completed.
+ * The slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms have no stepper: single domain only. */
+enum { MG3D_STEP_VCYCLES = 0, MG3D_STEP_WPCG = 1 };
+typedef struct mg3d_step_info {
+    int steps;       /* steps completed by this call */
+    int iterations;  /* MG3D_STEP_WPCG: iterations over all steps */
+    int converged;   /* MG3D_STEP_WPCG: 1 when every step reached rtol */
+    double time;     /* steps * dt */
+} mg3d_step_info;
+int mg3d_step_setup(mg3d_ctx *ctx, double dt, double theta, double kappa);
+int mg3d_step_set_source(mg3d_ctx *ctx, const double *s /* finest level, dense N^3 host; NULL: no source */);
+int mg3d_step_advance(mg3d_ctx *ctx, int nsteps, int method, int cycles, double rtol,
+                      double *norms /* NULL or nsteps entries */, mg3d_step_info *info /* may be NULL */);
 /* setupBoundaryConditions (mg_3d.h:1147-1239) on a device-resident field */
 int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
 
@@ -373,6 +428,8 @@ enum {
     MG3D_K_SWEEP1_RESTRICT, /* carried cycles: the last pre-smoothing pass + residual + restriction */
     MG3D_K_LEG_DOWN,        /* one launch per leg: the pre-smoothing passes + residual + restriction */
     MG3D_K_LEG_UP,          /* one launch per leg: prolongation + the post-smoothing passes (+ half of the norm) */
+    MG3D_K_PCG_APPLY,       /* mg3d_pcg_solve / mg3d_wpcg_solve: q = A p and its dot (the fold of the partial sums included) */
+    MG3D_K_STEP_RHS,        /* mg3d_step_advance: the right-hand side of a step */
     MG3D_NUM_KERNELS
 };
 const char *mg3d_kernel_name(int kernel);

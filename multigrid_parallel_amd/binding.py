@@ -73,6 +73,9 @@ SIGNATURES = {
     "mg3d_fmg_initialize": (C.c_int, [C.c_void_p]),
     "mg3d_fmg_interpolate": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_fmg_solve": (C.c_int, [C.c_void_p, C.c_int, dp]),
+    "mg3d_step_setup": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "mg3d_step_set_source": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_step_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_void_p]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -186,6 +189,14 @@ class WpcgInfo(C.Structure):
     """mg3d_wpcg_info: what mg3d_wpcg_solve reports"""
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("r0_norm", C.c_double), ("r_norm", C.c_double),
                 ("singular", C.c_int), ("rhs_mean", C.c_double)]
+
+
+class StepInfo(C.Structure):
+    """mg3d_step_info: what mg3d_step_advance reports"""
+    _fields_ = [("steps", C.c_int), ("iterations", C.c_int), ("converged", C.c_int), ("time", C.c_double)]
+
+
+STEP_METHODS = {"vcycles": 0, "wpcg": 1}  # MG3D_STEP_VCYCLES, MG3D_STEP_WPCG
 
 
 class EsParams(C.Structure):
@@ -558,6 +569,39 @@ class Solver:
         nrm = C.c_double(0)
         check(self.L.mg3d_fmg_solve(self._h, int(cycles), C.byref(nrm)))
         return nrm.value
+
+    # -- implicit time stepping, csrc/mg3d_step.hip
+    def step_setup(self, dt, theta=1.0, kappa=0.0):
+        """mg3d_step_setup: the theta-scheme (1: backward Euler, 0.5: Crank-Nicolson) for
+        u_t = div(eps grad u) - kappa*u + s with steps of dt.  Sets the shift to kappa + 1/(theta*dt) as set_shift does."""
+        check(self.L.mg3d_step_setup(self._h, float(dt), float(theta), float(kappa)))
+
+    def step_set_source(self, s):
+        """mg3d_step_set_source: the source s of the finest level ((N, N, N) or flat float64), kept on the device; None
+        drops it.  May be called between step_advance calls."""
+        if s is None:
+            check(self.L.mg3d_step_set_source(self._h, None))
+            return
+        s = np.asarray(s)
+        if s.dtype != np.float64:
+            raise TypeError(f"step_set_source: need float64, got {s.dtype}")
+        if s.size != self.N ** 3 or s.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"step_set_source: need shape ({self.N},)*3 or ({self.N ** 3},), got {s.shape}")
+        check(self.L.mg3d_step_set_source(self._h, P(np.ascontiguousarray(s).reshape(-1))))
+
+    def step_advance(self, nsteps, cycles=2, method="vcycles", rtol=1e-8):
+        """mg3d_step_advance: nsteps steps from u of the finest level, entirely on the device; each step forms its
+        right-hand side in one launch and solves with `cycles` V-cycles (method "vcycles") or with wpcg_solve(rtol,
+        max_iters=cycles) (method "wpcg"), warm-started from the previous step.  Returns (one norm per step, info dict:
+        steps, iterations, converged, time)."""
+        if method not in STEP_METHODS:
+            raise ValueError(f"step_advance: method {method!r} (need one of {', '.join(STEP_METHODS)})")
+        norms = np.zeros(max(int(nsteps), 0))
+        info = StepInfo()
+        check(self.L.mg3d_step_advance(self._h, int(nsteps), STEP_METHODS[method], int(cycles), float(rtol), P(norms),
+                                       C.byref(info)))
+        return norms, {"steps": info.steps, "iterations": info.iterations, "converged": bool(info.converged),
+                       "time": info.time}
 
     # -- the mixed-boundary ("electrospray") problem, csrc/mg3d_es.hip
     def es_setup(self, params=None):

@@ -74,6 +74,13 @@ struct mg3d_ctx {
     /* mg3d_pcg_solve (mg3d_pcg.hip): four work vectors of the finest level in its padded layout -- z, r, p, q -- allocated
      * on first use, freed with the context.  During a solve the first two stand in for the level's u and d */
     double *pcg_v[4] = {nullptr, nullptr, nullptr, nullptr};
+    /* the time stepper (mg3d_step.hip): dt, theta, kappa of mg3d_step_setup and the shift it set -- a context whose sigma
+     * is no longer that one refuses to advance; the source of the finest level in its padded layout, allocated on first
+     * use and kept (step_has_src says whether it is in use), freed with the context */
+    bool step_set = false;
+    double step_dt = 0., step_theta = 0., step_kappa = 0., step_sigma = 0.;
+    double *step_src = nullptr;
+    bool step_has_src = false;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */
@@ -131,6 +138,15 @@ static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
 }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
+/* scoped event pair of the timers (mg3d_timing_enable): a stage of the reference's timing table on level l, or
+ * (kernel = true) one kernel launch, s a MG3D_K_* id; nothing is recorded while the timers are off (mg3d_ctx.hip) */
+struct StageScope {
+    mg3d_ctx *ctx;
+    mg3d_ctx::Pending p;
+    bool on;
+    StageScope(mg3d_ctx *c, int l, int s, bool kernel = false);
+    ~StageScope();
+};
 /* records a failure text for mg3d_last_error() and returns `code` */
 int mg3d_fail(int code, const char *fmt, ...);
 /* enqueue one V-cycle from level q of a (single-domain) context; squared norm of level q to sumsq[slot] */

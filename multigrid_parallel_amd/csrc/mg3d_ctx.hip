@@ -54,7 +54,8 @@ static const char *const kStageNames[MG3D_NUM_STAGES] = {"Smoother1",          "
 
 static const char *const kKernelNames[MG3D_NUM_KERNELS] = {"sweep4", "sweep2", "sweep2+residual", "residual",
                                                            "restrict", "prolong", "coarse_solve", "colour_pass",
-                                                           "sweep4+norm", "sweep1+restrict", "leg_down", "leg_up"};
+                                                           "sweep4+norm", "sweep1+restrict", "leg_down", "leg_up",
+                                                           "pcg_apply", "step_rhs"};
 
 extern "C" const char *mg3d_kernel_name(int k) { return (k >= 0 && k < MG3D_NUM_KERNELS) ? kKernelNames[k] : "?"; }
 
@@ -113,30 +114,25 @@ static void resolve_timers(mg3d_ctx *ctx)
  * timing: 1 every level, 2 the finest level, 3 the finest level's kernel scopes only (what bench.py's roofline needs: 8
  * marker packets per cycle instead of 24; each costs ~5 us of idle queue, 0.09 against 0.04 ms of a 3.3 ms cycle.  Binding
  * the pair to the dispatch itself, hipExtLaunchKernelGGL, measured the same 0.04 ms as the 8 markers: not kept), 4 + k
- * (k >= 0): as 3, but only every (k + 2)-th full cycle carries the markers (a sample of the timed region). */
-struct StageScope {
-    mg3d_ctx *ctx;
-    mg3d_ctx::Pending p;
-    bool on;
-    StageScope(mg3d_ctx *c, int l, int s, bool kernel = false) : ctx(c)
-    {
-        p.slot = kernel ? c->L * MG3D_NUM_STAGES + l * MG3D_NUM_KERNELS + s : l * MG3D_NUM_STAGES + s;
-        p.a = p.b = nullptr;
-        on = ctx->timing == 1 || (ctx->timing == 2 && l == ctx->L - 1) ||
-             (ctx->timing >= 3 && kernel && l == ctx->L - 1 && ctx->timing_phase == 0);
-        if (on && (p.a = take_event(ctx)))
-            (void)hipEventRecord(p.a, ctx->stream);
-    }
-    ~StageScope()
-    {
-        if (!on)
-            return;
-        if ((p.b = take_event(ctx)))
-            (void)hipEventRecord(p.b, ctx->stream);
-        ctx->pending.push_back(p);
-    }
-};
-
+ * (k >= 0): as 3, but only every (k + 2)-th full cycle carries the markers (a sample of the timed region).
+ * Declared in mg3d_ctx.h: mg3d_pcg.hip and mg3d_step.hip time a launch of theirs with it. */
+StageScope::StageScope(mg3d_ctx *c, int l, int s, bool kernel) : ctx(c)
+{
+    p.slot = kernel ? c->L * MG3D_NUM_STAGES + l * MG3D_NUM_KERNELS + s : l * MG3D_NUM_STAGES + s;
+    p.a = p.b = nullptr;
+    on = ctx->timing == 1 || (ctx->timing == 2 && l == ctx->L - 1) ||
+         (ctx->timing >= 3 && kernel && l == ctx->L - 1 && ctx->timing_phase == 0);
+    if (on && (p.a = take_event(ctx)))
+        (void)hipEventRecord(p.a, ctx->stream);
+}
+StageScope::~StageScope()
+{
+    if (!on)
+        return;
+    if ((p.b = take_event(ctx)))
+        (void)hipEventRecord(p.b, ctx->stream);
+    ctx->pending.push_back(p);
+}
 
 static void free_band(LuBand &b)
 {
@@ -180,6 +176,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
     for (double *v : ctx->pcg_v)
         if (v)
             (void)hipFree(v);
+    if (ctx->step_src)
+        (void)hipFree(ctx->step_src);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)

@@ -141,6 +141,12 @@ int k_wpcg_direction(const Geom &g, int bc, double *p, const double *z, const do
 int k_wpcg_center(const Geom &g, int bc, double *r, const double *wsum, double W, double *partials, double *rr_out,
                   hipStream_t s);
 double k_wpcg_weight_sum(const Geom &g, int bc);
+/* The right-hand side of one theta-step (mg3d_step_advance) on a single-domain level, at the unknowns only:
+ *   d = -((a*u0 + c1*q) + b*src),  q = A u0 as apply_dot forms it (e, op, sigma, bc);  src NULL: no b*src term
+ *   backward_euler: c1 = 0 and q is not computed -- d = -(a*u0 + b*src), a streaming pass
+ * Return value: 0, or -1 when the level has no launch shape (nothing launched) */
+int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
+               double a, double c1, double b, bool backward_euler, double *d, hipStream_t s);
 /* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo = -1,
                 int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);

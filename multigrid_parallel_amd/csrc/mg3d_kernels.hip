@@ -873,6 +873,119 @@ double k_wpcg_weight_sum(const Geom &g, int bc)
     return W;
 }
 
+/* ------------------------------------------------------------- time stepping
+ * The right-hand side of one theta-step of mg3d_step_advance (mg3d_step.hip, include/mg3d.h) from u0 = v, written at the
+ * unknowns only: Dirichlet points and periodic duplicates of d keep what they hold (nothing reads them).
+ *     q    = invHsq*(s - dg*v[p])                 pcg_apply_kernel's expression, operand and neighbour order
+ *     d[p] = -((a*v[p] + c1*q) + b*src[p])        src == NULL: d[p] = -(a*v[p] + c1*q)
+ * theta < 1: pcg_apply_kernel's column walk with one more operand and neither a sum nor partials.  src is a uniform
+ * branch: the six instantiations stay six.  Both launches take the grids of the passes they are modelled on (column_grid,
+ * pair_grid) as they are: the cap on blocks those keep for the partial sums means nothing here and does no harm. */
+template <bool COEF, int BC>
+__global__ void __launch_bounds__(256) step_rhs_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
+                                                       const double *__restrict__ src, double invHsq, double dg0, double a,
+                                                       double c1, double b, double *__restrict__ d, int bc, int chunk,
+                                                       int i_lo, int i_hi)
+{
+    Column c;
+    if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
+        return;
+    long long p = gidx(g, c.i0, c.j, c.k);
+    const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
+    double vb = v[pb], vh = v[p];
+    double eb = 0., eh = 0.;
+    if constexpr (COEF) {
+        eb = e[pb];
+        eh = e[p];
+    }
+    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+        const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
+        const double va = v[pa];
+        double ea = 0.;
+        if constexpr (COEF)
+            ea = e[pa];
+        double s, dg;
+        stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
+        const double q = invHsq * (s - dg * vh);
+        double t = a * vh + c1 * q;
+        if (src)
+            t = t + b * src[p];
+        d[p] = -t;
+        vb = vh;
+        vh = va;
+        if constexpr (COEF) {
+            eb = eh;
+            eh = ea;
+        }
+    }
+}
+
+/* theta == 1 (backward Euler): c1 = 0 and no stencil -- d[p] = -(a*v[p] + b*src[p]), or -(a*v[p]) without a source, as a
+ * streaming pass over the k-pairs; the member of a pair that is no unknown keeps the d that was loaded */
+__global__ void __launch_bounds__(256) step_rhs_be_kernel(Geom g, const double *__restrict__ v,
+                                                          const double *__restrict__ src, double a, double b,
+                                                          double *__restrict__ d, PairRange u, int chunk)
+{
+    PairWalk w;
+    if (!pair_walk(g, u, chunk, w))
+        return;
+    for (int t = 0; t < w.n; t++, w.p += g.plane) {
+        double2 dd = *reinterpret_cast<double2 *>(d + w.p);
+        const double2 vv = *reinterpret_cast<const double2 *>(v + w.p);
+        double2 x = make_double2(a * vv.x, a * vv.y);
+        if (src) {
+            const double2 ss = *reinterpret_cast<const double2 *>(src + w.p);
+            x.x = x.x + b * ss.x;
+            x.y = x.y + b * ss.y;
+        }
+        if (w.m0)
+            dd.x = -x.x;
+        if (w.m1)
+            dd.y = -x.y;
+        *reinterpret_cast<double2 *>(d + w.p) = dd;
+    }
+}
+
+int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
+               double a, double c1, double b, bool backward_euler, double *d, hipStream_t s)
+{
+    if (backward_euler) {
+        dim3 grid;
+        int chunk;
+        PairRange u;
+        if (!pair_grid(g, bc, grid, chunk, u))
+            return -1;
+        hipLaunchKernelGGL(step_rhs_be_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, u0, src, a, b, d, u, chunk);
+        return 0;
+    }
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
+        return -1;
+    int i_lo = -1, i_hi = -1;
+    if (!stencil_window(g, bc, i_lo, i_hi))
+        return 0;
+    int chunk;
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const double dg0 = e ? sigma * op.hSq : op.dg;
+#define MG3D_STEP_RHS(COEF, BC)                                                                                            \
+    hipLaunchKernelGGL((step_rhs_kernel<COEF, BC>), grid, block, 0, s, g, u0, e, src, op.invHsq, dg0, a, c1, b, d, bc, chunk, \
+                       i_lo, i_hi)
+    const int mode = bc_mode(bc);
+    if (e && mode == BC_REFLECT)
+        MG3D_STEP_RHS(true, BC_REFLECT);
+    else if (e && mode == BC_WRAP)
+        MG3D_STEP_RHS(true, BC_WRAP);
+    else if (e)
+        MG3D_STEP_RHS(true, BC_PLAIN);
+    else if (mode == BC_REFLECT)
+        MG3D_STEP_RHS(false, BC_REFLECT);
+    else if (mode == BC_WRAP)
+        MG3D_STEP_RHS(false, BC_WRAP);
+    else
+        MG3D_STEP_RHS(false, BC_PLAIN);
+#undef MG3D_STEP_RHS
+    return 0;
+}
+
 /* GetL2NormOfVector (mg_3d.h:783-792) over every point of a level, boundary included */
 __global__ void __launch_bounds__(256) sumsq_kernel(Geom g, const double *__restrict__ a,
                                                     double *__restrict__ partials)

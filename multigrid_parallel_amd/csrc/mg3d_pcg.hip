@@ -126,7 +126,10 @@ static int pcg_iterate(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, 
             HIPCHK(hipMemcpyAsync(p, z, top.elems * sizeof(double), hipMemcpyDeviceToDevice, s)); /* p = z */
         else
             k_pcg_direction(top.g, bc, p, z, rz, rz_old, s);
-        k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s);
+        {
+            StageScope kt(ctx, q, MG3D_K_PCG_APPLY, true);
+            k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s);
+        }
         k_pcg_update_norm(top.g, bc, x, r, p, qv, rz, sc + S_PAP, ctx->partials, sc + S_RR, s);
         CHK(pcg_launch_ok(name, "iteration"));
         HIPCHK(hipMemcpyAsync(ctx->h_sumsq + S_RZ, sc + S_RZ, (S_END - S_RZ) * sizeof(double), hipMemcpyDeviceToHost, s));
