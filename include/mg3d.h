@@ -169,6 +169,55 @@ int mg3d_sync(mg3d_ctx *ctx);
 /* raw device view of a level for callers that share device memory (tests, bench) */
 int mg3d_device_view(mg3d_ctx *ctx, int field, int level, void **dev_ptr, int *pitch_doubles, long *plane_doubles);
 
+/* Device arrays: the four data entry points for arrays that already live in the memory of the context's device -- a field,
+ * the stepper's source, eps.  Ordered on streams, not on the host; the library sees every write, so unlike
+ * mg3d_device_view nothing is switched off (no raw-pointer flag, the run-ahead schedules stay) and nothing dangles.
+ * mg3d_array describes a dense-INDEXED N x N x N array (N of the level, of the finest level for source and eps): element
+ * (i, j, k) is ptr[stride[0]*i + stride[1]*j + stride[2]*k], strides in ELEMENTS, in any order and with any gaps (a
+ * permuted or sliced tensor); the index is formed in 64 bits.  The library reads or writes exactly these N^3 elements and
+ * trusts the strides: they must stay inside the caller's allocation.
+ *   values   : MG3D_F64 stores the same bytes as the host form -- the field, every level of the injected eps, the source.
+ *              MG3D_F32 is widened exactly on the way in and rounded to nearest (even) on the way out.  On the way in a
+ *              stride may be 0 (a broadcast array); mg3d_download_device needs every stride >= 1, and overlap between the
+ *              elements of dst beyond that is the caller's business.  The row padding of the device layout is neither
+ *              written by an upload nor read by a download, as in the host forms.
+ *   errors   : MG3D_ERR_ARG, nothing changed: a NULL context, array or ptr, an unknown dtype, a negative stride, a zero
+ *              stride on download, a bad field or level, a ptr that hipPointerGetAttributes does not report as device memory
+ *              of the context's device (the device current when the context was created).
+ *   state    : exactly the host forms'.  mg3d_upload_device finishes a cycle that has run ahead and marks the field written
+ *              as mg3d_upload does; mg3d_download_device only reads, as mg3d_download.
+ *   ordering : `stream` is the hipStream_t on which the caller produced src or will consume dst; NULL is the null stream.
+ *              The call makes the context's stream wait for an event recorded on `stream`, enqueues its kernel on the
+ *              context's stream, and makes `stream` wait for an event recorded behind the kernel.  On return the caller may
+ *              enqueue on `stream` anything that reads dst, and may overwrite or free src on `stream` (the discipline of a
+ *              stream-ordered caching allocator); work on OTHER streams of the caller is not ordered.  mg3d_upload_device,
+ *              mg3d_download_device and mg3d_step_set_source_device do not synchronise with the host.  The two events are
+ *              created once per context and freed with it.
+ * mg3d_step_set_source_device: mg3d_step_set_source from a device array -- the source field is allocated on first use
+ *   (MG3D_ERR_ALLOC, nothing changed, when it does not fit) and written behind any step still in flight; NULL drops the
+ *   source.  May be called between mg3d_step_advance calls; values at Dirichlet points and periodic duplicates are never used.
+ * mg3d_ctx_set_coefficient_device: mg3d_ctx_set_coefficient from a device array, the same contract in the same order.
+ *   The array is checked on the device before anything changes, as given (F32 widened), periodic duplicates skipped: an
+ *   entry that is not finite and > 0 is MG3D_ERR_ARG, the message names the LOWEST dense index (i*N + j)*N + k among them and
+ *   its value.  Otherwise a cycle that has run ahead is finished, eps of the finest level is written, its duplicates
+ *   refreshed, the coarser levels injected, level 0's eps read back for the coarse matrix (the subsample the host form
+ *   takes, bit for bit) and the coarse factor rebuilt or dropped.  This call DOES synchronise with the host, twice: for the
+ *   result of the check and for level 0's eps; when it returns the array has been read.  NULL: the constant operator again.
+ * kernel timer: MG3D_K_PACK counts the launches that read or write a caller's array.
+ * Out of scope: the slab form (mg3d_dist_*), the fp32 solver (mg3d32_*) and the mg3d_host_* forms take host arrays only;
+ * half precision and bf16; a persistent zero-copy alias of a field (the run-ahead schedules swap the buffers behind u and
+ * d, an alias cannot stay valid).  mg3d_device_view is unchanged. */
+enum { MG3D_F64 = 0, MG3D_F32 = 1 };
+typedef struct mg3d_array {
+    void *ptr;           /* element (0,0,0), device memory of the context's device */
+    int dtype;           /* MG3D_F64 / MG3D_F32 */
+    long long stride[3]; /* in ELEMENTS, for i, j, k */
+} mg3d_array;
+int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *src, void *stream);
+int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *dst, void *stream);
+int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s /* NULL: no source */, void *stream);
+int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps /* NULL: constant operator */, void *stream);
+
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)
  *                   postSmoother (post=1, mg_3d.h:711-781: iters x black,red)
@@ -430,6 +479,7 @@ enum {
     MG3D_K_LEG_UP,          /* one launch per leg: prolongation + the post-smoothing passes (+ half of the norm) */
     MG3D_K_PCG_APPLY,       /* mg3d_pcg_solve / mg3d_wpcg_solve: q = A p and its dot (the fold of the partial sums included) */
     MG3D_K_STEP_RHS,        /* mg3d_step_advance: the right-hand side of a step */
+    MG3D_K_PACK,            /* device arrays (mg3d_*_device): the pack and unpack launches */
     MG3D_NUM_KERNELS
 };
 const char *mg3d_kernel_name(int kernel);

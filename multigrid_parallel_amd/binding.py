@@ -29,6 +29,17 @@ def lib_path():
 
 _lib = None
 
+MG3D_F64, MG3D_F32 = 0, 1  # mg3d_array.dtype
+
+
+class mg3d_array(C.Structure):
+    """mg3d_array: a dense-indexed N x N x N array in device memory -- element (i, j, k) is
+    ptr[stride[0]*i + stride[1]*j + stride[2]*k], strides in elements.  array_desc() builds one from a torch tensor."""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("stride", C.c_longlong * 3)]
+
+
+_ap = C.POINTER(mg3d_array)
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/mg3d.h
 SIGNATURES = {
     "mg3d_last_error": (C.c_char_p, []),
@@ -58,6 +69,10 @@ SIGNATURES = {
     "mg3d_sync": (C.c_int, [C.c_void_p]),
     "mg3d_device_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
                                    C.POINTER(C.c_long)]),
+    "mg3d_upload_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ap, C.c_void_p]),
+    "mg3d_download_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ap, C.c_void_p]),
+    "mg3d_step_set_source_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_ctx_set_coefficient_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
     "mg3d_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mg3d_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_smooth_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, dp]),
@@ -240,6 +255,35 @@ def P(a):
 def check(rc):
     if rc != 0:
         raise Mg3dError(rc, lib().mg3d_last_error().decode(errors="replace"))
+
+
+def array_desc(t, writable=False, shape=None):
+    """The mg3d_array of a 3-D float64 / float32 torch tensor: data_ptr(), the dtype code and stride() in elements --
+    any view is described as it is, nothing is copied.  TypeError for anything else; ValueError for a shape other than
+    `shape` (when given) and, with writable=True, for a zero stride (an expanded tensor cannot be written).  The tensor
+    must stay alive until the call that takes the descriptor has returned.  torch is imported here, not with the package."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"array_desc: need a torch.Tensor, got {type(t).__name__}")
+    if t.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"array_desc: need float64 or float32, got {t.dtype}")
+    if t.dim() != 3:
+        raise TypeError(f"array_desc: need a 3-D tensor, got {t.dim()} dimensions")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"array_desc: need shape {tuple(shape)}, got {tuple(t.shape)}")
+    st = t.stride()
+    if writable and any(v == 0 for v in st):
+        raise ValueError(f"array_desc: a tensor that is written needs every stride >= 1, got {tuple(st)}")
+    return mg3d_array(t.data_ptr(), MG3D_F64 if t.dtype == torch.float64 else MG3D_F32, (C.c_longlong * 3)(*st))
+
+
+def _device_args(t, who, shape, writable=False):
+    """descriptor and stream handle of a GPU tensor for the mg3d_*_device entry points"""
+    import torch
+    a = array_desc(t, writable=writable, shape=shape)
+    if not t.is_cuda:
+        raise ValueError(f"{who}: need a tensor on the GPU, got device {t.device}")
+    return a, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 class Solver:
@@ -486,6 +530,48 @@ class Solver:
 
     def sync(self):
         check(self.L.mg3d_sync(self._h))
+
+    # -- data in device memory: torch tensors on the context's GPU, float64 or float32, any view (include/mg3d.h, "Device
+    # arrays").  Ordered on torch's current stream of the tensor's device, no host synchronisation in the first three.
+    def upload_tensor(self, field, level, t):
+        """mg3d_upload_device: the (n, n, n) tensor t into a field of a level; strides of 0 (expand) are fine.  When the
+        call returns t may be overwritten or freed on the current stream."""
+        n = self.level_n(level)
+        a, stream = _device_args(t, "upload_tensor", (n, n, n))
+        check(self.L.mg3d_upload_device(self._h, field, level, C.byref(a), stream))
+
+    def download_tensor(self, field, level, out=None, dtype=None):
+        """mg3d_download_device: a field of a level into `out` (any writable (n, n, n) view on the GPU) or into a new
+        contiguous tensor of `dtype` (default torch.float64) on the context's device; float32 rounds to nearest.  Work
+        enqueued on the current stream afterwards sees the values."""
+        import torch
+        n = self.level_n(level)
+        if out is None:
+            if n <= 0:
+                raise ValueError(f"download_tensor: bad level {level}")
+            out = torch.empty((n, n, n), dtype=torch.float64 if dtype is None else dtype,
+                              device=torch.device("cuda", torch.cuda.current_device()))
+        a, stream = _device_args(out, "download_tensor", (n, n, n), writable=True)
+        check(self.L.mg3d_download_device(self._h, field, level, C.byref(a), stream))
+        return out
+
+    def step_set_source_tensor(self, t):
+        """mg3d_step_set_source_device: step_set_source from an (N, N, N) tensor on the GPU, no host copy and no host
+        synchronisation -- for a source recomputed on the device between step_advance calls.  None drops the source."""
+        if t is None:
+            check(self.L.mg3d_step_set_source_device(self._h, None, None))
+            return
+        a, stream = _device_args(t, "step_set_source_tensor", (self.N,) * 3)
+        check(self.L.mg3d_step_set_source_device(self._h, C.byref(a), stream))
+
+    def set_coefficient_tensor(self, t):
+        """mg3d_ctx_set_coefficient_device: set_coefficient from an (N, N, N) tensor on the GPU; checked on the device
+        (Mg3dError code 1 names the lowest bad dense index), synchronises with the host.  None: the constant operator."""
+        if t is None:
+            check(self.L.mg3d_ctx_set_coefficient_device(self._h, None, None))
+            return
+        a, stream = _device_args(t, "set_coefficient_tensor", (self.N,) * 3)
+        check(self.L.mg3d_ctx_set_coefficient_device(self._h, C.byref(a), stream))
 
     # -- operators
     def smooth(self, level, post, iters):

@@ -81,6 +81,12 @@ struct mg3d_ctx {
     double step_dt = 0., step_theta = 0., step_kappa = 0., step_sigma = 0.;
     double *step_src = nullptr;
     bool step_has_src = false;
+    /* device arrays (mg3d_*_device): the device that was current when the context was created -- a caller's array must
+     * live there --, the two events of the stream join (io_ev[0] recorded on the caller's stream, io_ev[1] on the
+     * context's; created on first use, freed with the context) and the two 64-bit results of k_coef_check on the device */
+    int device = 0;
+    hipEvent_t io_ev[2] = {nullptr, nullptr};
+    unsigned long long *io_chk = nullptr;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */
@@ -162,5 +168,12 @@ bool mg3d_can_legs(const mg3d_ctx *ctx, int q);
 /* carried state -> the finished cycle's own u; a no-op (MG3D_OK) otherwise.  An error leaves the carried state in place. */
 int mg3d_drop_carry(mg3d_ctx *ctx);
 int mg3d_drop_carry_keep(mg3d_ctx *ctx); /* the same without clearing red_tail: mg3d_vcycle(s) themselves */
+/* device arrays (mg3d_ctx.hip; mg3d_step.hip uses them for the source).  mg3d_array_check: MG3D_ERR_ARG unless `a` is a
+ * usable descriptor of device memory of the context's device (`writable`: every stride >= 1).  mg3d_stream_join: the
+ * two-way join of the caller's stream with the context's -- out = false, before the kernel: the context's stream waits for
+ * what the caller's stream holds now; out = true, behind it: the caller's stream waits for what the context's holds now.
+ * No host synchronisation. */
+int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who);
+int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *who);
 
 #endif

@@ -55,7 +55,7 @@ static const char *const kStageNames[MG3D_NUM_STAGES] = {"Smoother1",          "
 static const char *const kKernelNames[MG3D_NUM_KERNELS] = {"sweep4", "sweep2", "sweep2+residual", "residual",
                                                            "restrict", "prolong", "coarse_solve", "colour_pass",
                                                            "sweep4+norm", "sweep1+restrict", "leg_down", "leg_up",
-                                                           "pcg_apply", "step_rhs"};
+                                                           "pcg_apply", "step_rhs", "pack"};
 
 extern "C" const char *mg3d_kernel_name(int k) { return (k >= 0 && k < MG3D_NUM_KERNELS) ? kKernelNames[k] : "?"; }
 
@@ -178,6 +178,11 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
             (void)hipFree(v);
     if (ctx->step_src)
         (void)hipFree(ctx->step_src);
+    if (ctx->io_chk)
+        (void)hipFree(ctx->io_chk);
+    for (hipEvent_t e : ctx->io_ev)
+        if (e)
+            (void)hipEventDestroy(e);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)
@@ -292,6 +297,8 @@ static mg3d_ctx *ctx_new(int L, int iters)
     ctx->legs_state = ctx->legs_slot = ctx->legs_npa = 0;
     mg3d_options_init(&ctx->opt);
     ctx->raw_top = false;
+    if (hipGetDevice(&ctx->device) != hipSuccess)
+        ctx->device = 0;
     ctx->keep_r = false;
     if (const char *e = getenv("MG3D_KEEP_R"))
         ctx->keep_r = e[0] == '1';
@@ -709,6 +716,27 @@ static void free_eps(mg3d_ctx *ctx)
     ctx->eps0.clear();
 }
 
+/* eps of every level in the padded layout, unless the context has them already */
+static int alloc_eps(mg3d_ctx *ctx)
+{
+    if (!ctx->eps.empty())
+        return MG3D_OK;
+    const int L = ctx->L;
+    std::vector<double *> e(L, nullptr);
+    for (int l = 0; l < L; l++) {
+        const hipError_t rc = hipMalloc(&e[l], ctx->lv[l].elems * sizeof(double));
+        if (rc == hipSuccess)
+            continue;
+        for (double *q : e)
+            if (q)
+                (void)hipFree(q);
+        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_coefficient: hipMalloc: %s",
+                    hipGetErrorString(rc));
+    }
+    ctx->eps = e;
+    return MG3D_OK;
+}
+
 /* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_kernels.hip) on every level: eps of the finest level
  * as given, of each coarser one by injection.  The array is checked before anything changes; then, as for a new sigma, a
  * cycle that has run ahead is finished with the operator it started with and the coarse factor is rebuilt or dropped.
@@ -739,20 +767,7 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
         free_eps(ctx);
         return operator_changed(ctx);
     }
-    if (ctx->eps.empty()) {
-        std::vector<double *> e(L, nullptr);
-        for (int l = 0; l < L; l++) {
-            const hipError_t rc = hipMalloc(&e[l], ctx->lv[l].elems * sizeof(double));
-            if (rc == hipSuccess)
-                continue;
-            for (double *q : e)
-                if (q)
-                    (void)hipFree(q);
-            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_coefficient: hipMalloc: %s",
-                        hipGetErrorString(rc));
-        }
-        ctx->eps = e;
-    }
+    CHK(alloc_eps(ctx));
     HIPCHK(hipMemcpy2DAsync(ctx->eps[L - 1], top.g.pitch * sizeof(double), eps, N * sizeof(double), N * sizeof(double),
                             (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
     k_per_refresh(top.g, ctx->eps[L - 1], ax, ctx->stream);
@@ -770,6 +785,110 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
             for (int k = 0; k < N0; k++)
                 ctx->eps0[((size_t)i * N0 + j) * N0 + k] =
                     eps[((long long)src(i * st, 1) * N + src(j * st, 2)) * N + src(k * st, 4)];
+    return operator_changed(ctx);
+}
+
+/* Device arrays (mg3d_array, include/mg3d.h): the descriptor checks and the stream join of every mg3d_*_device entry point. */
+int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who)
+{
+    if (!a || !a->ptr)
+        return fail(MG3D_ERR_ARG, "%s: NULL array", who);
+    if (a->dtype != MG3D_F64 && a->dtype != MG3D_F32)
+        return fail(MG3D_ERR_ARG, "%s: dtype %d (MG3D_F64 or MG3D_F32)", who, a->dtype);
+    for (int ax = 0; ax < 3; ax++)
+        if (a->stride[ax] < (writable ? 1 : 0))
+            return fail(MG3D_ERR_ARG, "%s: stride[%d] = %lld (%s)", who, ax, a->stride[ax],
+                        writable ? "an array that is written needs every stride >= 1" : "a stride must be >= 0");
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, a->ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* (an unknown pointer is the caller's error, not a launch failure of the next kernel) */
+        return fail(MG3D_ERR_ARG, "%s: %p is not device memory (%s)", who, a->ptr, hipGetErrorString(e));
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != ctx->device)
+        return fail(MG3D_ERR_ARG, "%s: %p is not device memory of device %d (memory type %d, device %d)", who, a->ptr,
+                    ctx->device, (int)at.type, at.device);
+    return MG3D_OK;
+}
+
+int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *who)
+{
+    hipEvent_t &ev = ctx->io_ev[out ? 1 : 0];
+    hipError_t e = hipSuccess;
+    if (!ev)
+        e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = hipEventRecord(ev, out ? ctx->stream : caller);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(out ? caller : ctx->stream, ev, 0);
+    if (e != hipSuccess)
+        return fail(MG3D_ERR_HIP, "%s: joining the caller's stream: %s", who, hipGetErrorString(e));
+    return MG3D_OK;
+}
+
+/* mg3d_ctx_set_coefficient from a device array, step for step: the check (a launch that reads the array as given; its two
+ * integers cross to the host), then the carried cycle, the pack into the finest level's eps, the duplicates, the
+ * injections; level 0's eps comes back from the device for the coarse matrix -- the injections of the refreshed top level
+ * are the subsample the host form takes.  Two host synchronisations; behind the second one the array has been read, so the
+ * caller's stream needs no event of ours. */
+extern "C" int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps, void *stream)
+{
+    static const char who[] = "mg3d_ctx_set_coefficient_device";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!eps)
+        return mg3d_ctx_set_coefficient(ctx, nullptr);
+    CHK(mg3d_array_check(ctx, eps, false, who));
+    const int L = ctx->L;
+    const Level &top = ctx->lv[L - 1];
+    const int N = top.g.N;
+    const int ax = ctx->periodic;
+    if (!ctx->io_chk) {
+        const hipError_t rc = hipMalloc(&ctx->io_chk, 2 * sizeof(unsigned long long));
+        if (rc != hipSuccess) {
+            ctx->io_chk = nullptr;
+            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
+        }
+    }
+    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
+    unsigned long long chk[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->io_chk + 1, 0xff, sizeof(unsigned long long), ctx->stream));
+    k_coef_check(top.g, *eps, ax, ctx->io_chk, ctx->stream);
+    HIPCHK(hipMemcpyAsync(chk, ctx->io_chk, sizeof chk, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
+    if (chk[0] != 0) {
+        const long long p = (long long)chk[1];
+        const long long off = eps->stride[0] * (p / ((long long)N * N)) + eps->stride[1] * ((p / N) % N) + eps->stride[2] * (p % N);
+        double v = 0.;
+        float v32 = 0.f;
+        if (eps->dtype == MG3D_F32) {
+            HIPCHK(hipMemcpy(&v32, (const float *)eps->ptr + off, sizeof v32, hipMemcpyDeviceToHost));
+            v = (double)v32;
+        } else {
+            HIPCHK(hipMemcpy(&v, (const double *)eps->ptr + off, sizeof v, hipMemcpyDeviceToHost));
+        }
+        return fail(MG3D_ERR_ARG, "%s: eps[%lld] = %g (every entry must be finite and > 0; %llu entries are not)", who, p, v,
+                    chk[0]);
+    }
+    CHK(mg3d_drop_carry(ctx));
+    CHK(alloc_eps(ctx));
+    {
+        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
+        k_pack(top.g, ctx->eps[L - 1], *eps, ctx->stream);
+    }
+    k_per_refresh(top.g, ctx->eps[L - 1], ax, ctx->stream);
+    for (int l = L - 1; l >= 1; l--)
+        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
+    const Level &l0 = ctx->lv[0];
+    const int N0 = l0.g.N;
+    ctx->eps0.resize((size_t)N0 * N0 * N0);
+    HIPCHK(hipMemcpy2DAsync(ctx->eps0.data(), N0 * sizeof(double), ctx->eps[0], l0.g.pitch * sizeof(double), N0 * sizeof(double),
+                            (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
     return operator_changed(ctx);
 }
 
@@ -933,6 +1052,41 @@ extern "C" int mg3d_download(mg3d_ctx *ctx, int field, int level, double *host)
                             (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MG3D_OK;
+}
+
+/* The device-array forms: the arguments are checked before anything happens, then the carried state is treated as in the
+ * host form, and the kernel runs on the context's stream between the two halves of the join -- no host synchronisation. */
+extern "C" int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *src, void *stream)
+{
+    static const char who[] = "mg3d_upload_device";
+    CHK(check_field_level(ctx, field, level, who));
+    CHK(mg3d_array_check(ctx, src, false, who));
+    CHK(mg3d_drop_carry(ctx));
+    const Level &l = ctx->lv[level];
+    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
+    {
+        StageScope kt(ctx, level, MG3D_K_PACK, true);
+        k_pack(l.g, l.f[field], *src, ctx->stream);
+    }
+    mg3d_ctx_touched(ctx, field, level);
+    CHK(launch_ok(who));
+    return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
+}
+
+extern "C" int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *dst, void *stream)
+{
+    static const char who[] = "mg3d_download_device";
+    CHK(check_field_level(ctx, field, level, who));
+    CHK(mg3d_array_check(ctx, dst, true, who));
+    CHK(mg3d_drop_carry_keep(ctx)); /* (reads only, as mg3d_download) */
+    const Level &l = ctx->lv[level];
+    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who)); /* (what the caller's stream still does with dst) */
+    {
+        StageScope kt(ctx, level, MG3D_K_PACK, true);
+        k_unpack(l.g, l.f[field], *dst, ctx->stream);
+    }
+    CHK(launch_ok(who));
+    return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
 }
 
 extern "C" int mg3d_zero(mg3d_ctx *ctx, int field, int level)

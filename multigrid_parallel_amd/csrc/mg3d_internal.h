@@ -331,6 +331,18 @@ void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, 
 void k_dirichlet_rhs(const Geom &g, const double *u, double *d, int bc, hipStream_t s);
 /* zeros on the faces of a single-domain level given as a MG3D_NEUMANN_* mask */
 void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);
+/* device arrays (mg3d_array, include/mg3d.h; single-domain levels): element (i,j,k) of the caller's array is
+ * ptr[stride[0]*i + stride[1]*j + stride[2]*k] in 64-bit arithmetic, float or double; the walk is the level-wide one, k
+ * fastest across the wave, so stride[2] == 1 is coalesced on both sides.
+ * k_pack: v[i,j,k] = (double)a[i,j,k] at the N^3 points -- the row padding of v is never written.
+ * k_unpack: a[i,j,k] = v[i,j,k], rounded to nearest for float -- the row padding of v is never read.
+ * k_coef_check: out[0] += the number of entries of a that are not finite and > 0, out[1] = min(out[1], the lowest dense
+ * index (i*N + j)*N + k among them); the duplicates of the periodic axes (bits 0..2 of bc) are skipped.  Folded per block,
+ * then one 64-bit atomic add and one atomic min per block that found any: integers, no order to depend on.  The caller sets
+ * out = {0, ~0} first. */
+void k_pack(const Geom &g, double *v, const mg3d_array &a, hipStream_t s);
+void k_unpack(const Geom &g, const double *v, const mg3d_array &a, hipStream_t s);
+void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

@@ -1719,6 +1719,106 @@ void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s)
     hipLaunchKernelGGL(zero_faces_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, v, faces);
 }
 
+/* ------------------------------------------------------------- device arrays
+ * A caller's N^3 array in device memory (mg3d_array: float or double, any element strides) into and out of a level's padded
+ * layout.  One thread per point, k across the wave: with a k stride of 1 both sides move whole rows; any other stride is
+ * served as it comes.  The strided index is 64-bit.  Only the N points of a row are touched on the padded side. */
+template <class T>
+__global__ void __launch_bounds__(256) pack_kernel(Geom g, double *__restrict__ v, const T *__restrict__ a, long long si,
+                                                   long long sj, long long sk)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    if (k >= g.N || j >= g.N)
+        return;
+    v[gidx(g, i, j, k)] = (double)a[si * i + sj * j + sk * k];
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) unpack_kernel(Geom g, const double *__restrict__ v, T *__restrict__ a, long long si,
+                                                     long long sj, long long sk)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    if (k >= g.N || j >= g.N)
+        return;
+    a[si * i + sj * j + sk * k] = (T)v[gidx(g, i, j, k)]; /* (float: round to nearest even) */
+}
+
+/* A wave is one row of 64 k: its bad entries as a ballot, the lowest bad lane is the lowest dense index of the row; the
+ * block's four rows meet in LDS and thread (0,0) issues the two atomics, only when the block found anything. */
+template <class T>
+__global__ void __launch_bounds__(256) coef_check_kernel(Geom g, const T *__restrict__ a, long long si, long long sj,
+                                                         long long sk, int axes, unsigned long long *__restrict__ out)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    bool bad = false;
+    if (k < N && j < N) {
+        const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
+        if (!dup) {
+            const double e = (double)a[si * i + sj * j + sk * k];
+            bad = !(e > 0.) || !(e <= 1.7976931348623157e308); /* NaN, <= 0, +inf */
+        }
+    }
+    __shared__ unsigned long long row_min[4];
+    __shared__ unsigned int row_cnt[4];
+    const unsigned long long m = __ballot(bad);
+    if (threadIdx.x == 0) {
+        row_cnt[threadIdx.y] = (unsigned int)__popcll(m);
+        row_min[threadIdx.y] = m ? ((unsigned long long)i * N + j) * N + (blockIdx.x * WAVE + (__ffsll((long long)m) - 1)) : ~0ULL;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned long long cnt = 0, lo = ~0ULL;
+        for (int r = 0; r < 4; r++) {
+            cnt += row_cnt[r];
+            lo = row_min[r] < lo ? row_min[r] : lo;
+        }
+        if (cnt) {
+            atomicAdd(out, cnt);
+            atomicMin(out + 1, lo);
+        }
+    }
+}
+
+void k_pack(const Geom &g, double *v, const mg3d_array &a, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    if (a.dtype == MG3D_F32)
+        hipLaunchKernelGGL(pack_kernel<float>, grid, dim3(WAVE, 4, 1), 0, s, g, v, (const float *)a.ptr, a.stride[0],
+                           a.stride[1], a.stride[2]);
+    else
+        hipLaunchKernelGGL(pack_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, v, (const double *)a.ptr, a.stride[0],
+                           a.stride[1], a.stride[2]);
+}
+
+void k_unpack(const Geom &g, const double *v, const mg3d_array &a, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    if (a.dtype == MG3D_F32)
+        hipLaunchKernelGGL(unpack_kernel<float>, grid, dim3(WAVE, 4, 1), 0, s, g, v, (float *)a.ptr, a.stride[0], a.stride[1],
+                           a.stride[2]);
+    else
+        hipLaunchKernelGGL(unpack_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, v, (double *)a.ptr, a.stride[0],
+                           a.stride[1], a.stride[2]);
+}
+
+void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    if (a.dtype == MG3D_F32)
+        hipLaunchKernelGGL(coef_check_kernel<float>, grid, dim3(WAVE, 4, 1), 0, s, g, (const float *)a.ptr, a.stride[0],
+                           a.stride[1], a.stride[2], bc & 7, out);
+    else
+        hipLaunchKernelGGL(coef_check_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, (const double *)a.ptr, a.stride[0],
+                           a.stride[1], a.stride[2], bc & 7, out);
+}
+
 /* ------------------------------------------------------- coarsest direct solve
  * solveWithLU, gauss_elim.h:31-60, on the banded factor.
  *   forward : z[i] = b[i] - sum_{j<i, ascending}  LU[i][j]*z[j]

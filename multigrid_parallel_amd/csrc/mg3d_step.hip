@@ -45,6 +45,27 @@ extern "C" int mg3d_step_setup(mg3d_ctx *ctx, double dt, double theta, double ka
     return MG3D_OK;
 }
 
+/* the source field of the finest level, zeroed, unless the context has it already */
+static int step_src_alloc(mg3d_ctx *ctx)
+{
+    if (ctx->step_src)
+        return MG3D_OK;
+    const Level &top = ctx->lv[ctx->L - 1];
+    double *v = nullptr;
+    hipError_t e = hipMalloc(&v, top.elems * sizeof(double));
+    if (e == hipSuccess)
+        e = hipMemsetAsync(v, 0, top.elems * sizeof(double), ctx->stream); /* (the padding of the rows) */
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (v)
+            (void)hipFree(v);
+        return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_step_set_source: the source field: %s",
+                    hipGetErrorString(e));
+    }
+    ctx->step_src = v;
+    return MG3D_OK;
+}
+
 extern "C" int mg3d_step_set_source(mg3d_ctx *ctx, const double *s)
 {
     if (!ctx)
@@ -55,20 +76,9 @@ extern "C" int mg3d_step_set_source(mg3d_ctx *ctx, const double *s)
     }
     const Level &top = ctx->lv[ctx->L - 1];
     const int N = top.g.N;
-    if (!ctx->step_src) {
-        double *v = nullptr;
-        hipError_t e = hipMalloc(&v, top.elems * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemsetAsync(v, 0, top.elems * sizeof(double), ctx->stream); /* (the padding of the rows) */
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx->stream);
-            if (v)
-                (void)hipFree(v);
-            return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_step_set_source: the source field: %s",
-                        hipGetErrorString(e));
-        }
-        ctx->step_src = v;
-    }
+    const int rc = step_src_alloc(ctx);
+    if (rc != MG3D_OK)
+        return rc;
     /* (a step still in flight reads the field: the copy is ordered behind it on the context's stream) */
     hipError_t e = hipMemcpy2DAsync(ctx->step_src, top.g.pitch * sizeof(double), s, N * sizeof(double), N * sizeof(double),
                                     (size_t)N * N, hipMemcpyHostToDevice, ctx->stream);
@@ -78,6 +88,36 @@ extern "C" int mg3d_step_set_source(mg3d_ctx *ctx, const double *s)
         return fail(MG3D_ERR_HIP, "mg3d_step_set_source: upload: %s", hipGetErrorString(e));
     ctx->step_has_src = true;
     return MG3D_OK;
+}
+
+/* the same from a device array (mg3d_array): packed into the source field on the context's stream, behind any step in
+ * flight and behind what the caller's stream did to the array; no host synchronisation */
+extern "C" int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s, void *stream)
+{
+    static const char who[] = "mg3d_step_set_source_device";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!s) {
+        ctx->step_has_src = false;
+        return MG3D_OK;
+    }
+    int rc = mg3d_array_check(ctx, s, false, who);
+    if (rc == MG3D_OK)
+        rc = step_src_alloc(ctx);
+    if (rc == MG3D_OK)
+        rc = mg3d_stream_join(ctx, (hipStream_t)stream, false, who);
+    if (rc != MG3D_OK)
+        return rc;
+    const int q = ctx->L - 1;
+    {
+        StageScope kt(ctx, q, MG3D_K_PACK, true);
+        k_pack(ctx->lv[q].g, ctx->step_src, *s, ctx->stream);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return fail(MG3D_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    ctx->step_has_src = true;
+    return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
 }
 
 /* steps [0, nsteps) of a checked call; `done` counts the completed ones */
