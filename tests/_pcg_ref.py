@@ -52,9 +52,16 @@ def precondition(prob, r_blk):
     return prob.u[-1].copy()
 
 
-def pcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None):
+_numpy_cycle = precondition
+
+
+def pcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None, precondition=None):
     """Returns (x, norms r_0 .. r_k, converged).  x0, d: (N, N, N) of the finest level; x0 is not modified.  history
-    (a list) receives a copy of x after every iteration."""
+    (a list) receives a copy of x after every iteration.  precondition(prob, r_blk) -> the whole array z (zero Dirichlet
+    faces, consistent duplicates) replaces the numpy cycle (`precondition` above) -- prob then needs no hierarchy, only
+    what residual_field reads and r = []; the residual, apply, every dot, the direction and the update stay the numpy
+    code below."""
+    cycle = _numpy_cycle if precondition is None else precondition
     axes, _ = _parts(prob)
     N = prob.N[-1]
     blk = P.unique_block(N, axes)
@@ -70,7 +77,7 @@ def pcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None):
     p = None
     rz_old = None
     for k in range(max_iters):
-        z = precondition(prob, r)
+        z = cycle(prob, r)
         rz = dot(r, z[blk], dots)
         if k == 0:
             p = z

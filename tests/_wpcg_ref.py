@@ -67,9 +67,15 @@ def precondition(prob, r_blk):
     return prob.u[-1].copy()
 
 
-def wpcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None):
+_numpy_cycle = precondition
+
+
+def wpcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None, precondition=None):
     """Returns (x, norms r_0 .. r_k, converged, rhs_mean).  x0, d: (N, N, N) of the finest level, not modified.  history
-    (a list) receives a copy of x after every iteration."""
+    (a list) receives a copy of x after every iteration.  precondition(prob, r_blk) -> the whole array z replaces the numpy
+    cycle (`precondition` above) -- prob then needs no hierarchy, only what residual_field and weights read and r = [];
+    the residual, apply, every sum, the projection, the direction and the update stay the numpy code below."""
+    cycle = _numpy_cycle if precondition is None else precondition
     N = prob.N[-1]
     blk = NR.block(N, prob.axes, prob.faces)
     w, W = weights(prob)
@@ -90,7 +96,7 @@ def wpcg(prob, x0, d, rtol, atol, max_iters, dots="exact", history=None):
     p = None
     rz_old = None
     for k in range(max_iters):
-        z = precondition(prob, r)
+        z = cycle(prob, r)
         rz = wdot(w, r, z[blk], dots)
         m = wsum(w, z[blk], dots) / W if sing else 0.
         if k == 0:

@@ -9,7 +9,12 @@ project's summation tolerance (1e-13 relative, tests/_oracle.py).
 4  the weighted-PCG method against _wpcg_ref.wpcg
 5  state and arguments
 
-Periodic masks need c - 1 even (mg3d_ctx_set_periodic): 37^3 (c = 10) runs the masks without a periodic axis."""
+Periodic masks need c - 1 even (mg3d_ctx_set_periodic): 37^3 and 145^3 (c = 10) run the masks without a periodic axis.
+
+The right-hand side has two walks.  theta < 1 takes the column walk of the stencil kernels (a lane per k); theta = 1 the
+pair walk of the CG vector passes (a lane per k-pair, pair_grid() of csrc/mg3d_kernels.hip, restated in
+tests/test_wpcg_ref_host.py), which needs 129^3 for a second 64-lane block and 257^3 with six Neumann faces to pass the
+cap on blocks; the shapes of the large sizes are those tests/test_gpu_cg_shapes.py recomputes from the header."""
 
 import numpy as np
 import pytest
@@ -28,16 +33,27 @@ NORM_RTOL = 1e-13
 DT, KAPPA = 0.01, 0.75
 SENTINEL = 12345.678
 # boundary word of a case: (periodic axes, Neumann faces)
-BCS = {"dirichlet": (0, 0), "per7": (7, 0), "per4_f15": (4, 15), "f63": (0, 63), "f22": (0, 22)}
+BCS = {"dirichlet": (0, 0), "per7": (7, 0), "per4_f15": (4, 15), "f63": (0, 63), "f22": (0, 22),
+       "f32": (0, 32), "f25": (0, 0b011001)}  # the high k face alone; ilo + jhi + klo
+SMALL_BCS = ("dirichlet", "per7", "per4_f15", "f63", "f22")
 THETA_SRC = [(theta, src) for theta in (1.0, 0.5) for src in (True, False)]
 # (c, L): 17, 37 (off the 2^k+1 ladder), 33 (31 unknown planes: a 16-plane chunk and a 15-plane tail), 65 with Neumann
-# k-faces (65 unknown k: a second 64-lane block with one live lane; 33 k-pairs)
-SIZES = {17: (5, 3), 37: (10, 3), 33: (5, 4), 65: (5, 5)}
-RHS_CASES = ([(17, coef, bc) for coef in (False, True) for bc in BCS]
+# k-faces (65 unknown k: in the column walk of theta < 1 a second 64-lane block with one live lane; the pair walk of
+# theta = 1 has 33 k-pairs there, one block).  The pair walk past one k-block and past the cap:
+#   129 f63, f32   65 pairs: a second k-block with one live lane; f63: 129 rows, a last j-block of one row
+#   129 per7       64 pairs, lo = 0 on every axis (the WRAP column kernels at 128 unknown k: two full blocks)
+#   145            off the ladder, 72 pairs: 8 live lanes in the second k-block; f25: lo/hi mixed per axis
+#   257 f63        129 pairs: three k-blocks, one live lane; 3 * 65 * 257 blocks exceed the cap: two planes per block
+#                  and a last chunk of ONE plane
+SIZES = {17: (5, 3), 37: (10, 3), 33: (5, 4), 65: (5, 5), 129: (5, 6), 145: (10, 5), 257: (9, 6)}
+RHS_CASES = ([(17, coef, bc) for coef in (False, True) for bc in SMALL_BCS]
              + [(37, coef, bc) for coef in (False, True) for bc in ("dirichlet", "f63", "f22")]
-             + [(33, coef, bc) for coef in (False, True) for bc in BCS]
-             + [(65, coef, bc) for coef in (False, True) for bc in ("f63", "per4_f15")])
-STEP_CASES = [(N, coef, bc) for N in (17, 33) for coef in (False, True) for bc in BCS]
+             + [(33, coef, bc) for coef in (False, True) for bc in SMALL_BCS]
+             + [(65, coef, bc) for coef in (False, True) for bc in ("f63", "per4_f15")]
+             + [(129, coef, bc) for coef in (False, True) for bc in ("f63", "f32", "per7")]
+             + [(145, coef, bc) for coef in (False, True) for bc in ("dirichlet", "f25")]
+             + [(257, False, "f63")])
+STEP_CASES = [(N, coef, bc) for N in (17, 33) for coef in (False, True) for bc in SMALL_BCS]
 
 
 def _same_bits(a, b):

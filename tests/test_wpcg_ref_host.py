@@ -1,7 +1,7 @@
 """The CPU restatement of mg3d_wpcg_solve (tests/_wpcg_ref.py) checked on its own, without a GPU: the reflected operator
 and the cycle are self-adjoint in the weighted inner product, every case of its table converges without breakdown, and
 the launch geometry of the library's new reductions, restated from MG3D_MAX_PARTIALS, reaches the shapes the GPU tests
-count on."""
+count on, and one term lost from a dot moves the iterate far beyond what tests/test_gpu_cg_shapes.py allows the GPU."""
 import os
 import re
 
@@ -95,3 +95,49 @@ def test_launch_geometry_of_the_new_reductions():
     for c, L, _, _, axes, faces in list(WR.CASES.values()) + [(9, 7, 0, None, 0, 63)]:
         N = O.level_sizes(c, L)[-1]
         assert N % 2 == 1 and ((N + 15) & ~15) >= N + 1
+
+
+# ------------------------------------------------------------------------------------------------------------ sharpness
+def test_one_lost_term_of_a_dot_moves_the_iterate(monkeypatch):
+    """129^3 (c = 5, L = 6), all six faces Neumann, constant operator, random guess, d = 0, one iteration of the restatement
+    alone: with the term of the single last unknown (128, 128, 128) -- the one live lane of the second k-block, the last
+    row, the last plane -- left out of r.z, and separately out of p.Ap, x_1 moves by at least 1000 times what
+    tests/test_gpu_cg_shapes.py allows the GPU at k = 1 (measured: 5.7e-7 either way): one lost lane, row or plane
+    cannot hide under that margin.  The three runs share one cycle, z = V(r_0) is the same in all of them, and take
+    numpy's sums: what a summation order is worth is nine orders below the effect."""
+    from test_gpu_cg_shapes import tolerances
+    N = 129
+    prob = WR.make_problem(5, 6, 2, 0.0, None, 0, 63)
+    x0, d = WR.random_guess(N, 0, 63), np.zeros((N, N, N))
+    z = []
+
+    def cycle(p, r_blk):
+        if not z:
+            z.append(WR.precondition(p, r_blk))
+        return z[0].copy()
+
+    real = WR.wdot
+
+    def x1(drop):
+        """drop: which weighted dot of the iteration loses the term (1: r.z, 2: p.Ap), or None"""
+        calls = [0]
+
+        def wdot(w, a, b, dots="exact"):
+            calls[0] += 1
+            if calls[0] == drop:
+                a = a.copy()
+                a[-1, -1, -1] = 0.  # (the product is then an exact zero: the term is gone from the sum)
+            return real(w, a, b, dots)
+
+        monkeypatch.setattr(WR, "wdot", wdot)
+        hist = []
+        WR.wpcg(prob, x0, d, 0., 1e-300, 1, "plain", hist, cycle)
+        assert calls[0] == 2
+        return hist[0]
+
+    base = x1(None)
+    tol = tolerances("wpcg", 1)[0]
+    for drop, what in ((1, "r.z"), (2, "p.Ap")):
+        moved = np.abs(x1(drop) - base).max() / np.abs(base).max()
+        print(what, "moved x_1 by", moved, "; allowed on the GPU:", tol)
+        assert moved >= 1000 * tol, (what, moved, tol)
