@@ -126,7 +126,7 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
  * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
  * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
- * k_per_* transfers */
+ * transfers k_restrict / k_prolong launch for a boundary word */
 static inline bool mg3d_fused(const mg3d_ctx *ctx)
 {
     return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0;

@@ -1240,23 +1240,17 @@ static bool pro_fusable(const mg3d_ctx *ctx, int iters, int want_res, int level)
     return mg3d_fused(ctx) && mg3d_stage_plan(ctx->opt, stage_ask(ctx, level, 1, iters, want_res, false, true, true)).step[0].pro;
 }
 
-/* the unfused grid transfers and the direct solve: the k_per_* forms when an axis is periodic or a face is a Neumann face */
+/* the unfused grid transfers and the direct solve (the launchers take the form for the context's boundary word) */
 static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    if (mg3d_ctx_bc(ctx))
-        k_per_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], mg3d_ctx_bc(ctx), ctx->stream);
-    else
-        k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], ctx->stream, -1, -1, faces_only);
+    k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], mg3d_ctx_bc(ctx), ctx->stream, -1, -1, faces_only);
 }
 
 static void enqueue_prolong(mg3d_ctx *ctx, int level)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    if (mg3d_ctx_bc(ctx))
-        k_per_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
-    else
-        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], ctx->stream);
+    k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
 }
 
 /* periodic: the factor of mg3d_coarse_matrix_bc solves for b = d with 0 in the identity rows of the duplicates and, in
@@ -1865,7 +1859,7 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
     k_lu_solve(ctx->lu, ctx->lu_in, ctx->lv[0].g, ctx->lv[0].f[MG3D_D], ctx->lv[0].f[MG3D_U], ctx->lu_work, s);         /* :783 */
     for (int l = 1; l < ctx->L; l++) {
         Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
-        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], s);                                              /* :795 */
+        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], 0, s);                                           /* :795 */
         k_fill_boundary(lev.g, lev.f[MG3D_U], lev.h, s);                                                     /* :798 */
         (void)hipMemsetAsync(lc.f[MG3D_U], 0, lc.elems * sizeof(double), s);                                 /* :801 */
         CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1));                                              /* :804 */
@@ -1907,10 +1901,7 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
     /* 1. the right-hand side down the hierarchy by the context's own restriction, u by injection: the Dirichlet values */
     for (int l = L - 1; l >= 1; l--) {
         const Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
-        if (bc)
-            k_per_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], bc, s);
-        else
-            k_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], s);
+        k_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], bc, s);
         k_coef_inject(lev.g, lev.f[MG3D_U], lc.g, lc.f[MG3D_U], s);
         mg3d_ctx_touched(ctx, MG3D_D, l - 1); /* its faces are no injection of r any more: the cycles inject them again */
     }

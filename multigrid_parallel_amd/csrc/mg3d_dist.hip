@@ -1469,7 +1469,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
             CHK(stage_smooth(D, l, 0, 2, keep ? none.data() : tgt.data(), l < L - 1));
         for (size_t ri = 0; ri < D->rs.size(); ri++) {
             SlabLevel &sl = SL(D, D->rs[ri], l);
-            k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, s, tgt[ri].lo, tgt[ri].hi, !keep && !D->coef);
+            k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, 0, s, tgt[ri].lo, tgt[ri].hi, !keep && !D->coef);
         }
         /* the coarser level starts from its right-hand side at once: only owned planes were produced */
         if (l - 1 < ld)
@@ -1517,7 +1517,7 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
             Level &lc = l - 1 >= ld ? SL(D, R, l - 1).lv : R.coarse->lv[ld - 1];
             pro[ri] = ProlongSource{&lc.g, lc.f[MG3D_U]};
             if (!fold)
-                k_prolong(lc.g, lc.f[MG3D_U], sl.lv.g, sl.lv.f[MG3D_U], s, 0, sl.lv.g.ni);
+                k_prolong(lc.g, lc.f[MG3D_U], sl.lv.g, sl.lv.f[MG3D_U], 0, s, 0, sl.lv.g.ni);
         }
         /* :1341 (+ :1354 at the top level): all H halo planes of u are exact here, the post-smoother uses up
          * 2*nu of them.  The next cycle's pre-smoother wants fresh halos on the finest u: that exchange starts

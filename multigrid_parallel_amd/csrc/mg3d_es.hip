@@ -239,7 +239,7 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
         es_smooth(ctx, l, 0, ctx->iters);                                                            /* :1282 */
         k_residual(lev.g, lev.f[MG3D_U], nullptr, lev.f[MG3D_D], mg3d_level_op(lev.h, 0.), 0., 0, lev.f[MG3D_R],
                    ctx->partials, ctx->sumsq + ctx->sumsq_slots - 1, s);                            /* :1294 */
-        k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], s);                                     /* :1310 */
+        k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], 0, s);                                  /* :1310 */
     }
     {
         Level &l0 = ctx->lv[0];
@@ -251,7 +251,7 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
     }
     for (int l = 1; l <= q; l++) {
         Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
-        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], s); /* :1331 */
+        k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], 0, s); /* :1331 */
         es_fill(ctx, l, l == ctx->L - 1 ? 1. : 0.);
         es_smooth(ctx, l, 1, ctx->iters);                       /* :1341 */
         if (l == q)

@@ -147,10 +147,12 @@ double k_wpcg_weight_sum(const Geom &g, int bc);
  * Return value: 0, or -1 when the level has no launch shape (nothing launched) */
 int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
                double a, double c1, double b, bool backward_euler, double *d, hipStream_t s);
-/* ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not a slab halo */
-void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo = -1,
+/* The grid transfers.  bc = 0: ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not
+ * a slab halo.  bc = mg3d_bc(periodic, neumann) != 0 (single-domain levels): every plane, full weighting on periodic and
+ * Neumann faces too, duplicates written with their sources; the window and faces_only are not looked at */
+void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s, int ic_lo = -1,
                 int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);
-void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, hipStream_t s, int if_lo = -1,
+void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo = -1,
                int if_hi = -1);
 /* BCFunc(i*h, j*h, k*h) = x*x - 2*y*y + z*z on the six faces of a field (mg_3d.h:89-90, 1147-1239) */
 void k_fill_boundary(const Geom &g, double *v, double h, hipStream_t s);
@@ -317,11 +319,8 @@ void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, co
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
 /* eps of the coarser level by injection at every point */
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
-/* periodic axes and Neumann faces (bc = mg3d_bc(periodic, neumann), single-domain levels): restriction (full weighting on
- * periodic and Neumann faces), prolongation, the coarse right-hand side (0 in the duplicates' and the pinned point's
- * identity rows) and a duplicate refresh */
-void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s);
-void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s);
+/* periodic axes and Neumann faces (bc = mg3d_bc(periodic, neumann), single-domain levels): the coarse right-hand side (0
+ * in the duplicates' and the pinned point's identity rows) and a duplicate refresh */
 void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s);
 void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
 /* full multigrid (mg3d_fmg_solve): every unknown of the fine level (and its periodic duplicates) overwritten with the

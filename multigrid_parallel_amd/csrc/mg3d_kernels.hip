@@ -31,9 +31,10 @@
  *     is 0), and every kernel that writes a unique point on a periodic face also writes its duplicates (edges and
  *     corners included), so written fields are always periodic-consistent.
  *   - Colour pass and residual keep the arithmetic above exactly; only neighbour indices change.
- *   - Restriction: the 27-point full weighting of restrict_kernel (same order) on every coarse point that lies on no
+ *   - Restriction: the 27-point full weighting (one order, restrict_kernel) on every coarse point that lies on no
  *     Dirichlet face, with wrapped fine neighbours on periodic axes; Dirichlet faces are injected as before.
- *   - Prolongation: the parent order of prolong_kernel, the coarse "high" parent wrapped to 0 on a periodic axis.
+ *   - Prolongation: the one parent order (stated at the prolongation kernels), the coarse "high" parent wrapped to 0 on
+ *     a periodic axis.
  *   tests/_periodic_ref.py states the same in numpy.
  *
  * Neumann faces (mg3d_ctx_set_neumann; a mask of MG3D_NEUMANN_ILO = 1, _IHI = 2, _JLO = 4, _JHI = 8, _KLO = 16, _KHI = 32
@@ -53,10 +54,12 @@
  */
 #include "mg3d_internal.h"
 
+#include <assert.h>
 #include <stdlib.h>
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 #define WAVE 64
 
@@ -68,6 +71,26 @@ __device__ __forceinline__ long long gidx(const Geom &g, int i, int j, int k)
 /* boundary modes of the stencil kernels and the bits of the boundary word */
 enum { BC_PLAIN = 0, BC_WRAP = 1, BC_REFLECT = 2 };
 static inline int bc_mode(int bc) { return (bc >> 3) ? BC_REFLECT : (bc ? BC_WRAP : BC_PLAIN); }
+/* the one launch ladder: f(coef, mode) with eps set or not and the boundary mode of bc as compile-time constants --
+ * dispatch_op(e, bc, [&](auto coef, auto mode) { hipLaunchKernelGGL((kernel<coef(), mode()>), ...); }) */
+template <class F>
+static void dispatch_op(const double *e, int bc, F f)
+{
+    const auto with_mode = [&](auto coef) {
+        switch (bc_mode(bc)) {
+        case BC_REFLECT:
+            return f(coef, std::integral_constant<int, BC_REFLECT>());
+        case BC_WRAP:
+            return f(coef, std::integral_constant<int, BC_WRAP>());
+        default:
+            return f(coef, std::integral_constant<int, BC_PLAIN>());
+        }
+    };
+    if (e)
+        with_mode(std::true_type());
+    else
+        with_mode(std::false_type());
+}
 /* is the low / high face of axis ax (0 i, 1 j, 2 k) a Neumann face */
 __host__ __device__ __forceinline__ bool bc_ref_lo(int bc, int ax) { return (bc >> (3 + 2 * ax)) & 1; }
 __host__ __device__ __forceinline__ bool bc_ref_hi(int bc, int ax) { return (bc >> (4 + 2 * ax)) & 1; }
@@ -211,6 +234,56 @@ static dim3 column_grid(const Geom &g, int bc, int planes, int &chunk)
     return dim3(gx, gy, (planes + chunk - 1) / chunk);
 }
 
+/* The column walk of every kernel below that keeps a column in registers: from plane c.i0 it carries v -- and eps with
+ * COEF -- of the planes i-1, i, i+1 (the plane behind the first one through nb_lo, the plane ahead through nb_hi) and calls
+ * body(pt) once per plane.  The stencil is the body's to evaluate: the colour pass skips it on the planes of the other
+ * colour. */
+template <bool COEF>
+struct ColumnPoint {
+    int i;       /* the plane */
+    long long p; /* the point's offset */
+    double vh;   /* v[p] as it was when the walk loaded it */
+    const Column &c;
+    const double *v; /* (not __restrict__, here and in the walk: the colour pass stores into v while the walk reads it) */
+    const double *__restrict__ e;
+    double vb, va, eb, eh, ea;
+    /* the point lies on the periodic face i = 0: store_dup's first flag (the other two are c.dj, c.dk) */
+    __device__ __forceinline__ bool di() const { return c.pi && i == 0; }
+    /* stencil<COEF> at this point */
+    __device__ __forceinline__ void sum(double dg0, double &s, double &dg) const
+    {
+        stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
+    }
+};
+
+template <bool COEF, class Body>
+__device__ __forceinline__ void walk_column(const Geom &g, const Column &c, const double *v, const double *__restrict__ e,
+                                            Body body)
+{
+    long long p = gidx(g, c.i0, c.j, c.k);
+    const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
+    double vb = v[pb], vh = v[p];
+    double eb = 0., eh = 0.;
+    if constexpr (COEF) {
+        eb = e[pb];
+        eh = e[p];
+    }
+    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+        const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
+        const double va = v[pa];
+        double ea = 0.;
+        if constexpr (COEF)
+            ea = e[pa];
+        body(ColumnPoint<COEF>{i, p, vh, c, v, e, vb, va, eb, eh, ea});
+        vb = vh;
+        vh = va;
+        if constexpr (COEF) {
+            eb = eh;
+            eh = ea;
+        }
+    }
+}
+
 /* ------------------------------------------------------------------ smoother
  * One red-black colour pass in place over the unique interior points.  Everything a point reads -- the six neighbours
  * -- has the other colour, which this pass never writes (the wrap joins 0 and N-2, of opposite parity); a duplicate has
@@ -253,24 +326,15 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
     Column c;
     if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
-    long long p = gidx(g, c.i0, c.j, c.k);
-    const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
-    double vb = v[pb], vh = v[p];
-    double eb = e[pb], eh = e[p];
-    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-        const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
-        const double va = v[pa], ea = e[pa];
-        if (((g.ig0 + i + c.j + c.k) & 1) == color) {
-            double s, dg;
-            stencil<true>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, shift, s, dg);
-            store_dup(g, v, p, (s - hSq * d[p]) / dg, c.pi && i == 0, c.dj, c.dk);
-        }
-        /* (a point updated here is the i-1 neighbour of a plane this pass does not update: its old value is never used) */
-        vb = vh;
-        vh = va;
-        eb = eh;
-        eh = ea;
-    }
+    /* (a point updated here is the i-1 neighbour of a plane this pass does not update: the old value the walk carries on
+     * is never used) */
+    walk_column<true>(g, c, v, e, [&](const ColumnPoint<true> &pt) {
+        if (((g.ig0 + pt.i + c.j + c.k) & 1) != color)
+            return;
+        double s, dg;
+        pt.sum(shift, s, dg);
+        store_dup(g, v, pt.p, (s - hSq * d[pt.p]) / dg, pt.di(), c.dj, c.dk);
+    });
 }
 
 void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
@@ -279,30 +343,18 @@ void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, 
     if (!stencil_window(g, bc, i_lo, i_hi))
         return;
     const dim3 block(WAVE, 4, 1);
-    const int mode = bc_mode(bc);
-    if (!e) {
-        const int pairs = (g.nk + 1) / 2;
-        const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(bc, 1) + 3) / 4, i_hi - i_lo);
-        if (mode == BC_REFLECT)
-            hipLaunchKernelGGL(smooth_color_kernel<BC_REFLECT>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
-        else if (mode == BC_WRAP)
-            hipLaunchKernelGGL(smooth_color_kernel<BC_WRAP>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
-        else
-            hipLaunchKernelGGL(smooth_color_kernel<BC_PLAIN>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
-        return;
-    }
-    int chunk;
-    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk);
-    const double shift = sigma * op.hSq;
-    if (mode == BC_REFLECT)
-        hipLaunchKernelGGL(coef_color_kernel<BC_REFLECT>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk,
-                           i_lo, i_hi);
-    else if (mode == BC_WRAP)
-        hipLaunchKernelGGL(coef_color_kernel<BC_WRAP>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk, i_lo,
-                           i_hi);
-    else
-        hipLaunchKernelGGL(coef_color_kernel<BC_PLAIN>, grid, block, 0, s, g, v, e, d, op.hSq, shift, color, bc, chunk, i_lo,
-                           i_hi);
+    dispatch_op(e, bc, [&](auto coef, auto mode) {
+        if constexpr (coef()) {
+            int chunk;
+            const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk);
+            hipLaunchKernelGGL(coef_color_kernel<mode()>, grid, block, 0, s, g, v, e, d, op.hSq, sigma * op.hSq, color, bc, chunk,
+                               i_lo, i_hi);
+        } else {
+            const int pairs = (g.nk + 1) / 2;
+            const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(bc, 1) + 3) / 4, i_hi - i_lo);
+            hipLaunchKernelGGL(smooth_color_kernel<mode()>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
+        }
+    });
 }
 
 /* ------------------------------------------------------------ boundary fill
@@ -375,6 +427,9 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
     double acc = 0.;
     Column c;
     if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
+        /* walk_column's walk written out: as a body of the walk, residual_kernel<false, 0> without r measured above the
+         * parent's two runs in one of the two benches that time it (profiles/kernels_refactor_ab.txt), so the kernel keeps
+         * its own copy; a change to the walk is made here too */
         long long p = gidx(g, c.i0, c.j, c.k);
         const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
         double vb = v[pb], vh = v[p];
@@ -449,23 +504,10 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-#define MG3D_RESIDUAL(COEF, BC)                                                                                            \
-    hipLaunchKernelGGL((residual_kernel<COEF, BC>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials, bc, chunk, \
-                       i_lo, i_hi, acc_lo, acc_hi)
-    const int mode = bc_mode(bc);
-    if (e && mode == BC_REFLECT)
-        MG3D_RESIDUAL(true, BC_REFLECT);
-    else if (e && mode == BC_WRAP)
-        MG3D_RESIDUAL(true, BC_WRAP);
-    else if (e)
-        MG3D_RESIDUAL(true, BC_PLAIN);
-    else if (mode == BC_REFLECT)
-        MG3D_RESIDUAL(false, BC_REFLECT);
-    else if (mode == BC_WRAP)
-        MG3D_RESIDUAL(false, BC_WRAP);
-    else
-        MG3D_RESIDUAL(false, BC_PLAIN);
-#undef MG3D_RESIDUAL
+    dispatch_op(e, bc, [&](auto coef, auto mode) {
+        hipLaunchKernelGGL((residual_kernel<coef(), mode()>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials, bc,
+                           chunk, i_lo, i_hi, acc_lo, acc_hi);
+    });
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
 
@@ -494,38 +536,19 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
     double acc = 0.;
     Column c;
     if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
-        long long p = gidx(g, c.i0, c.j, c.k);
-        const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
-        double vb = v[pb], vh = v[p];
-        double eb = 0., eh = 0.;
-        if constexpr (COEF) {
-            eb = e[pb];
-            eh = e[p];
-        }
         double wjk = 1.;
         if constexpr (BC == BC_REFLECT)
             wjk = bc_weight(bc, 1, c.j, g.N) * bc_weight(bc, 2, c.k, g.N);
-        for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-            const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
-            const double va = v[pa];
-            double ea = 0.;
-            if constexpr (COEF)
-                ea = e[pa];
+        walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
             double s, dg;
-            stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
-            const double ap = invHsq * (s - dg * vh);
-            q[p] = ap;
+            pt.sum(dg0, s, dg);
+            const double ap = invHsq * (s - dg * pt.vh);
+            q[pt.p] = ap;
             if constexpr (BC == BC_REFLECT)
-                acc += (wjk * bc_weight(bc, 0, i, g.N)) * (vh * ap);
+                acc += (wjk * bc_weight(bc, 0, pt.i, g.N)) * (pt.vh * ap);
             else
-                acc += vh * ap;
-            vb = vh;
-            vh = va;
-            if constexpr (COEF) {
-                eb = eh;
-                eh = ea;
-            }
-        }
+                acc += pt.vh * ap;
+        });
     }
     const double tot = block_sum_256(acc, lds4);
     if (threadIdx.x == 0 && threadIdx.y == 0)
@@ -543,22 +566,10 @@ int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const Level
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-#define MG3D_PCG_APPLY(COEF, BC) \
-    hipLaunchKernelGGL((pcg_apply_kernel<COEF, BC>), grid, block, 0, s, g, p, e, op.invHsq, dg0, q, partials, bc, chunk, i_lo, i_hi)
-    const int mode = bc_mode(bc);
-    if (e && mode == BC_REFLECT)
-        MG3D_PCG_APPLY(true, BC_REFLECT);
-    else if (e && mode == BC_WRAP)
-        MG3D_PCG_APPLY(true, BC_WRAP);
-    else if (e)
-        MG3D_PCG_APPLY(true, BC_PLAIN);
-    else if (mode == BC_REFLECT)
-        MG3D_PCG_APPLY(false, BC_REFLECT);
-    else if (mode == BC_WRAP)
-        MG3D_PCG_APPLY(false, BC_WRAP);
-    else
-        MG3D_PCG_APPLY(false, BC_PLAIN);
-#undef MG3D_PCG_APPLY
+    dispatch_op(e, bc, [&](auto coef, auto mode) {
+        hipLaunchKernelGGL((pcg_apply_kernel<coef(), mode()>), grid, block, 0, s, g, p, e, op.invHsq, dg0, q, partials, bc,
+                           chunk, i_lo, i_hi);
+    });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, dot_out, s);
     return np;
@@ -764,7 +775,7 @@ __global__ void __launch_bounds__(256) wpcg_center_kernel(Geom g, double *__rest
 
 /* the pair grid: the k-pairs (from 0 up to the last unknown k) and unknown rows of a level over (WAVE, 4) blocks, one
  * plane per block in z; planes per block doubled from 1 until the partial sums fit in `cap` */
-static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, PairRange &u, int cap = MG3D_MAX_PARTIALS)
+static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, PairRange &u, int cap)
 {
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
         return false;
@@ -781,85 +792,67 @@ static bool pair_grid(const Geom &g, int bc, dim3 &grid, int &chunk, PairRange &
     return true;
 }
 
-int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
-                      const double *pap, double *partials, double *rr_out, hipStream_t s)
+/* one pair pass: kernel(g, args..., u, chunk) over the pair grid with room for CAP partial sums; the number of blocks --
+ * of partial sums, where the kernel forms them -- or -1: the level has no launch shape, nothing launched */
+template <int CAP = MG3D_MAX_PARTIALS, class... P, class... A>
+static int pair_launch(void (*kernel)(Geom, P...), const Geom &g, int bc, hipStream_t s, A... args)
 {
     dim3 grid;
     int chunk;
     PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u))
+    if (!pair_grid(g, bc, grid, chunk, u, CAP))
         return -1;
-    hipLaunchKernelGGL(pcg_update_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, x, r, p, q, rz, pap, partials, u, chunk);
-    const int np = (int)(grid.x * grid.y * grid.z);
-    k_fold(partials, np, rr_out, s);
+    hipLaunchKernelGGL(kernel, grid, dim3(WAVE, 4, 1), 0, s, g, args..., u, chunk);
+    return (int)(grid.x * grid.y * grid.z);
+}
+
+int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
+                      const double *pap, double *partials, double *rr_out, hipStream_t s)
+{
+    const int np = pair_launch(pcg_update_kernel, g, bc, s, x, r, p, q, rz, pap, partials);
+    if (np > 0)
+        k_fold(partials, np, rr_out, s);
     return np;
 }
 
 int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s)
 {
-    dim3 grid;
-    int chunk;
-    PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u))
-        return -1;
-    hipLaunchKernelGGL(pcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, u, chunk);
-    const int np = (int)(grid.x * grid.y * grid.z);
-    k_fold(partials, np, dot_out, s);
+    const int np = pair_launch(pcg_dot_kernel, g, bc, s, a, b, partials);
+    if (np > 0)
+        k_fold(partials, np, dot_out, s);
     return np;
 }
 
 int k_pcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
                     hipStream_t s)
 {
-    dim3 grid;
-    int chunk;
-    PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u))
-        return -1;
-    hipLaunchKernelGGL(pcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, u, chunk);
-    return 0;
+    return pair_launch(pcg_direction_kernel, g, bc, s, p, z, rz_new, rz_old) < 0 ? -1 : 0;
 }
 
 int k_wpcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, double *sum_out,
                hipStream_t s)
 {
-    dim3 grid;
-    int chunk;
-    PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u, MG3D_MAX_PARTIALS / 2))
-        return -1;
     double *const pb = partials + MG3D_MAX_PARTIALS / 2;
-    hipLaunchKernelGGL(wpcg_dot_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, a, b, partials, pb, bc, u, chunk);
-    const int np = (int)(grid.x * grid.y * grid.z);
-    k_fold(partials, np, dot_out, s);
-    k_fold(pb, np, sum_out, s);
+    const int np = pair_launch<MG3D_MAX_PARTIALS / 2>(wpcg_dot_kernel, g, bc, s, a, b, partials, pb, bc);
+    if (np > 0) {
+        k_fold(partials, np, dot_out, s);
+        k_fold(pb, np, sum_out, s);
+    }
     return np;
 }
 
 int k_wpcg_direction(const Geom &g, int bc, double *p, const double *z, const double *rz_new, const double *rz_old,
                      const double *wsum, double W, bool first, hipStream_t s)
 {
-    dim3 grid;
-    int chunk;
-    PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u))
-        return -1;
-    hipLaunchKernelGGL(wpcg_direction_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, p, z, rz_new, rz_old, wsum, W, first ? 1 : 0,
-                       u, chunk);
-    return 0;
+    return pair_launch(wpcg_direction_kernel, g, bc, s, p, z, rz_new, rz_old, wsum, W, first ? 1 : 0) < 0 ? -1 : 0;
 }
 
 int k_wpcg_center(const Geom &g, int bc, double *r, const double *wsum, double W, double *partials, double *rr_out,
                   hipStream_t s)
 {
-    dim3 grid;
-    int chunk;
-    PairRange u;
-    if (!pair_grid(g, bc, grid, chunk, u))
-        return -1;
-    hipLaunchKernelGGL(wpcg_center_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, r, wsum, W, partials, u, chunk);
-    const int np = (int)(grid.x * grid.y * grid.z);
-    k_fold(partials, np, rr_out, s);
+    const int np = pair_launch(wpcg_center_kernel, g, bc, s, r, wsum, W, partials);
+    if (np > 0)
+        k_fold(partials, np, rr_out, s);
     return np;
 }
 
@@ -878,8 +871,8 @@ double k_wpcg_weight_sum(const Geom &g, int bc)
  * unknowns only: Dirichlet points and periodic duplicates of d keep what they hold (nothing reads them).
  *     q    = invHsq*(s - dg*v[p])                 pcg_apply_kernel's expression, operand and neighbour order
  *     d[p] = -((a*v[p] + c1*q) + b*src[p])        src == NULL: d[p] = -(a*v[p] + c1*q)
- * theta < 1: pcg_apply_kernel's column walk with one more operand and neither a sum nor partials.  src is a uniform
- * branch: the six instantiations stay six.  Both launches take the grids of the passes they are modelled on (column_grid,
+ * theta < 1: pcg_apply_kernel's body on the column walk with one more operand and neither a sum nor partials.  src is a
+ * uniform branch: the six instantiations stay six.  Both launches take the grids of the passes they are modelled on (column_grid,
  * pair_grid) as they are: the cap on blocks those keep for the partial sums means nothing here and does no harm. */
 template <bool COEF, int BC>
 __global__ void __launch_bounds__(256) step_rhs_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
@@ -890,34 +883,15 @@ __global__ void __launch_bounds__(256) step_rhs_kernel(Geom g, const double *__r
     Column c;
     if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
-    long long p = gidx(g, c.i0, c.j, c.k);
-    const long long pb = p + nb_lo(c.i0, g.N, c.pi, c.ril, g.plane);
-    double vb = v[pb], vh = v[p];
-    double eb = 0., eh = 0.;
-    if constexpr (COEF) {
-        eb = e[pb];
-        eh = e[p];
-    }
-    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
-        const long long pa = p + nb_hi(i, g.N, c.pi, c.rih, g.plane);
-        const double va = v[pa];
-        double ea = 0.;
-        if constexpr (COEF)
-            ea = e[pa];
+    walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
         double s, dg;
-        stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
-        const double q = invHsq * (s - dg * vh);
-        double t = a * vh + c1 * q;
+        pt.sum(dg0, s, dg);
+        const double q = invHsq * (s - dg * pt.vh);
+        double t = a * pt.vh + c1 * q;
         if (src)
-            t = t + b * src[p];
-        d[p] = -t;
-        vb = vh;
-        vh = va;
-        if constexpr (COEF) {
-            eb = eh;
-            eh = ea;
-        }
-    }
+            t = t + b * src[pt.p];
+        d[pt.p] = -t;
+    });
 }
 
 /* theta == 1 (backward Euler): c1 = 0 and no stencil -- d[p] = -(a*v[p] + b*src[p]), or -(a*v[p]) without a source, as a
@@ -949,15 +923,8 @@ __global__ void __launch_bounds__(256) step_rhs_be_kernel(Geom g, const double *
 int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
                double a, double c1, double b, bool backward_euler, double *d, hipStream_t s)
 {
-    if (backward_euler) {
-        dim3 grid;
-        int chunk;
-        PairRange u;
-        if (!pair_grid(g, bc, grid, chunk, u))
-            return -1;
-        hipLaunchKernelGGL(step_rhs_be_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, u0, src, a, b, d, u, chunk);
-        return 0;
-    }
+    if (backward_euler)
+        return pair_launch(step_rhs_be_kernel, g, bc, s, u0, src, a, b, d) < 0 ? -1 : 0;
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
         return -1;
     int i_lo = -1, i_hi = -1;
@@ -966,23 +933,10 @@ int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *s
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-#define MG3D_STEP_RHS(COEF, BC)                                                                                            \
-    hipLaunchKernelGGL((step_rhs_kernel<COEF, BC>), grid, block, 0, s, g, u0, e, src, op.invHsq, dg0, a, c1, b, d, bc, chunk, \
-                       i_lo, i_hi)
-    const int mode = bc_mode(bc);
-    if (e && mode == BC_REFLECT)
-        MG3D_STEP_RHS(true, BC_REFLECT);
-    else if (e && mode == BC_WRAP)
-        MG3D_STEP_RHS(true, BC_WRAP);
-    else if (e)
-        MG3D_STEP_RHS(true, BC_PLAIN);
-    else if (mode == BC_REFLECT)
-        MG3D_STEP_RHS(false, BC_REFLECT);
-    else if (mode == BC_WRAP)
-        MG3D_STEP_RHS(false, BC_WRAP);
-    else
-        MG3D_STEP_RHS(false, BC_PLAIN);
-#undef MG3D_STEP_RHS
+    dispatch_op(e, bc, [&](auto coef, auto mode) {
+        hipLaunchKernelGGL((step_rhs_kernel<coef(), mode()>), grid, block, 0, s, g, u0, e, src, op.invHsq, dg0, a, c1, b, d, bc,
+                           chunk, i_lo, i_hi);
+    });
     return 0;
 }
 
@@ -1014,41 +968,58 @@ void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out
 }
 
 /* --------------------------------------------------------------- restriction
- * restrictResidual, mg_3d.h:844-998.  Coarse faces: injection d_c = r(2i,2j,2k)
- * (:879-958).  Coarse interior: val = 0; val += r(2i-1+ti, 2j-1+tj, 2k-1+tk) * w[ti][tj][tk]
- * for ti, tj, tk = 0..2 in that nesting (:973-989), w = (1/4,1/2,1/4)^3.
- * "Face" in i means a PHYSICAL boundary plane (global index 0 or Nc-1); the
- * fine plane of coarse local plane ic is 2*(gc.ig0+ic) - gf.ig0. */
+ * restrictResidual, mg_3d.h:844-998.  Coarse Dirichlet faces: injection d_c = r(2i,2j,2k) (:879-958).  Every other coarse
+ * point: val = 0; val += r(2i-1+ti, 2j-1+tj, 2k-1+tk) * w[ti][tj][tk] for ti, tj, tk = 0..2 in that nesting (:973-989),
+ * w = (1/4,1/2,1/4)^3.  One thread per coarse point.
+ *   BC_PLAIN: the i-slabs' form.  "Face" in i means a PHYSICAL boundary plane (global index 0 or Nc-1); the fine plane of
+ *     coarse local plane ic is 2*(gc.ig0+ic) - gf.ig0; [ic_lo, ic_hi) are the local coarse planes produced.
+ *   otherwise (periodic axes, Neumann faces; one instantiation serves both; single-domain levels, every plane): a face
+ *     point is injected only where its face is a Dirichlet face; periodic and Neumann face points take the full
+ *     weighting, whose -1 / +1 taps are the neighbours the stencil has at the fine point (2i, 2j, 2k) -- nb_lo / nb_hi:
+ *     fine index -1 wrapped to Nf-2 on a periodic axis (2I+1 <= Nf-2 never wraps) and reflected to 1 at a Neumann low
+ *     face, fine index Nf reflected to Nf-2 at a Neumann high face.  A duplicate is written as a copy by the thread of
+ *     its source. */
+template <int BC>
 __global__ void __launch_bounds__(256) restrict_kernel(Geom gf, const double *__restrict__ r, Geom gc,
-                                                       double *__restrict__ dc, int ic_lo, int ic_hi, int faces_only)
+                                                       double *__restrict__ dc, int bc, int ic_lo, int ic_hi)
 {
-    const int kc = blockIdx.x * 64 + threadIdx.x;
+    const bool pi = BC && (bc & 1), pj = BC && (bc & 2), pk = BC && (bc & 4);
+    const bool ril = BC && bc_ref_lo(bc, 0), rih = BC && bc_ref_hi(bc, 0), rjl = BC && bc_ref_lo(bc, 1),
+               rjh = BC && bc_ref_hi(bc, 1), rkl = BC && bc_ref_lo(bc, 2), rkh = BC && bc_ref_hi(bc, 2);
+    const int kc = blockIdx.x * WAVE + threadIdx.x;
     const int jc = blockIdx.y * 4 + threadIdx.y;
     const int ic = ic_lo + blockIdx.z;
-    if (kc >= gc.nk || jc >= gc.nj || ic >= ic_hi)
+    const int nj = BC ? gc.N : gc.nj, nk = BC ? gc.N : gc.nk;
+    if (kc >= nk || jc >= nj || ic >= ic_hi)
         return;
-    const int icg = gc.ig0 + ic;
-    const int fi = 2 * icg - gf.ig0, fj = 2 * jc, fk = 2 * kc;
+    const int icg = (BC ? 0 : gc.ig0) + ic;
+    if ((pi && icg == gc.N - 1) || (pj && jc == nj - 1) || (pk && kc == nk - 1))
+        return; /* a duplicate: its source's thread writes it */
+    const int fi = 2 * icg - (BC ? 0 : gf.ig0), fj = 2 * jc, fk = 2 * kc;
     const long long pf = gidx(gf, fi, fj, fk);
-    const bool face = icg == 0 || icg == gc.N - 1 || jc == 0 || jc == gc.nj - 1 || kc == 0 || kc == gc.nk - 1;
+    const bool face = (!pi && ((icg == 0 && !ril) || (icg == gc.N - 1 && !rih))) ||
+                      (!pj && ((jc == 0 && !rjl) || (jc == nj - 1 && !rjh))) ||
+                      (!pk && ((kc == 0 && !rkl) || (kc == nk - 1 && !rkh)));
     double val;
     if (face) {
         val = r[pf];
-    } else if (faces_only) {
-        return;
     } else {
+        /* (BC_PLAIN: the constant offsets -plane, +plane, -pitch, +pitch, -1, +1) */
+        const long long oi[3] = {nb_lo(fi, gf.N, pi, ril, gf.plane), 0, nb_hi(fi, gf.N, pi, rih, gf.plane)};
+        const long long oj[3] = {nb_lo(fj, gf.N, pj, rjl, gf.pitch), 0, nb_hi(fj, gf.N, pj, rjh, gf.pitch)};
+        const long long ok[3] = {nb_lo(fk, gf.N, pk, rkl, 1), 0, nb_hi(fk, gf.N, pk, rkh, 1)};
         val = 0.;
 #pragma unroll
-        for (int ti = -1; ti <= 1; ti++)
+        for (int ti = 0; ti < 3; ti++)
 #pragma unroll
-            for (int tj = -1; tj <= 1; tj++)
+            for (int tj = 0; tj < 3; tj++)
 #pragma unroll
-                for (int tk = -1; tk <= 1; tk++) {
-                    const double w = (ti ? 0.25 : 0.5) * (tj ? 0.25 : 0.5) * (tk ? 0.25 : 0.5);
-                    val += r[pf + ti * gf.plane + tj * (long long)gf.pitch + tk] * w;
+                for (int tk = 0; tk < 3; tk++) {
+                    const double w = (ti != 1 ? 0.25 : 0.5) * (tj != 1 ? 0.25 : 0.5) * (tk != 1 ? 0.25 : 0.5);
+                    val += r[pf + oi[ti] + oj[tj] + ok[tk]] * w;
                 }
     }
-    dc[gidx(gc, ic, jc, kc)] = val;
+    store_dup(gc, dc, gidx(gc, ic, jc, kc), val, pi && icg == 0, pj && jc == 0, pk && kc == 0);
 }
 
 /* injection on the six coarse faces only (mg_3d.h:879-958): one thread per face point.
@@ -1082,81 +1053,29 @@ __global__ void __launch_bounds__(256) restrict_faces_kernel(Geom gf, const doub
     dc[gidx(gc, ic, jc, kc)] = r[gidx(gf, fi, 2 * jc, 2 * kc)];
 }
 
-void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, hipStream_t s, int ic_lo, int ic_hi,
+void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s, int ic_lo, int ic_hi,
                 bool faces_only)
 {
-    if (faces_only) {
-        const int lo = ic_lo >= 0 ? ic_lo : ((gc.ig0 == 0) ? 0 : 1);
-        const int hi = ic_hi >= 0 ? ic_hi : ((gc.ig0 + gc.ni == gc.N) ? gc.ni : gc.ni - 1);
-        if (hi <= lo)
-            return;
-        const int m = max(max(gc.nj, gc.nk), hi - lo);
-        dim3 grid((m + 63) / 64, (m + 3) / 4, 6);
-        hipLaunchKernelGGL(restrict_faces_kernel, grid, dim3(64, 4, 1), 0, s, gf, r, gc, dc, lo, hi);
+    const dim3 block(WAVE, 4, 1);
+    if (bc) { /* a single-domain level: every plane, never faces only -- periodic and Neumann faces are fully weighted */
+        const dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
+        hipLaunchKernelGGL(restrict_kernel<BC_WRAP>, grid, block, 0, s, gf, r, gc, dc, bc, 0, gc.N);
         return;
     }
-
     /* local coarse planes written: physical boundary planes and owned planes; a
      * halo plane (local 0 / ni-1 that is not a physical boundary) is the neighbour's */
     const int lo = ic_lo >= 0 ? ic_lo : ((gc.ig0 == 0) ? 0 : 1);
     const int hi = ic_hi >= 0 ? ic_hi : ((gc.ig0 + gc.ni == gc.N) ? gc.ni : gc.ni - 1);
     if (hi <= lo)
         return;
-    dim3 grid((gc.nk + 63) / 64, (gc.nj + 3) / 4, hi - lo);
-    hipLaunchKernelGGL(restrict_kernel, grid, dim3(64, 4, 1), 0, s, gf, r, gc, dc, lo, hi, faces_only ? 1 : 0);
-}
-
-/* Periodic axes and Neumann faces: one thread per coarse point.  A point on a Dirichlet face (index 0 or Nc-1 of a
- * non-periodic axis, unless that face is a Neumann face) is injected, dc = r(2I, 2J, 2K), as restrict_kernel does; every
- * other unique point -- periodic and Neumann face points included -- takes the full weighting val = 0;
- * val += r(2I-1+ti, ...) * w in restrict_kernel's order, with fine index -1 wrapped to Nf-2 on a periodic axis
- * (2I+1 <= Nf-2 never wraps) and reflected to 1 at a Neumann low face, fine index Nf reflected to Nf-2 at a Neumann high
- * face.  Duplicates are written as copies by the thread of their source. */
-__global__ void __launch_bounds__(256) per_restrict_kernel(Geom gf, const double *__restrict__ r, Geom gc,
-                                                           double *__restrict__ dc, int bc)
-{
-    const int axes = bc & 7;
-    const int kc = blockIdx.x * WAVE + threadIdx.x;
-    const int jc = blockIdx.y * 4 + threadIdx.y;
-    const int ic = blockIdx.z;
-    const int Nc = gc.N, Nf = gf.N;
-    const bool pi = axes & 1, pj = axes & 2, pk = axes & 4;
-    if (kc >= Nc || jc >= Nc || ic >= Nc)
+    if (faces_only) {
+        const int m = max(max(gc.nj, gc.nk), hi - lo);
+        const dim3 grid((m + 63) / 64, (m + 3) / 4, 6);
+        hipLaunchKernelGGL(restrict_faces_kernel, grid, block, 0, s, gf, r, gc, dc, lo, hi);
         return;
-    if ((pi && ic == Nc - 1) || (pj && jc == Nc - 1) || (pk && kc == Nc - 1))
-        return; /* a duplicate: its source's thread writes it */
-    const long long pf = gidx(gf, 2 * ic, 2 * jc, 2 * kc);
-    const bool face = (!pi && ((ic == 0 && !bc_ref_lo(bc, 0)) || (ic == Nc - 1 && !bc_ref_hi(bc, 0)))) ||
-                      (!pj && ((jc == 0 && !bc_ref_lo(bc, 1)) || (jc == Nc - 1 && !bc_ref_hi(bc, 1)))) ||
-                      (!pk && ((kc == 0 && !bc_ref_lo(bc, 2)) || (kc == Nc - 1 && !bc_ref_hi(bc, 2))));
-    double val;
-    if (face) {
-        val = r[pf];
-    } else {
-        /* (here index 0 is on a periodic axis or a Neumann low face, index Nc-1 on a Neumann high face) */
-        const long long oi[3] = {ic == 0 ? (pi ? (Nf - 2) * gf.plane : gf.plane) : -gf.plane, 0,
-                                 ic == Nc - 1 ? -gf.plane : gf.plane};
-        const long long oj[3] = {jc == 0 ? (pj ? (long long)(Nf - 2) * gf.pitch : (long long)gf.pitch) : -(long long)gf.pitch, 0,
-                                 jc == Nc - 1 ? -(long long)gf.pitch : (long long)gf.pitch};
-        const long long ok[3] = {kc == 0 ? (pk ? (long long)(Nf - 2) : 1LL) : -1LL, 0, kc == Nc - 1 ? -1LL : 1LL};
-        val = 0.;
-#pragma unroll
-        for (int ti = 0; ti < 3; ti++)
-#pragma unroll
-            for (int tj = 0; tj < 3; tj++)
-#pragma unroll
-                for (int tk = 0; tk < 3; tk++) {
-                    const double w = (ti != 1 ? 0.25 : 0.5) * (tj != 1 ? 0.25 : 0.5) * (tk != 1 ? 0.25 : 0.5);
-                    val += r[pf + oi[ti] + oj[tj] + ok[tk]] * w;
-                }
     }
-    store_dup(gc, dc, gidx(gc, ic, jc, kc), val, pi && ic == 0, pj && jc == 0, pk && kc == 0);
-}
-
-void k_per_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s)
-{
-    dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
-    hipLaunchKernelGGL(per_restrict_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, r, gc, dc, bc);
+    const dim3 grid((gc.nk + 63) / 64, (gc.nj + 3) / 4, hi - lo);
+    hipLaunchKernelGGL(restrict_kernel<BC_PLAIN>, grid, block, 0, s, gf, r, gc, dc, 0, lo, hi);
 }
 
 /* eps of the coarse level at every point, boundary included: ec[I,J,K] = ef[2I,2J,2K] (single-domain levels) */
@@ -1187,67 +1106,10 @@ void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec,
  *   one odd  : (low + high) * 0.5                                               (:1110-1133)
  *   none odd : copy                                                             (:1138)
  * The running sum starts from 0. (0. + x == x), as retVal does. */
-__global__ void __launch_bounds__(256) prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
-                                                      double *__restrict__ ef, int if_lo, int if_hi)
-{
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    const int j = blockIdx.y * 4 + threadIdx.y;
-    const int i = if_lo + blockIdx.z;
-    if (k >= gf.nk || j >= gf.nj || i >= if_hi)
-        return;
-    const int ig = gf.ig0 + i;
-    const int oi = ig & 1, oj = j & 1, ok = k & 1;
-    const int il = (ig - oi) / 2 - gc.ig0, jl = (j - oj) / 2, kl = (k - ok) / 2;
-    const long long c0 = gidx(gc, il, jl, kl);
-    const long long sI = gc.plane, sJ = gc.pitch, sK = 1;
-    double t = 0.;
-    switch (oi + oj + ok) {
-    case 3:
-        t += ec[c0];
-        t += ec[c0 + sK];
-        t += ec[c0 + sJ];
-        t += ec[c0 + sJ + sK];
-        t += ec[c0 + sI];
-        t += ec[c0 + sI + sK];
-        t += ec[c0 + sI + sJ];
-        t += ec[c0 + sI + sJ + sK];
-        t *= 0.125;
-        break;
-    case 2:
-        if (!oi) {
-            t += ec[c0];
-            t += ec[c0 + sJ];
-            t += ec[c0 + sK];
-            t += ec[c0 + sJ + sK];
-        } else if (!oj) {
-            t += ec[c0];
-            t += ec[c0 + sI];
-            t += ec[c0 + sK];
-            t += ec[c0 + sI + sK];
-        } else {
-            t += ec[c0];
-            t += ec[c0 + sJ];
-            t += ec[c0 + sI];
-            t += ec[c0 + sI + sJ];
-        }
-        t *= 0.25;
-        break;
-    case 1:
-        t += ec[c0];
-        t += ec[c0 + oi * sI + oj * sJ + ok * sK];
-        t *= 0.5;
-        break;
-    default:
-        t = ec[c0];
-    }
-    const long long p = gidx(gf, i, j, k);
-    ef[p] += t;
-}
-
-/* Cell-based form used by the V-cycle: a thread owns one coarse cell (jc, m) -- the 2 x 2 fine points
- * (2jc, 2jc+1) x (2m, 2m+1) of every fine plane -- and marches along i.  The eight coarse corners
+/* Cell-based form, the Dirichlet levels' (the V-cycle, the i-slabs): a thread owns one coarse cell (jc, m) -- the 2 x 2
+ * fine points (2jc, 2jc+1) x (2m, 2m+1) of every fine plane -- and marches along i.  The eight coarse corners
  * E[a][b][c] = ec(il+a, jc+b, m+c) of the current cell stay in registers and are reused by the two fine
- * planes that share them; fine data moves as 16-byte k-pairs.  Same parent order as prolong_kernel. */
+ * planes that share them; fine data moves as 16-byte k-pairs.  The parent order above. */
 __global__ void __launch_bounds__(256) prolong_cell_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
                                                            double *__restrict__ ef, int if_lo, int if_hi, int chunk)
 {
@@ -1319,32 +1181,14 @@ __global__ void __launch_bounds__(256) prolong_cell_kernel(Geom gc, const double
     }
 }
 
-void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, hipStream_t s, int if_lo, int if_hi)
-{
-    const int lo = if_lo >= 0 ? if_lo : ((gf.ig0 == 0) ? 0 : 1);
-    const int hi = if_hi >= 0 ? if_hi : ((gf.ig0 + gf.ni == gf.N) ? gf.ni : gf.ni - 1);
-    if (hi <= lo)
-        return;
-    if (gf.nk == 2 * gc.nk - 1 && gf.nj == 2 * gc.nj - 1) {
-        const int gx = ((gf.nk + 1) / 2 + 63) / 64, gy = ((gf.nj + 1) / 2 + 3) / 4;
-        int chunk = 64; /* a few hundred to a few thousand blocks, like the sweep */
-        while (chunk > 4 && (long long)gx * gy * ((hi - lo + chunk - 1) / chunk) < 2048)
-            chunk /= 2;
-        dim3 grid(gx, gy, (hi - lo + chunk - 1) / chunk);
-        hipLaunchKernelGGL(prolong_cell_kernel, grid, dim3(64, 4, 1), 0, s, gc, ec, gf, ef, lo, hi, chunk);
-        return;
-    }
-    dim3 grid((gf.nk + 63) / 64, (gf.nj + 3) / 4, hi - lo);
-    hipLaunchKernelGGL(prolong_kernel, grid, dim3(64, 4, 1), 0, s, gc, ec, gf, ef, lo, hi);
-}
-
-/* Periodic axes and Neumann faces: ef += P(ec) at every fine point that is not a duplicate (Dirichlet faces included, as
- * prolong_kernel: their coarse parents hold zeros), in prolong_kernel's parent order; on a periodic axis the high parent
- * il+1 = Nc-1 is read at its source 0.  The thread of a point writes the sum to its duplicates too, so neither a fine nor a
- * coarse duplicate is ever read.  A Neumann face needs nothing of its own: every parent of a fine face point lies on the
- * same face, and this kernel corrects the face points with the rest (axes: the periodic bits of the boundary word). */
-__global__ void __launch_bounds__(256) per_prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
-                                                          double *__restrict__ ef, int axes)
+/* Point form, one thread per fine point, for the levels with periodic axes or Neumann faces: ef += P(ec) at every fine
+ * point that is not a duplicate (Dirichlet faces included: their coarse parents hold zeros), in the parent order above;
+ * on a periodic axis the high parent il+1 = Nc-1 is read at its source 0.  The thread of a point writes the sum to its
+ * duplicates too, so neither a fine nor a coarse duplicate is ever read.  A Neumann face needs nothing of its own: every
+ * parent of a fine face point lies on the same face, and this kernel corrects the face points with the rest (axes: the
+ * periodic bits of the boundary word).  (A Dirichlet level never takes this form: k_prolong.) */
+__global__ void __launch_bounds__(256) prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
+                                                      double *__restrict__ ef, int axes)
 {
     const int k = blockIdx.x * WAVE + threadIdx.x;
     const int j = blockIdx.y * 4 + threadIdx.y;
@@ -1405,10 +1249,26 @@ __global__ void __launch_bounds__(256) per_prolong_kernel(Geom gc, const double 
     store_dup(gf, ef, p, ef[p] + t, pi && i == 0, pj && j == 0, pk && k == 0);
 }
 
-void k_per_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s)
+/* bc = 0: the cell form.  Its one condition, which every hierarchy meets -- a level keeps nj = nk = N and Nf = 2*Nc - 1 --
+ * is asserted: there is no other form for a Dirichlet level */
+void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo, int if_hi)
 {
-    dim3 grid((gf.N + WAVE - 1) / WAVE, (gf.N + 3) / 4, gf.N);
-    hipLaunchKernelGGL(per_prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
+    if (bc) { /* a single-domain level: every plane */
+        const dim3 grid((gf.N + WAVE - 1) / WAVE, (gf.N + 3) / 4, gf.N);
+        hipLaunchKernelGGL(prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
+        return;
+    }
+    assert(gf.nk == 2 * gc.nk - 1 && gf.nj == 2 * gc.nj - 1);
+    const int lo = if_lo >= 0 ? if_lo : ((gf.ig0 == 0) ? 0 : 1);
+    const int hi = if_hi >= 0 ? if_hi : ((gf.ig0 + gf.ni == gf.N) ? gf.ni : gf.ni - 1);
+    if (hi <= lo)
+        return;
+    const int gx = ((gf.nk + 1) / 2 + 63) / 64, gy = ((gf.nj + 1) / 2 + 3) / 4;
+    int chunk = 64; /* a few hundred to a few thousand blocks, like the sweep */
+    while (chunk > 4 && (long long)gx * gy * ((hi - lo + chunk - 1) / chunk) < 2048)
+        chunk /= 2;
+    const dim3 grid(gx, gy, (hi - lo + chunk - 1) / chunk);
+    hipLaunchKernelGGL(prolong_cell_kernel, grid, dim3(64, 4, 1), 0, s, gc, ec, gf, ef, lo, hi, chunk);
 }
 
 /* --------------------------------------------------------- FMG interpolation

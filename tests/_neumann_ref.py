@@ -206,8 +206,8 @@ def residual_blocks(u, d, e, h, sigma, axes, faces, r=None, planes=16):
 # ---- transfers
 
 def restrict(r, dc, axes, faces):
-    """k_per_restrict: Dirichlet faces injected, every other point fully weighted (restrict_kernel's order) with wrapped
-    or reflected fine neighbours; periodic duplicates copied"""
+    """k_restrict with a boundary word: Dirichlet faces injected, every other point fully weighted (restrict_kernel's
+    order) with wrapped or reflected fine neighbours; periodic duplicates copied"""
     Nf, Nc = r.shape[0], dc.shape[0]
     blk = PR._written(Nc, axes)
     idx = []
@@ -238,8 +238,8 @@ def restrict(r, dc, axes, faces):
 
 
 def prolong(ec, ef, axes, faces):
-    """k_per_prolong: ef += P(ec) at every fine point that is not a duplicate.  A Neumann face needs nothing of its own:
-    every parent of a fine face point lies on the same face"""
+    """k_prolong with a boundary word: ef += P(ec) at every fine point that is not a duplicate.  A Neumann face needs
+    nothing of its own: every parent of a fine face point lies on the same face"""
     PR.prolong(ec, ef, axes)
 
 

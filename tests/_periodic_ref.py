@@ -214,8 +214,8 @@ def _written(N, axes):
 
 
 def restrict(r, dc, axes):
-    """k_per_restrict: Dirichlet faces injected, every other point fully weighted (restrict_kernel's order) with wrapped
-    fine neighbours; duplicates copied"""
+    """k_restrict with a boundary word: Dirichlet faces injected, every other point fully weighted (restrict_kernel's
+    order) with wrapped fine neighbours; duplicates copied"""
     Nf, Nc = r.shape[0], dc.shape[0]
     blk = _written(Nc, axes)
     idx = []
@@ -242,8 +242,8 @@ def restrict(r, dc, axes):
 
 
 def prolong(ec, ef, axes):
-    """k_per_prolong: ef += P(ec) at every fine point that is not a duplicate (prolong_kernel's parent order, the high
-    parent wrapped on a periodic axis), duplicates copied.  Restated with the oracle's prolongation on copies whose
+    """k_prolong with a boundary word: ef += P(ec) at every fine point that is not a duplicate (the parent order, the
+    high parent wrapped on a periodic axis), duplicates copied.  Restated with the oracle's prolongation on copies whose
     duplicates are refreshed from their sources -- its parent at index Nc-1 is then the wrapped one."""
     Nc, Nf = ec.shape[0], ef.shape[0]
     c = np.ascontiguousarray(ec).copy()
