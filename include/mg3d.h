@@ -160,6 +160,48 @@ enum {
 int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces);
 int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces);
 
+/* Fixed points inside the domain (embedded conductors).  mask is one byte per point of the finest level, a dense N^3 host
+ * array; nonzero means FIXED.  A fixed point is a Dirichlet point, exactly like a point on a Dirichlet face: u there is
+ * whatever the caller uploaded and nothing ever changes it -- no smoother, prolongation, mg3d_pcg_solve / mg3d_wpcg_solve
+ * update or projection, no mg3d_step_advance (one exception to "bit for bit": the CG update pass visits fixed points and
+ * stores u + alpha*0. there, the same value, but a -0. the caller uploaded comes back as +0.) --, d there is never read, the residual there is 0 (r is stored as 0. where the
+ * residual stores, nothing enters the norm), and its neighbours read its u through the ordinary stencil (with a
+ * coefficient also its eps: mg3d_ctx_set_coefficient keeps checking eps at fixed points).  A byte on a point that is a
+ * Dirichlet face point already is ignored; on a periodic context the duplicates' bytes are ignored and take their sources'
+ * -- for good: whether the mask or the periodic axis comes first, index N-1 of that axis holds index 0's bytes from then on,
+ * also after the axis stops being periodic (pass the mask again to have other bytes there);
+ * a point on a Neumann face may be fixed.  The mask is orthogonal to the rest of the operator: constant or eps, sigma,
+ * periodic axes and Neumann faces keep their arithmetic and combine freely with it, the setters work in every order.
+ * Hierarchy: a coarser level takes the mask by injection (m_{l-1}[I,J,K] = m_l[2I,2J,2K], like eps); below the finest level
+ * u starts at zero, so the fixed points hold the zero error they must; the restriction is unchanged (it reads the zeros the
+ * residual stored); the prolongation skips fine fixed points (masked levels take the point form); at level 0 the
+ * right-hand side of the direct solve is 0 at fixed points and the matrix is mg3d_coarse_matrix_mask -- identity rows
+ * there (a one-level context solves with u's own values at its fixed points).  Restriction and prolongation stay transposes
+ * on the unknowns: the cycle remains a symmetric preconditioner.
+ * Injection loses a body thinner than the coarse spacing -- a one-point plate on an odd plane is gone from every coarse
+ * level -- and plain cycles then converge slowly or GROW: mg3d_vcycle(s) are for bodies that survive on the coarse grids,
+ * mg3d_pcg_solve / mg3d_wpcg_solve are the solvers for thin ones ("Embedded conductors").
+ * Singular cases: the pin of unknown (0,0,0) of level 0 applies iff the condition of mg3d_ctx_set_neumann holds AND level
+ * 0's mask has no fixed unknown; mg3d_wpcg_solve projects iff that condition holds and the FINEST mask has no fixed
+ * unknown (a fixed unknown removes the constants from the kernel).
+ * State, as for mg3d_ctx_set_coefficient: a cycle that has run ahead is finished first with the operator it started with;
+ * a factor of mg3d_ctx_build_coarse is rebuilt, one of mg3d_ctx_set_lu / mg3d_es_setup dropped.  NULL returns to the
+ * context without a mask, bit for bit and with its fused schedules; an all-zero mask is a mask: every grid value and norm
+ * is that of the context without one on the unfused kernels.  With a mask the fused, carried, per-leg and
+ * single-workgroup schedules do not apply (option values kept).  Refused with MG3D_ERR_STATE, nothing changed, on a context
+ * with a mask: mg3d_es_*, mg3d_fmg_initialize, mg3d_fmg_solve, mg3d_fmg_interpolate (full multigrid would need a
+ * mask-aware restriction of d and interpolation).  mg3d_step_advance works as it is: fixed points are Dirichlet values
+ * constant in time, d there is unspecified.  The slab, fp32 and mg3d_host_* forms and the drop-in header have no mask.
+ * mg3d_ctx_set_mask_device: the same from a device array (mg3d_array below) of dtype MG3D_U8 -- nothing else --, any
+ * element strides >= 0; the pointer is checked and the streams joined as for mg3d_ctx_set_coefficient_device.  Every byte
+ * value is valid, so nothing is checked on the device; the call synchronises with the host once, to read back level 0's
+ * mask for the coarse matrix and the numbers of fixed unknowns.  NULL: no mask.
+ * mg3d_ctx_get_mask: the injected mask of a level, dense n^3 (periodic duplicates hold their sources' bytes). */
+int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask); /* finest level, dense N^3 host array; NULL: no mask */
+int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on);
+int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host); /* the injected mask, dense n^3; MG3D_ERR_STATE without one */
+/* (mg3d_ctx_set_mask_device is declared with the other device-array calls, behind mg3d_array) */
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -207,16 +249,17 @@ int mg3d_device_view(mg3d_ctx *ctx, int field, int level, void **dev_ptr, int *p
  * Out of scope: the slab form (mg3d_dist_*), the fp32 solver (mg3d32_*) and the mg3d_host_* forms take host arrays only;
  * half precision and bf16; a persistent zero-copy alias of a field (the run-ahead schedules swap the buffers behind u and
  * d, an alias cannot stay valid).  mg3d_device_view is unchanged. */
-enum { MG3D_F64 = 0, MG3D_F32 = 1 };
+enum { MG3D_F64 = 0, MG3D_F32 = 1, MG3D_U8 = 2 /* bytes: mg3d_ctx_set_mask_device only, which takes nothing else */ };
 typedef struct mg3d_array {
     void *ptr;           /* element (0,0,0), device memory of the context's device */
-    int dtype;           /* MG3D_F64 / MG3D_F32 */
+    int dtype;           /* MG3D_F64 / MG3D_F32 (MG3D_U8: a mask) */
     long long stride[3]; /* in ELEMENTS, for i, j, k */
 } mg3d_array;
 int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *src, void *stream);
 int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *dst, void *stream);
 int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s /* NULL: no source */, void *stream);
 int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps /* NULL: constant operator */, void *stream);
+int mg3d_ctx_set_mask_device(mg3d_ctx *ctx, const mg3d_array *mask /* dtype MG3D_U8 only; NULL: no mask */, void *stream);
 
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)
@@ -626,6 +669,9 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  * mg3d_coarse_matrix_periodic: the same with periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
  * mg3d_coarse_matrix_bc   : the same with periodic axes and Neumann faces (mg3d_ctx_set_neumann): reflected rows for the
  *                           Neumann face unknowns; neumann_faces = 0: mg3d_coarse_matrix_periodic, the same bytes
+ * mg3d_coarse_matrix_mask : the same with fixed points (mg3d_ctx_set_mask; mask dense N^3 bytes): identity rows at the
+ *                           fixed unknowns, and the pin only without one; mask NULL or without a fixed unknown:
+ *                           mg3d_coarse_matrix_bc, the same bytes
  * mg3d_neumann_fold_flux  : a prescribed outward normal derivative g folded into the right-hand side d (dense N^3) of the
  *                           homogeneous Neumann operator: d -= 2*a*g/h at each point of each Neumann face in `faces`, a = 1
  *                           (eps NULL) or 0.5*(eps_face + eps_inner), summed over the faces an edge or corner point lies
@@ -645,6 +691,8 @@ void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps /
                                  int axes); /* host only, A zeroed by caller; axes = 0: _shift / _coef */
 void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
                            int periodic_axes, int neumann_faces); /* host only, A zeroed by caller */
+void mg3d_coarse_matrix_mask(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
+                             int periodic_axes, int neumann_faces, const unsigned char *mask /* NULL: none */);
 int mg3d_neumann_fold_flux(double *d, const double *eps /* NULL: constant */, int N, double h, int faces,
                            const double *const *g);
 void mg3d_lu_factor(double *a, int n);

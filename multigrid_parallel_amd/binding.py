@@ -29,7 +29,7 @@ def lib_path():
 
 _lib = None
 
-MG3D_F64, MG3D_F32 = 0, 1  # mg3d_array.dtype
+MG3D_F64, MG3D_F32, MG3D_U8 = 0, 1, 2  # mg3d_array.dtype (MG3D_U8: mg3d_ctx_set_mask_device only)
 
 
 class mg3d_array(C.Structure):
@@ -73,6 +73,10 @@ SIGNATURES = {
     "mg3d_download_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ap, C.c_void_p]),
     "mg3d_step_set_source_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
     "mg3d_ctx_set_coefficient_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_ctx_set_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte)]),
+    "mg3d_ctx_set_mask_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_ctx_has_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mg3d_ctx_get_mask": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte)]),
     "mg3d_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mg3d_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_smooth_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, dp]),
@@ -147,6 +151,7 @@ SIGNATURES = {
     "mg3d_coarse_matrix_coef": (None, [dp, C.c_int, C.c_double, dp, C.c_double]),
     "mg3d_coarse_matrix_periodic": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int]),
     "mg3d_coarse_matrix_bc": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int]),
+    "mg3d_coarse_matrix_mask": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]),
     "mg3d_neumann_fold_flux": (C.c_int, [dp, dp, C.c_int, C.c_double, C.c_int, C.POINTER(dp)]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
@@ -400,6 +405,36 @@ class Solver:
         check(self.L.mg3d_ctx_get_coefficient(self._h, level, P(out)))
         return out.reshape(n, n, n)
 
+    def set_mask(self, mask):
+        """mg3d_ctx_set_mask: fixed points inside the domain (embedded conductors).  mask is bool or uint8, (N, N, N) or
+        flat, nonzero = fixed: u there keeps what was uploaded and acts as a Dirichlet value, like a point on a Dirichlet
+        face; coarser levels take the mask by injection.  None: no mask again.  Plain cycles are for bodies that survive on
+        the coarse grids; pcg_solve / wpcg_solve are the solvers for thin ones.  Rebuilds a coarse factor of get_details();
+        drops one given to set_lu."""
+        if mask is None:
+            check(self.L.mg3d_ctx_set_mask(self._h, None))
+            return
+        mask = np.asarray(mask)
+        if mask.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise TypeError(f"set_mask: need bool or uint8, got {mask.dtype}")
+        if mask.size != self.N ** 3 or mask.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"set_mask: need shape ({self.N},)*3 or ({self.N ** 3},), got {mask.shape}")
+        m = np.ascontiguousarray(mask).reshape(-1).view(np.uint8)
+        check(self.L.mg3d_ctx_set_mask(self._h, m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    def has_mask(self):
+        on = C.c_int(0)
+        check(self.L.mg3d_ctx_has_mask(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def get_mask(self, level=None):
+        """the injected mask of a level as the kernels use it, (n, n, n) uint8"""
+        level = self.num_levels - 1 if level is None else level
+        n = self.level_n(level)
+        out = np.empty(n ** 3, dtype=np.uint8)
+        check(self.L.mg3d_ctx_get_mask(self._h, level, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out.reshape(n, n, n)
+
     def set_periodic(self, axes):
         """mg3d_ctx_set_periodic: periodic boundaries on the axes given as a mask (MG3D_PERIODIC_I = 1, _J = 2, _K = 4) or
         as an iterable of axis indices 0, 1, 2; 0 or () gives Dirichlet faces everywhere again.  On a periodic axis index
@@ -563,6 +598,24 @@ class Solver:
             return
         a, stream = _device_args(t, "step_set_source_tensor", (self.N,) * 3)
         check(self.L.mg3d_step_set_source_device(self._h, C.byref(a), stream))
+
+    def set_mask_tensor(self, t):
+        """mg3d_ctx_set_mask_device: set_mask from an (N, N, N) torch.bool or torch.uint8 tensor on the GPU, any view
+        (permuted, sliced, expanded); ordered on the tensor's current stream.  None: no mask."""
+        if t is None:
+            check(self.L.mg3d_ctx_set_mask_device(self._h, None, None))
+            return
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"set_mask_tensor: need a torch.Tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"set_mask_tensor: need torch.bool or torch.uint8, got {t.dtype}")
+        if tuple(t.shape) != (self.N,) * 3:
+            raise ValueError(f"set_mask_tensor: need shape {(self.N,) * 3}, got {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise ValueError(f"set_mask_tensor: need a tensor on the GPU, got device {t.device}")
+        a = mg3d_array(t.data_ptr(), MG3D_U8, (C.c_longlong * 3)(*t.stride()))
+        check(self.L.mg3d_ctx_set_mask_device(self._h, C.byref(a), C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)))
 
     def set_coefficient_tensor(self, t):
         """mg3d_ctx_set_coefficient_device: set_coefficient from an (N, N, N) tensor on the GPU; checked on the device

@@ -37,6 +37,12 @@ struct mg3d_ctx {
      * layout (empty: the constant-coefficient operator) and level 0's, dense, for the coarse matrix */
     std::vector<double *> eps;
     std::vector<double> eps0;
+    /* fixed points (mg3d_ctx_set_mask): one byte per point of every level in the padded layout, the finest level's as given
+     * and the others' by injection (empty: no mask); level 0's, dense, for the coarse matrix; and how many fixed UNKNOWNS
+     * level 0 and the finest level have under the present boundary masks (recounted when those change) */
+    std::vector<unsigned char *> mask;
+    std::vector<unsigned char> mask0;
+    unsigned long long mask_fixed0 = 0, mask_fixed_top = 0;
     /* periodic axes (mg3d_ctx_set_periodic; MG3D_PERIODIC_* mask, 0: Dirichlet faces everywhere) and the padded level-0
      * right-hand side of the direct solve that k_per_coarse_rhs builds from d (allocated with the first nonzero mask) */
     int periodic;
@@ -126,22 +132,29 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
  * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
  * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
- * transfers k_restrict / k_prolong launch for a boundary word */
+ * transfers k_restrict / k_prolong launch for a boundary word, nor with fixed points, whose levels run the MASK forms */
 static inline bool mg3d_fused(const mg3d_ctx *ctx)
 {
-    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0;
+    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty();
+}
+/* the fixed-point bytes of a level for the launchers (NULL: the context has no mask) */
+static inline const unsigned char *mg3d_ctx_mask(const mg3d_ctx *ctx, int level)
+{
+    return ctx->mask.empty() ? nullptr : ctx->mask[level];
 }
 /* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */
 static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodic, ctx->neumann); }
-/* sigma = 0 and every axis periodic or Neumann on both faces: constants are in the kernel, unknown (0,0,0) of level 0 is
- * pinned */
+/* sigma = 0, every axis periodic or Neumann on both faces and no fixed unknown on level 0: constants are in the kernel of
+ * the coarsest operator, unknown (0,0,0) of level 0 is pinned */
 static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
 {
     bool closed = true;
     for (int ax = 0; ax < 3; ax++)
         closed = closed && ((ctx->periodic >> ax & 1) || (ctx->neumann >> (2 * ax) & 3) == 3);
-    return closed && ctx->sigma == 0.;
+    return closed && ctx->sigma == 0. && ctx->mask_fixed0 == 0;
 }
+/* ... and none on the finest level either: the system itself is singular (mg3d_wpcg_solve projects) */
+static inline bool mg3d_ctx_singular(const mg3d_ctx *ctx) { return mg3d_ctx_pinned(ctx) && ctx->mask_fixed_top == 0; }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty) */
 void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
 /* scoped event pair of the timers (mg3d_timing_enable): a stage of the reference's timing table on level l, or
@@ -173,7 +186,7 @@ int mg3d_drop_carry_keep(mg3d_ctx *ctx); /* the same without clearing red_tail: 
  * two-way join of the caller's stream with the context's -- out = false, before the kernel: the context's stream waits for
  * what the caller's stream holds now; out = true, behind it: the caller's stream waits for what the context's holds now.
  * No host synchronisation. */
-int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who);
+int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who, bool bytes = false /* MG3D_U8 and nothing else: a mask */);
 int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *who);
 
 #endif

@@ -171,6 +171,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
     free_lu(ctx);
     for (double *e : ctx->eps)
         (void)hipFree(e);
+    for (unsigned char *m : ctx->mask)
+        (void)hipFree(m);
     if (ctx->per_b)
         (void)hipFree(ctx->per_b);
     for (double *v : ctx->pcg_v)
@@ -643,7 +645,10 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    if (ctx->periodic || ctx->neumann)
+    if (!ctx->mask.empty())
+        mg3d_coarse_matrix_mask(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
+                                ctx->neumann, ctx->mask0.data());
+    else if (ctx->periodic || ctx->neumann)
         mg3d_coarse_matrix_bc(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
                               ctx->neumann);
     else if (ctx->eps.empty())
@@ -789,11 +794,13 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
 }
 
 /* Device arrays (mg3d_array, include/mg3d.h): the descriptor checks and the stream join of every mg3d_*_device entry point. */
-int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who)
+int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who, bool bytes)
 {
     if (!a || !a->ptr)
         return fail(MG3D_ERR_ARG, "%s: NULL array", who);
-    if (a->dtype != MG3D_F64 && a->dtype != MG3D_F32)
+    if (bytes && a->dtype != MG3D_U8)
+        return fail(MG3D_ERR_ARG, "%s: dtype %d (MG3D_U8)", who, a->dtype);
+    if (!bytes && a->dtype != MG3D_F64 && a->dtype != MG3D_F32)
         return fail(MG3D_ERR_ARG, "%s: dtype %d (MG3D_F64 or MG3D_F32)", who, a->dtype);
     for (int ax = 0; ax < 3; ax++)
         if (a->stride[ax] < (writable ? 1 : 0))
@@ -915,6 +922,188 @@ extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
     return MG3D_OK;
 }
 
+/* Fixed points (mg3d_ctx_set_mask, mg3d_kernels.hip): one byte per point of every level. */
+static void free_mask(mg3d_ctx *ctx)
+{
+    for (unsigned char *m : ctx->mask)
+        (void)hipFree(m);
+    ctx->mask.clear();
+    ctx->mask0.clear();
+    ctx->mask_fixed0 = ctx->mask_fixed_top = 0;
+}
+
+/* The fixed UNKNOWNS of level 0 and of the finest level under the present boundary masks, and level 0's bytes on the host
+ * for the coarse matrix.  One host synchronisation.  (The context has a mask and io_chk.) */
+static int mask_recount(mg3d_ctx *ctx, const char *who)
+{
+    const Level &l0 = ctx->lv[0], &top = ctx->lv[ctx->L - 1];
+    const int N0 = l0.g.N, bc = mg3d_ctx_bc(ctx);
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof cnt, ctx->stream));
+    k_mask_count(l0.g, ctx->mask[0], bc, ctx->io_chk, ctx->stream);
+    k_mask_count(top.g, ctx->mask[ctx->L - 1], bc, ctx->io_chk + 1, ctx->stream);
+    HIPCHK(hipMemcpyAsync(cnt, ctx->io_chk, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->mask0.resize((size_t)N0 * N0 * N0);
+    HIPCHK(hipMemcpy2DAsync(ctx->mask0.data(), N0, ctx->mask[0], l0.g.pitch, N0, (size_t)N0 * N0, hipMemcpyDeviceToHost,
+                            ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
+    ctx->mask_fixed0 = cnt[0];
+    ctx->mask_fixed_top = cnt[1];
+    return MG3D_OK;
+}
+
+/* a mask whose bytes or counts could not be brought up to date (a HIP error): no half-installed mask stays behind -- the
+ * context is left without one, and without a factor of the operator that had it.  The first error is the one reported. */
+static int mask_abandon(mg3d_ctx *ctx, int rc)
+{
+    (void)hipStreamSynchronize(ctx->stream);
+    free_mask(ctx);
+    (void)operator_changed(ctx);
+    return rc;
+}
+
+/* the mask from a checked device array: the cycle that has run ahead, then everything that can fail for want of memory
+ * (nothing has changed when it does), the pack into the finest level (duplicates from their sources), the injections, the
+ * counts, the coarse factor */
+static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
+{
+    const int L = ctx->L;
+    CHK(mg3d_drop_carry(ctx));
+    auto alloc_fail = [&](hipError_t rc) {
+        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
+    };
+    if (!ctx->io_chk) {
+        const hipError_t rc = hipMalloc(&ctx->io_chk, 2 * sizeof(unsigned long long));
+        if (rc != hipSuccess) {
+            ctx->io_chk = nullptr;
+            return alloc_fail(rc);
+        }
+    }
+    if (!ctx->per_b) { /* the right-hand side of the direct solve (k_mask_coarse_rhs) */
+        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
+        if (rc != hipSuccess) {
+            ctx->per_b = nullptr;
+            return alloc_fail(rc);
+        }
+    }
+    std::vector<unsigned char *> m = ctx->mask;
+    if (m.empty()) {
+        m.assign(L, nullptr);
+        for (int l = 0; l < L; l++) {
+            hipError_t rc = hipMalloc(&m[l], ctx->lv[l].elems);
+            if (rc == hipSuccess)
+                rc = hipMemsetAsync(m[l], 0, ctx->lv[l].elems, ctx->stream); /* (the row padding) */
+            if (rc == hipSuccess)
+                continue;
+            (void)hipStreamSynchronize(ctx->stream);
+            for (unsigned char *q : m)
+                if (q)
+                    (void)hipFree(q);
+            return alloc_fail(rc);
+        }
+    }
+    ctx->mask = m;
+    const int bc = mg3d_ctx_bc(ctx);
+    {
+        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
+        k_mask_pack(ctx->lv[L - 1].g, ctx->mask[L - 1], a, bc, ctx->stream);
+    }
+    for (int l = L - 1; l >= 1; l--)
+        k_mask_inject(ctx->lv[l].g, ctx->mask[l], ctx->lv[l - 1].g, ctx->mask[l - 1], ctx->stream);
+    const int rc = mask_recount(ctx, who);
+    if (rc != MG3D_OK)
+        return mask_abandon(ctx, rc);
+    return operator_changed(ctx);
+}
+
+static int mask_clear(mg3d_ctx *ctx)
+{
+    CHK(mg3d_drop_carry(ctx));
+    if (ctx->mask.empty())
+        return MG3D_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read the bytes */
+    free_mask(ctx);
+    return operator_changed(ctx);
+}
+
+extern "C" int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask)
+{
+    static const char who[] = "mg3d_ctx_set_mask";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!mask)
+        return mask_clear(ctx);
+    /* through a dense device copy and the pack of the device form: one code path writes the levels */
+    const long long N = ctx->lv[ctx->L - 1].g.N, n = N * N * N;
+    unsigned char *tmp = nullptr;
+    const hipError_t rc = hipMalloc(&tmp, (size_t)n);
+    if (rc != hipSuccess)
+        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
+    int out = MG3D_OK;
+    const hipError_t cp = hipMemcpyAsync(tmp, mask, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+    if (cp != hipSuccess)
+        out = fail(MG3D_ERR_HIP, "%s: hipMemcpyAsync: %s", who, hipGetErrorString(cp));
+    else {
+        const mg3d_array a = {tmp, MG3D_U8, {N * N, N, 1}};
+        out = mask_install(ctx, a, who);
+    }
+    (void)hipStreamSynchronize(ctx->stream); /* (the host array and the copy may go once the call returns) */
+    (void)hipFree(tmp);
+    return out;
+}
+
+/* the device form: the descriptor is checked before anything happens; every byte value is valid, so there is no check on
+ * the device; the one host synchronisation is mask_recount's, behind which the array has been read */
+extern "C" int mg3d_ctx_set_mask_device(mg3d_ctx *ctx, const mg3d_array *mask, void *stream)
+{
+    static const char who[] = "mg3d_ctx_set_mask_device";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!mask)
+        return mask_clear(ctx);
+    CHK(mg3d_array_check(ctx, mask, false, who, true));
+    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
+    return mask_install(ctx, *mask, who);
+}
+
+extern "C" int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on)
+{
+    if (!ctx || !on)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_mask: NULL argument");
+    *on = ctx->mask.empty() ? 0 : 1;
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host)
+{
+    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_mask"));
+    if (!host)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_mask: NULL host pointer");
+    if (ctx->mask.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_mask: no mask set");
+    const Level &l = ctx->lv[level];
+    const int N = l.g.N;
+    HIPCHK(hipMemcpy2DAsync(host, N, ctx->mask[level], l.g.pitch, N, (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MG3D_OK;
+}
+
+/* the boundary masks changed under a mask: the duplicates of a periodic axis take their sources' bytes -- for good: the
+ * caller's bytes there are not kept, an axis that stops being periodic finds its plane N-1 with plane 0's bytes -- and which
+ * fixed points are unknowns is counted again; then the coarse factor, as for every change of the operator */
+static int mask_boundary_changed(mg3d_ctx *ctx, const char *who)
+{
+    if (ctx->mask.empty())
+        return operator_changed(ctx);
+    for (int l = 0; l < ctx->L; l++)
+        k_mask_refresh(ctx->lv[l].g, ctx->mask[l], mg3d_ctx_bc(ctx), ctx->stream);
+    const int rc = mask_recount(ctx, who);
+    if (rc != MG3D_OK)
+        return mask_abandon(ctx, rc);
+    return operator_changed(ctx);
+}
+
 /* The boundary masks changed from (periodic, neumann) = (per0, neu0): the coarse faces that the restriction weighted are
  * injections again (and vice versa), so every level's are redone; and on a face that was a face of unknowns and is a
  * Dirichlet face now, r of every level still holds the residuals of the other operator where a Dirichlet cycle never
@@ -967,7 +1156,7 @@ extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
     const int per0 = ctx->periodic;
     ctx->periodic = axes;
     boundary_changed(ctx, per0, ctx->neumann);
-    return operator_changed(ctx);
+    return mask_boundary_changed(ctx, "mg3d_ctx_set_periodic");
 }
 
 extern "C" int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes)
@@ -1006,7 +1195,7 @@ extern "C" int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces)
     const int neu0 = ctx->neumann;
     ctx->neumann = faces;
     boundary_changed(ctx, ctx->periodic, neu0);
-    return operator_changed(ctx);
+    return mask_boundary_changed(ctx, "mg3d_ctx_set_neumann");
 }
 
 extern "C" int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces)
@@ -1221,14 +1410,15 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     const int c1 = post ? 0 : 1;
     const LevelOp op = mg3d_op(ctx, l);
     const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
+    const unsigned char *m = mg3d_ctx_mask(ctx, level);
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), c1 ^ (it & 1), s);
+        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), c1 ^ (it & 1), s, -1, -1, m);
     }
     if (want_res) {
         StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
         k_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), want_res == 2 ? l.f[MG3D_R] : nullptr,
-                   ctx->partials, ctx->sumsq + slot, s);
+                   ctx->partials, ctx->sumsq + slot, s, -1, -1, 0, -1, m);
     }
     return MG3D_OK;
 }
@@ -1250,7 +1440,7 @@ static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
 static void enqueue_prolong(mg3d_ctx *ctx, int level)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
+    k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream, -1, -1, mg3d_ctx_mask(ctx, level));
 }
 
 /* periodic: the factor of mg3d_coarse_matrix_bc solves for b = d with 0 in the identity rows of the duplicates and, in
@@ -1261,6 +1451,15 @@ static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* N
     Level &l0 = ctx->lv[0];
     if (!rhs)
         rhs = l0.f[MG3D_D];
+    if (!ctx->mask.empty()) {
+        /* fixed points: 0 in their identity rows too (mg3d_coarse_matrix_mask) -- the zero error they hold; a one-level
+         * context has no cycle above the solve, its fixed points keep u's own values */
+        k_mask_coarse_rhs(l0.g, rhs, ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->mask[0],
+                          ctx->L == 1 ? l0.f[MG3D_U] : nullptr, ctx->stream);
+        k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
+        k_per_refresh(l0.g, l0.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
+        return;
+    }
     if (ctx->periodic || (ctx->neumann && mg3d_ctx_pinned(ctx))) {
         k_per_coarse_rhs(l0.g, rhs, ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->stream);
         k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
@@ -1850,6 +2049,8 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
+    if (!ctx->mask.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: no coarse LU set");
     if (ctx->have_es)
@@ -1872,6 +2073,8 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
  * that keep the interpolated guess (keep_guess of mg3d_enqueue_vcycle). */
 static int fmg_check(mg3d_ctx *ctx, const char *who)
 {
+    if (!ctx->mask.empty()) /* (full multigrid would need a mask-aware restriction of d and interpolation) */
+        return fail(MG3D_ERR_STATE, "%s: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL", who);
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "%s: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)", who);
     if (ctx->have_es)

@@ -167,33 +167,23 @@ void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, 
             }
 }
 
-/* The coarsest matrix with periodic axes and Neumann faces (mg3d_ctx_set_neumann; faces a MG3D_NEUMANN_* mask with no bit
- * on a periodic axis).  faces = 0: mg3d_coarse_matrix_periodic, the same bytes.  Otherwise its rows, except that a point
- * on a Neumann face is an unknown unless it lies on a Dirichlet face, and its row is the row of the kernels of
- * mg3d_kernels.hip with the neighbour across the face reflected (i-1 at 0 is 1, i+1 at N-1 is N-2): the two coincide, so
- * that column receives the sum of both entries, added in the kernels' operand order (i-, i+, j-, j+, k-, k+).  The pin
- * (identity row of point (0,0,0)) applies when sigma = 0 and every axis is periodic or Neumann on both faces.
- * Reflection does not widen the band.  A must be zero on entry. */
-void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double sigma, int axes, int faces)
+/* the rows of mg3d_coarse_matrix_bc for any axes and faces; pin: identity row at (0,0,0); mask (may be NULL): identity
+ * rows at its nonzero bytes too */
+static void bc_rows(double *A, int N, double h, const double *eps, double sigma, int axes, int faces, int pin,
+                    const unsigned char *mask)
 {
-    if (faces == 0) {
-        mg3d_coarse_matrix_periodic(A, N, h, eps, sigma, axes);
-        return;
-    }
     const long NN = (long)N * N, n = NN * N;
     const double hSq = h * h;
     const double invHsq = 1. / hSq;
     const double shift = sigma * hSq;
     const double dg0 = 6. + shift;
     const double off = 1. * invHsq, diag = dg0 * invHsq;
-    int per[3], rlo[3], rhi[3], closed = 1;
+    int per[3], rlo[3], rhi[3];
     for (int ax = 0; ax < 3; ax++) {
         per[ax] = (axes >> ax) & 1;
         rlo[ax] = (faces >> (2 * ax)) & 1;
         rhi[ax] = (faces >> (2 * ax + 1)) & 1;
-        closed = closed && (per[ax] || (rlo[ax] && rhi[ax]));
     }
-    const int pin = closed && sigma == 0.;
     const long st[3] = {NN, N, 1};
     long p = 0;
     for (int i = 0; i < N; i++)
@@ -201,7 +191,7 @@ void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double
             for (int k = 0; k < N; k++, p++) {
                 double *row = A + p * n;
                 const int x[3] = {i, j, k};
-                int fixed = pin && p == 0;
+                int fixed = (pin && p == 0) || (mask && mask[p]);
                 long q[6];
                 for (int ax = 0; ax < 3; ax++) {
                     if (per[ax] ? x[ax] == N - 1 : ((x[ax] == 0 && !rlo[ax]) || (x[ax] == N - 1 && !rhi[ax])))
@@ -230,6 +220,62 @@ void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double
                     row[q[t]] += a[t] * invHsq;
                 row[p] = -(dg * invHsq);
             }
+}
+
+/* sigma = 0 and every axis periodic or Neumann on both faces: constants are in the kernel */
+static int bc_closed(double sigma, int axes, int faces)
+{
+    int closed = 1;
+    for (int ax = 0; ax < 3; ax++)
+        closed = closed && (((axes >> ax) & 1) || ((faces >> (2 * ax)) & 3) == 3);
+    return closed && sigma == 0.;
+}
+
+/* The coarsest matrix with periodic axes and Neumann faces (mg3d_ctx_set_neumann; faces a MG3D_NEUMANN_* mask with no bit
+ * on a periodic axis).  faces = 0: mg3d_coarse_matrix_periodic, the same bytes.  Otherwise its rows, except that a point
+ * on a Neumann face is an unknown unless it lies on a Dirichlet face, and its row is the row of the kernels of
+ * mg3d_kernels.hip with the neighbour across the face reflected (i-1 at 0 is 1, i+1 at N-1 is N-2): the two coincide, so
+ * that column receives the sum of both entries, added in the kernels' operand order (i-, i+, j-, j+, k-, k+).  The pin
+ * (identity row of point (0,0,0)) applies when sigma = 0 and every axis is periodic or Neumann on both faces.
+ * Reflection does not widen the band.  A must be zero on entry. */
+void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double sigma, int axes, int faces)
+{
+    if (faces == 0) {
+        mg3d_coarse_matrix_periodic(A, N, h, eps, sigma, axes);
+        return;
+    }
+    bc_rows(A, N, h, eps, sigma, axes, faces, bc_closed(sigma, axes, faces), NULL);
+}
+
+/* The coarsest matrix with fixed points (mg3d_ctx_set_mask): mg3d_coarse_matrix_bc with identity rows at the fixed
+ * unknowns -- nonzero bytes of mask (dense N^3) on points that are neither periodic duplicates nor on a Dirichlet face;
+ * the other bytes are ignored.  The columns of a fixed point stay: its value is the right-hand side of its row, 0 in a
+ * cycle.  A fixed unknown removes the constants from the kernel, so the pin of (0,0,0) applies only without one.  mask NULL
+ * or without a fixed unknown: mg3d_coarse_matrix_bc, the same bytes.  A must be zero on entry. */
+void mg3d_coarse_matrix_mask(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
+                             const unsigned char *mask)
+{
+    long fixed = 0;
+    if (mask) {
+        long p = 0;
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++)
+                for (int k = 0; k < N; k++, p++) {
+                    const int x[3] = {i, j, k};
+                    int unknown = 1;
+                    for (int ax = 0; ax < 3; ax++) {
+                        const int per = (axes >> ax) & 1, rlo = (faces >> (2 * ax)) & 1, rhi = (faces >> (2 * ax + 1)) & 1;
+                        if (per ? x[ax] == N - 1 : ((x[ax] == 0 && !rlo) || (x[ax] == N - 1 && !rhi)))
+                            unknown = 0;
+                    }
+                    fixed += unknown && mask[p];
+                }
+    }
+    if (!fixed) {
+        mg3d_coarse_matrix_bc(A, N, h, eps, sigma, axes, faces);
+        return;
+    }
+    bc_rows(A, N, h, eps, sigma, axes, faces, 0, mask);
 }
 
 /* A prescribed outward normal derivative folded into the right-hand side of the homogeneous Neumann operator (mg3d.h) */

@@ -106,11 +106,13 @@ const char *mg3d_option_key(int index);           /* NULL past the end */
  * then reduces them, in a fixed order, into *sumsq_out.  Windows as k_sweep's: i_lo / i_hi the local planes produced,
  * acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
 static inline int mg3d_bc(int periodic, int neumann) { return periodic | neumann << 3; }
+/* m (optional, single-domain levels): the level's fixed-point bytes in the padded layout (mg3d_ctx_set_mask) -- the colour
+ * pass skips a fixed point, the residual is 0. there, apply_dot's q is 0. there, the prolongation skips it */
 void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int bc, int color, hipStream_t s, int i_lo = -1, int i_hi = -1);
+                    int bc, int color, hipStream_t s, int i_lo = -1, int i_hi = -1, const unsigned char *m = nullptr);
 void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
                 int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
-                int acc_lo = 0, int acc_hi = -1);
+                int acc_lo = 0, int acc_hi = -1, const unsigned char *m = nullptr);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
 /* The vector passes of mg3d_pcg_solve and mg3d_wpcg_solve on a single-domain level, bc the boundary word.  Each
  * touches the unknowns alone, the set the residual counts; sums are per-block partials folded in a fixed order into one
@@ -123,7 +125,7 @@ void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out
  *   dot         : *dot_out = sum of a*b
  *   direction   : beta = *rz_new / *rz_old; p = z + beta p */
 int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
-                    double *partials, double *dot_out, hipStream_t s);
+                    double *partials, double *dot_out, hipStream_t s, const unsigned char *m = nullptr);
 int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
                       const double *pap, double *partials, double *rr_out, hipStream_t s);
 int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s);
@@ -153,7 +155,7 @@ int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *s
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s, int ic_lo = -1,
                 int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);
 void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo = -1,
-               int if_hi = -1);
+               int if_hi = -1, const unsigned char *mf = nullptr /* the fine level's fixed points: the point form, skipping them */);
 /* BCFunc(i*h, j*h, k*h) = x*x - 2*y*y + z*z on the six faces of a field (mg_3d.h:89-90, 1147-1239) */
 void k_fill_boundary(const Geom &g, double *v, double h, hipStream_t s);
 /* folds np per-block partial sums, in a fixed order, into *out */
@@ -323,6 +325,17 @@ void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec,
  * in the duplicates' and the pinned point's identity rows) and a duplicate refresh */
 void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s);
 void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
+/* fixed points (mg3d_ctx_set_mask): one byte per point of a single-domain level in the padded layout (the doubles' index).
+ * k_mask_pack: the caller's dense-indexed bytes (mg3d_array of MG3D_U8, any strides) into it, periodic duplicates taking
+ * their sources'; k_mask_inject / k_mask_refresh: the coarser level's bytes by injection, the duplicates' from their sources;
+ * k_mask_count: *out += the number of fixed UNKNOWNS (no duplicate, on no Dirichlet face); k_mask_coarse_rhs: k_per_coarse_rhs
+ * with, at the fixed unknowns, 0. -- or ufix there when given (a one-level context) */
+void k_mask_pack(const Geom &g, unsigned char *m, const mg3d_array &a, int bc, hipStream_t s);
+void k_mask_inject(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s);
+void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s);
+void k_mask_count(const Geom &g, const unsigned char *m, int bc, unsigned long long *out, hipStream_t s);
+void k_mask_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
+                       hipStream_t s);
 /* full multigrid (mg3d_fmg_solve): every unknown of the fine level (and its periodic duplicates) overwritten with the
  * tensor-product cubic interpolant of the coarse u -- never a Dirichlet point; and d = u at the Dirichlet points of a level,
  * the right-hand side of the direct solve's identity rows.  Single-domain levels, bc the boundary word */

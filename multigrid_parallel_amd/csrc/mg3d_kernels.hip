@@ -48,6 +48,12 @@
  *   - Prolongation: unchanged -- every parent of a fine face point lies on the same face.
  *   tests/_neumann_ref.py states the same in numpy.
  *
+ * Fixed points (mg3d_ctx_set_mask): a level may carry one byte per point in its padded layout (the index of the doubles),
+ * nonzero = fixed.  A fixed unknown is a Dirichlet point: the colour pass skips it, the residual is 0. there (stored as
+ * 0., d not read, +0. into the norm), q = A p is 0. there, the prolongation skips it; its neighbours read it through the
+ * ordinary stencil.  Bytes on Dirichlet faces lie outside every launch; bytes on periodic duplicates are never read.
+ * Coarse levels take the mask by injection.  tests/_mask_ref.py states the same in numpy.
+ *
  * The launchers take both masks as one boundary word bc = periodic axes | Neumann faces << 3 (mg3d_bc); the stencil
  * kernels are instantiated per boundary mode: BC_PLAIN (bc = 0), BC_WRAP (periodic axes only), BC_REFLECT (a Neumann
  * face, with or without periodic axes).
@@ -71,25 +77,48 @@ __device__ __forceinline__ long long gidx(const Geom &g, int i, int j, int k)
 /* boundary modes of the stencil kernels and the bits of the boundary word */
 enum { BC_PLAIN = 0, BC_WRAP = 1, BC_REFLECT = 2 };
 static inline int bc_mode(int bc) { return (bc >> 3) ? BC_REFLECT : (bc ? BC_WRAP : BC_PLAIN); }
-/* the one launch ladder: f(coef, mode) with eps set or not and the boundary mode of bc as compile-time constants --
- * dispatch_op(e, bc, [&](auto coef, auto mode) { hipLaunchKernelGGL((kernel<coef(), mode()>), ...); }) */
+/* the one launch ladder: f(coef, mode, mask) with eps set or not, the boundary mode of bc and whether the level has fixed
+ * points (m) as compile-time constants --
+ * dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) { launch_op(mask, OP_KERNELS(kernel, coef(), mode()), ...); }) */
 template <class F>
-static void dispatch_op(const double *e, int bc, F f)
+static void dispatch_op(const double *e, int bc, const unsigned char *m, F f)
 {
-    const auto with_mode = [&](auto coef) {
+    const auto with_mode = [&](auto coef, auto mask) {
         switch (bc_mode(bc)) {
         case BC_REFLECT:
-            return f(coef, std::integral_constant<int, BC_REFLECT>());
+            return f(coef, std::integral_constant<int, BC_REFLECT>(), mask);
         case BC_WRAP:
-            return f(coef, std::integral_constant<int, BC_WRAP>());
+            return f(coef, std::integral_constant<int, BC_WRAP>(), mask);
         default:
-            return f(coef, std::integral_constant<int, BC_PLAIN>());
+            return f(coef, std::integral_constant<int, BC_PLAIN>(), mask);
         }
     };
-    if (e)
-        with_mode(std::true_type());
+    const auto with_coef = [&](auto mask) {
+        if (e)
+            with_mode(std::true_type(), mask);
+        else
+            with_mode(std::false_type(), mask);
+    };
+    if (m)
+        with_coef(std::true_type());
     else
-        with_mode(std::false_type());
+        with_coef(std::false_type());
+}
+/* MASK, the third constant of the family: the kernel takes the level's fixed-point bytes as one more, LAST argument.  The
+ * MASK = false instantiation has no such argument at all -- its argument list, and with it its code, is what it was before
+ * the flag existed.  launch_op appends m for the instantiation that takes it. */
+typedef const unsigned char *__restrict__ MaskPtr;
+__device__ __forceinline__ bool mask_fixed(long long) { return false; }
+__device__ __forceinline__ bool mask_fixed(long long p, const unsigned char *m) { return m[p] != 0; }
+#define OP_KERNELS(kernel, ...) kernel<__VA_ARGS__, false>, kernel<__VA_ARGS__, true, MaskPtr>
+template <class Mask, class... P0, class... P1, class... A>
+static void launch_op(Mask, void (*plain)(P0...), void (*masked)(P1...), dim3 grid, dim3 block, hipStream_t s,
+                      const unsigned char *m, A... args)
+{
+    if constexpr (Mask::value)
+        hipLaunchKernelGGL(masked, grid, block, 0, s, args..., m);
+    else
+        hipLaunchKernelGGL(plain, grid, block, 0, s, args...);
 }
 /* is the low / high face of axis ax (0 i, 1 j, 2 k) a Neumann face */
 __host__ __device__ __forceinline__ bool bc_ref_lo(int bc, int ax) { return (bc >> (3 + 2 * ax)) & 1; }
@@ -104,6 +133,17 @@ __device__ __forceinline__ long long nb_lo(int x, int N, bool per, bool rlo, lon
 __device__ __forceinline__ long long nb_hi(int x, int N, bool per, bool rhi, long long st)
 {
     return (per && x == N - 2) ? -(N - 2) * st : ((rhi && x == N - 1) ? -st : st);
+}
+
+/* is (i, j, k) an unknown of a single-domain level: no periodic duplicate, on no Dirichlet face */
+__device__ __forceinline__ bool bc_unknown(int bc, int N, int i, int j, int k)
+{
+    const int x[3] = {i, j, k};
+    bool unk = true;
+    for (int ax = 0; ax < 3; ax++)
+        unk = unk && ((bc >> ax & 1) ? x[ax] != N - 1
+                                     : !((x[ax] == 0 && !bc_ref_lo(bc, ax)) || (x[ax] == N - 1 && !bc_ref_hi(bc, ax))));
+    return unk;
 }
 
 /* x to p and to every duplicate of p: di / dj / dk say whether p lies on the periodic face 0 of that axis */
@@ -127,6 +167,8 @@ __device__ __forceinline__ void store_dup(const Geom &g, double *__restrict__ a,
  *   BC    the boundary mode: BC_PLAIN folds to the plain offsets; BC_WRAP an axis is periodic: wrapped neighbour offsets
  *         and duplicate stores; BC_REFLECT a face is a Neumann face: reflected offsets there, the unknowns of an axis are
  *         [lo, hi], and whatever axis is periodic beside it wraps as in BC_WRAP
+ *   MASK  the level has fixed points: one byte per point and pass, read where the point's own d would be (lanes
+ *         contiguous in k, as the walk has them); the bytes are the pack M of one trailing argument
  * The residual and the colour pass with eps give each thread one (j, k) column of `chunk` planes, lanes contiguous in
  * k, and keep the i-1 / i / i+1 values of v (and eps) of the column in registers; the constant colour pass gives a lane
  * one k-pair of a row (measured at 513^3 the column form of that pass took 0.76 ms against 0.64 ms).
@@ -291,10 +333,11 @@ __device__ __forceinline__ void walk_column(const Geom &g, const Column &c, cons
  * Constant operator: each lane owns the k-pair (2m, 2m+1) of one row and updates the member whose colour is being
  * swept.  A periodic level is single-domain (ig0 = 0, ni = nj = nk = N): with PER its range and colour come from N and
  * axes alone -- taken from i_lo, ig0, nj and nk the launch ran 3.5 % slower at 257^3. */
-template <int BC>
+template <int BC, bool MASK, class... M>
 __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ d,
-                                                           double hSq, double sixth, int color, int bc, int i_lo)
+                                                           double hSq, double sixth, int color, int bc, int i_lo, M... fixed)
 {
+    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
     constexpr bool REF = BC == BC_REFLECT;
     const bool pi = BC && (bc & 1), pj = BC && (bc & 2), pk = BC && (bc & 4);
     const bool ril = REF && bc_ref_lo(bc, 0), rih = REF && bc_ref_hi(bc, 0), rjl = REF && bc_ref_lo(bc, 1),
@@ -308,6 +351,9 @@ __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__res
     if (k < ((pk || rkl) ? 0 : 1) || k > (BC ? g.N : g.nk) - (rkh ? 1 : 2))
         return;
     const long long p = gidx(g, i, j, k);
+    if constexpr (MASK)
+        if (mask_fixed(p, fixed...))
+            return;
     double s = v[p + nb_lo(i, g.N, pi, ril, g.plane)] + v[p + nb_hi(i, g.N, pi, rih, g.plane)];
     s = s + v[p + nb_lo(j, g.N, pj, rjl, g.pitch)];
     s = s + v[p + nb_hi(j, g.N, pj, rjh, g.pitch)];
@@ -318,11 +364,12 @@ __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__res
 }
 
 /* eps set: a thread updates the points of its column that have colour `color` (every other plane) */
-template <int BC>
+template <int BC, bool MASK, class... M>
 __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ e,
                                                          const double *__restrict__ d, double hSq, double shift,
-                                                         int color, int bc, int chunk, int i_lo, int i_hi)
+                                                         int color, int bc, int chunk, int i_lo, int i_hi, M... fixed)
 {
+    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
     Column c;
     if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
@@ -331,6 +378,9 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
     walk_column<true>(g, c, v, e, [&](const ColumnPoint<true> &pt) {
         if (((g.ig0 + pt.i + c.j + c.k) & 1) != color)
             return;
+        if constexpr (MASK)
+            if (mask_fixed(pt.p, fixed...))
+                return;
         double s, dg;
         pt.sum(shift, s, dg);
         store_dup(g, v, pt.p, (s - hSq * d[pt.p]) / dg, pt.di(), c.dj, c.dk);
@@ -338,21 +388,22 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
 }
 
 void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int bc, int color, hipStream_t s, int i_lo, int i_hi)
+                    int bc, int color, hipStream_t s, int i_lo, int i_hi, const unsigned char *m)
 {
     if (!stencil_window(g, bc, i_lo, i_hi))
         return;
     const dim3 block(WAVE, 4, 1);
-    dispatch_op(e, bc, [&](auto coef, auto mode) {
+    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
         if constexpr (coef()) {
             int chunk;
             const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk);
-            hipLaunchKernelGGL(coef_color_kernel<mode()>, grid, block, 0, s, g, v, e, d, op.hSq, sigma * op.hSq, color, bc, chunk,
-                               i_lo, i_hi);
+            launch_op(mask, OP_KERNELS(coef_color_kernel, mode()), grid, block, s, m, g, v, e, d, op.hSq, sigma * op.hSq, color,
+                      bc, chunk, i_lo, i_hi);
         } else {
             const int pairs = (g.nk + 1) / 2;
             const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(bc, 1) + 3) / 4, i_hi - i_lo);
-            hipLaunchKernelGGL(smooth_color_kernel<mode()>, grid, block, 0, s, g, v, d, op.hSq, op.sixth, color, bc, i_lo);
+            launch_op(mask, OP_KERNELS(smooth_color_kernel, mode()), grid, block, s, m, g, v, d, op.hSq, op.sixth, color, bc,
+                      i_lo);
         }
     });
 }
@@ -417,12 +468,13 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const double *__rest
  * diff at every unique interior point; res (optional) receives it there and at the duplicates (mg_3d.h:824-825), partials
  * one sum of diff^2 per block (lanes by shuffle tree, waves 0..3 in order), folded by k_fold: the norm counts every
  * unknown once. */
-template <bool COEF, int BC>
+template <bool COEF, int BC, bool MASK, class... M>
 __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                        const double *__restrict__ d, double invHsq, double dg0,
                                                        double *__restrict__ res, double *__restrict__ partials, int bc,
-                                                       int chunk, int i_lo, int i_hi, int acc_lo, int acc_hi)
+                                                       int chunk, int i_lo, int i_hi, int acc_lo, int acc_hi, M... fixed)
 {
+    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
     __shared__ double lds4[4];
     double acc = 0.;
     Column c;
@@ -446,7 +498,11 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
                 ea = e[pa];
             double s, dg;
             stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
-            const double diff = d[p] - invHsq * (s - dg * vh);
+            double diff;
+            if constexpr (MASK) /* a fixed point: 0., whatever d and the sums hold */
+                diff = mask_fixed(p, fixed...) ? 0. : d[p] - invHsq * (s - dg * vh);
+            else
+                diff = d[p] - invHsq * (s - dg * vh);
             if (res)
                 store_dup(g, res, p, diff, c.pi && i == 0, c.dj, c.dk);
             if (BC || (i >= acc_lo && i < acc_hi)) /* periodic and Neumann levels have no windows */
@@ -493,7 +549,7 @@ void k_fold(const double *partials, int np, double *out, hipStream_t s)
 
 void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
                 int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
-                int acc_hi)
+                int acc_hi, const unsigned char *m)
 {
     if (!stencil_window(g, bc, i_lo, i_hi)) {
         (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
@@ -504,9 +560,9 @@ void k_residual(const Geom &g, const double *v, const double *e, const double *d
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-    dispatch_op(e, bc, [&](auto coef, auto mode) {
-        hipLaunchKernelGGL((residual_kernel<coef(), mode()>), grid, block, 0, s, g, v, e, d, op.invHsq, dg0, res, partials, bc,
-                           chunk, i_lo, i_hi, acc_lo, acc_hi);
+    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
+        launch_op(mask, OP_KERNELS(residual_kernel, coef(), mode()), grid, block, s, m, g, v, e, d, op.invHsq, dg0, res, partials,
+                  bc, chunk, i_lo, i_hi, acc_lo, acc_hi);
     });
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
@@ -526,12 +582,13 @@ __device__ __forceinline__ double bc_weight(int bc, int ax, int x, int N)
 {
     return ((x == 0 && bc_ref_lo(bc, ax)) || (x == N - 1 && bc_ref_hi(bc, ax))) ? 0.5 : 1.;
 }
-template <bool COEF, int BC>
+template <bool COEF, int BC, bool MASK, class... M>
 __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                         double invHsq, double dg0, double *__restrict__ q,
                                                         double *__restrict__ partials, int bc, int chunk, int i_lo,
-                                                        int i_hi)
+                                                        int i_hi, M... fixed)
 {
+    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
     __shared__ double lds4[4];
     double acc = 0.;
     Column c;
@@ -542,7 +599,11 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
         walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
             double s, dg;
             pt.sum(dg0, s, dg);
-            const double ap = invHsq * (s - dg * pt.vh);
+            double ap;
+            if constexpr (MASK) /* a fixed point: q = 0. (p is 0. there, so nothing enters the dot) */
+                ap = mask_fixed(pt.p, fixed...) ? 0. : invHsq * (s - dg * pt.vh);
+            else
+                ap = invHsq * (s - dg * pt.vh);
             q[pt.p] = ap;
             if constexpr (BC == BC_REFLECT)
                 acc += (wjk * bc_weight(bc, 0, pt.i, g.N)) * (pt.vh * ap);
@@ -556,7 +617,7 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
 }
 
 int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
-                    double *partials, double *dot_out, hipStream_t s)
+                    double *partials, double *dot_out, hipStream_t s, const unsigned char *m)
 {
     int i_lo = -1, i_hi = -1;
     if (!stencil_window(g, bc, i_lo, i_hi)) {
@@ -566,9 +627,9 @@ int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const Level
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-    dispatch_op(e, bc, [&](auto coef, auto mode) {
-        hipLaunchKernelGGL((pcg_apply_kernel<coef(), mode()>), grid, block, 0, s, g, p, e, op.invHsq, dg0, q, partials, bc,
-                           chunk, i_lo, i_hi);
+    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
+        launch_op(mask, OP_KERNELS(pcg_apply_kernel, coef(), mode()), grid, block, s, m, g, p, e, op.invHsq, dg0, q, partials, bc,
+                  chunk, i_lo, i_hi);
     });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, dot_out, s);
@@ -933,7 +994,8 @@ int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *s
     int chunk;
     const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     const double dg0 = e ? sigma * op.hSq : op.dg;
-    dispatch_op(e, bc, [&](auto coef, auto mode) {
+    /* (no MASK form: d at a fixed point is never read, what the pass writes there is unspecified) */
+    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
         hipLaunchKernelGGL((step_rhs_kernel<coef(), mode()>), grid, block, 0, s, g, u0, e, src, op.invHsq, dg0, a, c1, b, d, bc,
                            chunk, i_lo, i_hi);
     });
@@ -1079,8 +1141,8 @@ void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int
 }
 
 /* eps of the coarse level at every point, boundary included: ec[I,J,K] = ef[2I,2J,2K] (single-domain levels) */
-__global__ void __launch_bounds__(256) coef_inject_kernel(Geom gf, const double *__restrict__ ef, Geom gc,
-                                                          double *__restrict__ ec)
+template <class T>
+__global__ void __launch_bounds__(256) coef_inject_kernel(Geom gf, const T *__restrict__ ef, Geom gc, T *__restrict__ ec)
 {
     const int kc = blockIdx.x * WAVE + threadIdx.x;
     const int jc = blockIdx.y * 4 + threadIdx.y;
@@ -1093,7 +1155,14 @@ __global__ void __launch_bounds__(256) coef_inject_kernel(Geom gf, const double 
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s)
 {
     dim3 grid((gc.nk + WAVE - 1) / WAVE, (gc.nj + 3) / 4, gc.ni);
-    hipLaunchKernelGGL(coef_inject_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, ef, gc, ec);
+    hipLaunchKernelGGL(coef_inject_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, gf, ef, gc, ec);
+}
+
+/* the fixed-point bytes of the coarse level the same way: mc[I,J,K] = mf[2I,2J,2K] */
+void k_mask_inject(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s)
+{
+    dim3 grid((gc.nk + WAVE - 1) / WAVE, (gc.nj + 3) / 4, gc.ni);
+    hipLaunchKernelGGL(coef_inject_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, gf, mf, gc, mc);
 }
 
 /* -------------------------------------------------------------- prolongation
@@ -1181,14 +1250,21 @@ __global__ void __launch_bounds__(256) prolong_cell_kernel(Geom gc, const double
     }
 }
 
-/* Point form, one thread per fine point, for the levels with periodic axes or Neumann faces: ef += P(ec) at every fine
+/* Point form, one thread per fine point, for the levels with periodic axes, Neumann faces or fixed points: ef += P(ec) at every fine
  * point that is not a duplicate (Dirichlet faces included: their coarse parents hold zeros), in the parent order above;
  * on a periodic axis the high parent il+1 = Nc-1 is read at its source 0.  The thread of a point writes the sum to its
  * duplicates too, so neither a fine nor a coarse duplicate is ever read.  A Neumann face needs nothing of its own: every
  * parent of a fine face point lies on the same face, and this kernel corrects the face points with the rest (axes: the
- * periodic bits of the boundary word).  (A Dirichlet level never takes this form: k_prolong.) */
+ * periodic bits of the boundary word).  With fixed points (the pack M: the fine level's bytes and the boundary word, two
+ * trailing arguments) a fine fixed UNKNOWN is skipped -- a byte on a Dirichlet face is ignored, the face point is corrected
+ * as ever.  A Dirichlet level takes this form only when it has fixed points: k_prolong. */
+__device__ __forceinline__ bool prolong_fixed(const Geom &g, int i, int j, int k, const unsigned char *m, int bc)
+{
+    return bc_unknown(bc, g.N, i, j, k) && m[gidx(g, i, j, k)] != 0;
+}
+template <class... M>
 __global__ void __launch_bounds__(256) prolong_kernel(Geom gc, const double *__restrict__ ec, Geom gf,
-                                                      double *__restrict__ ef, int axes)
+                                                      double *__restrict__ ef, int axes, M... fixed)
 {
     const int k = blockIdx.x * WAVE + threadIdx.x;
     const int j = blockIdx.y * 4 + threadIdx.y;
@@ -1199,6 +1275,9 @@ __global__ void __launch_bounds__(256) prolong_kernel(Geom gc, const double *__r
         return;
     if ((pi && i == Nf - 1) || (pj && j == Nf - 1) || (pk && k == Nf - 1))
         return;
+    if constexpr (sizeof...(M) != 0)
+        if (prolong_fixed(gf, i, j, k, fixed...))
+            return;
     const int oi = i & 1, oj = j & 1, ok = k & 1;
     const int il = (i - oi) / 2, jl = (j - oj) / 2, kl = (k - ok) / 2;
     const long long c0 = gidx(gc, il, jl, kl);
@@ -1249,13 +1328,18 @@ __global__ void __launch_bounds__(256) prolong_kernel(Geom gc, const double *__r
     store_dup(gf, ef, p, ef[p] + t, pi && i == 0, pj && j == 0, pk && k == 0);
 }
 
-/* bc = 0: the cell form.  Its one condition, which every hierarchy meets -- a level keeps nj = nk = N and Nf = 2*Nc - 1 --
- * is asserted: there is no other form for a Dirichlet level */
-void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo, int if_hi)
+/* bc = 0 without fixed points: the cell form.  Its one condition, which every hierarchy meets -- a level keeps nj = nk = N
+ * and Nf = 2*Nc - 1 -- is asserted: a Dirichlet level without a mask has no other form.  A boundary word or fixed points
+ * (mf) select the point form */
+void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo, int if_hi,
+               const unsigned char *mf)
 {
-    if (bc) { /* a single-domain level: every plane */
+    if (bc || mf) { /* a single-domain level: every plane */
         const dim3 grid((gf.N + WAVE - 1) / WAVE, (gf.N + 3) / 4, gf.N);
-        hipLaunchKernelGGL(prolong_kernel, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
+        if (mf)
+            hipLaunchKernelGGL((prolong_kernel<MaskPtr, int>), grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7, mf, bc);
+        else
+            hipLaunchKernelGGL(prolong_kernel<>, grid, dim3(WAVE, 4, 1), 0, s, gc, ec, gf, ef, bc & 7);
         return;
     }
     assert(gf.nk == 2 * gc.nk - 1 && gf.nj == 2 * gc.nj - 1);
@@ -1537,7 +1621,8 @@ void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin
 /* Every duplicate of a field from its source: blockIdx.z = the axis whose duplicate plane a thread covers; (a, b) the
  * other two indices.  The source maps every periodic index N-1 to 0, so only unique points are read; an edge or corner
  * duplicate is written by each plane it lies in, with the same value. */
-__global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, double *__restrict__ v, int axes)
+template <class T>
+__global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, T *__restrict__ v, int axes)
 {
     const int b = blockIdx.x * WAVE + threadIdx.x, a = blockIdx.y * 4 + threadIdx.y, ax = blockIdx.z;
     const int N = g.N;
@@ -1555,7 +1640,101 @@ void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s)
     if (!axes)
         return;
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
-    hipLaunchKernelGGL(per_refresh_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes);
+    hipLaunchKernelGGL(per_refresh_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes);
+}
+
+void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s)
+{
+    const int axes = bc & 7;
+    if (!axes)
+        return;
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
+    hipLaunchKernelGGL(per_refresh_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, g, m, axes);
+}
+
+/* ------------------------------------------------------------- fixed points */
+
+/* The level-0 right-hand side of the direct solve on a context with fixed points: per_coarse_rhs_kernel's, and at a fixed
+ * unknown the value of its identity row -- 0., the error a fixed point holds in a cycle (ufix NULL), or u's own value there
+ * (a one-level context: the direct solve IS the solve). */
+__global__ void __launch_bounds__(256) mask_coarse_rhs_kernel(Geom g, const double *__restrict__ d, double *__restrict__ b,
+                                                              int bc, int pin, const unsigned char *__restrict__ m,
+                                                              const double *__restrict__ ufix)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    if (k >= N || j >= N)
+        return;
+    const int axes = bc & 7;
+    const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
+    const long long p = gidx(g, i, j, k);
+    double x;
+    if (dup || (pin && (i | j | k) == 0))
+        x = 0.;
+    else if (bc_unknown(bc, N, i, j, k) && m[p])
+        x = ufix ? ufix[p] : 0.;
+    else
+        x = d[p];
+    b[p] = x;
+}
+
+void k_mask_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
+                       hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(mask_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, bc, pin, m, ufix);
+}
+
+/* the fixed UNKNOWNS of a level, counted: one 64-bit atomic add per block that found any */
+__global__ void __launch_bounds__(256) mask_count_kernel(Geom g, const unsigned char *__restrict__ m, int bc,
+                                                         unsigned long long *__restrict__ out)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    const bool fixed = k < N && j < N && bc_unknown(bc, N, i, j, k) && m[gidx(g, i, j, k)] != 0;
+    __shared__ unsigned int row_cnt[4];
+    const unsigned long long bal = __ballot(fixed);
+    if (threadIdx.x == 0)
+        row_cnt[threadIdx.y] = (unsigned int)__popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        const unsigned long long cnt = (unsigned long long)row_cnt[0] + row_cnt[1] + row_cnt[2] + row_cnt[3];
+        if (cnt)
+            atomicAdd(out, cnt);
+    }
+}
+
+void k_mask_count(const Geom &g, const unsigned char *m, int bc, unsigned long long *out, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(mask_count_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, m, bc, out);
+}
+
+/* the caller's bytes (any element strides) into the level's padded layout; a periodic duplicate takes its source's byte */
+__global__ void __launch_bounds__(256) mask_pack_kernel(Geom g, unsigned char *__restrict__ m,
+                                                        const unsigned char *__restrict__ a, long long si, long long sj,
+                                                        long long sk, int axes)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = g.N;
+    if (k >= N || j >= N)
+        return;
+    const int qi = ((axes & 1) && i == N - 1) ? 0 : i, qj = ((axes & 2) && j == N - 1) ? 0 : j,
+              qk = ((axes & 4) && k == N - 1) ? 0 : k;
+    m[gidx(g, i, j, k)] = a[si * qi + sj * qj + sk * qk];
+}
+
+void k_mask_pack(const Geom &g, unsigned char *m, const mg3d_array &a, int bc, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(mask_pack_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, m, (const unsigned char *)a.ptr, a.stride[0],
+                       a.stride[1], a.stride[2], bc & 7);
 }
 
 /* Zeros of a field on the faces of the mask `faces` (MG3D_NEUMANN_* numbering: bit 2*ax low, 2*ax+1 high): blockIdx.z =

@@ -15,7 +15,11 @@
  * u -- the fused schedules exchange u and the level's second buffer as they go, so z is whatever the level calls u when the
  * cycle returns.  The pointers are put back on every way out.  The caller's Dirichlet faces of u and every bit of d are
  * therefore untouched by construction, not by copying back.  p and q = Ap are two more work vectors; Dirichlet faces of
- * z, r, p, q are zero from their allocation (z is cleared before every cycle) and no pass writes them.
+ * z, r, p, q are zero from their allocation (z is cleared before every cycle) and no pass writes them.  Fixed points
+ * (mg3d_ctx_set_mask) are Dirichlet points in the interior: the residual stores r = 0. there, the cycle never writes z
+ * there, apply + dot stores q = 0. there, so p stays 0. and the update, dot and direction passes -- which do visit them --
+ * move nothing: x keeps the caller's value (the update stores x + alpha*0. there: the same value, except that a -0. the
+ * caller uploaded becomes +0.).
  *
  * Per iteration (kernels in mg3d_kernels.hip, byte counts in DESIGN.md):
  *     apply + dot      q = A p, p.q                    one pass
@@ -128,7 +132,7 @@ static int pcg_iterate(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, 
             k_pcg_direction(top.g, bc, p, z, rz, rz_old, s);
         {
             StageScope kt(ctx, q, MG3D_K_PCG_APPLY, true);
-            k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s);
+            k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s, mg3d_ctx_mask(ctx, q));
         }
         k_pcg_update_norm(top.g, bc, x, r, p, qv, rz, sc + S_PAP, ctx->partials, sc + S_RR, s);
         CHK(pcg_launch_ok(name, "iteration"));
@@ -185,7 +189,7 @@ static int pcg_run(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, doub
         CHK(pcg_alloc(ctx, name));
     /* r_0 = d - A x; with iterations to come it is stored as the first right-hand side of the cycle */
     k_residual(top.g, top.f[MG3D_U], e, top.f[MG3D_D], mg3d_op(ctx, top), ctx->sigma, bc,
-               stored ? ctx->pcg_v[V_R] : nullptr, ctx->partials, ctx->sumsq + S_R0, s);
+               stored ? ctx->pcg_v[V_R] : nullptr, ctx->partials, ctx->sumsq + S_R0, s, -1, -1, 0, -1, mg3d_ctx_mask(ctx, q));
     if (ip.singular) {
         /* sum(w r_0) and sum(w d), then r_0 -= sum(w r_0)/W and its norm */
         double *const sc = ctx->sumsq, *const r = ctx->pcg_v[V_R];
@@ -271,7 +275,7 @@ extern "C" int mg3d_wpcg_solve(mg3d_ctx *ctx, double rtol, double atol, int max_
     CHK(pcg_check_state(name, ctx));
     /* without a Neumann face w = 1 and, unless the operator is singular, this is mg3d_pcg_solve's iteration: its passes */
     InnerProduct ip;
-    ip.singular = mg3d_ctx_pinned(ctx);
+    ip.singular = mg3d_ctx_singular(ctx); /* (a fixed unknown of the finest level removes the constants from the kernel) */
     ip.weighted = ctx->neumann != 0 || ip.singular;
     ip.W = k_wpcg_weight_sum(ctx->lv[ctx->L - 1].g, mg3d_ctx_bc(ctx));
     return pcg_run(ctx, name, ip, rtol, atol, max_iters, norms, info);
