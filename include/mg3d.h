@@ -261,6 +261,67 @@ int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s /* NULL: no s
 int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps /* NULL: constant operator */, void *stream);
 int mg3d_ctx_set_mask_device(mg3d_ctx *ctx, const mg3d_array *mask /* dtype MG3D_U8 only; NULL: no mask */, void *stream);
 
+/* ------------------------------------------------------------ field output
+ * What is wanted of a solved potential u of div(eps grad u) - sigma u = f: the field E = -grad u, the charge u induces on
+ * each embedded conductor, the stored energy (capacitance: C = Q/V = 2W/V^2) -- formed on the device from u of the FINEST
+ * level with the context's own periodic wraps, reflected Neumann faces, face means of eps and fixed-point bytes.  All four
+ * calls only read the context: a cycle that has run ahead is finished exactly as mg3d_download_device finishes it, and no
+ * field, option, factor or flag changes -- the next mg3d_vcycle(s) gives the bits it would have given.  They work with
+ * every operator and boundary combination of a context (constant or eps, any sigma, periodic axes, Neumann faces, with or
+ * without a mask); sigma enters none of the three quantities.
+ * Notation: N, h the finest level's points per side and spacing.  On axis a index x is a DUPLICATE if the axis is periodic
+ * and x = N-1; it lies ON A DIRICHLET FACE if the axis is not periodic and (x = 0 without the MG3D_NEUMANN_ low bit of the
+ * axis or x = N-1 without its high bit), ON A NEUMANN FACE if the axis is not periodic and the matching bit is set.  w(p) is
+ * 1/2 per Neumann face the point p lies on (the weight of mg3d_wpcg_solve).
+ *
+ * mg3d_field_gradient_device: scale * du/dx_a at EVERY one of the N^3 points -- Dirichlet faces, fixed points and periodic
+ *   duplicates included -- into out[a] (a = 0, 1, 2 for i, j, k; NULL: component not wanted).  cs = scale * (0.5 / h), in
+ *   this order, on the host.  A point is first taken to its source (index N-1 of a periodic axis -> 0, on all three axes:
+ *   no duplicate of u is read and a duplicate gets its source's bits); then per axis, the other two indices held:
+ *     periodic axis           : lo = (x == 0) ? N-2 : x-1, hi = (x == N-2) ? 0 : x+1, value (u[hi] - u[lo]) * cs
+ *     1 <= x <= N-2 otherwise : (u[x+1] - u[x-1]) * cs
+ *     x = 0,   Neumann face   : (u[1] - u[1]) * cs          (the reflected tap: a zero)
+ *     x = 0,   Dirichlet face : ((4.0*u[1] - 3.0*u[0]) - u[2]) * cs
+ *     x = N-1, Neumann face   : (u[N-2] - u[N-2]) * cs
+ *     x = N-1, Dirichlet face : ((3.0*u[N-1] - 4.0*u[N-2]) + u[N-3]) * cs
+ *   Operands in this order, uncontracted.  scale = 1: the gradient; scale = -1: E.  The mask is IGNORED: a body held at one
+ *   potential differences to zero inside on its own, and its surface is resolved as the grid resolves any surface.
+ *   out[a] follows the mg3d_array contract of mg3d_download_device word for word -- MG3D_F64 (these bytes) or MG3D_F32
+ *   (rounded to nearest even) per component, strides >= 1 in elements in any order and with any gaps, 64-bit index, the
+ *   pointer checked, the two-event stream ordering, no host synchronisation.  All wanted components come out of ONE launch
+ *   that reads u once; overlap between the output arrays is the caller's business.  MG3D_ERR_ARG, nothing written: a NULL
+ *   context, all three components NULL, a scale that is not finite, a bad dtype, a stride < 1, a foreign pointer.  The
+ *   launch counts under the kernel timer MG3D_K_PACK (it writes a caller's array).
+ * mg3d_field_gradient: the same into dense N^3 host arrays (NULL: not wanted).  It runs the launch once per wanted
+ *   component into one dense N^3 scratch buffer on the device, allocated for the call and freed at return (MG3D_ERR_ALLOC,
+ *   nothing written, when it does not fit), each followed by a copy to the host; no field of the context is used.
+ * mg3d_field_flux: the flux of eps grad u into the fixed points.  The mask's bytes are kept verbatim everywhere, so a byte
+ *   value 1..255 is a free LABEL of a body.  P = the fixed unknowns (no duplicate, on no Dirichlet face, byte != 0) whose
+ *   byte equals `label`, or all of them for label = 0:
+ *       t_p = w(p) * (s - D*u_p),   *flux = h * (sum of t_p over P)
+ *   s and D the neighbour sum and diagonal of the context's stencil at p, wrapped or reflected neighbours and operand order
+ *   as in the residual, at sigma = 0: D = 6 for the constant operator, else the sum of the six face means 0.5*(eps_p + eps_q).
+ *   This is h^3 times the sigma = 0 operator at the body's points; for a converged solution with d = 0 around the body it is
+ *   the net flux of eps grad u into it -- times -eps_0 the charge (the caller's constant).  Per-block partial sums folded in
+ *   a fixed order, the multiplication by h on the host: the same call on the same data gives the same bits.  MG3D_ERR_STATE
+ *   on a context without a mask; MG3D_ERR_ARG for a label outside 0..255 or a NULL flux; a label no point carries gives +0.
+ *   One host synchronisation.
+ * mg3d_field_energy:  *energy = 0.5 * h * (sum over the grid edges e = (p, q) of w_e * a_e * (u_q - u_p)^2).  An edge
+ *   belongs to its lower end p, which must be no duplicate on any axis; along axis a it runs to x+1, wrapped from N-2 to 0
+ *   on a periodic axis, absent at x = N-1 on another; it is LEFT OUT when p lies on a Dirichlet face of another axis (both
+ *   ends are boundary data); w_e = 1/2 per Neumann face of another axis p lies on; a_e = 1 or 0.5*(eps_p + eps_q).  Each
+ *   term is (w_e * a_e) * ((u_q - u_p) * (u_q - u_p)), a point's three edges are added in i, j, k order; partial sums, fold,
+ *   synchronisation as above.  Works with or without a mask (edges inside a body contribute what their u gives).  With
+ *   these conventions the discrete Green identity is exact: for u vanishing on the Dirichlet faces
+ *       sum_e w_e a_e (u_q - u_p)^2 = - sum_p w(p) u_p (s - D u_p)   over every unknown p, fixed ones included,
+ *   so for a grounded box with one body at potential V and a converged solve with d = 0:  W = -1/2 V F.
+ * Out of scope: the slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms; levels below the finest; eps grad u as an
+ * output; max |E|; the flux through patches of Dirichlet FACES. */
+int mg3d_field_gradient(mg3d_ctx *ctx, double scale, double *gi, double *gj, double *gk); /* dense N^3 host arrays; NULL: component not wanted */
+int mg3d_field_gradient_device(mg3d_ctx *ctx, double scale, const mg3d_array *const out[3] /* out[a] NULL: not wanted */, void *stream);
+int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux);
+int mg3d_field_energy(mg3d_ctx *ctx, double *energy);
+
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)
  *                   postSmoother (post=1, mg_3d.h:711-781: iters x black,red)

@@ -95,6 +95,10 @@ SIGNATURES = {
     "mg3d_step_setup": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
     "mg3d_step_set_source": (C.c_int, [C.c_void_p, dp]),
     "mg3d_step_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_void_p]),
+    "mg3d_field_gradient": (C.c_int, [C.c_void_p, C.c_double, dp, dp, dp]),
+    "mg3d_field_gradient_device": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(_ap), C.c_void_p]),
+    "mg3d_field_flux": (C.c_int, [C.c_void_p, C.c_int, dp]),
+    "mg3d_field_energy": (C.c_int, [C.c_void_p, dp]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -410,7 +414,8 @@ class Solver:
         flat, nonzero = fixed: u there keeps what was uploaded and acts as a Dirichlet value, like a point on a Dirichlet
         face; coarser levels take the mask by injection.  None: no mask again.  Plain cycles are for bodies that survive on
         the coarse grids; pcg_solve / wpcg_solve are the solvers for thin ones.  Rebuilds a coarse factor of get_details();
-        drops one given to set_lu."""
+        drops one given to set_lu.  The bytes are kept as given: a uint8 value 1..255 is a label of its body, which
+        field_flux(label) asks for."""
         if mask is None:
             check(self.L.mg3d_ctx_set_mask(self._h, None))
             return
@@ -625,6 +630,56 @@ class Solver:
             return
         a, stream = _device_args(t, "set_coefficient_tensor", (self.N,) * 3)
         check(self.L.mg3d_ctx_set_coefficient_device(self._h, C.byref(a), stream))
+
+    # -- field output (include/mg3d.h, "Field output"): read-only, the finest level
+    def gradient(self, scale=1.0):
+        """mg3d_field_gradient: scale * du/dx_a at every point of the finest level, three (N, N, N) float64 arrays for the
+        axes i, j, k (scale=-1: E).  Periodic wraps, reflected Neumann faces, one-sided differences on Dirichlet faces; the
+        mask is ignored."""
+        N = self.N
+        out = [np.empty(N ** 3) for _ in range(3)]
+        check(self.L.mg3d_field_gradient(self._h, float(scale), P(out[0]), P(out[1]), P(out[2])))
+        return tuple(a.reshape(N, N, N) for a in out)
+
+    def gradient_tensor(self, out=None, dtype=None, scale=1.0):
+        """mg3d_field_gradient_device: the same into GPU tensors, one launch for all wanted components, ordered on the
+        current stream, no host synchronisation.  out=None: a new (3, N, N, N) tensor of `dtype` (default torch.float64) on
+        the context's device; else a (3, N, N, N)-shaped tensor (any view) or a sequence of three (N, N, N) tensors or None
+        (component not wanted), float64 or float32 each.  Returns out."""
+        import torch
+        N = self.N
+        if out is None:
+            out = torch.empty((3, N, N, N), dtype=torch.float64 if dtype is None else dtype,
+                              device=torch.device("cuda", torch.cuda.current_device()))
+        if isinstance(out, torch.Tensor):
+            if tuple(out.shape) != (3, N, N, N):
+                raise ValueError(f"gradient_tensor: need shape {(3, N, N, N)}, got {tuple(out.shape)}")
+            parts = [out[0], out[1], out[2]]
+        else:
+            parts = list(out)
+            if len(parts) != 3:
+                raise ValueError(f"gradient_tensor: need three components, got {len(parts)}")
+        descs, stream = [None] * 3, None
+        for a, t in enumerate(parts):
+            if t is not None:
+                descs[a], st = _device_args(t, "gradient_tensor", (N, N, N), writable=True)
+                stream = st if stream is None else stream
+        ptrs = (_ap * 3)(*[C.pointer(d) if d is not None else _ap() for d in descs])
+        check(self.L.mg3d_field_gradient_device(self._h, float(scale), ptrs, stream))
+        return out
+
+    def field_flux(self, label=0):
+        """mg3d_field_flux: h * the sum of w(p)*(s - D*u_p) over the fixed unknowns whose mask byte is `label` (0: all) --
+        the net flux of eps grad u into that body for a converged solution; times -eps_0 its charge."""
+        f = C.c_double(0.)
+        check(self.L.mg3d_field_flux(self._h, int(label), C.byref(f)))
+        return f.value
+
+    def field_energy(self):
+        """mg3d_field_energy: 0.5 * h * the sum over the grid edges of w_e * a_e * (u_q - u_p)^2."""
+        w = C.c_double(0.)
+        check(self.L.mg3d_field_energy(self._h, C.byref(w)))
+        return w.value
 
     # -- operators
     def smooth(self, level, post, iters):

@@ -355,6 +355,17 @@ void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);
 void k_pack(const Geom &g, double *v, const mg3d_array &a, hipStream_t s);
 void k_unpack(const Geom &g, const double *v, const mg3d_array &a, hipStream_t s);
 void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s);
+/* field output (mg3d_field.hip; single-domain levels, bc the boundary word; include/mg3d.h "Field output" has the formulas).
+ * k_gradient: cs * (the central / wrapped / reflected / one-sided difference of u) per axis at all N^3 points into the
+ * caller's arrays out[0..2] (NULL: not wanted; at least one; float or double each, any strides >= 1), one launch.
+ * k_field_flux: *out = the sum of w(p)*(s - D*u_p) over the fixed unknowns whose byte m[p] is `label` (0: any nonzero).
+ * k_field_energy: *out = the sum of (w_e*a_e)*(u_q - u_p)^2 over the owned edges.
+ * Both sums: one partial per block, folded in a fixed order.  Return value: the number of partials (k_gradient: 0), -1 when
+ * the level has no launch shape (nothing launched). */
+int k_gradient(const Geom &g, const double *u, int bc, double cs, const mg3d_array *const out[3], hipStream_t s);
+int k_field_flux(const Geom &g, const double *u, const double *e, const unsigned char *m, int label, int bc, double *partials,
+                 double *out, hipStream_t s);
+int k_field_energy(const Geom &g, const double *u, const double *e, int bc, double *partials, double *out, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

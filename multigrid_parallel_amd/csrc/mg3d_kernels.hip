@@ -1858,6 +1858,293 @@ void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long
                            a.stride[1], a.stride[2], bc & 7, out);
 }
 
+/* --------------------------------------------------------------- field output
+ * The gradient of u of a single-domain level at every one of its N^3 points, into up to three caller's arrays (GradOut,
+ * include/mg3d.h "Field output").  cs = scale * (0.5 / h).  Per axis, at index x of the point's SOURCE (a periodic
+ * duplicate N-1 takes index 0 of that axis, on all three axes, so no duplicate of u is read and a duplicate gets its
+ * source's bits), with c = u at the source:
+ *   periodic axis, Neumann face, interior : (u[hi] - u[lo]) * cs -- wrapped (nb_lo / nb_hi) or reflected: at a Neumann
+ *                                           face both taps are the same inner neighbour, a zero
+ *   x = 0 on a Dirichlet face             : ((4.0*u[1] - 3.0*c) - u[2]) * cs
+ *   x = N-1 on a Dirichlet face           : ((3.0*c - 4.0*u[N-2]) + u[N-3]) * cs
+ * GradAxis holds that for one index: two tap offsets relative to the source point and which of the three forms applies.
+ * Shape: (WAVE, 4) blocks, lanes contiguous in k, over ALL N indices of k and j (not column<BC>'s unknowns); a thread
+ * walks a chunk of planes and carries u of the planes behind, at and ahead of the source plane in registers, as
+ * walk_column does -- one new plane tap per point, plus the third tap on the two planes of a Dirichlet i face; the four
+ * in-plane taps are the cache lines the neighbouring rows and lanes load (taking the k taps from the neighbouring lanes'
+ * registers instead measured slower: 1.39 against 1.29 ms).  With a k stride of 1 each component store is a row segment.
+ * eps and the mask play no part. */
+struct GradOut {
+    void *p[3];         /* NULL: component not wanted */
+    long long s[3][3];  /* element strides of component a for i, j, k */
+    int f32[3];         /* float (rounded to nearest even) instead of double */
+};
+struct GradAxis {
+    int src;          /* the source index */
+    long long oa, ob; /* kind 0: the +1 and -1 taps; 1: indices 1 and 2; 2: indices N-2 and N-3 */
+    int kind;         /* 0 central, 1 / 2 one-sided at the low / high Dirichlet face */
+};
+template <int BC>
+__device__ __forceinline__ GradAxis grad_axis(int bc, int ax, int x, int N, long long st)
+{
+    const bool per = BC && (bc >> ax & 1);
+    const bool rlo = BC == BC_REFLECT && bc_ref_lo(bc, ax), rhi = BC == BC_REFLECT && bc_ref_hi(bc, ax);
+    GradAxis a;
+    a.src = (per && x == N - 1) ? 0 : x;
+    a.kind = per ? 0 : ((x == 0 && !rlo) ? 1 : ((x == N - 1 && !rhi) ? 2 : 0));
+    if (a.kind == 1) {
+        a.oa = st;
+        a.ob = 2 * st;
+    } else if (a.kind == 2) {
+        a.oa = -st;
+        a.ob = -2 * st;
+    } else {
+        a.oa = nb_hi(a.src, N, per, rhi, st);
+        a.ob = nb_lo(a.src, N, per, rlo, st);
+    }
+    return a;
+}
+/* the value of one axis from its two taps ta (at oa), tb (at ob) and the centre c */
+__device__ __forceinline__ double grad_value(int kind, double ta, double tb, double c, double cs)
+{
+    if (kind == 1)
+        return ((4.0 * ta - 3.0 * c) - tb) * cs;
+    if (kind == 2)
+        return ((3.0 * c - 4.0 * ta) + tb) * cs;
+    return (ta - tb) * cs;
+}
+__device__ __forceinline__ void grad_store(const GradOut &o, int a, int i, int j, int k, double x)
+{
+    if (!o.p[a])
+        return;
+    const long long q = o.s[a][0] * i + o.s[a][1] * j + o.s[a][2] * k;
+    /* written once, read by nobody here: nontemporal, the cache keeps u's planes (513^3, three float64 components, 16
+     * planes per thread: 1.36 -> 1.29 ms) */
+    if (o.f32[a])
+        __builtin_nontemporal_store((float)x, (float *)o.p[a] + q); /* (round to nearest even) */
+    else
+        __builtin_nontemporal_store(x, (double *)o.p[a] + q);
+}
+/* planes per thread.  The carry pays from two planes on (one plane per thread, every tap loaded: 1.36 ms at 513^3); past
+ * that a SHORTER chunk is faster with three components -- 16 planes 1.29 ms, 8 1.25, 4 1.19, 2 1.18 -- though not with one
+ * (0.79 - 0.80 ms throughout): the blocks in flight then cover few plane positions, and the four arrays are streamed
+ * through nearly in order instead of at some thirty places each */
+#define GRAD_CHUNK 4
+
+template <int BC>
+__global__ void __launch_bounds__(256) gradient_kernel(Geom g, const double *__restrict__ u, GradOut o, double cs, int bc,
+                                                       int chunk)
+{
+    const int N = g.N;
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    if (k >= N || j >= N)
+        return;
+    const int i0 = blockIdx.z * chunk, i1 = min(i0 + chunk, N);
+    const GradAxis aj = grad_axis<BC>(bc, 1, j, N, g.pitch), ak = grad_axis<BC>(bc, 2, k, N, 1);
+    const long long row = (long long)g.pitch * aj.src + ak.src;
+    /* u at and behind the first source plane: the -1 tap, plane N-2 on the Dirichlet high face (a chunk may start there);
+     * on the Dirichlet low face nothing lies behind and the one-sided form does not look at vb */
+    GradAxis ai = grad_axis<BC>(bc, 0, i0, N, g.plane);
+    long long p = g.plane * ai.src + row;
+    double vh = u[p];
+    double vb = ai.kind == 0 ? u[p + ai.ob] : (ai.kind == 2 ? u[p + ai.oa] : vh);
+    for (int i = i0; i < i1; i++) {
+        ai = grad_axis<BC>(bc, 0, i, N, g.plane);
+        p = g.plane * ai.src + row;
+        /* the plane ahead; on the Dirichlet high face there is none and the taps are N-2 (carried) and N-3 */
+        const double va = ai.kind == 2 ? vb : u[p + ai.oa];
+        double gi;
+        if (ai.kind == 0)
+            gi = grad_value(0, va, vb, vh, cs);
+        else
+            gi = grad_value(ai.kind, va, u[p + ai.ob], vh, cs);
+        const double gj = grad_value(aj.kind, u[p + aj.oa], u[p + aj.ob], vh, cs);
+        const double gk = grad_value(ak.kind, u[p + ak.oa], u[p + ak.ob], vh, cs);
+        grad_store(o, 0, i, j, k, gi);
+        grad_store(o, 1, i, j, k, gj);
+        grad_store(o, 2, i, j, k, gk);
+        vb = vh;
+        vh = va;
+    }
+}
+
+int k_gradient(const Geom &g, const double *u, int bc, double cs, const mg3d_array *const out[3], hipStream_t s)
+{
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
+        return -1;
+    GradOut o;
+    for (int a = 0; a < 3; a++) {
+        o.p[a] = out[a] ? out[a]->ptr : nullptr;
+        o.f32[a] = out[a] && out[a]->dtype == MG3D_F32;
+        for (int t = 0; t < 3; t++)
+            o.s[a][t] = out[a] ? out[a]->stride[t] : 0;
+    }
+    const int chunk = GRAD_CHUNK;
+    const dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, (g.N + chunk - 1) / chunk), block(WAVE, 4, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(gradient_kernel<BC_REFLECT>, grid, block, 0, s, g, u, o, cs, bc, chunk);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(gradient_kernel<BC_WRAP>, grid, block, 0, s, g, u, o, cs, bc, chunk);
+        break;
+    default:
+        hipLaunchKernelGGL(gradient_kernel<BC_PLAIN>, grid, block, 0, s, g, u, o, cs, bc, chunk);
+    }
+    return 0;
+}
+
+/* The flux through the fixed unknowns: t_p = w(p) * (s - D*u_p) summed over the fixed unknowns p whose byte is `label`
+ * (label 0: every nonzero byte), s and D of stencil<COEF> with dg0 = 6 (constant) or 0 (eps: D the sum of the six face
+ * means) -- h^2 times the sigma = 0 operator --, w(p) = 1/2 per Neumann face p lies on.  The residual's column walk over
+ * the unknowns, so bytes on Dirichlet faces and periodic duplicates are never looked at; one partial per block. */
+template <bool COEF, int BC>
+__global__ void __launch_bounds__(256) field_flux_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
+                                                         const unsigned char *__restrict__ m, int label, double dg0,
+                                                         double *__restrict__ partials, int bc, int chunk, int i_lo, int i_hi)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    Column c;
+    if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
+        double wjk = 1.;
+        if constexpr (BC == BC_REFLECT)
+            wjk = bc_weight(bc, 1, c.j, g.N) * bc_weight(bc, 2, c.k, g.N);
+        walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
+            const int b = m[pt.p];
+            if (b == 0 || (label != 0 && b != label))
+                return;
+            double s, dg;
+            pt.sum(dg0, s, dg);
+            if constexpr (BC == BC_REFLECT)
+                acc += (wjk * bc_weight(bc, 0, pt.i, g.N)) * (s - dg * pt.vh);
+            else
+                acc += s - dg * pt.vh;
+        });
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+int k_field_flux(const Geom &g, const double *u, const double *e, const unsigned char *m, int label, int bc, double *partials,
+                 double *out, hipStream_t s)
+{
+    int i_lo = -1, i_hi = -1;
+    if (!stencil_window(g, bc, i_lo, i_hi)) {
+        (void)hipMemsetAsync(out, 0, sizeof(double), s);
+        return 0;
+    }
+    int chunk;
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const double dg0 = e ? 0. : 6.;
+    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
+        hipLaunchKernelGGL((field_flux_kernel<coef(), mode()>), grid, block, 0, s, g, u, e, m, label, dg0, partials, bc, chunk,
+                           i_lo, i_hi);
+    });
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, out, s);
+    return np;
+}
+
+/* The energy sum: over the edges e = (p, q) owned by their lower end p -- no duplicate on any axis --, along axis a to
+ * x+1 (wrapped from N-2 to 0 on a periodic axis, absent at x = N-1 on another), left out when p lies on a Dirichlet face
+ * of another axis,  (w_e * a_e) * ((u_q - u_p) * (u_q - u_p)),  w_e = 1/2 per Neumann face of another axis p lies on,
+ * a_e = 1 or 0.5*(eps_p + eps_q); a point's edges are added in i, j, k order.  Threads over ALL N indices of j and k,
+ * chunks of planes (16, doubled until the partial sums fit), u and eps of the plane ahead carried. */
+struct EnergyAxis {
+    bool own, edge, dir; /* the index is no duplicate; it has an edge to x+1; it lies on a Dirichlet face */
+    double w;            /* 1/2 on a Neumann face */
+    long long o;         /* offset to the upper end */
+};
+template <int BC>
+__device__ __forceinline__ EnergyAxis energy_axis(int bc, int ax, int x, int N, long long st)
+{
+    const bool per = BC && (bc >> ax & 1);
+    const bool rlo = BC == BC_REFLECT && bc_ref_lo(bc, ax), rhi = BC == BC_REFLECT && bc_ref_hi(bc, ax);
+    EnergyAxis a;
+    a.own = !(per && x == N - 1);
+    a.edge = x <= N - 2;
+    a.dir = !per && ((x == 0 && !rlo) || (x == N - 1 && !rhi));
+    a.w = BC == BC_REFLECT ? bc_weight(bc, ax, x, N) : 1.;
+    a.o = nb_hi(x, N, per, false, st);
+    return a;
+}
+template <bool COEF, int BC>
+__global__ void __launch_bounds__(256) field_energy_kernel(Geom g, const double *__restrict__ u, const double *__restrict__ e,
+                                                           double *__restrict__ partials, int bc, int chunk)
+{
+    __shared__ double lds4[4];
+    double acc = 0.;
+    const int N = g.N;
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i0 = blockIdx.z * chunk, i1 = min(i0 + chunk, N);
+    if (k < N && j < N) {
+        const EnergyAxis aj = energy_axis<BC>(bc, 1, j, N, g.pitch), ak = energy_axis<BC>(bc, 2, k, N, 1);
+        if (aj.own && ak.own) {
+            long long p = gidx(g, i0, j, k);
+            double uh = u[p], eh = 0.;
+            if constexpr (COEF)
+                eh = e[p];
+            for (int i = i0; i < i1; i++, p += g.plane) {
+                const EnergyAxis ai = energy_axis<BC>(bc, 0, i, N, g.plane);
+                double ua = 0., ea = 0.;
+                if (ai.edge) { /* (also the next plane's own values) */
+                    ua = u[p + ai.o];
+                    if constexpr (COEF)
+                        ea = e[p + ai.o];
+                }
+                if (ai.own) {
+                    if (ai.edge && !aj.dir && !ak.dir) {
+                        const double du = ua - uh;
+                        acc += ((aj.w * ak.w) * (COEF ? 0.5 * (eh + ea) : 1.)) * (du * du);
+                    }
+                    if (aj.edge && !ai.dir && !ak.dir) {
+                        const double du = u[p + aj.o] - uh;
+                        double a = 1.;
+                        if constexpr (COEF)
+                            a = 0.5 * (eh + e[p + aj.o]);
+                        acc += ((ai.w * ak.w) * a) * (du * du);
+                    }
+                    if (ak.edge && !ai.dir && !aj.dir) {
+                        const double du = u[p + ak.o] - uh;
+                        double a = 1.;
+                        if constexpr (COEF)
+                            a = 0.5 * (eh + e[p + ak.o]);
+                        acc += ((ai.w * aj.w) * a) * (du * du);
+                    }
+                }
+                /* the plane ahead in memory is i+1 unless the edge wrapped (i = N-2 of a periodic axis): then i+1 = N-1 is the
+                 * duplicate plane, owned by nobody, and the walk ends there */
+                uh = ua;
+                eh = ea;
+            }
+        }
+    }
+    const double tot = block_sum_256(acc, lds4);
+    if (threadIdx.x == 0 && threadIdx.y == 0)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+}
+
+int k_field_energy(const Geom &g, const double *u, const double *e, int bc, double *partials, double *out, hipStream_t s)
+{
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
+        return -1;
+    const int gx = (g.N + WAVE - 1) / WAVE, gy = (g.N + 3) / 4;
+    int chunk = 16;
+    while ((long long)gx * gy * ((g.N + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
+        chunk *= 2;
+    const dim3 grid(gx, gy, (g.N + chunk - 1) / chunk), block(WAVE, 4, 1);
+    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
+        hipLaunchKernelGGL((field_energy_kernel<coef(), mode()>), grid, block, 0, s, g, u, e, partials, bc, chunk);
+    });
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, out, s);
+    return np;
+}
+
 /* ------------------------------------------------------- coarsest direct solve
  * solveWithLU, gauss_elim.h:31-60, on the banded factor.
  *   forward : z[i] = b[i] - sum_{j<i, ascending}  LU[i][j]*z[j]
