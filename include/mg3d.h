@@ -724,15 +724,17 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
 /* --------------------------------------------------- host-only helpers (no device)
  * mg3d_bc_func            : BCFunc (mg_3d.h:89-90)
  * mg3d_fill_boundary_host : setupBoundaryConditions (mg_3d.h:1147-1239)
- * mg3d_coarse_matrix      : constructCoarseMatrixA (mg_3d.h:147-273), A zeroed by caller
- * mg3d_coarse_matrix_shift: the same for the screened operator (diagonal -(6 + sigma*h^2)/h^2; sigma = 0: the same bytes)
- * mg3d_coarse_matrix_coef : the same for the variable-coefficient operator (mg3d_ctx_set_coefficient; eps dense N^3)
- * mg3d_coarse_matrix_periodic: the same with periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
- * mg3d_coarse_matrix_bc   : the same with periodic axes and Neumann faces (mg3d_ctx_set_neumann): reflected rows for the
- *                           Neumann face unknowns; neumann_faces = 0: mg3d_coarse_matrix_periodic, the same bytes
- * mg3d_coarse_matrix_mask : the same with fixed points (mg3d_ctx_set_mask; mask dense N^3 bytes): identity rows at the
- *                           fixed unknowns, and the pin only without one; mask NULL or without a fixed unknown:
- *                           mg3d_coarse_matrix_bc, the same bytes
+ * mg3d_coarse_matrix*     : constructCoarseMatrixA (mg_3d.h:147-273), A zeroed by caller.  ONE builder writes every form;
+ *                           each entry point is that builder with the arguments it does not name at their neutral
+ *                           values (sigma = 0, eps NULL, no periodic axis, no Neumann face, mask NULL), so any two agree
+ *                           byte for byte where their arguments do:
+ *   mg3d_coarse_matrix         : the reference's Dirichlet matrix
+ *   mg3d_coarse_matrix_shift   : + the screened operator (diagonal -(6 + sigma*h^2)/h^2)
+ *   mg3d_coarse_matrix_coef    : + the variable-coefficient operator (mg3d_ctx_set_coefficient; eps dense N^3)
+ *   mg3d_coarse_matrix_periodic: + periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
+ *   mg3d_coarse_matrix_bc      : + Neumann faces (mg3d_ctx_set_neumann): reflected rows for the Neumann face unknowns
+ *   mg3d_coarse_matrix_mask    : + fixed points (mg3d_ctx_set_mask; mask dense N^3 bytes): identity rows at the fixed
+ *                                unknowns, and the pin only without one -- the form mg3d_ctx_build_coarse calls
  * mg3d_neumann_fold_flux  : a prescribed outward normal derivative g folded into the right-hand side d (dense N^3) of the
  *                           homogeneous Neumann operator: d -= 2*a*g/h at each point of each Neumann face in `faces`, a = 1
  *                           (eps NULL) or 0.5*(eps_face + eps_inner), summed over the faces an edge or corner point lies

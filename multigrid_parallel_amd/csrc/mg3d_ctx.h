@@ -109,8 +109,6 @@ struct mg3d_ctx {
     std::vector<hipEvent_t> event_pool;
 };
 
-/* the operator constants of a level of this context (its spacing, the context's sigma) */
-static inline LevelOp mg3d_op(const mg3d_ctx *ctx, const Level &l) { return mg3d_level_op(l.h, ctx->sigma); }
 /* the fused sweep writes out of place: u and its second copy change roles behind every launch with colour passes */
 static inline void swap_u(Level &l)
 {
@@ -123,7 +121,7 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
 {
     SweepLaunch w;
     w.g = &l.g;
-    w.op = mg3d_op(ctx, l);
+    w.op = mg3d_level_op(l.h, ctx->sigma);
     w.vin = l.f[MG3D_U];
     w.d = l.f[MG3D_D];
     w.vout = l.alt;
@@ -137,13 +135,15 @@ static inline bool mg3d_fused(const mg3d_ctx *ctx)
 {
     return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty();
 }
-/* the fixed-point bytes of a level for the launchers (NULL: the context has no mask) */
-static inline const unsigned char *mg3d_ctx_mask(const mg3d_ctx *ctx, int level)
-{
-    return ctx->mask.empty() ? nullptr : ctx->mask[level];
-}
 /* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */
 static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodic, ctx->neumann); }
+/* the operator of a level of this context for the stencil launchers: the constants of its spacing and the context's sigma,
+ * its eps (NULL: constant), the boundary word and its fixed-point bytes (NULL: the context has no mask) */
+static inline LevelOperator mg3d_level_operator(const mg3d_ctx *ctx, int level)
+{
+    return {mg3d_level_op(ctx->lv[level].h, ctx->sigma), ctx->sigma, ctx->eps.empty() ? nullptr : ctx->eps[level],
+            mg3d_ctx_bc(ctx), ctx->mask.empty() ? nullptr : ctx->mask[level]};
+}
 /* sigma = 0, every axis periodic or Neumann on both faces and no fixed unknown on level 0: constants are in the kernel of
  * the coarsest operator, unknown (0,0,0) of level 0 is pinned */
 static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
@@ -168,6 +168,11 @@ struct StageScope {
 };
 /* records a failure text for mg3d_last_error() and returns `code` */
 int mg3d_fail(int code, const char *fmt, ...);
+/* a HIP call that may have allocated failed: MG3D_ERR_ALLOC when the device is out of memory, else MG3D_ERR_HIP, with the
+ * text "<who>: <what>: <HIP's text>" (what NULL: "<who> failed: <HIP's text>", who the call itself) */
+int mg3d_alloc_fail(hipError_t e, const char *who, const char *what = nullptr);
+/* hipMalloc for entry point `who`; *p is NULL when it fails */
+int mg3d_device_alloc(void **p, size_t bytes, const char *who);
 /* enqueue one V-cycle from level q of a (single-domain) context; squared norm of level q to sumsq[slot] */
 /* carry_out: end the cycle with the launch that also starts the next one (only mg3d_vcycles asks, and never for the
  * last cycle of a call); ignored where mg3d_can_carry() says no */

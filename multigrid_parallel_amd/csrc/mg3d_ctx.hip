@@ -31,6 +31,21 @@ int mg3d_fail(int code, const char *fmt, ...)
 }
 #define fail mg3d_fail
 
+int mg3d_alloc_fail(hipError_t e, const char *who, const char *what)
+{
+    const int code = e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP;
+    return what ? fail(code, "%s: %s: %s", who, what, hipGetErrorString(e)) : fail(code, "%s failed: %s", who, hipGetErrorString(e));
+}
+
+int mg3d_device_alloc(void **p, size_t bytes, const char *who)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess)
+        return MG3D_OK;
+    *p = nullptr;
+    return mg3d_alloc_fail(e, who, "hipMalloc");
+}
+
 #define HIPCHK(call)                                                                                       \
     do {                                                                                                   \
         hipError_t e_ = (call);                                                                            \
@@ -377,8 +392,7 @@ static int ctx_create_sizes(const int *n_per_level, const double *h_per_level, i
     do {                                                                                                 \
         hipError_t e_ = (call);                                                                          \
         if (e_ != hipSuccess) {                                                                          \
-            int rc_ = fail(e_ == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s failed: %s", \
-                           #call, hipGetErrorString(e_));                                                \
+            int rc_ = mg3d_alloc_fail(e_, #call);                                                        \
             mg3d_ctx_destroy(ctx);                                                                       \
             return rc_;                                                                                  \
         }                                                                                                \
@@ -645,16 +659,8 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    if (!ctx->mask.empty())
-        mg3d_coarse_matrix_mask(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
-                                ctx->neumann, ctx->mask0.data());
-    else if (ctx->periodic || ctx->neumann)
-        mg3d_coarse_matrix_bc(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
-                              ctx->neumann);
-    else if (ctx->eps.empty())
-        mg3d_coarse_matrix_shift(A, N0, h_coarse, ctx->sigma); /* mg_3d.h:288 */
-    else
-        mg3d_coarse_matrix_coef(A, N0, h_coarse, ctx->eps0.data(), ctx->sigma);
+    mg3d_coarse_matrix_mask(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
+                            ctx->neumann, ctx->mask.empty() ? nullptr : ctx->mask0.data()); /* mg_3d.h:288 */
     mg3d_lu_factor(A, (int)n);                             /* mg_3d.h:289 */
     const int rc = mg3d_ctx_set_lu(ctx, A);
     free(A);
@@ -729,17 +735,46 @@ static int alloc_eps(mg3d_ctx *ctx)
     const int L = ctx->L;
     std::vector<double *> e(L, nullptr);
     for (int l = 0; l < L; l++) {
-        const hipError_t rc = hipMalloc(&e[l], ctx->lv[l].elems * sizeof(double));
-        if (rc == hipSuccess)
+        const int rc = mg3d_device_alloc((void **)&e[l], ctx->lv[l].elems * sizeof(double), "mg3d_ctx_set_coefficient");
+        if (rc == MG3D_OK)
             continue;
         for (double *q : e)
             if (q)
                 (void)hipFree(q);
-        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_coefficient: hipMalloc: %s",
-                    hipGetErrorString(rc));
+        return rc;
     }
     ctx->eps = e;
     return MG3D_OK;
+}
+
+/* the two 64-bit device words of k_coef_check and k_mask_count, and the padded level-0 right-hand side of the direct solve
+ * (k_coarse_rhs): allocated on first use, freed with the context */
+static int ensure_io_chk(mg3d_ctx *ctx, const char *who)
+{
+    return ctx->io_chk ? MG3D_OK : mg3d_device_alloc((void **)&ctx->io_chk, 2 * sizeof(unsigned long long), who);
+}
+static int ensure_per_b(mg3d_ctx *ctx, const char *who)
+{
+    return ctx->per_b ? MG3D_OK : mg3d_device_alloc((void **)&ctx->per_b, ctx->lv[0].elems * sizeof(double), who);
+}
+
+/* what both forms of mg3d_ctx_set_coefficient do once the finest level's eps is written: its duplicates, the injections,
+ * level 0's eps back on the host for the coarse matrix, one host synchronisation -- behind it the caller's array has been
+ * read --, the coarse factor */
+static int coefficient_written(mg3d_ctx *ctx, const char *who)
+{
+    const int L = ctx->L;
+    k_per_refresh(ctx->lv[L - 1].g, ctx->eps[L - 1], ctx->periodic, ctx->stream);
+    for (int l = L - 1; l >= 1; l--)
+        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
+    const Level &l0 = ctx->lv[0];
+    const int N0 = l0.g.N;
+    ctx->eps0.resize((size_t)N0 * N0 * N0);
+    HIPCHK(hipMemcpy2DAsync(ctx->eps0.data(), N0 * sizeof(double), ctx->eps[0], l0.g.pitch * sizeof(double), N0 * sizeof(double),
+                            (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
+    return operator_changed(ctx);
 }
 
 /* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_kernels.hip) on every level: eps of the finest level
@@ -775,22 +810,7 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
     CHK(alloc_eps(ctx));
     HIPCHK(hipMemcpy2DAsync(ctx->eps[L - 1], top.g.pitch * sizeof(double), eps, N * sizeof(double), N * sizeof(double),
                             (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
-    k_per_refresh(top.g, ctx->eps[L - 1], ax, ctx->stream);
-    for (int l = L - 1; l >= 1; l--)
-        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
-    HIPCHK(hipStreamSynchronize(ctx->stream)); /* (the host array may go once the call returns) */
-    CHK(launch_ok("mg3d_ctx_set_coefficient"));
-    /* level 0's eps on the host for the coarse matrix: the same subsample the injections took */
-    const int N0 = ctx->lv[0].g.N;
-    const long long st = 1LL << (L - 1);
-    ctx->eps0.resize((size_t)N0 * N0 * N0);
-    auto src = [&](int x, int bit) { return ((ax & bit) && x == N - 1) ? 0 : x; }; /* (a duplicate's source) */
-    for (int i = 0; i < N0; i++)
-        for (int j = 0; j < N0; j++)
-            for (int k = 0; k < N0; k++)
-                ctx->eps0[((size_t)i * N0 + j) * N0 + k] =
-                    eps[((long long)src(i * st, 1) * N + src(j * st, 2)) * N + src(k * st, 4)];
-    return operator_changed(ctx);
+    return coefficient_written(ctx, "mg3d_ctx_set_coefficient"); /* (the host array may go once the call returns) */
 }
 
 /* Device arrays (mg3d_array, include/mg3d.h): the descriptor checks and the stream join of every mg3d_*_device entry point. */
@@ -836,8 +856,7 @@ int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *wh
 
 /* mg3d_ctx_set_coefficient from a device array, step for step: the check (a launch that reads the array as given; its two
  * integers cross to the host), then the carried cycle, the pack into the finest level's eps, the duplicates, the
- * injections; level 0's eps comes back from the device for the coarse matrix -- the injections of the refreshed top level
- * are the subsample the host form takes.  Two host synchronisations; behind the second one the array has been read, so the
+ * injections (coefficient_written).  Two host synchronisations; behind the second one the array has been read, so the
  * caller's stream needs no event of ours. */
 extern "C" int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps, void *stream)
 {
@@ -851,13 +870,7 @@ extern "C" int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *
     const Level &top = ctx->lv[L - 1];
     const int N = top.g.N;
     const int ax = ctx->periodic;
-    if (!ctx->io_chk) {
-        const hipError_t rc = hipMalloc(&ctx->io_chk, 2 * sizeof(unsigned long long));
-        if (rc != hipSuccess) {
-            ctx->io_chk = nullptr;
-            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
-        }
-    }
+    CHK(ensure_io_chk(ctx, who));
     CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
     unsigned long long chk[2] = {0, 0};
     HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof(unsigned long long), ctx->stream));
@@ -886,17 +899,7 @@ extern "C" int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *
         StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
         k_pack(top.g, ctx->eps[L - 1], *eps, ctx->stream);
     }
-    k_per_refresh(top.g, ctx->eps[L - 1], ax, ctx->stream);
-    for (int l = L - 1; l >= 1; l--)
-        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
-    const Level &l0 = ctx->lv[0];
-    const int N0 = l0.g.N;
-    ctx->eps0.resize((size_t)N0 * N0 * N0);
-    HIPCHK(hipMemcpy2DAsync(ctx->eps0.data(), N0 * sizeof(double), ctx->eps[0], l0.g.pitch * sizeof(double), N0 * sizeof(double),
-                            (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    return operator_changed(ctx);
+    return coefficient_written(ctx, who);
 }
 
 extern "C" int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on)
@@ -970,23 +973,8 @@ static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
 {
     const int L = ctx->L;
     CHK(mg3d_drop_carry(ctx));
-    auto alloc_fail = [&](hipError_t rc) {
-        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
-    };
-    if (!ctx->io_chk) {
-        const hipError_t rc = hipMalloc(&ctx->io_chk, 2 * sizeof(unsigned long long));
-        if (rc != hipSuccess) {
-            ctx->io_chk = nullptr;
-            return alloc_fail(rc);
-        }
-    }
-    if (!ctx->per_b) { /* the right-hand side of the direct solve (k_mask_coarse_rhs) */
-        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
-        if (rc != hipSuccess) {
-            ctx->per_b = nullptr;
-            return alloc_fail(rc);
-        }
-    }
+    CHK(ensure_io_chk(ctx, who));
+    CHK(ensure_per_b(ctx, who));
     std::vector<unsigned char *> m = ctx->mask;
     if (m.empty()) {
         m.assign(L, nullptr);
@@ -1000,7 +988,7 @@ static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
             for (unsigned char *q : m)
                 if (q)
                     (void)hipFree(q);
-            return alloc_fail(rc);
+            return mg3d_alloc_fail(rc, who, "hipMalloc");
         }
     }
     ctx->mask = m;
@@ -1037,9 +1025,7 @@ extern "C" int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask)
     /* through a dense device copy and the pack of the device form: one code path writes the levels */
     const long long N = ctx->lv[ctx->L - 1].g.N, n = N * N * N;
     unsigned char *tmp = nullptr;
-    const hipError_t rc = hipMalloc(&tmp, (size_t)n);
-    if (rc != hipSuccess)
-        return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: hipMalloc: %s", who, hipGetErrorString(rc));
+    CHK(mg3d_device_alloc((void **)&tmp, (size_t)n, who));
     int out = MG3D_OK;
     const hipError_t cp = hipMemcpyAsync(tmp, mask, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
     if (cp != hipSuccess)
@@ -1104,16 +1090,22 @@ static int mask_boundary_changed(mg3d_ctx *ctx, const char *who)
     return operator_changed(ctx);
 }
 
-/* The boundary masks changed from (periodic, neumann) = (per0, neu0): the coarse faces that the restriction weighted are
- * injections again (and vice versa), so every level's are redone; and on a face that was a face of unknowns and is a
- * Dirichlet face now, r of every level still holds the residuals of the other operator where a Dirichlet cycle never
- * writes and the injection reads -- zeroed, as in a context that never had the mask. */
-static void boundary_changed(mg3d_ctx *ctx, int per0, int neu0)
+/* The tail of mg3d_ctx_set_periodic and mg3d_ctx_set_neumann: the boundary masks become (per, neu).  The coarse faces that
+ * the restriction weighted are injections again (and vice versa), so every level's are redone; and on a face that was a
+ * face of unknowns and is a Dirichlet face now, r of every level still holds the residuals of the other operator where a
+ * Dirichlet cycle never writes and the injection reads -- zeroed, as in a context that never had the mask.  Then the mask's
+ * bytes and the coarse factor (mask_boundary_changed). */
+static int set_boundaries(mg3d_ctx *ctx, int per, int neu, const char *who)
 {
-    auto unknown_faces = [](int per, int neu) {
-        int m = neu;
+    if (per || neu)
+        CHK(ensure_per_b(ctx, who));
+    const int per0 = ctx->periodic, neu0 = ctx->neumann;
+    ctx->periodic = per;
+    ctx->neumann = neu;
+    auto unknown_faces = [](int periodic, int neumann) {
+        int m = neumann;
         for (int ax = 0; ax < 3; ax++)
-            if (per >> ax & 1)
+            if (periodic >> ax & 1)
                 m |= 3 << (2 * ax);
         return m;
     };
@@ -1121,6 +1113,7 @@ static void boundary_changed(mg3d_ctx *ctx, int per0, int neu0)
     for (int l = 0; l < ctx->L; l++)
         k_zero_faces(ctx->lv[l].g, ctx->lv[l].f[MG3D_R], back, ctx->stream);
     std::fill(ctx->faces_dirty.begin(), ctx->faces_dirty.end(), 1);
+    return mask_boundary_changed(ctx, who);
 }
 
 /* Periodic axes (mg3d_kernels.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
@@ -1145,18 +1138,7 @@ extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
     CHK(mg3d_drop_carry(ctx));
     if (axes == ctx->periodic)
         return MG3D_OK;
-    if (axes && !ctx->per_b) {
-        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
-        if (rc != hipSuccess) {
-            ctx->per_b = nullptr;
-            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_periodic: hipMalloc: %s",
-                        hipGetErrorString(rc));
-        }
-    }
-    const int per0 = ctx->periodic;
-    ctx->periodic = axes;
-    boundary_changed(ctx, per0, ctx->neumann);
-    return mask_boundary_changed(ctx, "mg3d_ctx_set_periodic");
+    return set_boundaries(ctx, axes, ctx->neumann, "mg3d_ctx_set_periodic");
 }
 
 extern "C" int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes)
@@ -1184,18 +1166,7 @@ extern "C" int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces)
     CHK(mg3d_drop_carry(ctx));
     if (faces == ctx->neumann)
         return MG3D_OK;
-    if (faces && !ctx->per_b) { /* the pinned right-hand side of the direct solve (k_per_coarse_rhs) */
-        const hipError_t rc = hipMalloc(&ctx->per_b, ctx->lv[0].elems * sizeof(double));
-        if (rc != hipSuccess) {
-            ctx->per_b = nullptr;
-            return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_ctx_set_neumann: hipMalloc: %s",
-                        hipGetErrorString(rc));
-        }
-    }
-    const int neu0 = ctx->neumann;
-    ctx->neumann = faces;
-    boundary_changed(ctx, ctx->periodic, neu0);
-    return mask_boundary_changed(ctx, "mg3d_ctx_set_neumann");
+    return set_boundaries(ctx, ctx->periodic, faces, "mg3d_ctx_set_neumann");
 }
 
 extern "C" int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces)
@@ -1408,17 +1379,14 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
         return MG3D_OK;
     }
     const int c1 = post ? 0 : 1;
-    const LevelOp op = mg3d_op(ctx, l);
-    const double *e = ctx->eps.empty() ? nullptr : ctx->eps[level];
-    const unsigned char *m = mg3d_ctx_mask(ctx, level);
+    const LevelOperator A = mg3d_level_operator(ctx, level);
     for (int it = 0; it < 2 * iters; it++) {
         StageScope kt(ctx, level, MG3D_K_COLOUR_PASS, true);
-        k_smooth_color(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), c1 ^ (it & 1), s, -1, -1, m);
+        k_smooth_color(l.g, l.f[MG3D_U], l.f[MG3D_D], A, c1 ^ (it & 1), s);
     }
     if (want_res) {
         StageScope kt(ctx, level, MG3D_K_RESIDUAL, true);
-        k_residual(l.g, l.f[MG3D_U], e, l.f[MG3D_D], op, ctx->sigma, mg3d_ctx_bc(ctx), want_res == 2 ? l.f[MG3D_R] : nullptr,
-                   ctx->partials, ctx->sumsq + slot, s, -1, -1, 0, -1, m);
+        k_residual(l.g, l.f[MG3D_U], l.f[MG3D_D], A, want_res == 2 ? l.f[MG3D_R] : nullptr, ctx->partials, ctx->sumsq + slot, s);
     }
     return MG3D_OK;
 }
@@ -1440,33 +1408,27 @@ static void enqueue_restrict(mg3d_ctx *ctx, int level, bool faces_only = false)
 static void enqueue_prolong(mg3d_ctx *ctx, int level)
 {
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream, -1, -1, mg3d_ctx_mask(ctx, level));
+    k_prolong(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream, -1, -1, mg3d_level_operator(ctx, level).m);
 }
 
-/* periodic: the factor of mg3d_coarse_matrix_bc solves for b = d with 0 in the identity rows of the duplicates and, in
- * the singular case (mg3d_ctx_pinned), of the pinned point (0,0,0); the duplicates of x are then copied from their
- * sources.  Neumann faces alone have no duplicates: only the pinned case takes the detour over per_b */
+/* The direct solve.  Where the coarsest matrix has identity rows inside the domain -- fixed points, the duplicates of a
+ * periodic axis, the pinned point (mg3d_ctx_pinned) of Neumann faces all round -- the factor solves for b = d with those
+ * rows' values in place (k_coarse_rhs: 0; a one-level context has no cycle above the solve, its fixed points keep u's own
+ * values); the duplicates of x are then copied from their sources.  Otherwise (Dirichlet faces, Neumann faces without the
+ * pin) b is d itself, and there is no duplicate to refresh */
 static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* NULL: d of level 0 */)
 {
     Level &l0 = ctx->lv[0];
     if (!rhs)
         rhs = l0.f[MG3D_D];
-    if (!ctx->mask.empty()) {
-        /* fixed points: 0 in their identity rows too (mg3d_coarse_matrix_mask) -- the zero error they hold; a one-level
-         * context has no cycle above the solve, its fixed points keep u's own values */
-        k_mask_coarse_rhs(l0.g, rhs, ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->mask[0],
-                          ctx->L == 1 ? l0.f[MG3D_U] : nullptr, ctx->stream);
-        k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
-        k_per_refresh(l0.g, l0.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
-        return;
-    }
-    if (ctx->periodic || (ctx->neumann && mg3d_ctx_pinned(ctx))) {
-        k_per_coarse_rhs(l0.g, rhs, ctx->per_b, mg3d_ctx_bc(ctx), mg3d_ctx_pinned(ctx), ctx->stream);
-        k_lu_solve(ctx->lu, ctx->lu_in, l0.g, ctx->per_b, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
-        k_per_refresh(l0.g, l0.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
-        return;
+    const int bc = mg3d_ctx_bc(ctx), pin = mg3d_ctx_pinned(ctx);
+    const unsigned char *m = mg3d_level_operator(ctx, 0).m;
+    if (m || ctx->periodic || (ctx->neumann && pin)) {
+        k_coarse_rhs(l0.g, rhs, ctx->per_b, bc, pin, m, ctx->L == 1 ? l0.f[MG3D_U] : nullptr, ctx->stream);
+        rhs = ctx->per_b;
     }
     k_lu_solve(ctx->lu, ctx->lu_in, l0.g, rhs, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
+    k_per_refresh(l0.g, l0.f[MG3D_U], bc, ctx->stream);
 }
 
 static int enqueue_smooth(mg3d_ctx *ctx, int level, int post, int iters)
@@ -1733,10 +1695,10 @@ static void down_leg_tiny(mg3d_ctx *ctx, const CycleState &c)
         StageScope kt(ctx, 1, MG3D_K_SWEEP4, true);
         if (c.tiny_cyc)
             k_tiny_cycle(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], l0.g, l0.f[MG3D_D], l0.f[MG3D_U], ctx->lu, ctx->lu_in,
-                         mg3d_op(ctx, lev), ctx->iters, ctx->stream);
+                         mg3d_level_operator(ctx, 1).op, ctx->iters, ctx->stream);
         else
-            k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], l0.g, l0.f[MG3D_D], mg3d_op(ctx, lev), ctx->iters,
-                        ctx->stream);
+            k_tiny_down(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], lev.f[MG3D_R], l0.g, l0.f[MG3D_D], mg3d_level_operator(ctx, 1).op,
+                        ctx->iters, ctx->stream);
     }
     { StageScope t(ctx, 1, MG3D_ST_RESIDUAL1); } /* inside the launch above: counted, ~0 s */
     { StageScope t(ctx, 1, MG3D_ST_RESTRICT); }
@@ -1798,7 +1760,7 @@ static void up_leg_tiny(mg3d_ctx *ctx, const CycleState &c)
         StageScope t(ctx, 1, MG3D_ST_SMOOTH2);
         if (!c.tiny_cyc) {
             StageScope kt(ctx, 1, MG3D_K_SWEEP4, true);
-            k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], l0.g, l0.f[MG3D_U], mg3d_op(ctx, lev), ctx->iters, ctx->stream);
+            k_tiny_up(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], l0.g, l0.f[MG3D_U], mg3d_level_operator(ctx, 1).op, ctx->iters, ctx->stream);
         }
     }
     { StageScope t(ctx, 1, MG3D_ST_RESIDUAL2); }

@@ -456,8 +456,7 @@ extern "C" int mg3d_dist_create(int coarse_pts, int num_levels, int smooth_iters
     do {                                                                                  \
         hipError_t e_ = (call);                                                           \
         if (e_ != hipSuccess) {                                                           \
-            int rc_ = fail(e_ == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP,    \
-                           "%s failed: %s", #call, hipGetErrorString(e_));                \
+            int rc_ = mg3d_alloc_fail(e_, #call);                                         \
             mg3d_dist_destroy(D);                                                         \
             return rc_;                                                                   \
         }                                                                                 \
@@ -697,7 +696,7 @@ extern "C" int mg3d_dist_build_coarse(mg3d_dist *D, double h_coarse)
 }
 
 /* the screened operator (mg3d_ctx_set_shift) on every local rank: its slab levels take sigma from the rank's replicated
- * context (mg3d_op), whose coarse factor is rebuilt there.  A multi-rank job must agree on sigma (not checked). */
+ * context (mg3d_level_op), whose coarse factor is rebuilt there.  A multi-rank job must agree on sigma (not checked). */
 extern "C" int mg3d_dist_set_shift(mg3d_dist *D, double sigma)
 {
     if (!D || !(sigma >= 0.) || !isfinite(sigma))
@@ -778,13 +777,11 @@ extern "C" int mg3d_dist_set_coefficient(mg3d_dist *D, const double *eps)
     if (!D->coef) {
         for (auto &R : D->rs)
             for (auto &sl : R.dl) {
-                const hipError_t rc = hipMalloc(&sl.eps, sl.lv.elems * sizeof(double));
-                if (rc == hipSuccess)
+                const int rc = mg3d_device_alloc((void **)&sl.eps, sl.lv.elems * sizeof(double), "mg3d_dist_set_coefficient");
+                if (rc == MG3D_OK)
                     continue;
-                sl.eps = nullptr;
                 dist_free_eps(D);
-                return fail(rc == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP,
-                            "mg3d_dist_set_coefficient: hipMalloc: %s", hipGetErrorString(rc));
+                return rc;
             }
     }
     std::vector<double> sub;
@@ -1222,15 +1219,14 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
         SlabLevel &sl = SL(D, R, l);
         Level &lv = sl.lv;
         mg3d_ctx *cx = R.coarse;
-        const LevelOp op = mg3d_op(cx, lv);
+        const LevelOperator A = {mg3d_level_op(lv.h, cx->sigma), cx->sigma, sl.eps, 0, nullptr}; /* (slabs: no boundary word, no mask) */
         for (int t = 1; t <= S; t++) { /* :1282 / :1341 */
             const int w = margin + S - t;
-            k_smooth_color(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, c1 ^ ((t - 1) & 1), s,
-                           sl.own_lo - w, sl.own_hi + w);
+            k_smooth_color(lv.g, lv.f[MG3D_U], lv.f[MG3D_D], A, c1 ^ ((t - 1) & 1), s, sl.own_lo - w, sl.own_hi + w);
         }
         if (want_res == 2) /* :1294 */
-            k_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, lv.f[MG3D_R], cx->partials,
-                       cx->sumsq + cx->sumsq_slots - 1, s, sl.own_lo - 1, sl.own_hi + 1, 0, 0);
+            k_residual(lv.g, lv.f[MG3D_U], lv.f[MG3D_D], A, lv.f[MG3D_R], cx->partials, cx->sumsq + cx->sumsq_slots - 1, s,
+                       sl.own_lo - 1, sl.own_hi + 1, 0, 0);
     }
     if (want_res != 1)
         return MG3D_OK;
@@ -1239,9 +1235,9 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
         SlabLevel &sl = SL(D, R, l);
         Level &lv = sl.lv;
         mg3d_ctx *cx = R.coarse;
-        const LevelOp op = mg3d_op(cx, lv);
-        k_residual(lv.g, lv.f[MG3D_U], sl.eps, lv.f[MG3D_D], op, cx->sigma, 0, nullptr, cx->partials, cx->sumsq, s,
-                   sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
+        const LevelOperator A = {mg3d_level_op(lv.h, cx->sigma), cx->sigma, sl.eps, 0, nullptr}; /* (slabs: no boundary word, no mask) */
+        k_residual(lv.g, lv.f[MG3D_U], lv.f[MG3D_D], A, nullptr, cx->partials, cx->sumsq, s, sl.own_lo, sl.own_hi, sl.own_lo,
+                   sl.own_hi);
     }
     return MG3D_OK;
 }

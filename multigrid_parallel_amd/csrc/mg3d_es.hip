@@ -231,6 +231,9 @@ extern "C" int mg3d_es_smooth(mg3d_ctx *ctx, int level, int post, int iters)
     return launch_ok_es("mg3d_es_smooth");
 }
 
+/* the plain operator of a level: the reference's Laplacian, no shift, no eps, Dirichlet faces as the kernels see them */
+static LevelOperator es_operator(const Level &lev) { return {mg3d_level_op(lev.h, 0.), 0., nullptr, 0, nullptr}; }
+
 static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
 {
     hipStream_t s = ctx->stream;
@@ -241,8 +244,8 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
         if (l < ctx->L - 1)
             HIPCHK(hipMemsetAsync(lev.f[MG3D_U], 0, lev.elems * sizeof(double), s)); /* mg_3d.h:1258-1259 */
         es_smooth(ctx, l, 0, ctx->iters);                                                            /* :1282 */
-        k_residual(lev.g, lev.f[MG3D_U], nullptr, lev.f[MG3D_D], mg3d_level_op(lev.h, 0.), 0., 0, lev.f[MG3D_R],
-                   ctx->partials, ctx->sumsq + ctx->sumsq_slots - 1, s);                            /* :1294 */
+        k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], es_operator(lev), lev.f[MG3D_R], ctx->partials,
+                   ctx->sumsq + ctx->sumsq_slots - 1, s);                                           /* :1294 */
         k_restrict(lev.g, lev.f[MG3D_R], lc.g, lc.f[MG3D_D], 0, s);                                  /* :1310 */
     }
     {
@@ -259,8 +262,8 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
         es_fill(ctx, l, l == ctx->L - 1 ? 1. : 0.);
         es_smooth(ctx, l, 1, ctx->iters);                       /* :1341 */
         if (l == q)
-            k_residual(lev.g, lev.f[MG3D_U], nullptr, lev.f[MG3D_D], mg3d_level_op(lev.h, 0.), 0., 0, nullptr, ctx->partials,
-                       ctx->sumsq + slot, s);                   /* :1354 */
+            k_residual(lev.g, lev.f[MG3D_U], lev.f[MG3D_D], es_operator(lev), nullptr, ctx->partials, ctx->sumsq + slot,
+                       s);                                      /* :1354 */
     }
     return launch_ok_es("mg3d_es_vcycles");
 }

@@ -854,8 +854,7 @@ int mg3d32_create_slabs(int coarse_pts, int num_levels, int smooth_iters, double
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
         if (e_ != hipSuccess) {                                                                \
-            const int rc_ = fail(e_ == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP,   \
-                                 "%s failed: %s", #call, hipGetErrorString(e_));               \
+            const int rc_ = mg3d_alloc_fail(e_, #call);                                        \
             mg3d32_destroy(ctx);                                                               \
             return rc_;                                                                        \
         }                                                                                      \

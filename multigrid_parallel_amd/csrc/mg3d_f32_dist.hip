@@ -194,8 +194,7 @@ extern "C" int mg3d32_dist_create(int coarse_pts, int num_levels, int smooth_ite
     do {                                                                               \
         hipError_t e_ = (call);                                                        \
         if (e_ != hipSuccess) {                                                        \
-            int rc_ = fail(e_ == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, \
-                           "%s failed: %s", #call, hipGetErrorString(e_));             \
+            int rc_ = mg3d_alloc_fail(e_, #call);                                      \
             mg3d32_dist_destroy(D);                                                    \
             return rc_;                                                                \
         }                                                                              \

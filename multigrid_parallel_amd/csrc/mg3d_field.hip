@@ -99,8 +99,7 @@ extern "C" int mg3d_field_gradient(mg3d_ctx *ctx, double scale, double *gi, doub
     hipError_t e = hipMalloc(&scratch, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: the scratch buffer (%zu bytes): %s", who,
-                    bytes, hipGetErrorString(e));
+        return mg3d_alloc_fail(e, who, "the scratch buffer");
     }
     const mg3d_array dense = {scratch, MG3D_F64, {(long long)N * N, N, 1}};
     double *const host[3] = {gi, gj, gk};
@@ -153,8 +152,7 @@ extern "C" int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux)
         return rc;
     const int q = ctx->L - 1, slot = ctx->sumsq_slots - 1;
     const Level &top = ctx->lv[q];
-    if (k_field_flux(top.g, top.f[MG3D_U], ctx->eps.empty() ? nullptr : ctx->eps[q], ctx->mask[q], label, mg3d_ctx_bc(ctx),
-                     ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
+    if (k_field_flux(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q), label, ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
         return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", who);
     rc = field_launch_ok(who);
     double sum = 0.;
@@ -180,8 +178,7 @@ extern "C" int mg3d_field_energy(mg3d_ctx *ctx, double *energy)
         return rc;
     const int q = ctx->L - 1, slot = ctx->sumsq_slots - 1;
     const Level &top = ctx->lv[q];
-    if (k_field_energy(top.g, top.f[MG3D_U], ctx->eps.empty() ? nullptr : ctx->eps[q], mg3d_ctx_bc(ctx), ctx->partials,
-                       ctx->sumsq + slot, ctx->stream) < 0)
+    if (k_field_energy(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q), ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
         return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", who);
     rc = field_launch_ok(who);
     double sum = 0.;

@@ -35,175 +35,76 @@ void mg3d_fill_boundary_host(double *v, int N, double h)
     }
 }
 
-/* constructCoarseMatrixA, mg_3d.h:147-273, of the screened operator Delta_h - sigma.  Row `p` of the dense n x n
- * matrix: identity on boundary nodes (:179-185), (1,1,1,1,1,1,-dg)/h^2 on interior nodes (:257-268) with
- * dg = 6 + sigma*h^2 (sigma = 0: the reference's 6, bit for bit).  A must be zero on entry (calloc, mg_3d.h:283). */
-void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma)
-{
-    const long NN = (long)N * N, n = NN * N;
-    const double hSq = h * h;
-    const double invHsq = 1. / hSq;
-    const double dg = 6. + sigma * hSq;
-    const double off = 1. * invHsq, diag = dg * invHsq;
-    long p = 0;
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++)
-            for (int k = 0; k < N; k++, p++) {
-                double *row = A + p * n;
-                const int interior = i > 0 && i < N - 1 && j > 0 && j < N - 1 && k > 0 && k < N - 1;
-                if (!interior) {
-                    row[p] = 1.;
-                    continue;
-                }
-                row[p - NN] = off;
-                row[p + NN] = off;
-                row[p - N] = off;
-                row[p + N] = off;
-                row[p - 1] = off;
-                row[p + 1] = off;
-                row[p] = -diag;
-            }
-}
-
-void mg3d_coarse_matrix(double *A, int N, double h) { mg3d_coarse_matrix_shift(A, N, h, 0.); }
-
-/* The coarsest matrix of the variable-coefficient operator div(eps grad u) - sigma u (mg3d_ctx_set_coefficient): identity
- * on boundary nodes; on interior node p the face means a = 0.5*(eps[p] + eps[q]) of its six neighbours q (order i-, i+,
- * j-, j+, k-, k+) divided by h^2 off the diagonal, -dg/h^2 on it, dg = (((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp)
- * + sigma*h^2 -- the diagonal of the kernels of mg3d_kernels.hip.  eps is dense N^3; eps = 1 everywhere gives the bytes of
- * mg3d_coarse_matrix_shift.  A must be zero on entry. */
-void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma)
-{
-    const long NN = (long)N * N, n = NN * N;
-    const double hSq = h * h;
-    const double invHsq = 1. / hSq;
-    const double shift = sigma * hSq;
-    long p = 0;
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++)
-            for (int k = 0; k < N; k++, p++) {
-                double *row = A + p * n;
-                const int interior = i > 0 && i < N - 1 && j > 0 && j < N - 1 && k > 0 && k < N - 1;
-                if (!interior) {
-                    row[p] = 1.;
-                    continue;
-                }
-                const double e = eps[p];
-                const double a_im = 0.5 * (e + eps[p - NN]), a_ip = 0.5 * (e + eps[p + NN]);
-                const double a_jm = 0.5 * (e + eps[p - N]), a_jp = 0.5 * (e + eps[p + N]);
-                const double a_km = 0.5 * (e + eps[p - 1]), a_kp = 0.5 * (e + eps[p + 1]);
-                const double dg = ((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp + shift;
-                row[p - NN] = a_im * invHsq;
-                row[p + NN] = a_ip * invHsq;
-                row[p - N] = a_jm * invHsq;
-                row[p + N] = a_jp * invHsq;
-                row[p - 1] = a_km * invHsq;
-                row[p + 1] = a_kp * invHsq;
-                row[p] = -(dg * invHsq);
-            }
-}
-
-/* The coarsest matrix with periodic axes (mg3d_ctx_set_periodic; axes a MG3D_PERIODIC_* mask, eps dense N^3 or NULL for
- * the constant operator).  axes = 0: mg3d_coarse_matrix_shift / _coef, the same bytes.  Otherwise identity rows on the
- * Dirichlet faces (index 0 or N-1 of a non-periodic axis), on the duplicates (index N-1 of a periodic axis) and, all three
- * axes periodic with sigma = 0 (the operator then annihilates constants), on the pinned point (0,0,0); every other row
- * is the row of the kernels of mg3d_kernels.hip with its neighbours wrapped (i-1 at 0 is N-2, i+1 at N-2 is 0).  Needs
- * N - 1 >= 4 on a periodic axis (distinct neighbours).  A must be zero on entry. */
-void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, double sigma, int axes)
-{
-    if (axes == 0) {
-        if (eps)
-            mg3d_coarse_matrix_coef(A, N, h, eps, sigma);
-        else
-            mg3d_coarse_matrix_shift(A, N, h, sigma);
-        return;
-    }
-    const long NN = (long)N * N, n = NN * N;
-    const double hSq = h * h;
-    const double invHsq = 1. / hSq;
-    const double shift = sigma * hSq;
-    const double dg0 = 6. + shift;
-    const double off = 1. * invHsq, diag = dg0 * invHsq;
-    const int pi = axes & 1, pj = (axes >> 1) & 1, pk = (axes >> 2) & 1;
-    const int pin = axes == 7 && sigma == 0.;
-    long p = 0;
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j < N; j++)
-            for (int k = 0; k < N; k++, p++) {
-                double *row = A + p * n;
-                const int dup = (pi && i == N - 1) || (pj && j == N - 1) || (pk && k == N - 1);
-                const int face = (!pi && (i == 0 || i == N - 1)) || (!pj && (j == 0 || j == N - 1)) ||
-                                 (!pk && (k == 0 || k == N - 1));
-                if (dup || face || (pin && p == 0)) {
-                    row[p] = 1.;
-                    continue;
-                }
-                /* (index 0 occurs on periodic axes only; N-2 wraps only there) */
-                const long im = (i == 0 ? N - 2 : i - 1) * NN + j * N + k, ip = (pi && i == N - 2 ? 0 : i + 1) * NN + j * N + k;
-                const long jm = i * NN + (j == 0 ? N - 2 : j - 1) * N + k, jp = i * NN + (pj && j == N - 2 ? 0 : j + 1) * N + k;
-                const long km = i * NN + j * N + (k == 0 ? N - 2 : k - 1), kp = i * NN + j * N + (pk && k == N - 2 ? 0 : k + 1);
-                if (!eps) {
-                    row[im] = off;
-                    row[ip] = off;
-                    row[jm] = off;
-                    row[jp] = off;
-                    row[km] = off;
-                    row[kp] = off;
-                    row[p] = -diag;
-                    continue;
-                }
-                const double e = eps[p];
-                const double a_im = 0.5 * (e + eps[im]), a_ip = 0.5 * (e + eps[ip]);
-                const double a_jm = 0.5 * (e + eps[jm]), a_jp = 0.5 * (e + eps[jp]);
-                const double a_km = 0.5 * (e + eps[km]), a_kp = 0.5 * (e + eps[kp]);
-                const double dg = ((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp + shift;
-                row[im] = a_im * invHsq;
-                row[ip] = a_ip * invHsq;
-                row[jm] = a_jm * invHsq;
-                row[jp] = a_jp * invHsq;
-                row[km] = a_km * invHsq;
-                row[kp] = a_kp * invHsq;
-                row[p] = -(dg * invHsq);
-            }
-}
-
-/* the rows of mg3d_coarse_matrix_bc for any axes and faces; pin: identity row at (0,0,0); mask (may be NULL): identity
- * rows at its nonzero bytes too */
-static void bc_rows(double *A, int N, double h, const double *eps, double sigma, int axes, int faces, int pin,
-                    const unsigned char *mask)
-{
-    const long NN = (long)N * N, n = NN * N;
-    const double hSq = h * h;
-    const double invHsq = 1. / hSq;
-    const double shift = sigma * hSq;
-    const double dg0 = 6. + shift;
-    const double off = 1. * invHsq, diag = dg0 * invHsq;
+/* The coarsest matrix, every form of it: constructCoarseMatrixA, mg_3d.h:147-273, for the operator
+ * div(eps grad u) - sigma u with periodic axes, Neumann faces and fixed points.  Dense n x n, n = N^3; A must be zero on
+ * entry (calloc, mg_3d.h:283).  eps: dense N^3, NULL for the constant operator; axes a MG3D_PERIODIC_* mask; faces a
+ * MG3D_NEUMANN_* mask with no bit on a periodic axis; mask: dense N^3 bytes, NULL for none.
+ * Identity rows (mg_3d.h:179-185) on the Dirichlet faces (index 0 or N-1 of an axis that is not periodic, unless that face
+ * is a Neumann face), on the duplicates (index N-1 of a periodic axis), at the fixed unknowns -- nonzero bytes of mask on
+ * points that are neither; the other bytes change nothing -- and on the pinned point (0,0,0): the pin applies when
+ * sigma = 0, every axis is periodic or Neumann on both faces and there is no fixed unknown, for the operator then
+ * annihilates constants.  The columns of a fixed point stay: its value is the right-hand side of its row, 0 in a cycle.
+ * Every other row is the row of the kernels of mg3d_kernels.hip: its six neighbours q in the order i-, i+, j-, j+, k-, k+,
+ * wrapped on a periodic axis (i-1 at 0 is N-2, i+1 at N-2 is 0; needs N - 1 >= 4 there) and reflected across a Neumann
+ * face (i-1 at 0 is 1, i+1 at N-1 is N-2: the two coincide, so that column receives the sum of both entries, added in
+ * that order; reflection does not widen the band).  Off the diagonal a_q/h^2 with the face mean a_q = 0.5*(eps[p] + eps[q]),
+ * on it -dg/h^2, dg = (((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp) + sigma*h^2; the constant operator writes
+ * (1,1,1,1,1,1,-dg)/h^2 with dg = 6 + sigma*h^2 (mg_3d.h:257-268; sigma = 0: the reference's 6, bit for bit).  Where the
+ * six neighbours are distinct, += on the zeroed row stores the entry itself. */
+struct bc_axes {
     int per[3], rlo[3], rhi[3];
-    for (int ax = 0; ax < 3; ax++) {
-        per[ax] = (axes >> ax) & 1;
-        rlo[ax] = (faces >> (2 * ax)) & 1;
-        rhi[ax] = (faces >> (2 * ax + 1)) & 1;
-    }
+};
+/* a point with an identity row for the boundary's sake: a periodic duplicate, or on a Dirichlet face */
+static int bc_bound(const struct bc_axes *b, int N, const int x[3])
+{
+    int bound = 0;
+    for (int ax = 0; ax < 3; ax++)
+        bound = bound || (b->per[ax] ? x[ax] == N - 1 : ((x[ax] == 0 && !b->rlo[ax]) || (x[ax] == N - 1 && !b->rhi[ax])));
+    return bound;
+}
+static void coarse_rows(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
+                        const unsigned char *mask)
+{
+    const long NN = (long)N * N, n = NN * N;
+    const double hSq = h * h;
+    const double invHsq = 1. / hSq;
+    const double shift = sigma * hSq;
+    const double dg0 = 6. + shift;
+    const double off = 1. * invHsq, diag = dg0 * invHsq;
     const long st[3] = {NN, N, 1};
+    struct bc_axes b;
+    int pin = sigma == 0.;
+    for (int ax = 0; ax < 3; ax++) {
+        b.per[ax] = (axes >> ax) & 1;
+        b.rlo[ax] = (faces >> (2 * ax)) & 1;
+        b.rhi[ax] = (faces >> (2 * ax + 1)) & 1;
+        pin = pin && (b.per[ax] || (b.rlo[ax] && b.rhi[ax]));
+    }
     long p = 0;
+    if (pin && mask) /* a fixed unknown lifts the pin */
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++)
+                for (int k = 0; k < N; k++, p++) {
+                    const int x[3] = {i, j, k};
+                    if (mask[p] && !bc_bound(&b, N, x))
+                        pin = 0;
+                }
+    p = 0;
     for (int i = 0; i < N; i++)
         for (int j = 0; j < N; j++)
             for (int k = 0; k < N; k++, p++) {
                 double *row = A + p * n;
                 const int x[3] = {i, j, k};
-                int fixed = (pin && p == 0) || (mask && mask[p]);
-                long q[6];
-                for (int ax = 0; ax < 3; ax++) {
-                    if (per[ax] ? x[ax] == N - 1 : ((x[ax] == 0 && !rlo[ax]) || (x[ax] == N - 1 && !rhi[ax])))
-                        fixed = 1; /* a duplicate, or on a Dirichlet face */
-                    const int lo = x[ax] == 0 ? (per[ax] ? N - 2 : 1) : x[ax] - 1;
-                    const int hi = (per[ax] && x[ax] == N - 2) ? 0 : (x[ax] == N - 1 ? N - 2 : x[ax] + 1);
-                    q[2 * ax] = p + (lo - x[ax]) * st[ax];
-                    q[2 * ax + 1] = p + (hi - x[ax]) * st[ax];
-                }
-                if (fixed) {
+                if (bc_bound(&b, N, x) || (pin && p == 0) || (mask && mask[p])) {
                     row[p] = 1.;
                     continue;
+                }
+                long q[6];
+                for (int ax = 0; ax < 3; ax++) {
+                    const int lo = x[ax] == 0 ? (b.per[ax] ? N - 2 : 1) : x[ax] - 1;
+                    const int hi = (b.per[ax] && x[ax] == N - 2) ? 0 : (x[ax] == N - 1 ? N - 2 : x[ax] + 1);
+                    q[2 * ax] = p + (lo - x[ax]) * st[ax];
+                    q[2 * ax + 1] = p + (hi - x[ax]) * st[ax];
                 }
                 if (!eps) {
                     for (int t = 0; t < 6; t++)
@@ -222,60 +123,25 @@ static void bc_rows(double *A, int N, double h, const double *eps, double sigma,
             }
 }
 
-/* sigma = 0 and every axis periodic or Neumann on both faces: constants are in the kernel */
-static int bc_closed(double sigma, int axes, int faces)
+/* the exported forms (include/mg3d.h): coarse_rows at the arguments each one names */
+void mg3d_coarse_matrix(double *A, int N, double h) { coarse_rows(A, N, h, NULL, 0., 0, 0, NULL); }
+void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma) { coarse_rows(A, N, h, NULL, sigma, 0, 0, NULL); }
+void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma)
 {
-    int closed = 1;
-    for (int ax = 0; ax < 3; ax++)
-        closed = closed && (((axes >> ax) & 1) || ((faces >> (2 * ax)) & 3) == 3);
-    return closed && sigma == 0.;
+    coarse_rows(A, N, h, eps, sigma, 0, 0, NULL);
 }
-
-/* The coarsest matrix with periodic axes and Neumann faces (mg3d_ctx_set_neumann; faces a MG3D_NEUMANN_* mask with no bit
- * on a periodic axis).  faces = 0: mg3d_coarse_matrix_periodic, the same bytes.  Otherwise its rows, except that a point
- * on a Neumann face is an unknown unless it lies on a Dirichlet face, and its row is the row of the kernels of
- * mg3d_kernels.hip with the neighbour across the face reflected (i-1 at 0 is 1, i+1 at N-1 is N-2): the two coincide, so
- * that column receives the sum of both entries, added in the kernels' operand order (i-, i+, j-, j+, k-, k+).  The pin
- * (identity row of point (0,0,0)) applies when sigma = 0 and every axis is periodic or Neumann on both faces.
- * Reflection does not widen the band.  A must be zero on entry. */
+void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, double sigma, int axes)
+{
+    coarse_rows(A, N, h, eps, sigma, axes, 0, NULL);
+}
 void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double sigma, int axes, int faces)
 {
-    if (faces == 0) {
-        mg3d_coarse_matrix_periodic(A, N, h, eps, sigma, axes);
-        return;
-    }
-    bc_rows(A, N, h, eps, sigma, axes, faces, bc_closed(sigma, axes, faces), NULL);
+    coarse_rows(A, N, h, eps, sigma, axes, faces, NULL);
 }
-
-/* The coarsest matrix with fixed points (mg3d_ctx_set_mask): mg3d_coarse_matrix_bc with identity rows at the fixed
- * unknowns -- nonzero bytes of mask (dense N^3) on points that are neither periodic duplicates nor on a Dirichlet face;
- * the other bytes are ignored.  The columns of a fixed point stay: its value is the right-hand side of its row, 0 in a
- * cycle.  A fixed unknown removes the constants from the kernel, so the pin of (0,0,0) applies only without one.  mask NULL
- * or without a fixed unknown: mg3d_coarse_matrix_bc, the same bytes.  A must be zero on entry. */
 void mg3d_coarse_matrix_mask(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
                              const unsigned char *mask)
 {
-    long fixed = 0;
-    if (mask) {
-        long p = 0;
-        for (int i = 0; i < N; i++)
-            for (int j = 0; j < N; j++)
-                for (int k = 0; k < N; k++, p++) {
-                    const int x[3] = {i, j, k};
-                    int unknown = 1;
-                    for (int ax = 0; ax < 3; ax++) {
-                        const int per = (axes >> ax) & 1, rlo = (faces >> (2 * ax)) & 1, rhi = (faces >> (2 * ax + 1)) & 1;
-                        if (per ? x[ax] == N - 1 : ((x[ax] == 0 && !rlo) || (x[ax] == N - 1 && !rhi)))
-                            unknown = 0;
-                    }
-                    fixed += unknown && mask[p];
-                }
-    }
-    if (!fixed) {
-        mg3d_coarse_matrix_bc(A, N, h, eps, sigma, axes, faces);
-        return;
-    }
-    bc_rows(A, N, h, eps, sigma, axes, faces, 0, mask);
+    coarse_rows(A, N, h, eps, sigma, axes, faces, mask);
 }
 
 /* A prescribed outward normal derivative folded into the right-hand side of the homogeneous Neumann operator (mg3d.h) */

@@ -97,35 +97,43 @@ void mg3d_options_init(mg3d_options *o);          /* defaults + environment */
 int mg3d_option_index(const char *key);           /* -1: no such key */
 const char *mg3d_option_key(int index);           /* NULL past the end */
 
-/* launchers (mg3d_kernels.hip); all asynchronous on `s` */
-/* One colour pass in place and the residual of a level's operator: e = eps of the level in the padded layout for
- * div(eps grad u) - sigma u (mg3d_ctx_set_coefficient), NULL for the constant operator of op; sigma the context's shift;
- * bc the boundary word mg3d_bc(periodic, neumann): the MG3D_PERIODIC_* mask of wrapped axes (mg3d_ctx_set_periodic), whose
+/* One level's operator as the stencil launchers take it: the constants op; sigma, the context's shift; e, eps of the level
+ * in the padded layout for div(eps grad u) - sigma u (mg3d_ctx_set_coefficient), NULL for the constant operator of op; bc,
+ * the boundary word mg3d_bc(periodic, neumann): the MG3D_PERIODIC_* mask of wrapped axes (mg3d_ctx_set_periodic), whose
  * duplicate points receive copies, and above it the MG3D_NEUMANN_* mask of reflected faces (mg3d_ctx_set_neumann), whose
- * points are unknowns; nonzero on single-domain levels only, no windows.  The residual writes res (optional) on the interior and partials (one per block),
- * then reduces them, in a fixed order, into *sumsq_out.  Windows as k_sweep's: i_lo / i_hi the local planes produced,
- * acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
+ * points are unknowns; m, the level's fixed-point bytes in the padded layout (mg3d_ctx_set_mask), NULL for none -- the
+ * colour pass skips a fixed point, the residual is 0. there, apply_dot's q is 0. there.  bc and m are nonzero on
+ * single-domain levels only, which take no windows.  A context's level: mg3d_level_operator (mg3d_ctx.h). */
+struct LevelOperator {
+    LevelOp op;
+    double sigma;
+    const double *e;
+    int bc;
+    const unsigned char *m;
+};
 static inline int mg3d_bc(int periodic, int neumann) { return periodic | neumann << 3; }
-/* m (optional, single-domain levels): the level's fixed-point bytes in the padded layout (mg3d_ctx_set_mask) -- the colour
- * pass skips a fixed point, the residual is 0. there, apply_dot's q is 0. there, the prolongation skips it */
-void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int bc, int color, hipStream_t s, int i_lo = -1, int i_hi = -1, const unsigned char *m = nullptr);
-void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1,
-                int acc_lo = 0, int acc_hi = -1, const unsigned char *m = nullptr);
+
+/* launchers (mg3d_kernels.hip); all asynchronous on `s` */
+/* One colour pass in place and the residual of a level's operator A.  The residual writes res (optional) on the interior
+ * and partials (one per block), then reduces them, in a fixed order, into *sumsq_out.  Windows as k_sweep's: i_lo / i_hi
+ * the local planes produced, acc_lo / acc_hi those entering the norm; -1 / -1 every plane (a single-domain level) */
+void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOperator &A, int color, hipStream_t s,
+                    int i_lo = -1, int i_hi = -1);
+void k_residual(const Geom &g, const double *v, const double *d, const LevelOperator &A, double *res, double *partials,
+                double *sumsq_out, hipStream_t s, int i_lo = -1, int i_hi = -1, int acc_lo = 0, int acc_hi = -1);
 void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out, hipStream_t s);
 /* The vector passes of mg3d_pcg_solve and mg3d_wpcg_solve on a single-domain level, bc the boundary word.  Each
  * touches the unknowns alone, the set the residual counts; sums are per-block partials folded in a fixed order into one
  * device double.  Scalars are read from device memory.  Return value: the number of partials (0: none needed), -1 when the
  * level has no launch shape.  k_pcg_dot and k_pcg_direction take periodic axes only (no Neumann face).
- *   apply_dot   : q = A p (the operator of k_residual: e, op, sigma), *dot_out = sum of w*p*q, w = 1/2 per Neumann face
+ *   apply_dot   : q = A p (the operator of k_residual), *dot_out = sum of w*p*q, w = 1/2 per Neumann face
  *                 the point lies on (1 everywhere without one)
  *   update_norm : alpha = *rz / *pap; x += alpha p, r -= alpha q, *rr_out = sum of r*r; writes nothing unless both dots
  *                 are finite and negative (the operator is negative definite)
  *   dot         : *dot_out = sum of a*b
  *   direction   : beta = *rz_new / *rz_old; p = z + beta p */
-int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
-                    double *partials, double *dot_out, hipStream_t s, const unsigned char *m = nullptr);
+int k_pcg_apply_dot(const Geom &g, const double *p, const LevelOperator &A, double *q, double *partials, double *dot_out,
+                    hipStream_t s);
 int k_pcg_update_norm(const Geom &g, int bc, double *x, double *r, const double *p, const double *q, const double *rz,
                       const double *pap, double *partials, double *rr_out, hipStream_t s);
 int k_pcg_dot(const Geom &g, int bc, const double *a, const double *b, double *partials, double *dot_out, hipStream_t s);
@@ -144,11 +152,11 @@ int k_wpcg_center(const Geom &g, int bc, double *r, const double *wsum, double W
                   hipStream_t s);
 double k_wpcg_weight_sum(const Geom &g, int bc);
 /* The right-hand side of one theta-step (mg3d_step_advance) on a single-domain level, at the unknowns only:
- *   d = -((a*u0 + c1*q) + b*src),  q = A u0 as apply_dot forms it (e, op, sigma, bc);  src NULL: no b*src term
+ *   d = -((a*u0 + c1*q) + b*src),  q = A u0 as apply_dot forms it (A.m is not looked at);  src NULL: no b*src term
  *   backward_euler: c1 = 0 and q is not computed -- d = -(a*u0 + b*src), a streaming pass
  * Return value: 0, or -1 when the level has no launch shape (nothing launched) */
-int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
-               double a, double c1, double b, bool backward_euler, double *d, hipStream_t s);
+int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOperator &A, double a, double c1, double b,
+               bool backward_euler, double *d, hipStream_t s);
 /* The grid transfers.  bc = 0: ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not
  * a slab halo.  bc = mg3d_bc(periodic, neumann) != 0 (single-domain levels): every plane, full weighting on periodic and
  * Neumann faces too, duplicates written with their sources; the window and faces_only are not looked at */
@@ -321,21 +329,20 @@ void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, co
                   const LuBand &lu, const LuBand &lin, const LevelOp &op, int iters, hipStream_t s);
 /* eps of the coarser level by injection at every point */
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
-/* periodic axes and Neumann faces (bc = mg3d_bc(periodic, neumann), single-domain levels): the coarse right-hand side (0
- * in the duplicates' and the pinned point's identity rows) and a duplicate refresh */
-void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s);
+/* periodic axes, Neumann faces and fixed points (bc = mg3d_bc(periodic, neumann), single-domain levels): the right-hand
+ * side of the direct solve -- b = d except in identity rows: 0 in the duplicates' and (pin) the pinned point's, and at the
+ * fixed unknowns of m (NULL: no mask) 0. -- or ufix there when given (a one-level context) --; and a duplicate refresh */
+void k_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
+                  hipStream_t s);
 void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
 /* fixed points (mg3d_ctx_set_mask): one byte per point of a single-domain level in the padded layout (the doubles' index).
  * k_mask_pack: the caller's dense-indexed bytes (mg3d_array of MG3D_U8, any strides) into it, periodic duplicates taking
  * their sources'; k_mask_inject / k_mask_refresh: the coarser level's bytes by injection, the duplicates' from their sources;
- * k_mask_count: *out += the number of fixed UNKNOWNS (no duplicate, on no Dirichlet face); k_mask_coarse_rhs: k_per_coarse_rhs
- * with, at the fixed unknowns, 0. -- or ufix there when given (a one-level context) */
+ * k_mask_count: *out += the number of fixed UNKNOWNS (no duplicate, on no Dirichlet face) */
 void k_mask_pack(const Geom &g, unsigned char *m, const mg3d_array &a, int bc, hipStream_t s);
 void k_mask_inject(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s);
 void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s);
 void k_mask_count(const Geom &g, const unsigned char *m, int bc, unsigned long long *out, hipStream_t s);
-void k_mask_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
-                       hipStream_t s);
 /* full multigrid (mg3d_fmg_solve): every unknown of the fine level (and its periodic duplicates) overwritten with the
  * tensor-product cubic interpolant of the coarse u -- never a Dirichlet point; and d = u at the Dirichlet points of a level,
  * the right-hand side of the direct solve's identity rows.  Single-domain levels, bc the boundary word */
@@ -363,9 +370,9 @@ void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long
  * Both sums: one partial per block, folded in a fixed order.  Return value: the number of partials (k_gradient: 0), -1 when
  * the level has no launch shape (nothing launched). */
 int k_gradient(const Geom &g, const double *u, int bc, double cs, const mg3d_array *const out[3], hipStream_t s);
-int k_field_flux(const Geom &g, const double *u, const double *e, const unsigned char *m, int label, int bc, double *partials,
-                 double *out, hipStream_t s);
-int k_field_energy(const Geom &g, const double *u, const double *e, int bc, double *partials, double *out, hipStream_t s);
+int k_field_flux(const Geom &g, const double *u, const LevelOperator &A, int label, double *partials, double *out,
+                 hipStream_t s);
+int k_field_energy(const Geom &g, const double *u, const LevelOperator &A, double *partials, double *out, hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

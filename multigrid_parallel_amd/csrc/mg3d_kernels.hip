@@ -387,23 +387,23 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
     });
 }
 
-void k_smooth_color(const Geom &g, double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                    int bc, int color, hipStream_t s, int i_lo, int i_hi, const unsigned char *m)
+void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOperator &A, int color, hipStream_t s, int i_lo,
+                    int i_hi)
 {
-    if (!stencil_window(g, bc, i_lo, i_hi))
+    if (!stencil_window(g, A.bc, i_lo, i_hi))
         return;
     const dim3 block(WAVE, 4, 1);
-    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
+    dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
         if constexpr (coef()) {
             int chunk;
-            const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk);
-            launch_op(mask, OP_KERNELS(coef_color_kernel, mode()), grid, block, s, m, g, v, e, d, op.hSq, sigma * op.hSq, color,
-                      bc, chunk, i_lo, i_hi);
+            const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk);
+            launch_op(mask, OP_KERNELS(coef_color_kernel, mode()), grid, block, s, A.m, g, v, A.e, d, A.op.hSq,
+                      A.sigma * A.op.hSq, color, A.bc, chunk, i_lo, i_hi);
         } else {
             const int pairs = (g.nk + 1) / 2;
-            const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(bc, 1) + 3) / 4, i_hi - i_lo);
-            launch_op(mask, OP_KERNELS(smooth_color_kernel, mode()), grid, block, s, m, g, v, d, op.hSq, op.sixth, color, bc,
-                      i_lo);
+            const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(A.bc, 1) + 3) / 4, i_hi - i_lo);
+            launch_op(mask, OP_KERNELS(smooth_color_kernel, mode()), grid, block, s, A.m, g, v, d, A.op.hSq, A.op.sixth, color,
+                      A.bc, i_lo);
         }
     });
 }
@@ -547,22 +547,23 @@ void k_fold(const double *partials, int np, double *out, hipStream_t s)
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, np, out);
 }
 
-void k_residual(const Geom &g, const double *v, const double *e, const double *d, const LevelOp &op, double sigma,
-                int bc, double *res, double *partials, double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo,
-                int acc_hi, const unsigned char *m)
+/* the diagonal's constant term as the column kernels take it: sigma*h^2 beside the face means of eps, else op's 6 + sigma*h^2 */
+static double op_dg0(const LevelOperator &A) { return A.e ? A.sigma * A.op.hSq : A.op.dg; }
+
+void k_residual(const Geom &g, const double *v, const double *d, const LevelOperator &A, double *res, double *partials,
+                double *sumsq_out, hipStream_t s, int i_lo, int i_hi, int acc_lo, int acc_hi)
 {
-    if (!stencil_window(g, bc, i_lo, i_hi)) {
+    if (!stencil_window(g, A.bc, i_lo, i_hi)) {
         (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
         return;
     }
     if (acc_hi < 0)
         acc_hi = g.ni;
     int chunk;
-    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
-    const double dg0 = e ? sigma * op.hSq : op.dg;
-    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
-        launch_op(mask, OP_KERNELS(residual_kernel, coef(), mode()), grid, block, s, m, g, v, e, d, op.invHsq, dg0, res, partials,
-                  bc, chunk, i_lo, i_hi, acc_lo, acc_hi);
+    const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
+        launch_op(mask, OP_KERNELS(residual_kernel, coef(), mode()), grid, block, s, A.m, g, v, A.e, d, A.op.invHsq, op_dg0(A),
+                  res, partials, A.bc, chunk, i_lo, i_hi, acc_lo, acc_hi);
     });
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
@@ -616,20 +617,19 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
         partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
-int k_pcg_apply_dot(const Geom &g, const double *p, const double *e, const LevelOp &op, double sigma, int bc, double *q,
-                    double *partials, double *dot_out, hipStream_t s, const unsigned char *m)
+int k_pcg_apply_dot(const Geom &g, const double *p, const LevelOperator &A, double *q, double *partials, double *dot_out,
+                    hipStream_t s)
 {
     int i_lo = -1, i_hi = -1;
-    if (!stencil_window(g, bc, i_lo, i_hi)) {
+    if (!stencil_window(g, A.bc, i_lo, i_hi)) {
         (void)hipMemsetAsync(dot_out, 0, sizeof(double), s);
         return 0;
     }
     int chunk;
-    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
-    const double dg0 = e ? sigma * op.hSq : op.dg;
-    dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) {
-        launch_op(mask, OP_KERNELS(pcg_apply_kernel, coef(), mode()), grid, block, s, m, g, p, e, op.invHsq, dg0, q, partials, bc,
-                  chunk, i_lo, i_hi);
+    const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
+        launch_op(mask, OP_KERNELS(pcg_apply_kernel, coef(), mode()), grid, block, s, A.m, g, p, A.e, A.op.invHsq, op_dg0(A), q,
+                  partials, A.bc, chunk, i_lo, i_hi);
     });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, dot_out, s);
@@ -981,23 +981,22 @@ __global__ void __launch_bounds__(256) step_rhs_be_kernel(Geom g, const double *
     }
 }
 
-int k_step_rhs(const Geom &g, const double *u0, const double *e, const double *src, const LevelOp &op, double sigma, int bc,
-               double a, double c1, double b, bool backward_euler, double *d, hipStream_t s)
+int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOperator &A, double a, double c1, double b,
+               bool backward_euler, double *d, hipStream_t s)
 {
     if (backward_euler)
-        return pair_launch(step_rhs_be_kernel, g, bc, s, u0, src, a, b, d) < 0 ? -1 : 0;
+        return pair_launch(step_rhs_be_kernel, g, A.bc, s, u0, src, a, b, d) < 0 ? -1 : 0;
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
         return -1;
     int i_lo = -1, i_hi = -1;
-    if (!stencil_window(g, bc, i_lo, i_hi))
+    if (!stencil_window(g, A.bc, i_lo, i_hi))
         return 0;
     int chunk;
-    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
-    const double dg0 = e ? sigma * op.hSq : op.dg;
+    const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     /* (no MASK form: d at a fixed point is never read, what the pass writes there is unspecified) */
-    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
-        hipLaunchKernelGGL((step_rhs_kernel<coef(), mode()>), grid, block, 0, s, g, u0, e, src, op.invHsq, dg0, a, c1, b, d, bc,
-                           chunk, i_lo, i_hi);
+    dispatch_op(A.e, A.bc, nullptr, [&](auto coef, auto mode, auto) {
+        hipLaunchKernelGGL((step_rhs_kernel<coef(), mode()>), grid, block, 0, s, g, u0, A.e, src, A.op.invHsq, op_dg0(A), a, c1, b,
+                           d, A.bc, chunk, i_lo, i_hi);
     });
     return 0;
 }
@@ -1595,27 +1594,47 @@ void k_dirichlet_rhs(const Geom &g, const double *u, double *d, int bc, hipStrea
 }
 
 /* ------------------------------------------------------------- coarsest level
- * Periodic axes: the right-hand side of the direct solve (mg3d_coarse_matrix_periodic): d at every point, except 0 in the identity
- * rows of the duplicates and of the pinned point (0,0,0) -- so a duplicate's d is never read, and those rows' solution
- * is 0 until the refresh below copies the sources over the duplicates. */
-__global__ void __launch_bounds__(256) per_coarse_rhs_kernel(Geom g, const double *__restrict__ d, double *__restrict__ b,
-                                                             int axes, int pin)
+ * The level-0 right-hand side of the direct solve where the coarsest matrix (mg3d_coarse_matrix_mask) has identity rows
+ * inside the domain: d at every point, except 0 in the rows of the periodic duplicates and of the pinned point (0,0,0) --
+ * so a duplicate's d is never read, and those rows' solution is 0 until the refresh below copies the sources over the
+ * duplicates -- and, MASK, at a fixed unknown the value of its row: 0., the error a fixed point holds in a cycle (ufix NULL),
+ * or u's own value there (a one-level context: the direct solve IS the solve).  MASK = false has neither argument. */
+__device__ __forceinline__ bool coarse_fixed(long long, double &) { return false; }
+__device__ __forceinline__ bool coarse_fixed(long long p, double &x, const unsigned char *m, const double *ufix)
 {
+    if (!m[p])
+        return false;
+    x = ufix ? ufix[p] : 0.;
+    return true;
+}
+template <bool MASK, class... M>
+__global__ void __launch_bounds__(256) coarse_rhs_kernel(Geom g, const double *__restrict__ d, double *__restrict__ b, int bc,
+                                                         int pin, M... fixed)
+{
+    static_assert(sizeof...(M) == (MASK ? 2 : 0), "MASK: the mask and ufix are the two trailing arguments");
     const int k = blockIdx.x * WAVE + threadIdx.x;
     const int j = blockIdx.y * 4 + threadIdx.y;
     const int i = blockIdx.z;
     const int N = g.N;
     if (k >= N || j >= N)
         return;
+    const int axes = bc & 7;
     const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
     const long long p = gidx(g, i, j, k);
-    b[p] = (dup || (pin && (i | j | k) == 0)) ? 0. : d[p];
+    double x = 0.;
+    if (!(dup || (pin && (i | j | k) == 0)) && !(MASK && bc_unknown(bc, N, i, j, k) && coarse_fixed(p, x, fixed...)))
+        x = d[p];
+    b[p] = x;
 }
 
-void k_per_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, hipStream_t s)
+void k_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
+                  hipStream_t s)
 {
-    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
-    hipLaunchKernelGGL(per_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, bc & 7, pin);
+    const dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N), block(WAVE, 4, 1);
+    if (m)
+        hipLaunchKernelGGL((coarse_rhs_kernel<true, MaskPtr, const double *>), grid, block, 0, s, g, d, b, bc, pin, m, ufix);
+    else
+        hipLaunchKernelGGL((coarse_rhs_kernel<false>), grid, block, 0, s, g, d, b, bc, pin);
 }
 
 /* Every duplicate of a field from its source: blockIdx.z = the axis whose duplicate plane a thread covers; (a, b) the
@@ -1653,39 +1672,6 @@ void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s)
 }
 
 /* ------------------------------------------------------------- fixed points */
-
-/* The level-0 right-hand side of the direct solve on a context with fixed points: per_coarse_rhs_kernel's, and at a fixed
- * unknown the value of its identity row -- 0., the error a fixed point holds in a cycle (ufix NULL), or u's own value there
- * (a one-level context: the direct solve IS the solve). */
-__global__ void __launch_bounds__(256) mask_coarse_rhs_kernel(Geom g, const double *__restrict__ d, double *__restrict__ b,
-                                                              int bc, int pin, const unsigned char *__restrict__ m,
-                                                              const double *__restrict__ ufix)
-{
-    const int k = blockIdx.x * WAVE + threadIdx.x;
-    const int j = blockIdx.y * 4 + threadIdx.y;
-    const int i = blockIdx.z;
-    const int N = g.N;
-    if (k >= N || j >= N)
-        return;
-    const int axes = bc & 7;
-    const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
-    const long long p = gidx(g, i, j, k);
-    double x;
-    if (dup || (pin && (i | j | k) == 0))
-        x = 0.;
-    else if (bc_unknown(bc, N, i, j, k) && m[p])
-        x = ufix ? ufix[p] : 0.;
-    else
-        x = d[p];
-    b[p] = x;
-}
-
-void k_mask_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
-                       hipStream_t s)
-{
-    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
-    hipLaunchKernelGGL(mask_coarse_rhs_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, d, b, bc, pin, m, ufix);
-}
 
 /* the fixed UNKNOWNS of a level, counted: one 64-bit atomic add per block that found any */
 __global__ void __launch_bounds__(256) mask_count_kernel(Geom g, const unsigned char *__restrict__ m, int bc,
@@ -2028,20 +2014,20 @@ __global__ void __launch_bounds__(256) field_flux_kernel(Geom g, const double *_
         partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
-int k_field_flux(const Geom &g, const double *u, const double *e, const unsigned char *m, int label, int bc, double *partials,
-                 double *out, hipStream_t s)
+int k_field_flux(const Geom &g, const double *u, const LevelOperator &A, int label, double *partials, double *out,
+                 hipStream_t s)
 {
     int i_lo = -1, i_hi = -1;
-    if (!stencil_window(g, bc, i_lo, i_hi)) {
+    if (!stencil_window(g, A.bc, i_lo, i_hi)) {
         (void)hipMemsetAsync(out, 0, sizeof(double), s);
         return 0;
     }
     int chunk;
-    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
-    const double dg0 = e ? 0. : 6.;
-    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
-        hipLaunchKernelGGL((field_flux_kernel<coef(), mode()>), grid, block, 0, s, g, u, e, m, label, dg0, partials, bc, chunk,
-                           i_lo, i_hi);
+    const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const double dg0 = A.e ? 0. : 6.; /* (the flux of div(eps grad u): sigma is no part of it) */
+    dispatch_op(A.e, A.bc, nullptr, [&](auto coef, auto mode, auto) {
+        hipLaunchKernelGGL((field_flux_kernel<coef(), mode()>), grid, block, 0, s, g, u, A.e, A.m, label, dg0, partials, A.bc,
+                           chunk, i_lo, i_hi);
     });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, out, s);
@@ -2128,7 +2114,7 @@ __global__ void __launch_bounds__(256) field_energy_kernel(Geom g, const double 
         partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
-int k_field_energy(const Geom &g, const double *u, const double *e, int bc, double *partials, double *out, hipStream_t s)
+int k_field_energy(const Geom &g, const double *u, const LevelOperator &A, double *partials, double *out, hipStream_t s)
 {
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
         return -1;
@@ -2137,8 +2123,8 @@ int k_field_energy(const Geom &g, const double *u, const double *e, int bc, doub
     while ((long long)gx * gy * ((g.N + chunk - 1) / chunk) > MG3D_MAX_PARTIALS)
         chunk *= 2;
     const dim3 grid(gx, gy, (g.N + chunk - 1) / chunk), block(WAVE, 4, 1);
-    dispatch_op(e, bc, nullptr, [&](auto coef, auto mode, auto) {
-        hipLaunchKernelGGL((field_energy_kernel<coef(), mode()>), grid, block, 0, s, g, u, e, partials, bc, chunk);
+    dispatch_op(A.e, A.bc, nullptr, [&](auto coef, auto mode, auto) {
+        hipLaunchKernelGGL((field_energy_kernel<coef(), mode()>), grid, block, 0, s, g, u, A.e, partials, A.bc, chunk);
     });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, out, s);

@@ -85,8 +85,7 @@ static int pcg_alloc(mg3d_ctx *ctx, const char *name)
             for (double *w : v)
                 if (w)
                     (void)hipFree(w);
-            return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "%s: work vectors: %s", name,
-                        hipGetErrorString(e));
+            return mg3d_alloc_fail(e, name, "work vectors");
         }
     }
     for (int t = 0; t < 4; t++)
@@ -108,8 +107,7 @@ static int pcg_iterate(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, 
 {
     Level &top = ctx->lv[ctx->L - 1];
     const int q = ctx->L - 1, bc = mg3d_ctx_bc(ctx);
-    const double *e = ctx->eps.empty() ? nullptr : ctx->eps[q];
-    const LevelOp op = mg3d_op(ctx, top);
+    const LevelOperator A = mg3d_level_operator(ctx, q);
     hipStream_t s = ctx->stream;
     double *const sc = ctx->sumsq, *const r = ctx->pcg_v[V_R], *const p = ctx->pcg_v[V_P], *const qv = ctx->pcg_v[V_Q];
     for (int k = 0;; k++) {
@@ -132,7 +130,7 @@ static int pcg_iterate(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, 
             k_pcg_direction(top.g, bc, p, z, rz, rz_old, s);
         {
             StageScope kt(ctx, q, MG3D_K_PCG_APPLY, true);
-            k_pcg_apply_dot(top.g, p, e, op, ctx->sigma, bc, qv, ctx->partials, sc + S_PAP, s, mg3d_ctx_mask(ctx, q));
+            k_pcg_apply_dot(top.g, p, A, qv, ctx->partials, sc + S_PAP, s);
         }
         k_pcg_update_norm(top.g, bc, x, r, p, qv, rz, sc + S_PAP, ctx->partials, sc + S_RR, s);
         CHK(pcg_launch_ok(name, "iteration"));
@@ -182,14 +180,13 @@ static int pcg_run(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, doub
     CHK(mg3d_drop_carry(ctx)); /* a cycle that has run ahead is finished first */
     const int q = ctx->L - 1, bc = mg3d_ctx_bc(ctx);
     Level &top = ctx->lv[q];
-    const double *e = ctx->eps.empty() ? nullptr : ctx->eps[q];
     hipStream_t s = ctx->stream;
     const bool stored = max_iters > 0 || ip.singular; /* the projection works on the stored residual */
     if (stored)
         CHK(pcg_alloc(ctx, name));
     /* r_0 = d - A x; with iterations to come it is stored as the first right-hand side of the cycle */
-    k_residual(top.g, top.f[MG3D_U], e, top.f[MG3D_D], mg3d_op(ctx, top), ctx->sigma, bc,
-               stored ? ctx->pcg_v[V_R] : nullptr, ctx->partials, ctx->sumsq + S_R0, s, -1, -1, 0, -1, mg3d_ctx_mask(ctx, q));
+    k_residual(top.g, top.f[MG3D_U], top.f[MG3D_D], mg3d_level_operator(ctx, q), stored ? ctx->pcg_v[V_R] : nullptr,
+               ctx->partials, ctx->sumsq + S_R0, s);
     if (ip.singular) {
         /* sum(w r_0) and sum(w d), then r_0 -= sum(w r_0)/W and its norm */
         double *const sc = ctx->sumsq, *const r = ctx->pcg_v[V_R];

@@ -59,8 +59,7 @@ static int step_src_alloc(mg3d_ctx *ctx)
         (void)hipStreamSynchronize(ctx->stream);
         if (v)
             (void)hipFree(v);
-        return fail(e == hipErrorOutOfMemory ? MG3D_ERR_ALLOC : MG3D_ERR_HIP, "mg3d_step_set_source: the source field: %s",
-                    hipGetErrorString(e));
+        return mg3d_alloc_fail(e, "mg3d_step_set_source", "the source field");
     }
     ctx->step_src = v;
     return MG3D_OK;
@@ -124,7 +123,7 @@ extern "C" int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s, v
 static int step_run(mg3d_ctx *ctx, int nsteps, int method, int cycles, double rtol, double *norms, int &done, int &iters,
                     int &converged)
 {
-    const int q = ctx->L - 1, bc = mg3d_ctx_bc(ctx);
+    const int q = ctx->L - 1;
     const double theta = ctx->step_theta;
     const bool be = theta == 1.0;
     const double c0 = 1.0 / (theta * ctx->step_dt);
@@ -144,9 +143,8 @@ static int step_run(mg3d_ctx *ctx, int nsteps, int method, int cycles, double rt
         const Level &top = ctx->lv[q];
         {
             StageScope kt(ctx, q, MG3D_K_STEP_RHS, true);
-            if (k_step_rhs(top.g, top.f[MG3D_U], ctx->eps.empty() ? nullptr : ctx->eps[q],
-                           ctx->step_has_src ? ctx->step_src : nullptr, mg3d_op(ctx, top), ctx->sigma, bc, a, c1, b, be,
-                           top.f[MG3D_D], ctx->stream) < 0)
+            if (k_step_rhs(top.g, top.f[MG3D_U], ctx->step_has_src ? ctx->step_src : nullptr, mg3d_level_operator(ctx, q), a, c1,
+                           b, be, top.f[MG3D_D], ctx->stream) < 0)
                 return fail(MG3D_ERR_STATE, "mg3d_step_advance: the level has no launch shape");
         }
         const hipError_t e = hipGetLastError();

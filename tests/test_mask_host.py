@@ -172,6 +172,20 @@ def test_pin_rule():
     assert MR.pinned(0, 63, 0.0, MR.inject(top, 2)[0]) and not MR.singular(0, 63, 0.0, MR.inject(top, 2)[0], top)
 
 
+@pytest.mark.parametrize("N", [3, 5, 9])
+@pytest.mark.parametrize("sigma", [0.0, 3.5])
+def test_the_plain_arguments_give_the_reference_matrix(N, sigma):
+    """the long hop in one step: no eps, no periodic axis, no Neumann face and no mask (NULL and all-zero) is the
+    reference's Dirichlet matrix (orc_coarse_matrix_shift), byte for byte; the same with eps = 1 everywhere"""
+    import _oracle as O
+    h = 0.125
+    want = np.zeros(N ** 6)
+    O.lib().orc_coarse_matrix_shift(O.P(want), N, h, sigma)
+    for e in (None, np.ones((N, N, N))):
+        for mask in (None, np.zeros((N, N, N), dtype=np.uint8)):
+            assert _lib_matrix(N, h, e, sigma, 0, 0, mask).tobytes() == want.tobytes(), (e is not None, mask is not None)
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="GPU present")
 def test_entry_points_without_a_device():
     L = M.lib()
