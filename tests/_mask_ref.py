@@ -95,6 +95,35 @@ def prolong(ec, ef, axes, faces, mask_f):
     ef[keep] = old
 
 
+# ---- block forms, for levels too large for whole-array temporaries (_neumann_ref's block forms with the mask)
+
+def colour_pass_blocks(u, d, e, h, sigma, axes, faces, colour, mask, planes=16):
+    keep = _keep(mask, axes, faces)
+    old = u[keep].copy()
+    NR.colour_pass_blocks(u, d, e, h, sigma, axes, faces, colour, planes)
+    u[keep] = old
+
+
+def residual_blocks(u, d, e, h, sigma, axes, faces, mask, r=None, planes=16):
+    """residual over blocks of i-planes: r (optional) receives what residual() stores, bit for bit; returns the norm over
+    the free unknowns, squares summed in extended precision"""
+    N = u.shape[0]
+    invHsq = 1.0 / (h * h)
+    _, jb, kb = NR.block(N, axes, faces)
+    fx = fixed(mask, axes, faces)
+    total = np.longdouble(0)
+    for a, b, rows in NR._i_blocks(N, axes, faces, planes):
+        s, dg, c = NR._block_sum_diag(u, e, h, sigma, axes, faces, rows)
+        blk = (slice(a, b), jb, kb)
+        with np.errstate(all="ignore"):
+            diff = d[blk] - invHsq * (s - dg * c)
+        diff[fx[blk]] = 0.
+        if r is not None:
+            NR.put(r, diff, blk, axes if a == 0 else axes & 6)
+        total += np.sum((diff * diff).astype(np.longdouble))
+    return float(np.sqrt(total))
+
+
 def pinned(axes, faces, sigma, mask0):
     """the pin of unknown (0,0,0) of level 0: the old condition, and no fixed unknown on level 0"""
     return NR.pinned(axes, faces, sigma) and not fixed(mask0, axes, faces).any()
@@ -360,11 +389,21 @@ def exact_problem(which, N=17):
     return 6, 0, mask, u0, exact
 
 
+def spread(make, x0, d, iters):
+    """two restatement runs of max(iters) iterations from x0 with right-hand side d on make()'s Hierarchy, exactly rounded
+    dots against numpy's pairwise float64 sums: ([relative difference of the iterates x_k, max|a - b| / max|a|, for k in
+    iters], the largest relative difference of the norms r_1 .. r_max)"""
+    ha, hb = [], []
+    _, na, _, _, _ = wpcg(make(), x0, d, 0., 1e-300, max(iters), "exact", ha)
+    _, nb, _, _, _ = wpcg(make(), x0, d, 0., 1e-300, max(iters), "plain", hb)
+    return ([float(np.abs(ha[k - 1] - hb[k - 1]).max() / np.abs(ha[k - 1]).max()) for k in iters],
+            float((np.abs(na[1:] - nb[1:]) / na[1:]).max()))
+
+
 def summation_spread(iters=(1, 2, 5)):
     """What a summation order is worth on the masked solver problems of tests/test_gpu_mask.py, measured as
-    _pcg_ref.summation_spread does: two restatement runs from the tests' own start, exactly rounded dots against numpy's
-    pairwise float64 sums; per problem the relative difference of the iterates x_k (max|a - b| / max|a|) and the largest
-    relative difference of the norms r_1 .. r_5"""
+    _pcg_ref.summation_spread does (`spread`), from the tests' own start; per problem the relative difference of the
+    iterates x_k and the largest relative difference of the norms r_1 .. r_5"""
     cases = {}
     for which in ("a", "b"):
         axes, faces, mask, u0, _ = exact_problem(which)
@@ -373,14 +412,7 @@ def summation_spread(iters=(1, 2, 5)):
     u0 = np.zeros((33, 33, 33))
     u0[ball != 0] = 1.0
     cases["sphere 33"] = (lambda: Hierarchy(5, 4, 2, 0.0, None, 0, 0, ball), u0)
-    out = {}
-    for name, (make, x0) in cases.items():
-        ha, hb = [], []
-        _, na, _, _, _ = wpcg(make(), x0, np.zeros_like(x0), 0., 1e-300, max(iters), "exact", ha)
-        _, nb, _, _, _ = wpcg(make(), x0, np.zeros_like(x0), 0., 1e-300, max(iters), "plain", hb)
-        out[name] = ([float(np.abs(ha[k - 1] - hb[k - 1]).max() / np.abs(ha[k - 1]).max()) for k in iters],
-                     float((np.abs(na[1:] - nb[1:]) / na[1:]).max()))
-    return out
+    return {name: spread(make, x0, np.zeros_like(x0), iters) for name, (make, x0) in cases.items()}
 
 
 if __name__ == "__main__":

@@ -162,8 +162,10 @@ def test_single_operators(axes, faces, sigma, field):
 @pytest.mark.parametrize("c,axes", [(18, 0), (19, 7)])
 @pytest.mark.parametrize("field", ["const", "eps"])
 def test_launch_tails(c, axes, field):
-    """the colour pass and the residual at 69^3 (all Dirichlet) and 73^3 (periodic): two k-blocks of 64 lanes, a partial
-    last row group, several 16-plane chunks; fixed points at the first and last unknown of a row, a column and a chunk.
+    """the colour pass and the residual at 69^3 (all Dirichlet) and 73^3 (periodic): a partial last row group, several
+    16-plane chunks and, for the column kernels (the residual and the eps colour pass), two k-blocks of 64 lanes; the
+    constant colour pass, whose lanes own k-pairs, has one k-block of 35 or 37 pairs here (two from 65 pairs on:
+    tests/test_gpu_mask_shapes.py).  Fixed points at the first and last unknown of a row, a column and a chunk.
     (No coarse factor: c^3 unknowns are too many for a dense one, and these entry points need none.)"""
     L, sigma = 3, 3.5
     N = _n(c, L)

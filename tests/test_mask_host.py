@@ -198,3 +198,35 @@ def test_entry_points_without_a_device():
     with pytest.raises(M.Mg3dError) as ei:
         M.Solver(5, 3, 2).set_mask(np.zeros(17 ** 3, dtype=np.uint8))
     assert ei.value.code == 2  # MG3D_ERR_NO_DEVICE, from the context
+
+
+@pytest.mark.parametrize("axes,faces", BCS)
+@pytest.mark.parametrize("field", ["const", "eps"])
+def test_block_forms_equal_the_whole_array_forms(axes, faces, field):
+    """colour_pass_blocks and residual_blocks (the forms the 513^3 GPU test is held to) against colour_pass and residual at
+    21^3 with blocks of 5 planes -- a short last block -- and d poisoned at the fixed unknowns: u and r bit for bit, the
+    norm that of exact_residual_norm"""
+    N, h, sigma = 21, 0.05, 3.5
+    e = _eps(N) if field == "eps" else None
+    if e is not None:
+        NR.refresh(e, axes)
+    rng = np.random.default_rng(axes + 8 * faces)
+    mask = MR.stored((rng.uniform(size=(N, N, N)) < 0.2).astype(np.uint8), axes)
+    u, d = rng.standard_normal((N, N, N)), rng.standard_normal((N, N, N))
+    NR.refresh(u, axes)
+    fx = MR.fixed(mask, axes, faces)
+    assert fx.any()
+    d[fx] = np.nan
+    for colour in (1, 0):
+        a, b = u.copy(), u.copy()
+        MR.colour_pass(a, d, e, h, sigma, axes, faces, colour, mask)
+        MR.colour_pass_blocks(b, d, e, h, sigma, axes, faces, colour, mask, planes=5)
+        assert np.array_equal(a, b) and np.array_equal(np.signbit(a), np.signbit(b)) and not np.array_equal(a, u)
+        u = a
+    ra = rng.standard_normal((N, N, N))
+    rb = ra.copy()
+    MR.residual(u, d, e, h, sigma, axes, faces, mask, ra)
+    got = MR.residual_blocks(u, d, e, h, sigma, axes, faces, mask, rb, planes=5)
+    assert np.array_equal(ra, rb) and np.array_equal(np.signbit(ra), np.signbit(rb)) and not rb[fx].any()
+    exact = MR.exact_residual_norm(u, d, e, h, sigma, axes, faces, mask)
+    assert abs(got - exact) <= 1e-14 * exact
