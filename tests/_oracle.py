@@ -81,6 +81,10 @@ def lib():
         L.orc_es_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, dp, dp, dp]
         L.orc_es_dirichlet_x0.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
         L.orc_es_dirichlet_xl.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
+        L.orc_es_coarse_matrix.argtypes = [dp, C.c_int, C.c_double, C.c_void_p]
+        L.orc_es_coarse_matrix.restype = None
+        L.orc_es_vcycle.restype = C.c_double
+        L.orc_es_vcycle.argtypes = [C.POINTER(dp)] * 3 + [C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_void_p]
         L.orc_max_threads.restype = C.c_int
         L.orc_set_threads.argtypes = [C.c_int]
         # one thread unless a test asks for more: on a box whose core count exceeds this process's CPU share (the GPU
@@ -158,3 +162,51 @@ def es_run(c, L, nu, cycles, params=None):
     norms, u, init = np.zeros(cycles), np.zeros(N ** 3), C.c_double(0)
     lib().orc_es_run(c, L, nu, cycles, C.byref(p), P(norms), P(u), C.cast(C.byref(init), dp))
     return norms, u, init.value
+
+
+ES_SETS = ("default", "wide", "lattice")
+ES_LATTICE_H = 2.0 ** -10
+
+
+def es_params(name, N=None):
+    """A named parameter set of the mixed-boundary problem for a finest level of N^3, as (EsParams of the oracle, EsParams
+    of the binding): the same six doubles under the two structs' field names.
+    default  mg_3d_bkup.c:12-18: both patches in the middle of their faces, the capillary at 0 V.
+    wide     an annulus that reaches the rows next to the walls and the face edges, a disc of thousands of points at 75 V.
+    lattice  h = 2^-10 and radii that are whole multiples of it: rr and the squared radii are exact, so the inclusive
+             disc (5h: the offsets (3, 4) and (5, 0) lie ON it) and the strict annulus (10h .. 13h: (6, 8) and (5, 12) lie
+             on its two circles) are met with equality on the finest level.  The solver takes grid_length = length."""
+    p = EsParams()
+    if name == "wide":
+        p.capillary_radius, p.extractor_inner, p.extractor_outer, p.capillary_voltage = 0.9e-4, 1.2e-4, 2.0e-4, 75.0
+    elif name == "lattice":
+        h = ES_LATTICE_H
+        p.length = (N - 1) * h
+        p.capillary_radius, p.extractor_inner, p.extractor_outer = 5 * h, 10 * h, 13 * h
+        p.capillary_voltage, p.extractor_voltage = 75.0, -1350.0
+    else:
+        assert name == "default", name
+    from multigrid_parallel_amd.binding import EsParams as ProductEsParams
+    return p, ProductEsParams(*[getattr(p, f) for f, _ in EsParams._fields_])
+
+
+def es_patches(p, N, h):
+    """the Dirichlet patches of an N^3 level with spacing h as two (N, N) bool arrays over (j, k): x = 0 and x = L"""
+    L_ = lib()
+    x0 = np.array([[L_.orc_es_dirichlet_x0(C.byref(p), h, j, k) for k in range(N)] for j in range(N)], dtype=bool)
+    xl = np.array([[L_.orc_es_dirichlet_xl(C.byref(p), h, j, k) for k in range(N)] for j in range(N)], dtype=bool)
+    return x0, xl
+
+
+def es_factor(c, h0, p):
+    """the factored coarsest operator of the mixed-boundary problem as orc_es_run builds it"""
+    A = np.zeros(c ** 3 * c ** 3)
+    lib().orc_es_coarse_matrix(P(A), c, h0, C.byref(p))
+    lib().orc_lu_factor(P(A), c ** 3)
+    return A
+
+
+def es_vcycle(H, nu, LU, p):
+    """one orc_es_vcycle from the finest level of the Hierarchy H (u, d, r of every level stay observable); its norm"""
+    N = H.N[-1]
+    return lib().orc_es_vcycle(H.ptrs(H.u), H.ptrs(H.d), H.ptrs(H.r), p.length / (N - 1), H.L - 1, H.L, nu, N, P(LU), C.byref(p))

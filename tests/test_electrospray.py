@@ -4,7 +4,8 @@ patches on the two x faces, zero-gradient walls by ghost copy everywhere else, c
 PARITY UNPINNED: mg_3d_bkup.c does not compile against the current headers and its smoother is the order-dependent
 lexicographic Gauss-Seidel, so the reference can produce no vector for it.  The CPU tests pin the statement
 (oracle/mg3d_oracle_es.c) to the properties the problem must have; the GPU tests hold csrc/mg3d_es.hip to that
-statement bit for bit."""
+statement bit for bit.  The launch shapes past one k-block, the parameter sets off the default, random data on every level
+and every level after a cycle are in tests/test_gpu_es_shapes.py (cases checked by tests/test_es_host.py)."""
 import ctypes as C
 
 import numpy as np
