@@ -56,13 +56,13 @@ def exact_residual_norm32(u, d, N, hd):
     return float(np.sqrt(total))
 
 
-def coarse_lu(c, L):
+def coarse_lu(c, L, grid_length=1.0):
     """the coarsest level's factors with the coarsest spacing, as orc32_run_problem builds them"""
     lib = O.lib()
     N = O.level_sizes(c, L)[-1]
     n0 = c ** 3
     LU = np.zeros(n0 * n0)
-    lib.orc_coarse_matrix(O.P(LU), c, (1.0 / (N - 1)) * (1 << (L - 1)))
+    lib.orc_coarse_matrix(O.P(LU), c, (grid_length / (N - 1)) * (1 << (L - 1)))
     lib.orc_lu_factor(O.P(LU), n0)
     return LU
 
@@ -77,7 +77,7 @@ class Cycle:
         return self.u_top.nbytes + sum(a.nbytes for a in self.u_low) + sum(a.nbytes for a in self.d_low)
 
 
-def run_cycles(c, L, nu, cycles, u0, d0, r0):
+def run_cycles(c, L, nu, cycles, u0, d0, r0, grid_length=1.0):
     """`cycles` V-cycles of the restatement from (u0, d0, r0) on the top level and zeros below: a list of Cycle"""
     lib = O.lib()
     sizes = O.level_sizes(c, L)
@@ -88,8 +88,8 @@ def run_cycles(c, L, nu, cycles, u0, d0, r0):
     s = [np.zeros(n ** 3, dtype=np.float32) for n in sizes]
     u[top][:], d[top][:], r[top][:] = u0, d0, r0
     ptrs = [(O.fp * L)(*[O.PF(a) for a in xs]) for xs in (u, d, r, s)]
-    LU = coarse_lu(c, L)
-    hd = 1.0 / (N - 1)
+    LU = coarse_lu(c, L, grid_length)
+    hd = grid_length / (N - 1)
     out = []
     # the sweeps are pointwise (any thread count gives the same bits); everything else of the restatement is serial
     lib.orc_set_threads(min(8, len(os.sched_getaffinity(0))))
@@ -108,14 +108,14 @@ def random_start(c, L, seed):
     return rnd(N, seed), rnd(N, seed + 1), rnd(N, seed + 2)
 
 
-def random_cycles(c, L, nu, cycles, seed):
+def random_cycles(c, L, nu, cycles, seed, grid_length=1.0):
     """run_cycles from seeded uniform(-1, 1) u, d and r on the top level; one CPU run per (c, L, nu, cycles, seed).
     The results are shared: nobody writes to them."""
-    key = (c, L, nu, cycles, seed)
+    key = (c, L, nu, cycles, seed, grid_length)
     if key in _cache:
         _cache.move_to_end(key)
         return _cache[key]
-    out = run_cycles(c, L, nu, cycles, *random_start(c, L, seed))
+    out = run_cycles(c, L, nu, cycles, *random_start(c, L, seed), grid_length)
     for cyc in out:
         for a in [cyc.u_top] + cyc.u_low + cyc.d_low:
             a.flags.writeable = False
@@ -125,18 +125,20 @@ def random_cycles(c, L, nu, cycles, seed):
     return out
 
 
-def check_operators(c, L, sweeps, sequential_norm):
+def check_operators(c, L, sweeps, sequential_norm, grid_length=1.0, d_scale=1.0):
     """Every stand-alone operator of Solver32 on the top level of (c, L) against the restatement, on seeded random
     fields, bit for bit.  The residual's norm is held to the exactly rounded sum; with `sequential_norm` also to the
-    restatement's own (sequentially summed) return value, which only small levels can meet at 1e-12."""
+    restatement's own (sequentially summed) return value, which only small levels can meet at 1e-12.  grid_length: the
+    box both sides are created for; d_scale: d is uniform(-1, 1) times this (1 / grid_length^2 keeps h^2 d in sight of u)."""
     import multigrid_parallel_amd as M
     from multigrid_parallel_amd.binding import MG3D_D, MG3D_R, MG3D_U
     lib = O.lib()
-    with M.Solver32(c, L, 2, OMEGA) as s:
+    with M.Solver32(c, L, 2, OMEGA, grid_length) as s:
         top = L - 1
         N, Nc = s.level_n(top), s.level_n(top - 1)
-        h = np.float32(1.0 / (N - 1))
-        u, d = rnd(N, 1), rnd(N, 2)
+        hd = grid_length / (N - 1)
+        h = np.float32(hd)
+        u, d = rnd(N, 1), (rnd(N, 2) * np.float32(d_scale)).astype(np.float32)
         s.upload(MG3D_U, top, u)
         s.upload(MG3D_D, top, d)
         # smoother: the sweep counts exercise both buffer parities, pairs and pair + single
@@ -157,7 +159,7 @@ def check_operators(c, L, sweeps, sequential_norm):
         assert np.array_equal(got_r, want_r), first_difference(got_r, want_r, N, top)  # boundary of r untouched
         if sequential_norm:
             assert got_norm == pytest.approx(want_norm, rel=1e-12)
-        exact = exact_residual_norm32(want, d, N, 1.0 / (N - 1))
+        exact = exact_residual_norm32(want, d, N, hd)
         print(f"operators ({c},{L}) {N}^3: residual norm / exactly rounded - 1 = {got_norm / exact - 1:.3e}")
         assert got_norm == pytest.approx(exact, rel=1e-12)
         # restriction
@@ -177,7 +179,7 @@ def check_operators(c, L, sweeps, sequential_norm):
         s.zero(MG3D_U, top)
         s.fill_boundary(MG3D_U, top)
         want_b = np.zeros(N ** 3, dtype=np.float32)
-        lib.orc32_fill_boundary(O.PF(want_b), N, 1.0 / (N - 1))
+        lib.orc32_fill_boundary(O.PF(want_b), N, hd)
         assert np.array_equal(s.download(MG3D_U, top), want_b)
         # coarsest solve through double
         n0 = c ** 3
@@ -185,5 +187,5 @@ def check_operators(c, L, sweeps, sequential_norm):
         s.upload(MG3D_D, 0, b0)
         s.coarse_solve()
         want_x = np.zeros(n0, dtype=np.float32)
-        lib.orc32_coarse_solve(O.P(coarse_lu(c, L)), n0, O.PF(b0), O.PF(want_x))
+        lib.orc32_coarse_solve(O.P(coarse_lu(c, L, grid_length)), n0, O.PF(b0), O.PF(want_x))
         assert np.array_equal(s.download(MG3D_U, 0), want_x)

@@ -114,11 +114,11 @@ def slab_eps(N, jump=1e4):
     return np.ascontiguousarray(np.broadcast_to(np.where((x > 0.3) & (x < 0.62), jump, 1.0)[:, None, None], (N, N, N)))
 
 
-def make_problem(c, L, nu, sigma=0.0, eps=None, axes=0):
+def make_problem(c, L, nu, sigma=0.0, eps=None, axes=0, grid_length=1.0):
     """the restatement whose cycle the library runs for these settings"""
     if axes:
-        return P.Problem(c, L, nu, sigma, eps, axes)
-    return CR.Problem(c, L, nu, sigma, eps)
+        return P.Problem(c, L, nu, sigma, eps, axes, grid_length)
+    return CR.Problem(c, L, nu, sigma, eps, grid_length)
 
 
 # ------------------------------------------------------------------------------------------------ the cases of the tests

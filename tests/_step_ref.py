@@ -40,8 +40,8 @@ def rhs(prob, u0, s, dt, theta, kappa):
     return -((a * u + c1 * q) + b * s[blk])
 
 
-def make_problem(c, L, nu, dt, theta, kappa, eps=None, axes=0, faces=0):
-    return NR.Problem(c, L, nu, sigma_of(dt, theta, kappa), eps, axes, faces)
+def make_problem(c, L, nu, dt, theta, kappa, eps=None, axes=0, faces=0, grid_length=1.0):
+    return NR.Problem(c, L, nu, sigma_of(dt, theta, kappa), eps, axes, faces, grid_length)
 
 
 def write_rhs(prob, s, dt, theta, kappa):

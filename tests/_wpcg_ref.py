@@ -164,8 +164,8 @@ def cycle_blk(prob, r_blk):
     return precondition(prob, r_blk)[NR.block(prob.N[-1], prob.axes, prob.faces)]
 
 
-def make_problem(c, L, nu, sigma=0.0, eps=None, axes=0, faces=0):
-    return NR.Problem(c, L, nu, sigma, eps, axes, faces)
+def make_problem(c, L, nu, sigma=0.0, eps=None, axes=0, faces=0, grid_length=1.0):
+    return NR.Problem(c, L, nu, sigma, eps, axes, faces, grid_length)
 
 
 # ------------------------------------------------------------------------------------------------ the cases of the tests
