@@ -550,6 +550,8 @@ int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
  *   sweep_tune_log  0        MG3D_SWEEP_TUNE_LOG       print the measured choices
  *   sweep_ci        0        MG3D_SWEEP_CI             > 0: planes per chunk of every fused sweep launch (measurement)
  *   sweep_rj/nw/pf  0        MG3D_SWEEP_CFG="rj,nw,pf" another compiled tile shape (unknown ones fall back to the default)
+ *   d_zero_skip     1        MG3D_D_ZERO_SKIP          the fused launches of the finest level do not read the planes of d that
+ *                                                      are +0.0 at every interior point (the zero map, below); 0: every plane
  * mg3d_option_name(i) enumerates the keys (NULL past the end).  mg3d_dist_set_option forwards to every local rank (carry /
  * carry_min of a multi-rank job are agreed at creation and refuse to change); mg3d32_set_option knows "pairs", "fuse",
  * "carry" (MG3D_F32_NO_PAIRS / _NO_FUSE / _NO_CARRY at creation).  A context with a variable coefficient
@@ -558,6 +560,18 @@ int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
 int mg3d_ctx_set_option(mg3d_ctx *ctx, const char *key, int value);
 int mg3d_ctx_get_option(const mg3d_ctx *ctx, const char *key, int *value);
 const char *mg3d_option_name(int index);
+/* The zero map.  A source-free problem (d = 0 inside the domain: a Laplace problem with boundary values, conductors, fixed
+ * potentials) or a localised source leaves most planes i = const of the finest level's d at +0.0 in every interior point.
+ * The context keeps one bit per plane saying so, and the fused launches of the finest level form such a plane's d in
+ * registers instead of reading it: the same bits -- -0.0, denormals and NaNs count as non-zero, faces are not looked at
+ * (no face entry of d enters a value the fused kernels store) --, a read of the level less per launch.  mg3d_zero sets every
+ * bit; mg3d_fill_boundary leaves the map alone; mg3d_upload / mg3d_upload_device have the next cycle scan the new d once
+ * (one pass over it and one host synchronisation per upload, none per cycle); mg3d_step_advance, mg3d_pcg_solve /
+ * mg3d_wpcg_solve and mg3d_device_view of that d switch the map off (the last for good, as the run-ahead of mg3d_vcycle).
+ * Contexts with a variable coefficient, periodic axes, Neumann faces or fixed points never use it.
+ * mg3d_ctx_dzero_planes: how many planes the map holds (0 unless it is valid) and its state -- 0 off, 1 to be scanned by
+ * the next cycle, 2 valid; either pointer may be NULL.  For tests and tools. */
+int mg3d_ctx_dzero_planes(const mg3d_ctx *ctx, int *planes, int *state);
 
 /* per-stage timers (timing_info.h:6-47), filled from hipEvent pairs recorded in-stream (no stall).
  * on: 0 = off, 1 = every level, 2 = finest level only, 3 = the kernel timers of the finest level only (no stage

@@ -119,6 +119,7 @@ SIGNATURES = {
     "mg3d_ctx_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mg3d_ctx_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "mg3d_option_name": (C.c_char_p, [C.c_int]),
+    "mg3d_ctx_dzero_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mg3d32_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mg3d32_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d32_kernel_name": (C.c_char_p, [C.c_int]),
@@ -354,6 +355,12 @@ class Solver:
             out[k] = self.get_option(k)
             i += 1
         return out
+
+    def dzero_planes(self):
+        """mg3d_ctx_dzero_planes: (planes of the finest level's d the zero map holds, state: 0 off, 1 to be scanned, 2 valid)."""
+        n, st = C.c_int(0), C.c_int(0)
+        check(self.L.mg3d_ctx_dzero_planes(self._h, C.byref(n), C.byref(st)))
+        return n.value, st.value
 
     # -- geometry
     def level_n(self, level):

@@ -6,6 +6,8 @@
 
 #include "mg3d_internal.h"
 
+enum { MG3D_DZ_NONE = 0, MG3D_DZ_UNKNOWN, MG3D_DZ_VALID }; /* mg3d_ctx::dz_state */
+
 struct Level {
     Geom g;
     double h;
@@ -94,6 +96,18 @@ struct mg3d_ctx {
     hipEvent_t io_ev[2] = {nullptr, nullptr};
     unsigned long long *io_chk = nullptr;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
+    /* The zero map of d of the top level (k_dzero_scan: bit i = plane i is +0.0 at every interior point), which the fused
+     * sweep launches of that level take so as not to read those planes (mg3d_level_sweep).  Every writer of that d says
+     * what it did through mg3d_ctx_touched; dz_state is what is known since:
+     *   MG3D_DZ_NONE    nothing, and nothing will be found out: a kernel of the library wrote d (the time stepper, the inner
+     *                   solves of the CG drivers, the slab path) -- no launch takes the map
+     *   MG3D_DZ_UNKNOWN the caller gave a new d (mg3d_upload, mg3d_upload_device): the next cycle from the top level of a fused
+     *                   context scans it, once
+     *   MG3D_DZ_VALID   the map is d's; dz_planes bits are set (0: no launch takes it)
+     * dz_raw: a raw pointer to that d is out (mg3d_device_view) -- MG3D_DZ_NONE for good, as raw_top */
+    unsigned *dz_map = nullptr; /* device, mg3d_dzero_words(ni) words, allocated with the context */
+    int dz_state = MG3D_DZ_UNKNOWN, dz_planes = 0; /* (created zeroed: the first cycle's scan finds that out) */
+    bool dz_raw = false;
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */
     int timing; /* 0 off, 1 every level, 2 finest level only, 3 finest level's kernel timers only, 4 + k: 3 on every (k+2)-th cycle */
@@ -116,6 +130,14 @@ static inline void swap_u(Level &l)
     l.f[MG3D_U] = l.alt;
     l.alt = t;
 }
+/* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
+ * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
+ * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
+ * transfers k_restrict / k_prolong launch for a boundary word, nor with fixed points, whose levels run the MASK forms */
+static inline bool mg3d_fused(const mg3d_ctx *ctx)
+{
+    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty();
+}
 /* a sweep launch on a level of this context, u -> alt: the caller adds what the launch does (SweepLaunch) */
 static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
 {
@@ -124,16 +146,12 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
     w.op = mg3d_level_op(l.h, ctx->sigma);
     w.vin = l.f[MG3D_U];
     w.d = l.f[MG3D_D];
+    /* the top level's d comes with its zero map when that is known to hold a plane (the one place a launch gets its d) */
+    if (&l == &ctx->lv[ctx->L - 1] && ctx->dz_state == MG3D_DZ_VALID && ctx->dz_planes > 0 && ctx->opt.v[MG3D_OPT_D_ZERO_SKIP] &&
+        mg3d_fused(ctx))
+        w.d_zero = ctx->dz_map;
     w.vout = l.alt;
     return w;
-}
-/* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
- * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
- * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
- * transfers k_restrict / k_prolong launch for a boundary word, nor with fixed points, whose levels run the MASK forms */
-static inline bool mg3d_fused(const mg3d_ctx *ctx)
-{
-    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty();
 }
 /* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */
 static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodic, ctx->neumann); }
@@ -155,8 +173,13 @@ static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
 }
 /* ... and none on the finest level either: the system itself is singular (mg3d_wpcg_solve projects) */
 static inline bool mg3d_ctx_singular(const mg3d_ctx *ctx) { return mg3d_ctx_pinned(ctx) && ctx->mask_fixed_top == 0; }
-/* field `field` of `level` was written from outside the cycle (see faces_dirty) */
-void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false);
+/* field `field` of `level` was written from outside the cycle (see faces_dirty), and how -- what the zero map of the top
+ * level's d (dz_state) makes of it: MG3D_WROTE_DEVICE a kernel of the library wrote values nobody has looked at (NONE),
+ * MG3D_WROTE_CALLER the caller's values arrived (UNKNOWN: scanned before the next cycle), MG3D_WROTE_ZERO the field was
+ * cleared (VALID, every interior plane, no scan), MG3D_WROTE_FACES only its faces were written (unchanged: the map is about
+ * interior points) */
+enum { MG3D_WROTE_DEVICE = 0, MG3D_WROTE_CALLER, MG3D_WROTE_ZERO, MG3D_WROTE_FACES };
+void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer = false, int how = MG3D_WROTE_DEVICE);
 /* scoped event pair of the timers (mg3d_timing_enable): a stage of the reference's timing table on level l, or
  * (kernel = true) one kernel launch, s a MG3D_K_* id; nothing is recorded while the timers are off (mg3d_ctx.hip) */
 struct StageScope {

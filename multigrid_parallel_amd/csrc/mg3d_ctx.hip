@@ -200,6 +200,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
     for (hipEvent_t e : ctx->io_ev)
         if (e)
             (void)hipEventDestroy(e);
+    if (ctx->dz_map)
+        (void)hipFree(ctx->dz_map);
     if (ctx->partials)
         (void)hipFree(ctx->partials);
     if (ctx->sumsq)
@@ -240,6 +242,7 @@ static const OptionRow kOptionTable[MG3D_OPT_COUNT] = {
     {"sweep_rj", "MG3D_SWEEP_CFG", 2, 0},
     {"sweep_nw", nullptr, 0, 0},
     {"sweep_pf", nullptr, 0, 0},
+    {"d_zero_skip", "MG3D_D_ZERO_SKIP", 0, 1},
 };
 
 void mg3d_options_init(mg3d_options *o)
@@ -370,8 +373,21 @@ int mg3d_drop_carry_keep(mg3d_ctx *ctx)
     return MG3D_OK;
 }
 
-void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer)
+void mg3d_ctx_touched(mg3d_ctx *ctx, int field, int level, bool raw_pointer, int how)
 {
+    /* d of the top level: what its zero map is worth now (dz_state, mg3d_ctx.h) */
+    if (field == MG3D_D && level == ctx->L - 1 && how != MG3D_WROTE_FACES) {
+        ctx->dz_raw = ctx->dz_raw || raw_pointer;
+        if (ctx->dz_raw || how == MG3D_WROTE_DEVICE || !ctx->dz_map) {
+            ctx->dz_state = MG3D_DZ_NONE;
+        } else if (how == MG3D_WROTE_CALLER) {
+            ctx->dz_state = MG3D_DZ_UNKNOWN;
+        } else { /* cleared, in stream order behind the memset: every interior plane, nothing to scan */
+            k_dzero_fill(ctx->lv[level].g, ctx->dz_map, ctx->stream);
+            ctx->dz_state = MG3D_DZ_VALID;
+            ctx->dz_planes = ctx->lv[level].g.ni > 2 ? ctx->lv[level].g.ni - 2 : 0;
+        }
+    }
     /* a raw device pointer to u or d of the top level: the library no longer sees every write to them, so a single
      * mg3d_vcycle call does not run ahead into the next cycle any more (mg3d_vcycles still carries INSIDE a call) */
     if (raw_pointer && level == ctx->L - 1 && (field == MG3D_U || field == MG3D_D))
@@ -415,6 +431,7 @@ static int ctx_create_sizes(const int *n_per_level, const double *h_per_level, i
         CTXCHK(hipMalloc(&lev.alt, lev.elems * sizeof(double)));
         CTXCHK(hipMemsetAsync(lev.alt, 0, lev.elems * sizeof(double), ctx->stream));
     }
+    CTXCHK(hipMalloc(&ctx->dz_map, mg3d_dzero_words(ctx->lv[L - 1].g.ni) * sizeof(unsigned)));
     CTXCHK(hipMalloc(&ctx->partials, MG3D_MAX_PARTIALS * sizeof(double)));
     ctx->sumsq_slots = 1024;
     CTXCHK(hipMalloc(&ctx->sumsq, ctx->sumsq_slots * sizeof(double)));
@@ -1196,7 +1213,7 @@ extern "C" int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *ho
     HIPCHK(hipMemcpy2DAsync(l.f[field], l.g.pitch * sizeof(double), host, N * sizeof(double), N * sizeof(double),
                             (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    mg3d_ctx_touched(ctx, field, level);
+    mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_CALLER);
     return MG3D_OK;
 }
 
@@ -1228,7 +1245,7 @@ extern "C" int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3
         StageScope kt(ctx, level, MG3D_K_PACK, true);
         k_pack(l.g, l.f[field], *src, ctx->stream);
     }
-    mg3d_ctx_touched(ctx, field, level);
+    mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_CALLER);
     CHK(launch_ok(who));
     return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
 }
@@ -1255,7 +1272,7 @@ extern "C" int mg3d_zero(mg3d_ctx *ctx, int field, int level)
     CHK(check_field_level(ctx, field, level, "mg3d_zero"));
     const Level &l = ctx->lv[level];
     HIPCHK(hipMemsetAsync(l.f[field], 0, l.elems * sizeof(double), ctx->stream));
-    mg3d_ctx_touched(ctx, field, level);
+    mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_ZERO);
     return MG3D_OK;
 }
 
@@ -1281,6 +1298,19 @@ extern "C" int mg3d_device_view(mg3d_ctx *ctx, int field, int level, void **dev_
         *pitch_doubles = l.g.pitch;
     if (plane_doubles)
         *plane_doubles = (long)l.g.plane;
+    return MG3D_OK;
+}
+
+/* what the context knows of the zero map of the top level's d (tests, tools): the planes whose bit is set -- 0 unless the
+ * map is valid -- and the state itself */
+extern "C" int mg3d_ctx_dzero_planes(const mg3d_ctx *ctx, int *planes, int *state)
+{
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_dzero_planes: NULL context");
+    if (planes)
+        *planes = ctx->dz_state == MG3D_DZ_VALID ? ctx->dz_planes : 0;
+    if (state)
+        *state = ctx->dz_state;
     return MG3D_OK;
 }
 
@@ -1864,6 +1894,23 @@ static int up_leg_ordinary(mg3d_ctx *ctx, const CycleState &c, int l)
     return MG3D_OK;
 }
 
+/* The caller's new d of the top level (dz_state, mg3d_ctx.h): one pass over it, once, and the map read back -- the launches
+ * take it only when it holds a plane.  The one host synchronisation is paid per upload of d, not per cycle. */
+static int dzero_scan(mg3d_ctx *ctx)
+{
+    const Level &top = ctx->lv[ctx->L - 1];
+    std::vector<unsigned> words((size_t)mg3d_dzero_words(top.g.ni));
+    k_dzero_scan(top.g, top.f[MG3D_D], ctx->dz_map, ctx->stream);
+    CHK(launch_ok("mg3d_vcycle: zero map of d"));
+    HIPCHK(hipMemcpyAsync(words.data(), ctx->dz_map, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->dz_planes = 0;
+    for (unsigned w : words)
+        ctx->dz_planes += __builtin_popcount(w);
+    ctx->dz_state = MG3D_DZ_VALID;
+    return MG3D_OK;
+}
+
 int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out, bool keep_guess)
 {
     if (!ctx->have_lu)
@@ -1899,6 +1946,8 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out, bool keep
     ctx->legs_state = 0;
     c.red_in = q == L - 1 && c.legs_in == 0 && !c.carry_in && ctx->red_tail && c.can_legs && !ctx->raw_top;
     ctx->red_tail = false;
+    if (q == L - 1 && ctx->dz_state == MG3D_DZ_UNKNOWN && ctx->opt.v[MG3D_OPT_D_ZERO_SKIP] && mg3d_fused(ctx))
+        CHK(dzero_scan(ctx));
     /* ---- down: the top level continues what ran ahead of it, level 1 fits one workgroup, the rest is ordinary */
     for (int l = q; l >= 1; l--) {
         if (l == q && c.can_legs && (c.legs_in != 0 || c.red_in))
@@ -1997,7 +2046,7 @@ extern "C" int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level)
     if (ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     k_fill_boundary(ctx->lv[level].g, ctx->lv[level].f[field], ctx->lv[level].h, ctx->stream);
-    mg3d_ctx_touched(ctx, field, level);
+    mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_FACES);
     return launch_ok("mg3d_fill_boundary");
 }
 

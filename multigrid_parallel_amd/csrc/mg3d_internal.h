@@ -88,6 +88,7 @@ enum {
     MG3D_OPT_SWEEP_RJ,     /* > 0: another compiled tile shape (rows per thread, waves, planes in flight); unknown ones */
     MG3D_OPT_SWEEP_NW,     /*      fall back to the default */
     MG3D_OPT_SWEEP_PF,
+    MG3D_OPT_D_ZERO_SKIP,  /* the planes of the top level's d that are +0.0 at every interior point are not read (1; the zero map, mg3d_ctx.h) */
     MG3D_OPT_COUNT
 };
 struct mg3d_options {
@@ -166,6 +167,13 @@ void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int
                int if_hi = -1, const unsigned char *mf = nullptr /* the fine level's fixed points: the point form, skipping them */);
 /* BCFunc(i*h, j*h, k*h) = x*x - 2*y*y + z*z on the six faces of a field (mg_3d.h:89-90, 1147-1239) */
 void k_fill_boundary(const Geom &g, double *v, double h, hipStream_t s);
+/* The zero map of a right-hand side: one bit per plane of a single-domain level, 32 planes a word; bit i set = every
+ * interior point of plane i (1 <= j <= nj-2, 1 <= k <= nk-2) has the bit pattern of +0.0 -- -0.0, denormals and NaNs count
+ * as non-zero --, never set for planes 0 and ni-1.  k_dzero_scan: the map of d, one pass over it; k_dzero_fill: every
+ * interior plane's bit, the map of a d that was just zeroed */
+__host__ __device__ static inline int mg3d_dzero_words(int ni) { return (ni + 31) / 32; }
+void k_dzero_scan(const Geom &g, const double *d, unsigned *map, hipStream_t s);
+void k_dzero_fill(const Geom &g, unsigned *map, hipStream_t s);
 /* folds np per-block partial sums, in a fixed order, into *out */
 void k_fold(const double *partials, int np, double *out, hipStream_t s);
 /* the same over two runs of partial sums (a norm whose halves two launches formed): *out = fold(pa) + fold(pb) */
@@ -193,6 +201,9 @@ struct SweepLaunch {
     LevelOp op = {};
     const double *vin = nullptr; /* NULL: identically zero, not read (the zero guess of a coarser level) */
     const double *d = nullptr;
+    /* optional: the zero map of d (k_dzero_scan), bit i set = plane i of d is +0.0 at every interior point and is not read.
+     * Single-domain levels with Dirichlet faces only: there no face entry of d enters a stored value */
+    const unsigned *d_zero = nullptr;
     double *vout = nullptr;
     /* what the launch does */
     SweepKind kind = SWEEP_PASSES;

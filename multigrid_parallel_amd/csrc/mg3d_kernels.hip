@@ -1028,6 +1028,65 @@ void k_sumsq(const Geom &g, const double *a, double *partials, double *sumsq_out
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(256), 0, s, partials, nb, sumsq_out);
 }
 
+/* ------------------------------------------------------- the zero map of a right-hand side
+ * Bit i of map (32 planes a word) is set when every INTERIOR point of plane i of d -- 1 <= j <= nj-2, 1 <= k <= nk-2 -- has
+ * the bit pattern of +0.0.  The 64-bit patterns are ORed, not compared as numbers: -0.0, a denormal and a NaN all make a
+ * plane non-zero.  The faces and the row padding are not looked at; planes 0 and ni-1 never get their bit.  One block per
+ * interior plane, one pass over d in 16-byte loads (rows are 128-byte aligned, pairs start on even k), one atomicOr per
+ * plane that is zero. */
+__global__ void __launch_bounds__(1024) dzero_scan_kernel(Geom g, const double *__restrict__ d, unsigned *__restrict__ map)
+{
+    __shared__ unsigned long long lds16[16];
+    const int i = blockIdx.x + 1;
+    const unsigned long long *p = reinterpret_cast<const unsigned long long *>(d) + g.plane * i;
+    unsigned long long acc = 0ull;
+    for (int j = 1 + threadIdx.y; j <= g.nj - 2; j += 16) {
+        const ulonglong2 *row = reinterpret_cast<const ulonglong2 *>(p + (long long)g.pitch * j);
+        for (int k = 2 * threadIdx.x; k <= g.nk - 2; k += 128) {
+            const ulonglong2 v = row[k >> 1];
+            acc |= (k >= 1 ? v.x : 0ull) | (k + 1 <= g.nk - 2 ? v.y : 0ull);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        acc |= __shfl_down(acc, off, 64);
+    if (threadIdx.x == 0)
+        lds16[threadIdx.y] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+        unsigned long long all = 0ull;
+        for (int w = 0; w < 16; w++)
+            all |= lds16[w];
+        if (all == 0ull)
+            atomicOr(map + (i >> 5), 1u << (i & 31));
+    }
+}
+
+/* every interior plane's bit: what the scan makes of a d that was just zeroed */
+__global__ void __launch_bounds__(64) dzero_fill_kernel(int ni, unsigned *__restrict__ map)
+{
+    const int w = blockIdx.x * 64 + threadIdx.x;
+    if (w >= mg3d_dzero_words(ni))
+        return;
+    unsigned v = 0u;
+    for (int b = 0; b < 32; b++) {
+        const int i = 32 * w + b;
+        v |= (i >= 1 && i <= ni - 2) ? 1u << b : 0u;
+    }
+    map[w] = v;
+}
+
+void k_dzero_scan(const Geom &g, const double *d, unsigned *map, hipStream_t s)
+{
+    (void)hipMemsetAsync(map, 0, mg3d_dzero_words(g.ni) * sizeof(unsigned), s);
+    if (g.ni >= 3 && g.nj >= 3 && g.nk >= 3)
+        hipLaunchKernelGGL(dzero_scan_kernel, dim3(g.ni - 2), dim3(64, 16, 1), 0, s, g, d, map);
+}
+
+void k_dzero_fill(const Geom &g, unsigned *map, hipStream_t s)
+{
+    hipLaunchKernelGGL(dzero_fill_kernel, dim3((mg3d_dzero_words(g.ni) + 63) / 64), dim3(64), 0, s, g.ni, map);
+}
+
 /* --------------------------------------------------------------- restriction
  * restrictResidual, mg_3d.h:844-998.  Coarse Dirichlet faces: injection d_c = r(2i,2j,2k) (:879-958).  Every other coarse
  * point: val = 0; val += r(2i-1+ti, 2j-1+tj, 2k-1+tk) * w[ti][tj][tk] for ti, tj, tk = 0..2 in that nesting (:973-989),

@@ -218,6 +218,7 @@ static int pcg_run(mg3d_ctx *ctx, const char *name, const InnerProduct &ip, doub
         double *const x = top.f[MG3D_U], *const d = top.f[MG3D_D];
         top.f[MG3D_U] = ctx->pcg_v[V_Z];
         top.f[MG3D_D] = ctx->pcg_v[V_R];
+        mg3d_ctx_touched(ctx, MG3D_D, q); /* the cycles' d is the residual, rewritten every iteration: no zero map of it */
         rc = pcg_iterate(ctx, name, ip, x, target, max_iters, norms, iters, converged, r_norm);
         if (rc != MG3D_OK)
             (void)hipStreamSynchronize(s);

@@ -89,6 +89,21 @@ static int device_cus() /* of the CURRENT device (a process may drive several: m
     return it->second;
 }
 
+/* The zero map of d (SweepArgs::dz) has instantiations of its own, taken when a launch brings a map: every other launch --
+ * the levels below the top one, a dense d, the slab path -- runs a kernel with no trace of it.  Compiled for the tile shapes
+ * the default schedules use; the shapes only the options sweep_rj / nw / pf reach read every plane. */
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K>
+static void launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s)
+{
+    if constexpr (NW == 8 && ((RJ == 4 && PF == 1) || (RJ == 2 && PF >= 2))) {
+        if (a.dz) {
+            hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
+}
+
 template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1>
 static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s)
 {
@@ -120,7 +135,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
             return -1;
         a.CI = a.edge;
         a.xcd_remap = 2 * T < 64 ? 0 : 2 * T <= ncu ? 1 : 2;
-        hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>), dim3((unsigned)(2 * T)), dim3(NW * WAVE), 0, s, a);
+        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>(a, (unsigned)(2 * T), s);
         return (int)(2 * T);
     }
     const int ovh = Sh::HI + Sh::ST + (RES == 2 ? 2 : 0) + 1;
@@ -191,7 +206,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
         static_assert(C1K < 0 || !PRO || C1K == 0, "PRO launches are post-smoothers");
         if (C1K >= 0 && a.c1 != C1K)
             return;
-        hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>), dim3((unsigned)nb), dim3(NW * WAVE), 0, s, a);
+        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>(a, (unsigned)nb, s);
     };
     /* Measured choice.  The model above ranks chunk lengths by steps; what a step costs depends on how many CUs stream
      * at once and on how well the chunks keep in lock-step, which it does not know.  The first launch of a shape on a
@@ -203,11 +218,11 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
      * into per-block partial sums, and a timing-dependent choice would make it differ from run to run */
     if (!forced && tune_on && !a.partials && T * nout >= 1024) {
         struct Key {
-            int v[13];
+            int v[14];
             bool operator<(const Key &o) const { return memcmp(v, o.v, sizeof v) < 0; }
         };
         const Key key = {{g.ni, g.nj, g.nk, g.N, g.ig0 & 1, a.i_lo, a.i_hi, a.vin != nullptr, a.partials != nullptr,
-                          a.r != nullptr, a.vk, max_partials, current_device()}};
+                          a.r != nullptr, a.vk, max_partials, current_device(), a.dz != nullptr}};
         static std::mutex mu;
         static std::map<Key, int> tuned; /* chunk length */
         std::lock_guard<std::mutex> lock(mu);
@@ -375,6 +390,7 @@ static bool fill_args(SweepArgs &a, const SweepLaunch &w)
     a.g = g;
     a.vin = w.vin;
     a.d = w.d;
+    a.dz = w.d_zero;
     a.vout = w.vout;
     a.r = w.r;
     a.partials = w.partials;

@@ -35,6 +35,9 @@ struct SweepArgs {
     double *dc;
     int ic_lo, ic_hi;
     int xcd_remap;  /* 1: blocks of one XCD group (blockIdx % 8) take consecutive shares of the work; 2: per chunk layer */
+    /* the DZ instantiations: bit i set = every interior point of plane i of d is +0.0, the plane is not read (load_plane).
+     * Only where the faces of d enter no stored value (a single-domain level with Dirichlet faces) */
+    const unsigned *dz;
 };
 
 /* RES: 0 = smoothing only, 1 = + residual (r store and/or norm), 2 = + residual AND full-weighting
@@ -170,7 +173,7 @@ __device__ unsigned long long g_dbg_bt[8][1024];
 #define MG3D_DEBUG_BT_COND (PRO && S == 4 && TAP == 4)
 #endif
 #endif
-template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1>
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false>
 __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepArgs a)
 {
     using Sh = SweepShape<S, RES>;
@@ -446,15 +449,33 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
             for (int rr = 0; rr < RJ; rr++)
                 vv[rr] = make_double2(0., 0.);
         }
+        /* DZ: bit id of the map a.dz says that plane id of d is +0.0 at every interior point, and only interior points of d
+         * enter a stored value -- the +0.0 comes from a register, the same bits.  An instantiation of its own (the launcher
+         * takes it when there is a map): without one the kernel carries no test, with one no test for NULL -- that test is what
+         * cost the tapped down-leg a dword of scratch.  The map does not change while the kernel runs: read through the
+         * constant address space, one scalar load a plane.  Planes 0 and ni - 1 (where the clamp puts the warm-up planes)
+         * never have their bit */
+        bool have_d = true; /* uniform */
+        if constexpr (DZ) {
+            typedef const unsigned __attribute__((address_space(4))) *cwords;
+            const unsigned word = reinterpret_cast<cwords>(reinterpret_cast<unsigned long long>(a.dz))[id >> 5];
+            have_d = ((word >> (id & 31)) & 1u) == 0u;
+        }
+        if (have_d) {
 #pragma unroll
-        for (int rr = 0; rr < RJ; rr++) {
-            const gcbytes pd = dbase + row_base[rr] + lane_off(col_off);
+            for (int rr = 0; rr < RJ; rr++) {
+                const gcbytes pd = dbase + row_base[rr] + lane_off(col_off);
 #if (MG3D_NT & 8)
-            if (S == 0 && row_once[rr])
-                dd[rr] = ld_stream<8>(pd);
-            else
+                if (S == 0 && row_once[rr])
+                    dd[rr] = ld_stream<8>(pd);
+                else
 #endif
-                dd[rr] = ld_stream<4>(pd);
+                    dd[rr] = ld_stream<4>(pd);
+            }
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < RJ; rr++)
+                dd[rr] = make_double2(0., 0.);
         }
     };
 

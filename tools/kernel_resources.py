@@ -25,5 +25,5 @@ for r in rows:
     name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
     if flt and flt not in name:
         continue
-    print(f"{name[:70]:70s} VGPR {r.get('VGPRs','?'):>4s} AGPR {r.get('AGPRs','?'):>3s} spill {r.get('VGPR Spill','?'):>3s} "
+    print(f"{name[:78]:78s} VGPR {r.get('VGPRs','?'):>4s} AGPR {r.get('AGPRs','?'):>3s} spill {r.get('VGPR Spill','?'):>3s} "
           f"scratch {r.get('ScratchSize','?'):>5s} occ {r.get('Occupancy','?'):>2s} LDS {r.get('LDS Size','?'):>6s}")

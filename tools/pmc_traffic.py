@@ -62,7 +62,7 @@ for k in sorted(A, key=lambda k: -max(sum(v) / len(v) for (g, c), v in A[k].item
     for pat, t in timer_of.items():
         if pat in k and t not in res:
             res[t] = rd + wr
-json.dump({"source_sha256": bench.kernel_source_hash(), "command": " ".join(cmd[1:]), "bytes_per_launch": res},
+json.dump({"source_sha256": bench.kernel_source_hash(), "command": "bench.py " + " ".join(cmd[2:]), "bytes_per_launch": res},
           open(os.path.join(out, "pmc_traffic.json"), "w"), indent=1)
 hdr = (f"rocprofv3 --pmc passes (separate runs: FETCH_SIZE ; WRITE_SIZE TCC_HIT_sum TCC_MISS_sum) of\\n  {' '.join(cmd)}\\n"
        "Per kernel: the finest level's steady-state dispatch group (most launches), mean per launch.  gfx950 correction:\\n"
