@@ -322,6 +322,91 @@ int mg3d_field_gradient_device(mg3d_ctx *ctx, double scale, const mg3d_array *co
 int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux);
 int mg3d_field_energy(mg3d_ctx *ctx, double *energy);
 
+/* ------------------------------------------------------------ particles
+ * The two halves of a particle-in-cell or droplet-tracking loop that touch the grid: the GATHER of the potential and its
+ * gradient at points (mg3d_field_sample*) and the SCATTER of point charges into the right-hand side (mg3d_deposit*) --
+ * on the FINEST level of a single-domain fp64 context, with the context's own periodic wraps, reflected Neumann faces and
+ * one-sided differences on Dirichlet faces, in the notation of "Field output" above.  Both are deterministic, and the
+ * deposit does not depend on the order of the points either; tests/_particle_ref.py restates both bit for bit.
+ *
+ * mg3d_vec: a 1-D strided vector in device memory -- element m is ptr[stride*m], stride in ELEMENTS, the index formed in 64
+ *   bits.  Three of them are the positions (pos[0] the coordinate along i, pos[1] along j, pos[2] along k): an (M, 3) array
+ *   is three vectors of stride 3 whose pointers are one element apart, three separate arrays are three vectors of stride
+ *   1.  Checked as mg3d_array is: ptr must be device memory of the context's device, dtype MG3D_F64 or MG3D_F32 (widened
+ *   exactly on the way in, rounded to nearest even on the way out), stride >= 0 on input (0: a broadcast) and >= 1 on
+ *   output; the library trusts the stride to stay inside the caller's allocation.
+ *
+ * Locating a point, per axis a with coordinate x (node index <-> coordinate is index*h, as in mg3d_fill_boundary_host):
+ *     t = x / h                                               (one IEEE division)
+ *     periodic axis : t = t - (double)(N-1) * floor(t / (double)(N-1)); every finite x is inside.  (A t that the rounding
+ *                     of these three operations leaves below 0 or above N-1 -- a point within rounding of the period's
+ *                     seam, or a coordinate so large that its ulp exceeds h -- is taken to 0 or N-1.)
+ *     another axis  : the point is OUTSIDE unless 0 <= t && t <= N-1  (x = 0, -0.0 and x = length are inside)
+ *     a coordinate or a quotient t that is not finite makes the point OUTSIDE on any axis
+ *     c = (int)floor(t), c = N-2 where it would be larger;  f = t - (double)c;  w0 = 1.0 - f,  w1 = f
+ *   The point's cell has the nodes c and c+1 on each axis, with the weights w0 and w1.  A node index that is a duplicate
+ *   is read or written at its source: no duplicate of u or d is ever read.
+ *
+ * mg3d_field_sample_device: for each of `count` points, into element m of the wanted outputs (u_out, grad_out[0..2]; NULL:
+ *   not wanted, at least one must be):
+ *     u_out       = sum_a wi_a * ( sum_b wj_b * ( sum_c wk_c * u[corner a,b,c] ) )
+ *     grad_out[d] = the same nested sum over g_d[corner], g_d exactly what mg3d_field_gradient_device stores at that node
+ *                   for component d with this `scale` (cs = scale * (0.5 / h) formed on the host): the trilinear interpolant
+ *                   of the nodal gradient, the momentum-conserving gather of PIC codes.  scale = -1: E.
+ *   Each sum is (w0*v0) + (w1*v1), left to right, uncontracted.  `scale` does not enter u_out; eps and the mask play no
+ *   part.  An OUTSIDE point gets a quiet NaN in every wanted output; no count of them is reported (that would need a
+ *   synchronisation).  Read-only in the sense of "Field output": a cycle that has run ahead is finished as
+ *   mg3d_download_device finishes it, nothing else changes.  The two-event stream ordering of "Device arrays", no host
+ *   synchronisation.  ONE launch serves all wanted outputs (one thread per point, 256 per block, at most
+ *   MG3D_PARTICLE_MAX_BLOCKS blocks, each thread striding on); it counts under the kernel timer MG3D_K_PACK.
+ *   MG3D_ERR_ARG, nothing written: a NULL context or pos, count < 0 or > 2^40, nothing wanted, a scale that is not finite,
+ *   a bad vector.  count == 0: MG3D_OK, nothing launched (the pointers of the vectors are then not looked at).
+ * mg3d_deposit_device: ADDS the cloud-in-cell density of `count` point charges q to d of the finest level:
+ *       d[p] += scale * nf(p) * (sum_m q_m W_m(p)) / h^3,    W_m(p) = (wi*wj)*wk of point m at node p
+ *   nf(p) = 2 per Neumann face p lies on (1, 2, 4 or 8) = 1 / w(p): the node's control volume is a half, a quarter, an
+ *   eighth -- the reflected operator sees the mirror charge.  For div(eps grad u) = -rho/eps_0 pass scale = -1/eps_0.
+ *   OUTSIDE points and points whose q is not finite add nothing.  Fixed points and Dirichlet points receive their share
+ *   like any node: d there is never read, a charge landing on a conductor is absorbed.
+ *   The sum is accumulated in 64-bit INTEGERS (integer atomic adds commute: no order to depend on), in four launches:
+ *     scan       : A = max |q_m| over the points that are inside with a finite q (an integer atomic max on the bit pattern).
+ *                  A == 0 (or no such point): d is not touched.
+ *     unit       : E = ilogb(A) + 1, K the smallest integer with count <= 2^K, ue = E + K - 62 -- chosen by the kernels
+ *                  from A in device memory, the host never sees it.  No sum can overflow: count * A / 2^ue <= 2^62.
+ *     accumulate : per point and corner n = llrint(ldexp(q * ((wi*wj)*wk), -ue)) (to nearest even; the product in this order,
+ *                  uncontracted), added to a dense accumulator of one long long per node that the call zeroes first.
+ *     apply      : where acc != 0:  d[p] = d[p] + f * ldexp((double)acc, ue),  f = (scale * inv_h3) * nf(p),
+ *                  inv_h3 = 1.0 / ((h*h)*h) formed on the host in this order; nodes with acc == 0 are not written.
+ *     refresh    : on a context with a periodic axis the duplicates of d are then refreshed from their sources (the launch
+ *                  writes nothing while A == 0).
+ *   Precision: each contribution is rounded to a multiple of 2^ue <= A * 2^(K-61) -- with 10^6 points 2^-41 of the largest
+ *   charge --, eight of them per point: the total charge is conserved to 4 * count * 2^ue (plus the rounding of the weights).
+ *   State: exactly mg3d_upload_device's on MG3D_D of the finest level -- a cycle that has run ahead is finished and the next
+ *   one starts afresh, d counts as the caller's new values (the zero map is rescanned by the next cycle) -- also when
+ *   A == 0 or count == 0 (count == 0 launches nothing).  Stream ordering as above, no host synchronisation.  The
+ *   accumulator (N^3 long long in the device layout) is allocated on the first deposit and freed with the context:
+ *   MG3D_ERR_ALLOC, nothing changed, when it does not fit.  Kernel timer: scan, accumulate and apply count under
+ *   MG3D_K_PACK, 3 launches per call; the duplicate refresh of a periodic context is a fourth.
+ *   MG3D_ERR_ARG, nothing changed: the conditions of the sample, or a NULL q.
+ * mg3d_field_sample, mg3d_deposit: the same from host arrays -- xyz is count x 3 (x, y, z of point m at xyz[3*m ..]), u and
+ *   q hold count doubles, grad count x 3; u or grad may be NULL (not wanted).  They stage through device buffers allocated
+ *   for the call (MG3D_ERR_ALLOC, nothing changed, when they do not fit), run the same launches and synchronise once;
+ *   the results have the bits of the device forms.
+ * Out of scope: the slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms; higher-order shapes (TSC); sorting the
+ * points; a count of the points that were outside. */
+typedef struct mg3d_vec {
+    void *ptr;        /* element 0, device memory of the context's device */
+    int dtype;        /* MG3D_F64 / MG3D_F32 */
+    long long stride; /* in ELEMENTS */
+} mg3d_vec;
+int mg3d_field_sample_device(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3], double scale,
+                             const mg3d_vec *u_out /* NULL: not wanted */,
+                             const mg3d_vec *const grad_out[3] /* NULL, or entries NULL: not wanted */, void *stream);
+int mg3d_deposit_device(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3], const mg3d_vec *q, double scale,
+                        void *stream);
+int mg3d_field_sample(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 */, double scale, double *u /* count; NULL: not wanted */,
+                      double *grad /* count x 3; NULL: not wanted */);
+int mg3d_deposit(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 */, const double *q /* count */, double scale);
+
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)
  *                   postSmoother (post=1, mg_3d.h:711-781: iters x black,red)

@@ -6,4 +6,4 @@ sources in ``csrc/``, ABI in ``include/mg3d.h``, drop-in headers ``include/mg_3d
 This Python package is only the thin ctypes mirror used by the tests and by bench.py.
 """
 from .binding import Solver, Solver32, DistSolver, DistSolver32, EsParams, Mg3dError, lib, lib_path  # noqa: F401
-from .binding import MG3D_F32, MG3D_F64, array_desc, mg3d_array  # noqa: F401  (device arrays; torch is imported on use only)
+from .binding import MG3D_F32, MG3D_F64, array_desc, mg3d_array, mg3d_vec, vec_desc  # noqa: F401  (device arrays; torch is imported on use only)

@@ -40,6 +40,15 @@ class mg3d_array(C.Structure):
 
 _ap = C.POINTER(mg3d_array)
 
+
+class mg3d_vec(C.Structure):
+    """mg3d_vec: a 1-D strided vector in device memory -- element m is ptr[stride*m], stride in elements.  vec_desc()
+    builds one from a 1-D torch tensor."""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("stride", C.c_longlong)]
+
+
+_vp = C.POINTER(mg3d_vec)
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/mg3d.h
 SIGNATURES = {
     "mg3d_last_error": (C.c_char_p, []),
@@ -99,6 +108,11 @@ SIGNATURES = {
     "mg3d_field_gradient_device": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(_ap), C.c_void_p]),
     "mg3d_field_flux": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_field_energy": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_field_sample": (C.c_int, [C.c_void_p, C.c_longlong, dp, C.c_double, dp, dp]),
+    "mg3d_field_sample_device": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(_vp), C.c_double, _vp, C.POINTER(_vp),
+                                           C.c_void_p]),
+    "mg3d_deposit": (C.c_int, [C.c_void_p, C.c_longlong, dp, dp, C.c_double]),
+    "mg3d_deposit_device": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(_vp), _vp, C.c_double, C.c_void_p]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -294,6 +308,56 @@ def _device_args(t, who, shape, writable=False):
     if not t.is_cuda:
         raise ValueError(f"{who}: need a tensor on the GPU, got device {t.device}")
     return a, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def vec_desc(t, writable=False, count=None):
+    """The mg3d_vec of a 1-D float64 / float32 torch tensor: data_ptr(), the dtype code and stride(0) in elements -- any
+    view is described as it is, nothing is copied.  TypeError for anything else; ValueError for a length other than
+    `count` (when given) and, with writable=True, for a zero stride.  The tensor must stay alive until the call that takes
+    the descriptor has returned."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"vec_desc: need a torch.Tensor, got {type(t).__name__}")
+    if t.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"vec_desc: need float64 or float32, got {t.dtype}")
+    if t.dim() != 1:
+        raise TypeError(f"vec_desc: need a 1-D tensor, got {t.dim()} dimensions")
+    if count is not None and t.shape[0] != count:
+        raise ValueError(f"vec_desc: need {count} elements, got {t.shape[0]}")
+    st = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), 1)
+    if writable and st == 0:
+        raise ValueError("vec_desc: a tensor that is written needs a stride >= 1, got 0")
+    return mg3d_vec(t.data_ptr(), MG3D_F64 if t.dtype == torch.float64 else MG3D_F32, st)
+
+
+def _vec_ptrs(descs):
+    return (_vp * 3)(*[C.pointer(d) if d is not None else _vp() for d in descs])
+
+
+def _position_args(pos, who):
+    """the three position vectors of an (M, 3) tensor (any view) or of a sequence of three 1-D tensors of one length, all on
+    one GPU: (descriptors, M, device, stream handle)"""
+    import torch
+    if isinstance(pos, torch.Tensor):
+        if pos.dim() != 2 or pos.shape[1] != 3:
+            raise ValueError(f"{who}: positions need shape (M, 3), got {tuple(pos.shape)}")
+        parts = [pos[:, 0], pos[:, 1], pos[:, 2]]
+    else:
+        parts = list(pos)
+        if len(parts) != 3:
+            raise ValueError(f"{who}: positions need three coordinate vectors, got {len(parts)}")
+    for t in parts:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: need torch tensors, got {type(t).__name__}")
+        if not t.is_cuda:
+            raise ValueError(f"{who}: need tensors on the GPU, got device {t.device}")
+        if t.device != parts[0].device:
+            raise ValueError(f"{who}: positions on different devices ({t.device}, {parts[0].device})")
+    if any(t.dim() != 1 for t in parts):
+        raise ValueError(f"{who}: each coordinate vector must be 1-D")
+    M = parts[0].shape[0]
+    descs = [vec_desc(t, count=M) for t in parts]
+    return descs, M, parts[0].device, C.c_void_p(torch.cuda.current_stream(parts[0].device).cuda_stream)
 
 
 class Solver:
@@ -687,6 +751,70 @@ class Solver:
         w = C.c_double(0.)
         check(self.L.mg3d_field_energy(self._h, C.byref(w)))
         return w.value
+
+    # -- particles (include/mg3d.h, "Particles"): gather at points, scatter of point charges; the finest level
+    def sample(self, xyz, scale=1.0):
+        """mg3d_field_sample: u and scale * grad u at the points xyz ((M, 3) float64: x along i, y along j, z along k),
+        trilinear in the nodal values, NaN for a point outside the box.  Returns (u (M,), grad (M, 3))."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"sample: positions need shape (M, 3), got {xyz.shape}")
+        M = xyz.shape[0]
+        u, g = np.empty(M), np.empty((M, 3))
+        check(self.L.mg3d_field_sample(self._h, M, P(xyz.reshape(-1)), float(scale), P(u), P(g.reshape(-1))))
+        return u, g
+
+    def deposit(self, xyz, q, scale=1.0):
+        """mg3d_deposit: d of the finest level += scale * (cloud-in-cell density of the charges q (M,) at xyz (M, 3)),
+        doubled per Neumann face a node lies on.  Deterministic and independent of the order of the points."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"deposit: positions need shape (M, 3), got {xyz.shape}")
+        if q.shape != (xyz.shape[0],):
+            raise ValueError(f"deposit: q needs shape ({xyz.shape[0]},), got {q.shape}")
+        check(self.L.mg3d_deposit(self._h, xyz.shape[0], P(xyz.reshape(-1)), P(q), float(scale)))
+
+    def sample_tensor(self, pos, want_u=True, want_grad=True, scale=1.0, out_u=None, out_grad=None, dtype=None):
+        """mg3d_field_sample_device: the same on GPU tensors, one launch, ordered on the current stream, no host
+        synchronisation.  pos is an (M, 3) tensor (any view) or a sequence of three 1-D tensors, float64 or float32.
+        out_u (M,) / out_grad (M, 3) (any writable views) are written when given, else new tensors of `dtype` (default
+        torch.float64) are made for what want_u / want_grad ask for.  Returns (u or None, grad or None)."""
+        import torch
+        descs, M, dev, stream = _position_args(pos, "sample_tensor")
+        dt = torch.float64 if dtype is None else dtype
+        if out_u is None and want_u:
+            out_u = torch.empty((M,), dtype=dt, device=dev)
+        if out_grad is None and want_grad:
+            out_grad = torch.empty((M, 3), dtype=dt, device=dev)
+        du, dg = None, [None] * 3
+        if out_u is not None:
+            if not (isinstance(out_u, torch.Tensor) and out_u.is_cuda and out_u.device == dev):
+                raise ValueError(f"sample_tensor: out_u must be a tensor on {dev}")
+            if tuple(out_u.shape) != (M,):
+                raise ValueError(f"sample_tensor: out_u needs shape ({M},), got {tuple(out_u.shape)}")
+            du = vec_desc(out_u, writable=True, count=M)
+        if out_grad is not None:
+            if not (isinstance(out_grad, torch.Tensor) and out_grad.is_cuda and out_grad.device == dev):
+                raise ValueError(f"sample_tensor: out_grad must be a tensor on {dev}")
+            if tuple(out_grad.shape) != (M, 3):
+                raise ValueError(f"sample_tensor: out_grad needs shape ({M}, 3), got {tuple(out_grad.shape)}")
+            dg = [vec_desc(out_grad[:, a], writable=True, count=M) for a in range(3)]
+        check(self.L.mg3d_field_sample_device(self._h, M, _vec_ptrs(descs), float(scale),
+                                              C.byref(du) if du is not None else None, _vec_ptrs(dg), stream))
+        return out_u, out_grad
+
+    def deposit_tensor(self, pos, q, scale=1.0):
+        """mg3d_deposit_device: deposit() from GPU tensors -- pos as in sample_tensor, q an (M,) tensor, float64 or
+        float32, any view (expand: one charge for all) --, ordered on the current stream, no host synchronisation."""
+        import torch
+        descs, M, dev, stream = _position_args(pos, "deposit_tensor")
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and q.device == dev):
+            raise ValueError(f"deposit_tensor: q must be a tensor on {dev}")
+        if tuple(q.shape) != (M,):
+            raise ValueError(f"deposit_tensor: q needs shape ({M},), got {tuple(q.shape)}")
+        dq = vec_desc(q, count=M)
+        check(self.L.mg3d_deposit_device(self._h, M, _vec_ptrs(descs), C.byref(dq), float(scale), stream))
 
     # -- operators
     def smooth(self, level, post, iters):

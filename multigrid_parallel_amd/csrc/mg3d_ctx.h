@@ -95,6 +95,10 @@ struct mg3d_ctx {
     int device = 0;
     hipEvent_t io_ev[2] = {nullptr, nullptr};
     unsigned long long *io_chk = nullptr;
+    /* mg3d_deposit(_device) (mg3d_particle.hip): the integer accumulator, one long long per element of the finest level's
+     * layout, and the word that takes max |q|; allocated on the first deposit, freed with the context */
+    long long *dep_acc = nullptr;
+    unsigned long long *dep_max = nullptr;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     /* The zero map of d of the top level (k_dzero_scan: bit i = plane i is +0.0 at every interior point), which the fused
      * sweep launches of that level take so as not to read those planes (mg3d_level_sweep).  Every writer of that d says
@@ -216,5 +220,8 @@ int mg3d_drop_carry_keep(mg3d_ctx *ctx); /* the same without clearing red_tail: 
  * No host synchronisation. */
 int mg3d_array_check(const mg3d_ctx *ctx, const mg3d_array *a, bool writable, const char *who, bool bytes = false /* MG3D_U8 and nothing else: a mask */);
 int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *who);
+/* the finest level of a context as the field output and the particle calls need it (mg3d_field.hip): MG3D_ERR_STATE unless
+ * it is a single-domain level of at least three points per side */
+int mg3d_field_level(const mg3d_ctx *ctx, const char *who);
 
 #endif

@@ -197,6 +197,10 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
         (void)hipFree(ctx->step_src);
     if (ctx->io_chk)
         (void)hipFree(ctx->io_chk);
+    if (ctx->dep_acc)
+        (void)hipFree(ctx->dep_acc);
+    if (ctx->dep_max)
+        (void)hipFree(ctx->dep_max);
     for (hipEvent_t e : ctx->io_ev)
         if (e)
             (void)hipEventDestroy(e);

@@ -34,7 +34,7 @@ static int field_launch_ok(const char *who)
 }
 
 /* the finest level of a context these calls serve: a single-domain level of at least three points per side */
-static int field_level(const mg3d_ctx *ctx, const char *who)
+int mg3d_field_level(const mg3d_ctx *ctx, const char *who)
 {
     const Geom &g = ctx->lv[ctx->L - 1].g;
     if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
@@ -68,7 +68,7 @@ static int gradient_args(const mg3d_ctx *ctx, double scale, bool any, const char
         return fail(MG3D_ERR_ARG, "%s: no component wanted (all three NULL)", who);
     if (!isfinite(scale))
         return fail(MG3D_ERR_ARG, "%s: scale must be finite (%g)", who, scale);
-    return field_level(ctx, who);
+    return mg3d_field_level(ctx, who);
 }
 
 extern "C" int mg3d_field_gradient_device(mg3d_ctx *ctx, double scale, const mg3d_array *const out[3], void *stream)
@@ -145,7 +145,7 @@ extern "C" int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux)
         return fail(MG3D_ERR_ARG, "%s: label %d (0: every fixed point, 1..255: the points with that byte)", who, label);
     if (ctx->mask.empty())
         return fail(MG3D_ERR_STATE, "%s: the context has no mask (mg3d_ctx_set_mask)", who);
-    int rc = field_level(ctx, who);
+    int rc = mg3d_field_level(ctx, who);
     if (rc == MG3D_OK)
         rc = mg3d_drop_carry_keep(ctx);
     if (rc != MG3D_OK)
@@ -171,7 +171,7 @@ extern "C" int mg3d_field_energy(mg3d_ctx *ctx, double *energy)
         return fail(MG3D_ERR_ARG, "%s: NULL context", who);
     if (!energy)
         return fail(MG3D_ERR_ARG, "%s: NULL result pointer", who);
-    int rc = field_level(ctx, who);
+    int rc = mg3d_field_level(ctx, who);
     if (rc == MG3D_OK)
         rc = mg3d_drop_carry_keep(ctx);
     if (rc != MG3D_OK)

@@ -342,10 +342,11 @@ void k_tiny_cycle(const Geom &g, double *u, const double *d, const double *r, co
 void k_coef_inject(const Geom &gf, const double *ef, const Geom &gc, double *ec, hipStream_t s);
 /* periodic axes, Neumann faces and fixed points (bc = mg3d_bc(periodic, neumann), single-domain levels): the right-hand
  * side of the direct solve -- b = d except in identity rows: 0 in the duplicates' and (pin) the pinned point's, and at the
- * fixed unknowns of m (NULL: no mask) 0. -- or ufix there when given (a one-level context) --; and a duplicate refresh */
+ * fixed unknowns of m (NULL: no mask) 0. -- or ufix there when given (a one-level context) --; and a duplicate refresh
+ * (gate, a word in device memory: nothing is written while it is 0 -- the deposit's "did anything deposit") */
 void k_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, const unsigned char *m, const double *ufix,
                   hipStream_t s);
-void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s);
+void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s, const unsigned long long *gate = nullptr);
 /* fixed points (mg3d_ctx_set_mask): one byte per point of a single-domain level in the padded layout (the doubles' index).
  * k_mask_pack: the caller's dense-indexed bytes (mg3d_array of MG3D_U8, any strides) into it, periodic duplicates taking
  * their sources'; k_mask_inject / k_mask_refresh: the coarser level's bytes by injection, the duplicates' from their sources;
@@ -384,6 +385,26 @@ int k_gradient(const Geom &g, const double *u, int bc, double cs, const mg3d_arr
 int k_field_flux(const Geom &g, const double *u, const LevelOperator &A, int label, double *partials, double *out,
                  hipStream_t s);
 int k_field_energy(const Geom &g, const double *u, const LevelOperator &A, double *partials, double *out, hipStream_t s);
+/* particles (mg3d_particle.hip; single-domain levels, bc the boundary word, h the level's spacing; include/mg3d.h
+ * "Particles" has the formulas).  One thread per point in 256-thread blocks, at most MG3D_PARTICLE_MAX_BLOCKS of them:
+ * past that a thread strides on to further points.  pos, q: the caller's vectors, checked by the entry point.
+ * k_part_sample: u and the nodal gradient (cs = scale * (0.5 / h)) interpolated to the points, NaN for a point outside,
+ *   into u_out / grad_out[0..2] (NULL: not wanted), one launch.
+ * The deposit, K the smallest integer with count <= 2^K, amax one 64-bit word and acc one long long per element of the
+ * level's layout, both zeroed by the caller:
+ *   k_part_scan       : *amax = the largest bit pattern of |q| over the points inside with a finite q
+ *   k_part_accumulate : acc[source of node] += llrint(ldexp(q * w, -ue)) per point and corner, ue from *amax and K
+ *   k_part_apply      : d[p] = d[p] + (f0 * nf(p)) * ldexp((double)acc[p], ue) where acc[p] != 0, f0 = scale / h^3
+ * The last two do nothing while *amax is 0.  Return value: 0, -1 when the level has no launch shape (nothing launched). */
+#define MG3D_PARTICLE_MAX_BLOCKS 2048
+int k_part_sample(const Geom &g, const double *u, int bc, double h, double cs, long long count, const mg3d_vec *const pos[3],
+                  const mg3d_vec *u_out, const mg3d_vec *const grad_out[3], hipStream_t s);
+int k_part_scan(const Geom &g, int bc, double h, long long count, const mg3d_vec *const pos[3], const mg3d_vec *q,
+                unsigned long long *amax, hipStream_t s);
+int k_part_accumulate(const Geom &g, int bc, double h, long long count, int K, const mg3d_vec *const pos[3],
+                      const mg3d_vec *q, const unsigned long long *amax, long long *acc, hipStream_t s);
+int k_part_apply(const Geom &g, int bc, double f0, int K, const unsigned long long *amax, const long long *acc, double *d,
+                 hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

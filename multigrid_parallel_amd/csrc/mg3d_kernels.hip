@@ -1700,11 +1700,12 @@ void k_coarse_rhs(const Geom &g, const double *d, double *b, int bc, int pin, co
  * other two indices.  The source maps every periodic index N-1 to 0, so only unique points are read; an edge or corner
  * duplicate is written by each plane it lies in, with the same value. */
 template <class T>
-__global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, T *__restrict__ v, int axes)
+__global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, T *__restrict__ v, int axes,
+                                                          const unsigned long long *__restrict__ gate)
 {
     const int b = blockIdx.x * WAVE + threadIdx.x, a = blockIdx.y * 4 + threadIdx.y, ax = blockIdx.z;
     const int N = g.N;
-    if (a >= N || b >= N || !(axes & (1 << ax)))
+    if (a >= N || b >= N || !(axes & (1 << ax)) || (gate && *gate == 0))
         return;
     int i = ax == 0 ? N - 1 : a, j = ax == 1 ? N - 1 : (ax == 0 ? a : b), k = ax == 2 ? N - 1 : b;
     const int si = (axes & 1) && i == N - 1 ? 0 : i, sj = (axes & 2) && j == N - 1 ? 0 : j,
@@ -1712,13 +1713,13 @@ __global__ void __launch_bounds__(256) per_refresh_kernel(Geom g, T *__restrict_
     v[gidx(g, i, j, k)] = v[gidx(g, si, sj, sk)];
 }
 
-void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s)
+void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s, const unsigned long long *gate)
 {
     const int axes = bc & 7;
     if (!axes)
         return;
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
-    hipLaunchKernelGGL(per_refresh_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes);
+    hipLaunchKernelGGL(per_refresh_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, v, axes, gate);
 }
 
 void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s)
@@ -1727,7 +1728,8 @@ void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s)
     if (!axes)
         return;
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, 3);
-    hipLaunchKernelGGL(per_refresh_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, g, m, axes);
+    hipLaunchKernelGGL(per_refresh_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, g, m, axes,
+                       (const unsigned long long *)nullptr);
 }
 
 /* ------------------------------------------------------------- fixed points */
@@ -2037,6 +2039,329 @@ int k_gradient(const Geom &g, const double *u, int bc, double cs, const mg3d_arr
     default:
         hipLaunchKernelGGL(gradient_kernel<BC_PLAIN>, grid, block, 0, s, g, u, o, cs, bc, chunk);
     }
+    return 0;
+}
+
+/* ----------------------------------------------------------------- particles
+ * The gather and the scatter between points and a single-domain level (include/mg3d.h "Particles"; the launchers'
+ * contract is in mg3d_internal.h).  One thread per point, 256 per block, the grid capped at MG3D_PARTICLE_MAX_BLOCKS with
+ * a stride loop behind it.  PartVec is a caller's vector (mg3d_vec), PartCell the cell of a point on one axis: the lower
+ * node c (0 .. N-2) and the weights of c and c+1. */
+struct PartVec {
+    void *p; /* NULL: not given / not wanted */
+    long long s;
+    int f32;
+};
+struct PartPos {
+    PartVec x[3];
+};
+struct PartOut {
+    PartVec v[4]; /* u, then the three components of the gradient */
+};
+static PartVec part_vec(const mg3d_vec *v)
+{
+    PartVec o = {nullptr, 0, 0};
+    if (v) {
+        o.p = v->ptr;
+        o.s = v->stride;
+        o.f32 = v->dtype == MG3D_F32;
+    }
+    return o;
+}
+__device__ __forceinline__ double part_load(const PartVec &v, long long m)
+{
+    return v.f32 ? (double)((const float *)v.p)[v.s * m] : ((const double *)v.p)[v.s * m];
+}
+__device__ __forceinline__ void part_store(const PartVec &v, long long m, double x)
+{
+    if (!v.p)
+        return;
+    if (v.f32)
+        ((float *)v.p)[v.s * m] = (float)x; /* (round to nearest even) */
+    else
+        ((double *)v.p)[v.s * m] = x;
+}
+struct PartCell {
+    int c;
+    double w0, w1;
+};
+/* false: the point is outside on this axis */
+template <int BC>
+__device__ __forceinline__ bool part_locate(int bc, int ax, double x, double h, int N, PartCell &o)
+{
+    const double n1 = (double)(N - 1);
+    double t = x / h;
+    if (!isfinite(x) || !isfinite(t))
+        return false;
+    if (BC && (bc >> ax & 1)) {
+        t = t - n1 * floor(t / n1);
+        /* what the rounding of the wrap leaves outside [0, N-1] goes to the nearer end (-0.0 stays) */
+        if (!(t >= 0.0))
+            t = 0.0;
+        if (t > n1)
+            t = n1;
+    } else if (!(0.0 <= t && t <= n1)) {
+        return false;
+    }
+    int c = (int)floor(t);
+    if (c > N - 2)
+        c = N - 2;
+    const double f = t - (double)c;
+    o.c = c;
+    o.w0 = 1.0 - f;
+    o.w1 = f;
+    return true;
+}
+template <int BC>
+__device__ __forceinline__ bool part_locate3(int bc, const PartPos &pos, long long m, double h, int N, PartCell (&cell)[3])
+{
+    bool in = true;
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++)
+        in = part_locate<BC>(bc, ax, part_load(pos.x[ax], m), h, N, cell[ax]) && in;
+    return in;
+}
+/* the nested sum over the eight corners of a cell, val(a*4 + b*2 + c) the value at corner (a, b, c) */
+template <class F>
+__device__ __forceinline__ double part_trilinear(const PartCell (&cell)[3], F val)
+{
+    double mid[2];
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        const double in0 = (cell[2].w0 * val(a * 4 + 0)) + (cell[2].w1 * val(a * 4 + 1));
+        const double in1 = (cell[2].w0 * val(a * 4 + 2)) + (cell[2].w1 * val(a * 4 + 3));
+        mid[a] = (cell[1].w0 * in0) + (cell[1].w1 * in1);
+    }
+    return (cell[0].w0 * mid[0]) + (cell[0].w1 * mid[1]);
+}
+
+/* The sample.  The eight corners of the cell are taken to their sources and loaded once; the nodal gradient at a corner is
+ * grad_value of grad_axis's taps, as gradient_kernel forms it.  Of a corner's two taps along an axis one is, away from the
+ * boundary forms, the cell's other corner on that axis and comes from its register: 8 + 24 loads of u per point. */
+template <int BC>
+__global__ void __launch_bounds__(256) part_sample_kernel(Geom g, const double *__restrict__ u, PartPos pos, long long count,
+                                                          double h, double cs, int bc, PartOut o)
+{
+    const int N = g.N;
+    const bool want_grad[3] = {o.v[1].p != nullptr, o.v[2].p != nullptr, o.v[3].p != nullptr};
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        PartCell cell[3];
+        if (!part_locate3<BC>(bc, pos, m, h, N, cell)) {
+            const double nan = __builtin_nan("");
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+                part_store(o.v[t], m, nan);
+            continue;
+        }
+        GradAxis ga[3][2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            ga[0][e] = grad_axis<BC>(bc, 0, cell[0].c + e, N, g.plane);
+            ga[1][e] = grad_axis<BC>(bc, 1, cell[1].c + e, N, g.pitch);
+            ga[2][e] = grad_axis<BC>(bc, 2, cell[2].c + e, N, 1);
+        }
+        long long p[8];
+        double v[8];
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            p[t] = g.plane * ga[0][t >> 2].src + (long long)g.pitch * ga[1][(t >> 1) & 1].src + ga[2][t & 1].src;
+            v[t] = u[p[t]];
+        }
+        if (o.v[0].p)
+            part_store(o.v[0], m, part_trilinear(cell, [&](int t) { return v[t]; }));
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            if (!want_grad[d])
+                continue;
+            const int bit = 4 >> d;
+            const double gd = part_trilinear(cell, [&](int t) {
+                const GradAxis &A = ga[d][(t & bit) ? 1 : 0];
+                const long long po = p[t ^ bit], qa = p[t] + A.oa, qb = p[t] + A.ob;
+                const double ta = qa == po ? v[t ^ bit] : u[qa];
+                const double tb = qb == po ? v[t ^ bit] : u[qb];
+                return grad_value(A.kind, ta, tb, v[t], cs);
+            });
+            part_store(o.v[1 + d], m, gd);
+        }
+    }
+}
+
+static dim3 part_grid(long long count)
+{
+    const long long blocks = (count + 255) / 256;
+    return dim3((unsigned)(blocks < MG3D_PARTICLE_MAX_BLOCKS ? blocks : MG3D_PARTICLE_MAX_BLOCKS), 1, 1);
+}
+static bool part_level_ok(const Geom &g) { return g.N >= 3 && g.ni == g.N && g.nj == g.N && g.nk == g.N; }
+static PartPos part_pos(const mg3d_vec *const pos[3])
+{
+    PartPos p;
+    for (int a = 0; a < 3; a++)
+        p.x[a] = part_vec(pos[a]);
+    return p;
+}
+
+int k_part_sample(const Geom &g, const double *u, int bc, double h, double cs, long long count, const mg3d_vec *const pos[3],
+                  const mg3d_vec *u_out, const mg3d_vec *const grad_out[3], hipStream_t s)
+{
+    if (!part_level_ok(g) || count <= 0)
+        return -1;
+    PartOut o;
+    o.v[0] = part_vec(u_out);
+    for (int a = 0; a < 3; a++)
+        o.v[1 + a] = part_vec(grad_out ? grad_out[a] : nullptr);
+    const PartPos p = part_pos(pos);
+    const dim3 grid = part_grid(count), block(256, 1, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(part_sample_kernel<BC_REFLECT>, grid, block, 0, s, g, u, p, count, h, cs, bc, o);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(part_sample_kernel<BC_WRAP>, grid, block, 0, s, g, u, p, count, h, cs, bc, o);
+        break;
+    default:
+        hipLaunchKernelGGL(part_sample_kernel<BC_PLAIN>, grid, block, 0, s, g, u, p, count, h, cs, bc, o);
+    }
+    return 0;
+}
+
+/* The deposit.  scan: the largest |q| among the points that will deposit, as its bit pattern (for non-negative doubles the
+ * order of the patterns is the order of the values): a thread's own maximum, the wave's by shuffles, one atomic per wave. */
+template <int BC>
+__global__ void __launch_bounds__(256) part_scan_kernel(Geom g, PartPos pos, PartVec q, long long count, double h, int bc,
+                                                        unsigned long long *__restrict__ amax)
+{
+    unsigned long long best = 0;
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        const double qv = part_load(q, m);
+        PartCell cell[3];
+        if (!isfinite(qv) || !part_locate3<BC>(bc, pos, m, h, g.N, cell))
+            continue;
+        const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(qv));
+        best = b > best ? b : best;
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        const unsigned long long other = __shfl_xor(best, off, WAVE);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0 && best != 0)
+        atomicMax(amax, best);
+}
+/* the unit 2^ue of the accumulator from A = max |q| and K; false: nothing deposits */
+__device__ __forceinline__ bool part_unit(const unsigned long long *amax, int K, int &ue)
+{
+    const unsigned long long b = *amax;
+    if (b == 0)
+        return false;
+    ue = ilogb(__longlong_as_double((long long)b)) + 1 + K - 62;
+    return true;
+}
+/* accumulate: eight 64-bit integer adds per point, at the sources of the cell's nodes */
+template <int BC>
+__global__ void __launch_bounds__(256) part_accumulate_kernel(Geom g, PartPos pos, PartVec q, long long count, double h, int bc,
+                                                              int K, const unsigned long long *__restrict__ amax,
+                                                              long long *__restrict__ acc)
+{
+    int ue;
+    if (!part_unit(amax, K, ue))
+        return;
+    const int N = g.N;
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        const double qv = part_load(q, m);
+        PartCell cell[3];
+        if (!isfinite(qv) || !part_locate3<BC>(bc, pos, m, h, N, cell))
+            continue;
+        long long off[3][2];
+        const long long st[3] = {g.plane, g.pitch, 1};
+#pragma unroll
+        for (int ax = 0; ax < 3; ax++) {
+            const bool per = BC && (bc >> ax & 1);
+            off[ax][0] = st[ax] * cell[ax].c;
+            off[ax][1] = (per && cell[ax].c + 1 == N - 1) ? 0 : st[ax] * (cell[ax].c + 1);
+        }
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            const int a = t >> 2, b = (t >> 1) & 1, c = t & 1;
+            const double w = ((a ? cell[0].w1 : cell[0].w0) * (b ? cell[1].w1 : cell[1].w0)) * (c ? cell[2].w1 : cell[2].w0);
+            const long long n = llrint(ldexp(qv * w, -ue));
+            if (n != 0)
+                atomicAdd((unsigned long long *)(acc + (off[0][a] + off[1][b] + off[2][c])), (unsigned long long)n);
+        }
+    }
+}
+/* apply: over all N^3 nodes (the duplicates' accumulators stay 0), lanes contiguous in k */
+__global__ void __launch_bounds__(256) part_apply_kernel(Geom g, int bc, double f0, int K,
+                                                         const unsigned long long *__restrict__ amax,
+                                                         const long long *__restrict__ acc, double *__restrict__ d)
+{
+    int ue;
+    if (!part_unit(amax, K, ue))
+        return;
+    const int N = g.N;
+    const int k = blockIdx.x * WAVE + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, i = blockIdx.z;
+    if (k >= N || j >= N)
+        return;
+    const long long p = gidx(g, i, j, k);
+    const long long a = acc[p];
+    if (a == 0)
+        return;
+    const int x[3] = {i, j, k};
+    double nf = 1.0;
+#pragma unroll
+    for (int ax = 0; ax < 3; ax++)
+        if ((x[ax] == 0 && bc_ref_lo(bc, ax)) || (x[ax] == N - 1 && bc_ref_hi(bc, ax)))
+            nf *= 2.0;
+    d[p] = d[p] + (f0 * nf) * ldexp((double)a, ue);
+}
+
+int k_part_scan(const Geom &g, int bc, double h, long long count, const mg3d_vec *const pos[3], const mg3d_vec *q,
+                unsigned long long *amax, hipStream_t s)
+{
+    if (!part_level_ok(g) || count <= 0)
+        return -1;
+    const PartPos p = part_pos(pos);
+    const PartVec qv = part_vec(q);
+    const dim3 grid = part_grid(count), block(256, 1, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(part_scan_kernel<BC_REFLECT>, grid, block, 0, s, g, p, qv, count, h, bc, amax);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(part_scan_kernel<BC_WRAP>, grid, block, 0, s, g, p, qv, count, h, bc, amax);
+        break;
+    default:
+        hipLaunchKernelGGL(part_scan_kernel<BC_PLAIN>, grid, block, 0, s, g, p, qv, count, h, bc, amax);
+    }
+    return 0;
+}
+
+int k_part_accumulate(const Geom &g, int bc, double h, long long count, int K, const mg3d_vec *const pos[3],
+                      const mg3d_vec *q, const unsigned long long *amax, long long *acc, hipStream_t s)
+{
+    if (!part_level_ok(g) || count <= 0)
+        return -1;
+    const PartPos p = part_pos(pos);
+    const PartVec qv = part_vec(q);
+    const dim3 grid = part_grid(count), block(256, 1, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(part_accumulate_kernel<BC_REFLECT>, grid, block, 0, s, g, p, qv, count, h, bc, K, amax, acc);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(part_accumulate_kernel<BC_WRAP>, grid, block, 0, s, g, p, qv, count, h, bc, K, amax, acc);
+        break;
+    default:
+        hipLaunchKernelGGL(part_accumulate_kernel<BC_PLAIN>, grid, block, 0, s, g, p, qv, count, h, bc, K, amax, acc);
+    }
+    return 0;
+}
+
+int k_part_apply(const Geom &g, int bc, double f0, int K, const unsigned long long *amax, const long long *acc, double *d,
+                 hipStream_t s)
+{
+    if (!part_level_ok(g))
+        return -1;
+    const dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(part_apply_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, bc, f0, K, amax, acc, d);
     return 0;
 }
 
