@@ -636,7 +636,10 @@ int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
  *   sweep_ci        0        MG3D_SWEEP_CI             > 0: planes per chunk of every fused sweep launch (measurement)
  *   sweep_rj/nw/pf  0        MG3D_SWEEP_CFG="rj,nw,pf" another compiled tile shape (unknown ones fall back to the default)
  *   d_zero_skip     1        MG3D_D_ZERO_SKIP          the fused launches of the finest level do not read the planes of d that
- *                                                      are +0.0 at every interior point (the zero map, below); 0: every plane
+ *                                                      are +0.0 at every interior point (the zero map, below) and, when
+ *                                                      that holds for EVERY interior plane, the two leg launches of the
+ *                                                      finest level run kernels with no d at all; 2: the map only;
+ *                                                      0: every plane is read
  * mg3d_option_name(i) enumerates the keys (NULL past the end).  mg3d_dist_set_option forwards to every local rank (carry /
  * carry_min of a multi-rank job are agreed at creation and refuse to change); mg3d32_set_option knows "pairs", "fuse",
  * "carry" (MG3D_F32_NO_PAIRS / _NO_FUSE / _NO_CARRY at creation).  A context with a variable coefficient
@@ -657,6 +660,10 @@ const char *mg3d_option_name(int index);
  * mg3d_ctx_dzero_planes: how many planes the map holds (0 unless it is valid) and its state -- 0 off, 1 to be scanned by
  * the next cycle, 2 valid; either pointer may be NULL.  For tests and tools. */
 int mg3d_ctx_dzero_planes(const mg3d_ctx *ctx, int *planes, int *state);
+/* mg3d_ctx_dnone_launches: how many launches of this context have run a kernel without d because the map was full
+ * (d_zero_skip = 1, d +0.0 at every interior point of the finest level: the flagship problem, every source-free one).  The
+ * same bits as with the map alone or without it: h^2 * (+0.0) is +0.0, x - (+0.0) is x.  For tests and tools. */
+int mg3d_ctx_dnone_launches(const mg3d_ctx *ctx, unsigned long long *launches);
 
 /* per-stage timers (timing_info.h:6-47), filled from hipEvent pairs recorded in-stream (no stall).
  * on: 0 = off, 1 = every level, 2 = finest level only, 3 = the kernel timers of the finest level only (no stage

@@ -134,6 +134,7 @@ SIGNATURES = {
     "mg3d_ctx_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "mg3d_option_name": (C.c_char_p, [C.c_int]),
     "mg3d_ctx_dzero_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mg3d_ctx_dnone_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "mg3d32_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mg3d32_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d32_kernel_name": (C.c_char_p, [C.c_int]),
@@ -425,6 +426,12 @@ class Solver:
         n, st = C.c_int(0), C.c_int(0)
         check(self.L.mg3d_ctx_dzero_planes(self._h, C.byref(n), C.byref(st)))
         return n.value, st.value
+
+    def dnone_launches(self):
+        """mg3d_ctx_dnone_launches: launches that ran a kernel without d because the zero map was full."""
+        n = C.c_ulonglong(0)
+        check(self.L.mg3d_ctx_dnone_launches(self._h, C.byref(n)))
+        return n.value
 
     # -- geometry
     def level_n(self, level):

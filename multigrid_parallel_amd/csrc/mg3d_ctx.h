@@ -112,6 +112,9 @@ struct mg3d_ctx {
     unsigned *dz_map = nullptr; /* device, mg3d_dzero_words(ni) words, allocated with the context */
     int dz_state = MG3D_DZ_UNKNOWN, dz_planes = 0; /* (created zeroed: the first cycle's scan finds that out) */
     bool dz_raw = false;
+    /* launches that took a kernel without d because the map was full (SweepLaunch::d_none; mg3d_ctx_dnone_launches).
+     * Counted where the launch is described, through the const context of mg3d_level_sweep */
+    mutable unsigned long long dnone_launches = 0;
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */
     int timing; /* 0 off, 1 every level, 2 finest level only, 3 finest level's kernel timers only, 4 + k: 3 on every (k+2)-th cycle */
@@ -152,8 +155,14 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
     w.d = l.f[MG3D_D];
     /* the top level's d comes with its zero map when that is known to hold a plane (the one place a launch gets its d) */
     if (&l == &ctx->lv[ctx->L - 1] && ctx->dz_state == MG3D_DZ_VALID && ctx->dz_planes > 0 && ctx->opt.v[MG3D_OPT_D_ZERO_SKIP] &&
-        mg3d_fused(ctx))
+        mg3d_fused(ctx)) {
         w.d_zero = ctx->dz_map;
+        /* a full map: the launches that have a kernel without d take that one (option 1; 2: the map only) */
+        if (l.g.ni > 2 && ctx->dz_planes == l.g.ni - 2 && ctx->opt.v[MG3D_OPT_D_ZERO_SKIP] == 1) {
+            w.d_none = true;
+            w.d_none_taken = &ctx->dnone_launches;
+        }
+    }
     w.vout = l.alt;
     return w;
 }

@@ -1318,6 +1318,15 @@ extern "C" int mg3d_ctx_dzero_planes(const mg3d_ctx *ctx, int *planes, int *stat
     return MG3D_OK;
 }
 
+/* launches that took a kernel without d (mg3d_ctx.h, dnone_launches) */
+extern "C" int mg3d_ctx_dnone_launches(const mg3d_ctx *ctx, unsigned long long *launches)
+{
+    if (!ctx || !launches)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_dnone_launches: NULL argument");
+    *launches = ctx->dnone_launches;
+    return MG3D_OK;
+}
+
 /* ----------------------------------------------------------------- operators */
 static int launch_ok(const char *who)
 {

@@ -88,7 +88,7 @@ enum {
     MG3D_OPT_SWEEP_RJ,     /* > 0: another compiled tile shape (rows per thread, waves, planes in flight); unknown ones */
     MG3D_OPT_SWEEP_NW,     /*      fall back to the default */
     MG3D_OPT_SWEEP_PF,
-    MG3D_OPT_D_ZERO_SKIP,  /* the planes of the top level's d that are +0.0 at every interior point are not read (1; the zero map, mg3d_ctx.h) */
+    MG3D_OPT_D_ZERO_SKIP,  /* the planes of the top level's d that are +0.0 at every interior point are not read (the zero map, mg3d_ctx.h): 0 off, 1 the map and, when it is full, the leg kernels without d (default), 2 the map only */
     MG3D_OPT_COUNT
 };
 struct mg3d_options {
@@ -204,6 +204,11 @@ struct SweepLaunch {
     /* optional: the zero map of d (k_dzero_scan), bit i set = plane i of d is +0.0 at every interior point and is not read.
      * Single-domain levels with Dirichlet faces only: there no face entry of d enters a stored value */
     const unsigned *d_zero = nullptr;
+    /* optional: d is +0.0 at EVERY interior point (the map is full).  A launch that has a kernel without d (the legs) takes it
+     * and then looks at neither d nor the map; every other launch goes by d_zero as before.  d_none_taken, if given, is
+     * incremented by one for a launch that took such a kernel */
+    bool d_none = false;
+    unsigned long long *d_none_taken = nullptr;
     double *vout = nullptr;
     /* what the launch does */
     SweepKind kind = SWEEP_PASSES;

@@ -91,20 +91,25 @@ static int device_cus() /* of the CURRENT device (a process may drive several: m
 
 /* The zero map of d (SweepArgs::dz) has instantiations of its own, taken when a launch brings a map: every other launch --
  * the levels below the top one, a dense d, the slab path -- runs a kernel with no trace of it.  Compiled for the tile shapes
- * the default schedules use; the shapes only the options sweep_rj / nw / pf reach read every plane. */
-template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K>
+ * the default schedules use; the shapes only the options sweep_rj / nw / pf reach read every plane.
+ * ND: the launcher has chosen the kernel without d (SweepArgs::d_none, the leg launches): neither a.d nor a.dz is looked at. */
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND>
 static void launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s)
 {
-    if constexpr (NW == 8 && ((RJ == 4 && PF == 1) || (RJ == 2 && PF >= 2))) {
-        if (a.dz) {
-            hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
-            return;
+    if constexpr (ND) { /* (the else branch is discarded: an ND shape has no siblings that read d unless another launch names them) */
+        hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
+    } else {
+        if constexpr (NW == 8 && ((RJ == 4 && PF == 1) || (RJ == 2 && PF >= 2))) {
+            if (a.dz) {
+                hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
+                return;
+            }
         }
+        hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
     }
-    hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
 }
 
-template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1>
+template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1, bool ND = false>
 static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s)
 {
     using Sh = SweepShape<S, RES>;
@@ -135,7 +140,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
             return -1;
         a.CI = a.edge;
         a.xcd_remap = 2 * T < 64 ? 0 : 2 * T <= ncu ? 1 : 2;
-        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>(a, (unsigned)(2 * T), s);
+        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)(2 * T), s);
         return (int)(2 * T);
     }
     const int ovh = Sh::HI + Sh::ST + (RES == 2 ? 2 : 0) + 1;
@@ -206,7 +211,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
         static_assert(C1K < 0 || !PRO || C1K == 0, "PRO launches are post-smoothers");
         if (C1K >= 0 && a.c1 != C1K)
             return;
-        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K>(a, (unsigned)nb, s);
+        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)nb, s);
     };
     /* Measured choice.  The model above ranks chunk lengths by steps; what a step costs depends on how many CUs stream
      * at once and on how well the chunks keep in lock-step, which it does not know.  The first launch of a shape on a
@@ -218,11 +223,11 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
      * into per-block partial sums, and a timing-dependent choice would make it differ from run to run */
     if (!forced && tune_on && !a.partials && T * nout >= 1024) {
         struct Key {
-            int v[14];
+            int v[15];
             bool operator<(const Key &o) const { return memcmp(v, o.v, sizeof v) < 0; }
         };
         const Key key = {{g.ni, g.nj, g.nk, g.N, g.ig0 & 1, a.i_lo, a.i_hi, a.vin != nullptr, a.partials != nullptr,
-                          a.r != nullptr, a.vk, max_partials, current_device(), a.dz != nullptr}};
+                          a.r != nullptr, a.vk, max_partials, current_device(), a.dz != nullptr, (int)ND}};
         static std::mutex mu;
         static std::map<Key, int> tuned; /* chunk length */
         std::lock_guard<std::mutex> lock(mu);
@@ -391,6 +396,7 @@ static bool fill_args(SweepArgs &a, const SweepLaunch &w)
     a.vin = w.vin;
     a.d = w.d;
     a.dz = w.d_zero;
+    a.d_none = w.d_none ? 1 : 0;
     a.vout = w.vout;
     a.r = w.r;
     a.partials = w.partials;
@@ -518,6 +524,18 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
 #ifndef MG3D_LEG_DP_DOWN3
 #define MG3D_LEG_DP_DOWN3 2
 #endif
+/* The legs of a launch whose d is +0.0 at every interior point (SweepArgs::d_none; the flagship problem, every source-free
+ * one) run the ND instantiations: four rows, eight waves, no d window, nothing parked -- the down-leg then keeps two copies
+ * of its wave-edge rows and one barrier a step.  Planes of u in flight, 1 or 2: the registers the window gave back hold a
+ * second one without scratch (profiles/dnone_kernel_resources.txt); both are compiled, option sweep_pf picks the one that
+ * is not the default for a same-box A/B.  Measured at 513^3 (profiles/dnone_ab.txt; the kernels with the map: down 0.698,
+ * up 0.647 ms): down-leg 0.599 ms with one plane, 0.609 with two; up-leg 0.507 ms with one, 0.498 with two */
+#ifndef MG3D_LEG_ND_PF_DOWN
+#define MG3D_LEG_ND_PF_DOWN 1
+#endif
+#ifndef MG3D_LEG_ND_PF_UP
+#define MG3D_LEG_ND_PF_UP 2
+#endif
 
 /* the leg launches take the chunk model's choice, never the first-use measurement: their norm-forming variants cannot be measured
  * (reproducible partial sums), and the variants without a norm half -- the first cycle of a call behind an earlier one, the last
@@ -537,6 +555,15 @@ static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch
     const mg3d_options oq = leg_options(o);
     const int S = w.S, max_partials = w.max_partials;
     a.c1 = S == 4 ? 1 : 0;
+    if (a.d_none && S == 3) { /* d is +0.0 at every interior point: the kernels without a d window, nothing parked (DP = 0) */
+        constexpr int PFD = MG3D_LEG_ND_PF_DOWN, PFA = 3 - PFD;
+        if (o.v[MG3D_OPT_SWEEP_PF] == PFA) /* the other candidate of the choice (measurement only) */
+            return w.partials ? launch_sweep<3, 2, 4, 8, PFA, false, true, 0, 0, -1, true>(oq, a, max_partials, s)
+                              : launch_sweep<3, 2, 4, 8, PFA, false, true, 0, -1, -1, true>(oq, a, max_partials, s);
+        return w.partials ? launch_sweep<3, 2, 4, 8, PFD, false, true, 0, 0, -1, true>(oq, a, max_partials, s)
+                          : launch_sweep<3, 2, 4, 8, PFD, false, true, 0, -1, -1, true>(oq, a, max_partials, s);
+    }
+    a.d_none = 0; /* no such kernel for this request: d is read through its map as before */
 #if MG3D_LEG_DOWN_RJ == 4
     if (S == 3 && w.partials)
         return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s);
@@ -558,6 +585,14 @@ static int sweep_leg_up(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
     const mg3d_options oq = leg_options(o);
     const int max_partials = w.max_partials;
     a.c1 = 0;
+    if (a.d_none) {
+        constexpr int PFU = MG3D_LEG_ND_PF_UP, PFA = 3 - PFU;
+        if (o.v[MG3D_OPT_SWEEP_PF] == PFA)
+            return w.partials ? launch_sweep<4, 0, 4, 8, PFA, true, true, 0, 4, -1, true>(oq, a, max_partials, s)
+                              : launch_sweep<4, 0, 4, 8, PFA, true, true, 0, -1, -1, true>(oq, a, max_partials, s);
+        return w.partials ? launch_sweep<4, 0, 4, 8, PFU, true, true, 0, 4, -1, true>(oq, a, max_partials, s)
+                          : launch_sweep<4, 0, 4, 8, PFU, true, true, 0, -1, -1, true>(oq, a, max_partials, s);
+    }
 #if MG3D_LEG_UP_RJ == 4
     if (w.partials)
         return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s);
@@ -576,14 +611,21 @@ int k_sweep(const mg3d_options &o, const SweepLaunch &w, hipStream_t s)
     SweepArgs a;
     if (!fill_args(a, w))
         return 0;
+    int n;
     switch (w.kind) {
     case SWEEP_LEG_DOWN:
-        return sweep_leg_down(o, a, w, s);
+        n = sweep_leg_down(o, a, w, s);
+        break;
     case SWEEP_LEG_UP:
-        return sweep_leg_up(o, a, w, s);
+        n = sweep_leg_up(o, a, w, s);
+        break;
     default:
+        a.d_none = 0; /* only the legs have kernels without d */
         return sweep_passes(o, a, w, s);
     }
+    if (n >= 0 && a.d_none && w.d_none_taken)
+        ++*w.d_none_taken;
+    return n;
 }
 
 #ifdef MG3D_DEBUG_BLOCKTIMES

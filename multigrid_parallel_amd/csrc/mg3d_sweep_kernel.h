@@ -38,6 +38,9 @@ struct SweepArgs {
     /* the DZ instantiations: bit i set = every interior point of plane i of d is +0.0, the plane is not read (load_plane).
      * Only where the faces of d enter no stored value (a single-domain level with Dirichlet faces) */
     const unsigned *dz;
+    /* d is +0.0 at every interior point (the map is full): the launchers that have an ND instantiation take it, and that
+     * kernel looks at neither d nor dz.  A flag of its own, never inferred from the pointers */
+    int d_none;
 };
 
 /* RES: 0 = smoothing only, 1 = + residual (r store and/or norm), 2 = + residual AND full-weighting
@@ -173,7 +176,10 @@ __device__ unsigned long long g_dbg_bt[8][1024];
 #define MG3D_DEBUG_BT_COND (PRO && S == 4 && TAP == 4)
 #endif
 #endif
-template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false>
+/* ND: the launch's d is +0.0 at every interior point (SweepArgs::d_none).  No d window, no aging of it, nothing parked: the
+ * update is sixth * sum -- hSq is positive and finite, hSq * (+0.0) is +0.0 and sum - (+0.0) is sum, bit for bit, for every
+ * sum -- and the residual stays the SUBTRACTION 0. - invHsq * (...): 0 - (+0) is +0 where a negation would give -0. */
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false, bool ND = false>
 __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepArgs a)
 {
     using Sh = SweepShape<S, RES>;
@@ -183,6 +189,8 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
     constexpr bool NORM = RES == 1 || HASTAP; /* this shape accumulates diff^2 */
     static_assert(DP >= 0 && DP < ST, "at least one slot of the d window stays in registers");
     static_assert(TAPQ <= S, "tap behind the last pass");
+    static_assert(!ND || DP == 0, "no d window: nothing to park");
+    static_assert(!ND || !DZ, "no d window: no map to test");
     constexpr int KV = ST - DP; /* slots of the d window kept in VGPRs */
     constexpr int TJ = NW * RJ, VJ = TJ - 2 * HJ;
     static_assert(RJ % 2 == 0, "RJ must be even (row parity of a wave's first row)");
@@ -390,9 +398,11 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
 #pragma unroll
         for (int s = 0; s < STX; s++)
             last[rr][s][0] = last[rr][s][1] = 0.;
+        if constexpr (!ND) {
 #pragma unroll
-        for (int s = 0; s <= ST; s++)
-            dring[rr][s][0] = dring[rr][s][1] = 0.;
+            for (int s = 0; s <= ST; s++)
+                dring[rr][s][0] = dring[rr][s][1] = 0.;
+        }
         in_prev[rr][0] = in_prev[rr][1] = 0.;
         rkeep[rr] = 0.;
         cur_v[rr] = make_double2(0., 0.);
@@ -420,14 +430,21 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         const int iu = i < 0 ? 0 : (i >= g.ni ? g.ni - 1 : i), id = i - DLAG < 0 ? 0 : (i - DLAG >= g.ni ? g.ni - 1 : i - DLAG);
 #endif
         /* plane bases in bytes, uniform: one scalar 64-bit product per plane, not one re-materialised per row */
-        long long pbase = (long long)((unsigned long long)plane_bytes * (unsigned)iu), pbase_d = (long long)((unsigned long long)plane_bytes * (unsigned)id);
-        asm volatile("" : "+s"(pbase), "+s"(pbase_d));
+        long long pbase = (long long)((unsigned long long)plane_bytes * (unsigned)iu), pbase_d = ND ? 0ll : (long long)((unsigned long long)plane_bytes * (unsigned)id);
+        if constexpr (ND)
+            asm volatile("" : "+s"(pbase));
+        else
+            asm volatile("" : "+s"(pbase), "+s"(pbase_d));
         /* the plane's base ADDRESS opaque, not only its offset: otherwise `field + plane offset + row offset` is
          * re-associated into a loop-invariant 64-bit `field + row offset` per row and field (2 VGPRs each, kept across the
          * plane loop) plus a 64-bit vector add per access, instead of the saddr form `SGPR base + 32-bit lane offset` */
-        unsigned long long ub_ = reinterpret_cast<unsigned long long>(a.vin) + (unsigned long long)pbase,
-                           db_ = reinterpret_cast<unsigned long long>(a.d) + (unsigned long long)pbase_d;
-        asm volatile("" : "+s"(ub_), "+s"(db_));
+        unsigned long long ub_ = reinterpret_cast<unsigned long long>(a.vin) + (unsigned long long)pbase, db_ = 0ull;
+        if constexpr (ND) {
+            asm volatile("" : "+s"(ub_));
+        } else {
+            db_ = reinterpret_cast<unsigned long long>(a.d) + (unsigned long long)pbase_d;
+            asm volatile("" : "+s"(ub_), "+s"(db_));
+        }
         const gcbytes ubase = reinterpret_cast<gcbytes>(ub_), dbase = reinterpret_cast<gcbytes>(db_);
         /* vin == NULL: the input field is identically zero (a coarse level's initial guess, mg_3d.h:1258-1259) --
          * neither zeroed in memory beforehand nor read */
@@ -455,6 +472,11 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
          * cost the tapped down-leg a dword of scratch.  The map does not change while the kernel runs: read through the
          * constant address space, one scalar load a plane.  Planes 0 and ni - 1 (where the clamp puts the warm-up planes)
          * never have their bit */
+        if constexpr (ND) { /* no d: no load, no map test, dd stays untouched (nothing reads it) */
+            (void)dbase;
+            (void)dd;
+            return;
+        }
         bool have_d = true; /* uniform */
         if constexpr (DZ) {
             typedef const unsigned __attribute__((address_space(4))) *cwords;
@@ -599,20 +621,25 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
 #pragma unroll
             for (int rr = 0; rr < RJ; rr++) {
                 cur_v[rr] = nxt_v[PAR][rr];
-                dring[rr][0][0] = nxt_d[PAR][rr].x;
-                dring[rr][0][1] = nxt_d[PAR][rr].y;
+                if constexpr (!ND) {
+                    dring[rr][0][0] = nxt_d[PAR][rr].x;
+                    dring[rr][0][1] = nxt_d[PAR][rr].y;
+                }
             }
             load_plane(i + PF, nxt_v[PAR], nxt_d[PAR]);
         } else {
 #pragma unroll
             for (int rr = 0; rr < RJ; rr++) {
                 cur_v[rr] = nxt_v[0][rr];
-                dring[rr][0][0] = nxt_d[0][rr].x;
-                dring[rr][0][1] = nxt_d[0][rr].y;
+                if constexpr (!ND) {
+                    dring[rr][0][0] = nxt_d[0][rr].x;
+                    dring[rr][0][1] = nxt_d[0][rr].y;
+                }
 #pragma unroll
                 for (int f = 0; f + 1 < PF; f++) {
                     nxt_v[f][rr] = nxt_v[f + 1][rr];
-                    nxt_d[f][rr] = nxt_d[f + 1][rr];
+                    if constexpr (!ND)
+                        nxt_d[f][rr] = nxt_d[f + 1][rr];
                 }
             }
             load_plane(i + PF, nxt_v[PF - 1], nxt_d[PF - 1]);
@@ -779,7 +806,9 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                             kp = lane_from_right(last[rr][s - 1][0]);
                         }
                         double dd; /* DLAG: slot 0 = plane i - 1 (load_plane) */
-                        if constexpr (DP > 0) {
+                        if constexpr (ND) {
+                            dd = 0.; /* the residuals below stay `0. - invHsq * (...)`: a subtraction from +0.0 */
+                        } else if constexpr (DP > 0) {
                             if (s - 1 < KV) {
                                 dd = dring[rr][s - 1][X];
                             } else {
@@ -805,7 +834,11 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         #ifdef MG3D_EXPERIMENT_DROP_FLOPS /* timing experiment only (wrong results): is the step bound by its fp64 operations? */
                             const double val = sum - dd;
         #else
-                            const double val = a.sixth * (sum - a.hSq * dd); /* mg_3d.h:438-443 */
+                            double val;
+                            if constexpr (ND)
+                                val = a.sixth * sum; /* sum - hSq * (+0.0) is sum, bit for bit */
+                            else
+                                val = a.sixth * (sum - a.hSq * dd); /* mg_3d.h:438-443 */
         #endif
                             if constexpr (RES == 2) /* (the restricting shapes sit at the register limit: the step-wide lane masks push them into scratch) */
                                 nwG[g][s] = LM(updu ? (X ? LM_UPD1 : LM_UPD0) : 0) ? val : center;
@@ -911,13 +944,15 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
             }
             ring = ring + 1 == DP ? 0 : ring + 1;
         }
+        if constexpr (!ND) {
 #pragma unroll
-        for (int rr = 0; rr < RJ; rr++)
+            for (int rr = 0; rr < RJ; rr++)
 #pragma unroll
-            for (int s = (DP > 0 ? KV - 1 : ST - DLAG); s >= 1; s--) {
-                dring[rr][s][0] = dring[rr][s - 1][0];
-                dring[rr][s][1] = dring[rr][s - 1][1];
-            }
+                for (int s = (DP > 0 ? KV - 1 : ST - DLAG); s >= 1; s--) {
+                    dring[rr][s][0] = dring[rr][s - 1][0];
+                    dring[rr][s][1] = dring[rr][s - 1][1];
+                }
+        }
         /* publish this wave's edge rows for the next step */
 #pragma unroll
         for (int s = 0; s < ST; s++) {
