@@ -1018,11 +1018,43 @@ struct RestrictTarget { /* where a rank's restricted residual goes: coarse geome
     double *dc;
     int lo, hi;
 };
+static void restrict_into(SweepLaunch &w, const RestrictTarget &t)
+{
+    w.gc = t.gc;
+    w.dc = t.dc;
+    w.ic_lo = t.lo;
+    w.ic_hi = t.hi;
+}
 
-/* One smoothing stage on distributed level l for every local rank: iters x two colour passes, optional
- * residual (want_res 2: r stored or restricted on the fly into tgt[], 1: norm only, over OWNED planes, into
- * the rank's coarse->sumsq[0]).  Same launch policy as the single-domain path.  On entry the halos of u and
- * d on this level are exact (H planes); nothing is exchanged in here. */
+struct ProlongSource { /* per local rank: the coarse correction an up-leg folds into its first launch */
+    const Geom *gc;
+    const double *ec;
+};
+static void prolong_from(SweepLaunch &w, const ProlongSource &p)
+{
+    w.gce = p.gc;
+    w.ec = p.ec;
+}
+
+/* What one cycle does, settled before its first launch (dist_begin_cycle): the slab counterpart of mg3d_ctx.hip's CycleState.
+ * What a cycle leaves for the next one (carried, legs_pending, red_tail) stays on the handle. */
+struct SlabCycle {
+    int slot;
+    bool carry_out, legs_out; /* another cycle follows, and this one ends ahead into it (dist_enqueue_vcycle) */
+    bool carry_in, legs_in;   /* the previous cycle did */
+    bool red_in;              /* behind a finished cycle of an earlier call (red_tail): the one-launch down-leg without a norm half */
+    bool can_legs, can_carry, keep_r;
+};
+
+struct Window {
+    int lo, hi;
+};
+/* the owned planes of a slab level and m more on either side, as far as the slab has them */
+static Window slab_window(const SlabLevel &sl, int m)
+{
+    return Window{sl.own_lo - m < 0 ? 0 : sl.own_lo - m, sl.own_hi + m > sl.lv.g.ni ? sl.lv.g.ni : sl.own_hi + m};
+}
+
 /* The launches of a smoothing stage on distributed level l: the single domain's list (mg3d_stage_plan) with the slab path's
  * two differences as inputs -- it has no one-launch form of the whole down-leg (leg4_form), and the norm is wanted exactly
  * where want_res == 1 (the pre-smoothing norm is dropped, :1294).  has_coarse: a list of restriction targets was passed
@@ -1034,13 +1066,13 @@ static StagePlan dist_stage_plan(mg3d_dist *D, int l, int post, int want_res, bo
                            StageAsk{g.N, g.nj, post != 0, D->nu, want_res, has_coarse, want_res == 1, pro_offered, /* leg4_form */ false});
 }
 
-/* a sweep launch on rank ri's slab of level l, u -> alt; the norm counts the owned planes */
+/* a sweep launch on rank ri's slab of level l, u -> alt, over the owned planes; the norm counts the owned planes */
 static SweepLaunch slab_sweep(mg3d_dist *D, size_t ri, int l)
 {
     SlabLevel &sl = SL(D, D->rs[ri], l);
     SweepLaunch w = mg3d_level_sweep(D->rs[ri].coarse, sl.lv);
-    w.acc_lo = sl.own_lo;
-    w.acc_hi = sl.own_hi;
+    w.i_lo = w.acc_lo = sl.own_lo;
+    w.i_hi = w.acc_hi = sl.own_hi;
     return w;
 }
 
@@ -1050,158 +1082,149 @@ static void swap_u_all(mg3d_dist *D, int l) /* every local rank's u and alt of l
         swap_u(SL(D, R, l).lv);
 }
 
-struct ProlongSource { /* per local rank: the coarse correction a split up-leg folds into its first launch */
-    const Geom *gc;
-    const double *ec;
-};
-
-static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const RestrictTarget *tgt,
-                        bool zero_in = false /* u is identically zero: the first launch does not read it */,
-                        bool refresh_u = false /* start the exchange of the u halos (planes 2..H) as soon as u is final */,
-                        const ProlongSource *pro = nullptr,
-                        bool tap = false /* carried cycle: the stage's last launch is four passes with the norm tapped after
-                                            the second -- the next cycle's first pre-smoothing passes ride on it */)
+/* The launch that makes u of the finest level final for this cycle, over the owned planes +- margin, and the HALO_U_NEXT
+ * exchange behind it.  Edge windows first (round 4): the first and last E output planes -- the window's margin + the planes
+ * the exchange skips + those it sends -- go first, as ONE launch of two chunks per rank, u -> alt; the buffers change roles
+ * and the exchange runs on the communication stream underneath the second launch, alt -> u, which makes the interior.  Same
+ * bits: the chunking of a sweep launch is a work distribution only.  Without a communication stream, or where some rank's
+ * window is shorter than 2E + 2 planes (thin slabs): one launch per rank, the swap, the exchange.
+ * make(ri, split, n_edge) describes rank ri's launch but for its window: n_edge < 0 the first (or only) one, otherwise the
+ * interior behind an edge launch that wrote n_edge partial sums.  done(ri, n_first, n_in) follows the rank's last launch
+ * (n_in 0: not split): where the sums go and how they are folded is the callers', and the norm's bits depend on it. */
+template <class Make, class Done>
+static int edge_first(mg3d_dist *D, int l, int margin, int E, const char *what, Make make, Done done)
 {
-    hipStream_t s = D->stream;
-    const int c1 = post ? 0 : 1;
+    bool split = D->overlap && D->P > 1;
+    std::vector<Window> win;
+    for (auto &R : D->rs) {
+        win.push_back(slab_window(SL(D, R, l), margin));
+        split = split && win.back().hi - win.back().lo >= 2 * E + 2;
+    }
+    std::vector<int> n_first(D->rs.size());
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SweepLaunch w = make(ri, split, -1);
+        w.i_lo = win[ri].lo;
+        w.i_hi = win[ri].hi;
+        w.edge = split ? E : 0;
+        n_first[ri] = k_sweep(D->rs[ri].coarse->opt, w, D->stream);
+        if (n_first[ri] <= 0) /* nothing was launched: no buffer swap, no fold */
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for %s%s on level %d", split ? "the edge windows of " : "", what, l);
+        if (!split)
+            done(ri, n_first[ri], 0);
+    }
+    swap_u_all(D, l); /* the exchange sends from (and lands in) the NEW buffer */
+    CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
+    for (size_t ri = 0; split && ri < D->rs.size(); ri++) {
+        Level &lv = SL(D, D->rs[ri], l).lv;
+        SweepLaunch w = make(ri, split, n_first[ri]);
+        w.vin = lv.alt;
+        w.vout = lv.f[MG3D_U];
+        w.i_lo = win[ri].lo + E;
+        w.i_hi = win[ri].hi - E;
+        const int n_in = k_sweep(D->rs[ri].coarse->opt, w, D->stream);
+        if (n_in <= 0)
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior window of %s on level %d", what, l);
+        done(ri, n_first[ri], n_in);
+    }
+    return MG3D_OK;
+}
+
+/* ... where it ends with the top level's norm: the partial sums of a split launch go to the two halves of the rank's partials
+ * and are folded edges first.  (Never with the prolongation: mg3d_stage_plan puts that on a launch before the norm's.) */
+static int edge_first_norm(mg3d_dist *D, int l, int margin, int E, SweepKind kind, int S, int c1)
+{
+    auto make = [&](size_t ri, bool split, int n_edge) {
+        SweepLaunch w = slab_sweep(D, ri, l);
+        w.kind = kind;
+        w.S = S;
+        w.c1 = c1;
+        w.partials = D->rs[ri].coarse->partials + (n_edge < 0 ? 0 : MG3D_MAX_PARTIALS / 2);
+        w.max_partials = split ? MG3D_MAX_PARTIALS / 2 : MG3D_MAX_PARTIALS;
+        return w;
+    };
+    auto fold = [&](size_t ri, int n_first, int n_in) {
+        mg3d_ctx *cx = D->rs[ri].coarse;
+        if (n_in)
+            k_fold2(cx->partials, n_first, cx->partials + MG3D_MAX_PARTIALS / 2, n_in, cx->sumsq, D->stream);
+        else
+            k_fold(cx->partials, n_first, cx->sumsq, D->stream);
+    };
+    return edge_first(D, l, margin, E, kind == SWEEP_TAP ? "four passes + norm tap" : "colour passes + norm", make, fold);
+}
+
+/* One launch of a stage's list on distributed level l for every local rank, then the buffer swap (as mg3d_ctx.hip's
+ * enqueue_stage_step).  zero_in: u is identically zero and not read; tgt / pro: where st.rst restricts to, st.pro prolongs from. */
+static int slab_stage_step(mg3d_dist *D, int l, int post, int want_res, const StageStep &st, bool zero_in, const RestrictTarget *tgt,
+                           const ProlongSource *pro)
+{
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SlabLevel &sl = SL(D, D->rs[ri], l);
+        mg3d_ctx *cx = D->rs[ri].coarse;
+        const bool rst = st.rst && tgt[ri].dc != nullptr;
+        /* output planes of a smoothing launch: the owned planes plus what the next consumer reads beyond them -- the
+         * residual/restriction behind a pre-smoother needs u on owned +-2, the top-level norm owned +-1; the remaining halo
+         * planes are refreshed by an exchange before anything reads them again.  Only the LAST smoothing launch of the stage
+         * may be trimmed: an earlier one feeds the next launch's whole dependence cone. */
+        Window win = st.last ? slab_window(sl, post ? 1 : 2) : Window{0, sl.lv.g.ni};
+        /* a pure residual launch (S == 0) only has to produce what is consumed: the norm and the on-the-fly restriction need
+         * the owned planes (their neighbours come from the pipeline's warm-up / drain), a stored r one more on either side */
+        if (st.S == 0)
+            win = slab_window(sl, (want_res == 2 && !rst) ? 1 : 0);
+        SweepLaunch w = slab_sweep(D, ri, l);
+        w.kind = st.res ? SWEEP_PASSES_RES : SWEEP_PASSES;
+        w.S = st.S;
+        w.c1 = post ? 0 : 1;
+        if (zero_in)
+            w.vin = nullptr;
+        if (st.res && want_res == 2 && !rst)
+            w.r = sl.lv.f[MG3D_R];
+        if (st.res && want_res == 1) /* the pre-smoothing norm is dropped (:1294) */
+            w.partials = cx->partials;
+        if (rst)
+            restrict_into(w, tgt[ri]);
+        if (st.pro)
+            prolong_from(w, pro[ri]);
+        w.i_lo = win.lo;
+        w.i_hi = win.hi;
+        const int np = k_sweep(cx->opt, w, D->stream);
+        if (np < 0) /* nothing was launched: no buffer swap, no fold */
+            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for %d colour passes%s on level %d", st.S, st.res ? " + residual" : "", l);
+        if (st.res && want_res == 1)
+            k_fold(cx->partials, np, cx->sumsq, D->stream);
+    }
+    if (st.S > 0)
+        swap_u_all(D, l);
+    return MG3D_OK;
+}
+
+/* One smoothing stage on distributed level l for every local rank: iters x two colour passes, optional residual (want_res 2:
+ * r stored or restricted on the fly into tgt[], 1: norm only, over OWNED planes, into the rank's coarse->sumsq[0]).  Same launch
+ * policy as the single-domain path.  On entry the halos of u and d on this level are exact (H planes).  With want_res 1 (the
+ * top level's post-smoother) the exchange of the u halos for the next cycle, planes 2..H, starts as soon as u is final: with
+ * the last smoothing launch where that takes the norm (edge_first, E = the window's margin 1 + the plane skipped + the H - 1
+ * sent), else before the pure residual launch (it reads owned +-1 only).
+ * tgt: where the residual is restricted to (keep_r: a list of empty targets, see dist_stage_plan); pro: the correction the
+ * first launch may fold in; zero_in (down-leg): u is identically zero, the first launch does not read it. */
+static int stage_smooth(mg3d_dist *D, int l, int post, int want_res, const RestrictTarget *tgt, const ProlongSource *pro = nullptr,
+                        bool zero_in = false)
+{
     const StagePlan plan = dist_stage_plan(D, l, post, want_res, tgt != nullptr, pro != nullptr);
     for (int k = 0; mg3d_stage_launch(plan, k); k++) {
         const StageStep &st = *mg3d_stage_launch(plan, k);
-        const bool first = k == 0;
-        const int S = st.S;
-        const bool last = st.last, res = st.res;
-        if (S == 0 && refresh_u) { /* u is final; the pure residual launch below reads owned +-1 only */
+        if (want_res == 1 && st.S == 0)
             CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
-            refresh_u = false;
-        }
-        /* Edge windows first (round 4).  The stage's last launch makes the planes the next cycle's halo exchange sends:
-         * the first and last E output planes go first, as ONE launch of two chunks per rank; the exchange is issued behind
-         * it on the communication stream and runs underneath the launch that makes the interior -- instead of sitting
-         * between this launch and the next cycle's first one.  E = the window's margin beyond the owned planes + the planes
-         * the exchange skips + those it sends (carried: 0 + 0 + 3; plain: 1 + 1 + (H - 1)).  Same bits: the chunking of a
-         * sweep launch is a work distribution only, and the norm's per-block partial sums are folded from both launches. */
-        if (last && refresh_u && S > 0 && D->overlap && D->P > 1 && (res || tap) && want_res == 1) {
-            const int margin = tap ? 0 : 1, E = margin + (tap ? 0 : 1) + (tap ? 3 : D->H - 1);
-            std::vector<int> wlo(D->rs.size()), whi(D->rs.size()), npa(D->rs.size());
-            bool ok = true;
-            for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                SlabLevel &sl = SL(D, D->rs[ri], l);
-                wlo[ri] = sl.own_lo - margin < 0 ? 0 : sl.own_lo - margin;
-                whi[ri] = sl.own_hi + margin > sl.lv.g.ni ? sl.lv.g.ni : sl.own_hi + margin;
-                ok = ok && whi[ri] - wlo[ri] >= 2 * E + 2;
-            }
-            if (ok) {
-                auto launch = [&](size_t ri, const double *vin, double *vout, double *part, int lo, int hi, int edge) -> int {
-                    SweepLaunch w = slab_sweep(D, ri, l);
-                    w.vin = vin;
-                    w.vout = vout;
-                    w.kind = tap ? SWEEP_TAP : SWEEP_PASSES_RES;
-                    w.S = S;
-                    w.c1 = c1;
-                    w.partials = part;
-                    w.max_partials = MG3D_MAX_PARTIALS / 2;
-                    if (st.pro) {
-                        w.gce = pro[ri].gc;
-                        w.ec = pro[ri].ec;
-                    }
-                    w.i_lo = lo;
-                    w.i_hi = hi;
-                    w.edge = edge;
-                    return k_sweep(D->rs[ri].coarse->opt, w, s);
-                };
-                for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                    Level &lv = SL(D, D->rs[ri], l).lv;
-                    npa[ri] = launch(ri, lv.f[MG3D_U], lv.alt, D->rs[ri].coarse->partials, wlo[ri], whi[ri], E);
-                    if (npa[ri] < 0)
-                        return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the edge windows on level %d", l);
-                }
-                swap_u_all(D, l); /* the exchange sends from (and lands in) the NEW buffer */
-                CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
-                refresh_u = false;
-                for (size_t ri = 0; ri < D->rs.size(); ri++) {
-                    Level &lv = SL(D, D->rs[ri], l).lv;
-                    mg3d_ctx *cx = D->rs[ri].coarse;
-                    const int npb = launch(ri, lv.alt, lv.f[MG3D_U], cx->partials + MG3D_MAX_PARTIALS / 2, wlo[ri] + E, whi[ri] - E, 0);
-                    if (npb < 0)
-                        return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior window on level %d", l);
-                    k_fold2(cx->partials, npa[ri], cx->partials + MG3D_MAX_PARTIALS / 2, npb, cx->sumsq, s);
-                }
-                continue;
-            }
-        }
-        for (size_t ri = 0; ri < D->rs.size(); ri++) {
-            RankState &R = D->rs[ri];
-            SlabLevel &sl = SL(D, R, l);
-            Level &lv = sl.lv;
-            mg3d_ctx *cx = R.coarse;
-            const bool rst = st.rst && tgt[ri].dc != nullptr;
-            /* output planes of a smoothing launch: the owned planes plus what the next consumer reads beyond
-             * them -- the residual/restriction behind a pre-smoother needs u on owned +-2, the top-level norm
-             * owned +-1; the remaining halo planes are refreshed by an exchange before anything reads them
-             * again.  Only the LAST smoothing launch of the stage may be trimmed: an earlier one feeds the next
-             * launch's whole dependence cone. */
-            const int margin = post ? 1 : 2;
-            const bool trim = last;
-            int w_lo = (!trim || sl.own_lo - margin < 0) ? 0 : sl.own_lo - margin;
-            int w_hi = (!trim || sl.own_hi + margin > lv.g.ni) ? lv.g.ni : sl.own_hi + margin;
-            /* a pure residual launch (S == 0) only has to produce what is consumed: the norm and the on-the-fly
-             * restriction need the owned planes (their neighbours come from the pipeline's warm-up / drain), a
-             * stored r one more plane on either side */
-            if (S == 0) {
-                const int pad = (want_res == 2 && !rst) ? 1 : 0;
-                w_lo = sl.own_lo - pad < 0 ? 0 : sl.own_lo - pad;
-                w_hi = sl.own_hi + pad > lv.g.ni ? lv.g.ni : sl.own_hi + pad;
-            }
-            if (tap && last) {
-                /* output: the owned planes only -- the four passes use up the halo planes the first launch has left, and
-                 * the next launch (one pass + residual + restriction) gets three fresh ones by exchange first */
-                SweepLaunch w = slab_sweep(D, ri, l);
-                w.kind = SWEEP_TAP;
-                w.c1 = c1;
-                w.partials = cx->partials;
-                w.i_lo = sl.own_lo;
-                w.i_hi = sl.own_hi;
-                const int np = k_sweep(cx->opt, w, s);
-                if (np < 0)
-                    return fail(MG3D_ERR_STATE, "slab sweep: no kernel for four passes + norm tap on level %d", l);
-                k_fold(cx->partials, np, cx->sumsq, s);
-                continue;
-            }
-            SweepLaunch w = slab_sweep(D, ri, l);
-            w.kind = res ? SWEEP_PASSES_RES : SWEEP_PASSES;
-            w.S = S;
-            w.c1 = c1;
-            if (zero_in && first)
-                w.vin = nullptr;
-            if (res && want_res == 2 && !rst)
-                w.r = lv.f[MG3D_R];
-            if (res && want_res == 1) /* the pre-smoothing norm is dropped (:1294) */
-                w.partials = cx->partials;
-            if (rst) {
-                w.gc = tgt[ri].gc;
-                w.dc = tgt[ri].dc;
-                w.ic_lo = tgt[ri].lo;
-                w.ic_hi = tgt[ri].hi;
-            }
-            if (st.pro) {
-                w.gce = pro[ri].gc;
-                w.ec = pro[ri].ec;
-            }
-            w.i_lo = w_lo;
-            w.i_hi = w_hi;
-            const int np = k_sweep(cx->opt, w, s);
-            if (np < 0) /* nothing was launched: no buffer swap, no fold */
-                return fail(MG3D_ERR_STATE, "slab sweep: no kernel for %d colour passes%s on level %d", S,
-                            res ? " + residual" : "", l);
-            if (res && want_res == 1)
-                k_fold(cx->partials, np, cx->sumsq, s);
-        }
-        if (S > 0)
-            swap_u_all(D, l);
+        if (want_res == 1 && st.S > 0 && st.res)
+            CHK(edge_first_norm(D, l, 1, D->H + 1, SWEEP_PASSES_RES, st.S, post ? 0 : 1));
+        else
+            CHK(slab_stage_step(D, l, post, want_res, st, zero_in && k == 0, tgt, pro));
     }
-    if (refresh_u) /* the last launch smoothed and took the norm in one go */
-        CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
     return MG3D_OK;
+}
+
+/* the variable-coefficient operator on a rank's slab of a level (slabs: no boundary word, no mask) */
+static LevelOperator slab_operator(const RankState &R, const SlabLevel &sl)
+{
+    return LevelOperator{mg3d_level_op(sl.lv.h, R.coarse->sigma), R.coarse->sigma, sl.eps, 0, nullptr};
 }
 
 /* One smoothing stage of the variable-coefficient operator (mg3d_kernels.hip) on distributed level l for every local rank: the
@@ -1219,7 +1242,7 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
         SlabLevel &sl = SL(D, R, l);
         Level &lv = sl.lv;
         mg3d_ctx *cx = R.coarse;
-        const LevelOperator A = {mg3d_level_op(lv.h, cx->sigma), cx->sigma, sl.eps, 0, nullptr}; /* (slabs: no boundary word, no mask) */
+        const LevelOperator A = slab_operator(R, sl);
         for (int t = 1; t <= S; t++) { /* :1282 / :1341 */
             const int w = margin + S - t;
             k_smooth_color(lv.g, lv.f[MG3D_U], lv.f[MG3D_D], A, c1 ^ ((t - 1) & 1), s, sl.own_lo - w, sl.own_hi + w);
@@ -1233,11 +1256,8 @@ static int dist_coef_smooth(mg3d_dist *D, int l, int post, int want_res)
     CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
     for (auto &R : D->rs) { /* :1354 */
         SlabLevel &sl = SL(D, R, l);
-        Level &lv = sl.lv;
-        mg3d_ctx *cx = R.coarse;
-        const LevelOperator A = {mg3d_level_op(lv.h, cx->sigma), cx->sigma, sl.eps, 0, nullptr}; /* (slabs: no boundary word, no mask) */
-        k_residual(lv.g, lv.f[MG3D_U], lv.f[MG3D_D], A, nullptr, cx->partials, cx->sumsq, s, sl.own_lo, sl.own_hi, sl.own_lo,
-                   sl.own_hi);
+        k_residual(sl.lv.g, sl.lv.f[MG3D_U], sl.lv.f[MG3D_D], slab_operator(R, sl), nullptr, R.coarse->partials, R.coarse->sumsq, s,
+                   sl.own_lo, sl.own_hi, sl.own_lo, sl.own_hi);
     }
     return MG3D_OK;
 }
@@ -1278,28 +1298,21 @@ static bool dist_can_carry(mg3d_dist *D)
  * residual norm, whose red half the one-launch up-leg left in partials[0 .. legs_npa): folded and reduced here. */
 static int dist_down_leg_ahead(mg3d_dist *D, int l, const RestrictTarget *tgt, bool red_in, int slot)
 {
-    hipStream_t s = D->stream;
     for (size_t ri = 0; ri < D->rs.size(); ri++) {
         RankState &R = D->rs[ri];
         SlabLevel &sl = SL(D, R, l);
         mg3d_ctx *cx = R.coarse;
-        double *part_b = red_in ? nullptr : cx->partials + MG3D_MAX_PARTIALS / 2;
         SweepLaunch w = slab_sweep(D, ri, l);
         w.kind = SWEEP_LEG_DOWN;
         w.S = 3;
-        w.partials = part_b;
+        w.partials = red_in ? nullptr : cx->partials + MG3D_MAX_PARTIALS / 2;
         w.max_partials = MG3D_MAX_PARTIALS / 2;
-        w.gc = tgt[ri].gc;
-        w.dc = tgt[ri].dc;
-        w.ic_lo = tgt[ri].lo;
-        w.ic_hi = tgt[ri].hi;
-        w.i_lo = sl.own_lo;
-        w.i_hi = sl.own_hi;
-        const int npb = k_sweep(cx->opt, w, s);
+        restrict_into(w, tgt[ri]);
+        const int npb = k_sweep(cx->opt, w, D->stream);
         if (npb <= 0)
             return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch down-leg on level %d", l);
         if (!red_in)
-            k_fold2(cx->partials, R.legs_npa, part_b, npb, cx->sumsq, s);
+            k_fold2(cx->partials, R.legs_npa, w.partials, npb, cx->sumsq, D->stream);
         swap_u(sl.lv);
     }
     if (!red_in)
@@ -1318,12 +1331,7 @@ static int dist_down_leg_carried(mg3d_dist *D, int l, const RestrictTarget *tgt)
         w.kind = SWEEP_PASSES_RES;
         w.S = 1;
         w.c1 = 0;
-        w.gc = tgt[ri].gc;
-        w.dc = tgt[ri].dc;
-        w.ic_lo = tgt[ri].lo;
-        w.ic_hi = tgt[ri].hi;
-        w.i_lo = sl.own_lo;
-        w.i_hi = sl.own_hi;
+        restrict_into(w, tgt[ri]);
         if (k_sweep(D->rs[ri].coarse->opt, w, D->stream) < 0)
             return fail(MG3D_ERR_STATE, "slab sweep: no kernel for one pass + residual + restriction on level %d", l);
         swap_u(sl.lv);
@@ -1332,51 +1340,37 @@ static int dist_down_leg_carried(mg3d_dist *D, int l, const RestrictTarget *tgt)
 }
 
 /* Up-leg of the finest level as ONE launch: prolongation + four passes over the owned planes (it uses up four of the H halo
- * planes of u and of the correction), the red half of the norm from the last pass's own sums.  With a communication stream the
- * first and last five planes -- what the exchange for the next down-leg sends -- are made first, as one launch of two
- * chunks per rank; the exchange then runs underneath the launch that makes the interior. */
+ * planes of u and of the correction), the red half of the norm from the last pass's own sums.  The first and last five planes
+ * are what the exchange for the next down-leg sends (edge_first).  The sums of a split launch lie one behind the other in
+ * partials[0 .. legs_npa), unfolded: the next cycle's down-leg folds them with its black half (dist_down_leg_ahead). */
 static int dist_up_leg_legs(mg3d_dist *D, int l, const ProlongSource *pro)
 {
-    const int E = 5;
-    bool edge_first = D->overlap && D->P > 1;
-    for (auto &R : D->rs)
-        edge_first = edge_first && SL(D, R, l).own_hi - SL(D, R, l).own_lo >= 2 * E + 2;
-    auto up = [&](size_t ri, const double *vin, double *vout, double *part, int maxp, int lo, int hi, int edge) -> int {
+    auto up = [&](size_t ri, bool, int n_edge) {
         SweepLaunch w = slab_sweep(D, ri, l);
         w.kind = SWEEP_LEG_UP;
-        w.vin = vin;
-        w.vout = vout;
-        w.partials = part;
-        w.max_partials = maxp;
-        w.gce = pro[ri].gc;
-        w.ec = pro[ri].ec;
-        w.i_lo = lo;
-        w.i_hi = hi;
-        w.edge = edge;
-        return k_sweep(D->rs[ri].coarse->opt, w, D->stream);
+        w.partials = D->rs[ri].coarse->partials + (n_edge < 0 ? 0 : n_edge);
+        w.max_partials = n_edge < 0 ? MG3D_MAX_PARTIALS / 4 : MG3D_MAX_PARTIALS / 2 - n_edge;
+        prolong_from(w, pro[ri]);
+        return w;
     };
-    std::vector<int> n1(D->rs.size(), 0);
-    for (size_t ri = 0; ri < D->rs.size(); ri++) {
-        SlabLevel &sl = SL(D, D->rs[ri], l);
-        n1[ri] = up(ri, sl.lv.f[MG3D_U], sl.lv.alt, D->rs[ri].coarse->partials, MG3D_MAX_PARTIALS / 4, sl.own_lo, sl.own_hi, edge_first ? E : 0);
-        if (n1[ri] <= 0)
-            return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the one-launch up-leg on level %d", l);
-    }
-    swap_u_all(D, l); /* the exchange sends from (and lands in) the NEW buffer */
-    CHK(start_u_exchange(D, MG3D_XK_HALO_U_NEXT, l));
-    for (size_t ri = 0; ri < D->rs.size(); ri++) {
-        SlabLevel &sl = SL(D, D->rs[ri], l);
-        int n2 = 0;
-        if (edge_first) {
-            n2 = up(ri, sl.lv.alt, sl.lv.f[MG3D_U], D->rs[ri].coarse->partials + n1[ri], MG3D_MAX_PARTIALS / 2 - n1[ri], sl.own_lo + E,
-                    sl.own_hi - E, 0);
-            if (n2 <= 0)
-                return fail(MG3D_ERR_STATE, "slab sweep: no kernel for the interior of the one-launch up-leg on level %d", l);
-        }
-        D->rs[ri].legs_npa = n1[ri] + n2;
-    }
+    CHK(edge_first(D, l, 0, 5, "the one-launch up-leg", up, [&](size_t ri, int n1, int n2) { D->rs[ri].legs_npa = n1 + n2; }));
     D->legs_pending = true;
     D->n_legs++;
+    return MG3D_OK;
+}
+
+/* Up-leg of the finest level of a cycle that carries into the next one (as mg3d_ctx.hip's up_leg_carried): the first launch of
+ * the split post-smoothing stage -- prolongation + two passes, on every local plane -- then four passes with the norm tapped
+ * after the second: black, red (:1341, second half) <norm, :1354> black, red (:1282 of the next cycle, its first red pass
+ * being the identity).  The tap launch makes the owned planes only: its passes use up the halo planes the first launch has
+ * left, and dist_down_leg_carried gets three fresh ones by exchange first (E = 0 + 0 + 3). */
+static int dist_up_leg_carried(mg3d_dist *D, int l, const ProlongSource *pro)
+{
+    const StagePlan split = dist_stage_plan(D, l, 1, 1, false, true);
+    CHK(slab_stage_step(D, l, 1, 1, split.step[0], false, nullptr, pro));
+    CHK(edge_first_norm(D, l, 0, 3, SWEEP_TAP, 4, 0));
+    D->carried = true;
+    D->n_carried++;
     return MG3D_OK;
 }
 
@@ -1396,149 +1390,159 @@ static void restrict_targets(mg3d_dist *D, int l, RestrictTarget *tgt)
     for (size_t ri = 0; ri < D->rs.size(); ri++) {
         RankState &R = D->rs[ri];
         SlabLevel &sl = SL(D, R, l);
-        RestrictTarget &t = tgt[ri];
         if (l - 1 >= D->ld) {
             SlabLevel &sc = SL(D, R, l - 1);
-            t.gc = &sc.lv.g;
-            t.dc = sc.lv.f[MG3D_D];
-            t.lo = sc.own_lo;
-            t.hi = sc.own_hi;
+            tgt[ri] = RestrictTarget{&sc.lv.g, sc.lv.f[MG3D_D], sc.own_lo, sc.own_hi};
         } else {
             Level &lc = R.coarse->lv[D->ld - 1];
-            t.gc = &lc.g;
-            t.dc = lc.f[MG3D_D];
-            t.lo = R.rank == 0 ? 0 : sl.glo / 2;
-            t.hi = R.rank == D->P - 1 ? lc.g.N : sl.ghi / 2;
+            tgt[ri] = RestrictTarget{&lc.g, lc.f[MG3D_D], R.rank == 0 ? 0 : sl.glo / 2, R.rank == D->P - 1 ? lc.g.N : sl.ghi / 2};
         }
     }
 }
 
-/* carry_out: another cycle of this call follows (it may be enqueued ahead into); legs_out: it follows in the same batch of norm
- * slots (its down-leg completes this cycle's norm into slot `slot`, which the batch then reads back) */
-static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, bool legs_out = false)
+/* Settles what the cycle is before its first launch: which run-ahead state it continues, which it may leave, and the
+ * exchange plan that goes with the two.  carry_out / legs_out as asked for by dist_enqueue_vcycle. */
+static int dist_begin_cycle(mg3d_dist *D, SlabCycle &c, int slot, bool carry_out, bool legs_out)
 {
-    hipStream_t s = D->stream;
-    const int L = D->L, ld = D->ld;
     D->phase = 0;
-    const bool can_legs = dist_can_legs(D), legs_in = D->legs_pending;
-    const bool can = !can_legs && dist_can_carry(D), carry_in = D->carried;
-    if ((carry_in && !can) || (legs_in && (!can_legs || slot < 1))) {
+    c.slot = slot;
+    c.can_legs = dist_can_legs(D);
+    c.legs_in = D->legs_pending;
+    c.can_carry = !c.can_legs && dist_can_carry(D);
+    c.carry_in = D->carried;
+    if ((c.carry_in && !c.can_carry) || (c.legs_in && (!c.can_legs || slot < 1))) {
         D->carried = false;
         D->legs_pending = false;
         return fail(MG3D_ERR_STATE, "mg3d_dist_vcycles: carried state met a cycle that cannot continue it");
     }
-    carry_out = carry_out && can;
-    legs_out = legs_out && can_legs;
-    D->cur = legs_out ? &D->plans_legs[legs_in ? 1 : 0] : legs_in ? &D->plans_legs[2] : carry_out ? &D->plans_carry : &D->plans;
+    c.carry_out = carry_out && c.can_carry;
+    c.legs_out = legs_out && c.can_legs;
+    D->cur = c.legs_out ? &D->plans_legs[c.legs_in ? 1 : 0] : c.legs_in ? &D->plans_legs[2] : c.carry_out ? &D->plans_carry : &D->plans;
     D->carried = false;
     D->legs_pending = false;
-    /* behind a finished cycle of an earlier call (red_tail): the one-launch down-leg without a norm half */
-    const bool red_in = !legs_in && !carry_in && can_legs && D->red_tail;
+    c.red_in = !c.legs_in && !c.carry_in && c.can_legs && D->red_tail;
     D->red_tail = false;
-    DistScope cycle_timer(D, 0, s);
+    c.keep_r = D->rs[0].coarse->keep_r;
+    return MG3D_OK;
+}
+
+/* Down-leg of distributed level l.  On entry the halos of d are exact (upload / the exchange behind the restriction above)
+ * and those of u refreshed since it last changed (the finest level: upload, or the exchange the previous cycle ended with; below
+ * it u is the zero guess, mg_3d.h:1258, folded into the first sweep launch).  tgt is filled here; none: a list of empty targets. */
+static int dist_down_leg(mg3d_dist *D, const SlabCycle &c, int l, RestrictTarget *tgt, const RestrictTarget *none)
+{
+    const bool top = l == D->L - 1;
+    restrict_targets(D, l, tgt);
+    CHK(await_u(D, l));
+    if (top && (c.legs_in || c.red_in))
+        CHK(dist_down_leg_ahead(D, l, tgt, c.red_in, c.slot));
+    else if (top && c.carry_in)
+        CHK(dist_down_leg_carried(D, l, tgt));
+    else if (D->coef) {
+        /* variable coefficient: zero guess below the finest level (:1258) on every local plane, passes, r stored */
+        if (!top)
+            for (auto &R : D->rs)
+                (void)hipMemsetAsync(SL(D, R, l).lv.f[MG3D_U], 0, SL(D, R, l).lv.elems * sizeof(double), D->stream);
+        CHK(dist_coef_smooth(D, l, 0, 2));
+    } else /* :1282 + :1294 + :1310 (interior of the coarse rhs on the fly unless r is to be kept) */
+        CHK(stage_smooth(D, l, 0, 2, c.keep_r ? none : tgt, nullptr, !top));
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        SlabLevel &sl = SL(D, D->rs[ri], l);
+        k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, 0, D->stream, tgt[ri].lo, tgt[ri].hi, !c.keep_r && !D->coef);
+    }
+    /* the coarser level starts from its right-hand side at once: only owned planes were produced */
+    if (l - 1 < D->ld)
+        CHK(exchange(D, (D->policy & 1) ? MG3D_XK_RHS_GATHER : MG3D_XK_RHS_ALLGATHER, D->ld - 1, false));
+    else
+        CHK(exchange(D, MG3D_XK_HALO_D, l - 1, false));
+    /* u of this level is final until the prolongation on the way up: refresh its halos underneath the
+     * coarser levels (issued behind the right-hand side's exchange: one communicator, one in-order stream) */
+    return start_u_exchange(D, MG3D_XK_HALO_U_DOWN, l);
+}
+
+/* The replicated levels: the ordinary V-cycle from level ld-1 (its guess zeroed first, :1258), on every rank -- or,
+ * with MG3D_COARSE_GATHER=1, on rank 0 alone, whose correction is then broadcast (same bits either way: the ranks
+ * would have computed identical copies) */
+static int dist_replicated_levels(mg3d_dist *D)
+{
+    const int lc_top = D->ld - 1;
+    {
+        DistScope timer(D, 3, D->stream);
+        for (auto &R : D->rs) {
+            if ((D->policy & 1) && R.rank != 0)
+                continue;
+            Level &lc = R.coarse->lv[lc_top];
+            (void)hipMemsetAsync(lc.f[MG3D_U], 0, lc.elems * sizeof(double), D->stream);
+            R.coarse->red_tail = false; /* u and d of the context's top level were rewritten behind its back (here; the restriction) */
+            mg3d_ctx_touched(R.coarse, MG3D_D, lc_top); /* ... by kernels: its zero map is void (the slab path takes none) */
+            if (lc_top == 0)
+                CHK(mg3d_coarse_solve(R.coarse));
+            else
+                CHK(mg3d_enqueue_vcycle(R.coarse, lc_top, R.coarse->sumsq_slots - 1));
+        }
+    }
+    if (D->policy & 1)
+        CHK(exchange(D, MG3D_XK_CORR_BCAST, lc_top, false));
+    return MG3D_OK;
+}
+
+/* Up-leg of distributed level l: prolongation (:1331) on every local plane, halos included -- the correction's halos
+ * (post-smoothed on owned +-1 only) are refreshed first, those of u have been under way since the pre-smoother -- then the
+ * post-smoother and, on the finest level, the norm (:1341, :1354): all H halo planes of u are exact here, the post-smoother
+ * uses up 2*nu of them.  The next cycle's pre-smoother wants fresh halos on the finest u: that exchange starts underneath the
+ * norm, which reads the first halo plane on either side -- the post-smoother made it exact, the exchange leaves it alone. */
+static int dist_up_leg(mg3d_dist *D, const SlabCycle &c, int l)
+{
+    const bool top = l == D->L - 1;
+    if (l - 1 >= D->ld)
+        CHK(exchange(D, MG3D_XK_HALO_U_UP, l - 1, false));
+    CHK(await_u(D, l));
+    const int want = top ? 1 : 0;
+    /* the prolongation rides on the post-smoother's first launch: the top level's split stage, and (option fuse_up_max, as
+     * on a single domain) the four-pass launch of a V(2,2) cycle on the levels below it */
+    const bool fold = !D->coef && dist_stage_plan(D, l, 1, want, false, true).step[0].pro;
+    std::vector<ProlongSource> pro(D->rs.size());
+    for (size_t ri = 0; ri < D->rs.size(); ri++) {
+        RankState &R = D->rs[ri];
+        SlabLevel &sl = SL(D, R, l);
+        Level &lc = l - 1 >= D->ld ? SL(D, R, l - 1).lv : R.coarse->lv[D->ld - 1];
+        pro[ri] = ProlongSource{&lc.g, lc.f[MG3D_U]};
+        if (!fold)
+            k_prolong(lc.g, lc.f[MG3D_U], sl.lv.g, sl.lv.f[MG3D_U], 0, D->stream, 0, sl.lv.g.ni);
+    }
+    if (top && c.legs_out)
+        return dist_up_leg_legs(D, l, pro.data());
+    if (D->coef)
+        return dist_coef_smooth(D, l, 1, want);
+    if (top && c.carry_out)
+        return dist_up_leg_carried(D, l, pro.data());
+    return stage_smooth(D, l, 1, want, nullptr, fold ? pro.data() : nullptr);
+}
+
+/* One V-cycle: the distributed levels down, the replicated levels, the distributed levels up, the norm.
+ * carry_out: another cycle of this call follows (it may be enqueued ahead into); legs_out: it follows in the same batch of norm
+ * slots (its down-leg completes this cycle's norm into slot `slot`, which the batch then reads back) */
+static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, bool legs_out = false)
+{
+    SlabCycle c;
+    CHK(dist_begin_cycle(D, c, slot, carry_out, legs_out));
+    DistScope cycle_timer(D, 0, D->stream);
     if (D->timing)
         D->t_cycles++;
     for (auto &R : D->rs)
         if (!R.coarse->have_lu)
             return fail(MG3D_ERR_STATE, "mg3d_dist_vcycles: no coarse LU set (mg3d_dist_build_coarse)");
-    std::vector<RestrictTarget> tgt(D->rs.size());
-    /* ---- down: distributed levels.  On entry the halos of d are exact on all levels (upload / the exchange
-     * that follows each restriction below) and those of the finest u have been refreshed since it last
-     * changed (upload, or the exchange started at the end of the previous cycle). */
-    for (int l = L - 1; l >= ld; l--) {
-        /* mg_3d.h:1258: zero guess below the finest level -- folded into the first sweep launch */
-        restrict_targets(D, l, tgt.data());
-        const bool keep = D->rs[0].coarse->keep_r;
-        std::vector<RestrictTarget> none(D->rs.size(), RestrictTarget{nullptr, nullptr, -1, -1});
-        CHK(await_u(D, l));
-        if (l == L - 1 && (legs_in || red_in))
-            CHK(dist_down_leg_ahead(D, l, tgt.data(), red_in, slot));
-        else if (l == L - 1 && carry_in)
-            CHK(dist_down_leg_carried(D, l, tgt.data()));
-        else if (D->coef) {
-            /* variable coefficient: zero guess below the finest level (:1258) on every local plane, passes, r stored */
-            if (l < L - 1)
-                for (auto &R : D->rs)
-                    (void)hipMemsetAsync(SL(D, R, l).lv.f[MG3D_U], 0, SL(D, R, l).lv.elems * sizeof(double), s);
-            CHK(dist_coef_smooth(D, l, 0, 2));
-        } else /* :1282 + :1294 + :1310 (interior of the coarse rhs on the fly unless r is to be kept) */
-            CHK(stage_smooth(D, l, 0, 2, keep ? none.data() : tgt.data(), l < L - 1));
-        for (size_t ri = 0; ri < D->rs.size(); ri++) {
-            SlabLevel &sl = SL(D, D->rs[ri], l);
-            k_restrict(sl.lv.g, sl.lv.f[MG3D_R], *tgt[ri].gc, tgt[ri].dc, 0, s, tgt[ri].lo, tgt[ri].hi, !keep && !D->coef);
-        }
-        /* the coarser level starts from its right-hand side at once: only owned planes were produced */
-        if (l - 1 < ld)
-            CHK(exchange(D, (D->policy & 1) ? MG3D_XK_RHS_GATHER : MG3D_XK_RHS_ALLGATHER, ld - 1, false));
-        else
-            CHK(exchange(D, MG3D_XK_HALO_D, l - 1, false));
-        /* u of this level is final until the prolongation on the way up: refresh its halos underneath the
-         * coarser levels (issued behind the right-hand side's exchange: one communicator, one in-order stream) */
-        CHK(start_u_exchange(D, MG3D_XK_HALO_U_DOWN, l));
-    }
-    /* ---- replicated levels: the ordinary V-cycle from level ld-1 (its guess zeroed first, :1258), on every rank -- or,
-     * with MG3D_COARSE_GATHER=1, on rank 0 alone, whose correction is then broadcast (same bits either way: the ranks
-     * would have computed identical copies) */
-    {
-        DistScope timer(D, 3, s);
-        for (auto &R : D->rs) {
-            if ((D->policy & 1) && R.rank != 0)
-                continue;
-            Level &lc = R.coarse->lv[ld - 1];
-            (void)hipMemsetAsync(lc.f[MG3D_U], 0, lc.elems * sizeof(double), s);
-            R.coarse->red_tail = false; /* u and d of the context's top level were rewritten behind its back (here; the restriction) */
-            mg3d_ctx_touched(R.coarse, MG3D_D, ld - 1); /* ... by kernels: its zero map is void (the slab path takes none) */
-            if (ld - 1 == 0)
-                CHK(mg3d_coarse_solve(R.coarse));
-            else
-                CHK(mg3d_enqueue_vcycle(R.coarse, ld - 1, R.coarse->sumsq_slots - 1));
-        }
-    }
-    if (D->policy & 1)
-        CHK(exchange(D, MG3D_XK_CORR_BCAST, ld - 1, false));
-    /* ---- up */
-    for (int l = ld; l < L; l++) {
-        /* :1331 on every local plane, halos included: the correction's halos (post-smoothed on owned +-1 only)
-         * are refreshed first, those of u have been under way since the pre-smoother */
-        if (l - 1 >= ld)
-            CHK(exchange(D, MG3D_XK_HALO_U_UP, l - 1, false));
-        CHK(await_u(D, l));
-        const int want = l == L - 1 ? 1 : 0;
-        /* the prolongation rides on the post-smoother's first launch: the top level's split stage, and (option fuse_up_max, as
-         * on a single domain) the four-pass launch of a V(2,2) cycle on the levels below it */
-        const bool fold = !D->coef && dist_stage_plan(D, l, 1, want, false, true).step[0].pro;
-        std::vector<ProlongSource> pro(D->rs.size());
-        for (size_t ri = 0; ri < D->rs.size(); ri++) {
-            RankState &R = D->rs[ri];
-            SlabLevel &sl = SL(D, R, l);
-            Level &lc = l - 1 >= ld ? SL(D, R, l - 1).lv : R.coarse->lv[ld - 1];
-            pro[ri] = ProlongSource{&lc.g, lc.f[MG3D_U]};
-            if (!fold)
-                k_prolong(lc.g, lc.f[MG3D_U], sl.lv.g, sl.lv.f[MG3D_U], 0, s, 0, sl.lv.g.ni);
-        }
-        /* :1341 (+ :1354 at the top level): all H halo planes of u are exact here, the post-smoother uses up
-         * 2*nu of them.  The next cycle's pre-smoother wants fresh halos on the finest u: that exchange starts
-         * underneath the norm kernel, which reads the first halo plane on either side -- just produced
-         * exactly by the post-smoother, so the exchange leaves that plane alone. */
-        if (l == L - 1 && legs_out) {
-            CHK(dist_up_leg_legs(D, l, pro.data()));
-            continue;
-        }
-        if (D->coef) {
-            CHK(dist_coef_smooth(D, l, 1, want));
-            continue;
-        }
-        CHK(stage_smooth(D, l, 1, want, nullptr, false, l == L - 1, fold ? pro.data() : nullptr, l == L - 1 && carry_out));
-        if (l == L - 1 && carry_out) {
-            D->carried = true;
-            D->n_carried++;
-        }
-    }
-    if (!legs_out)
+    std::vector<RestrictTarget> tgt(D->rs.size()), none(D->rs.size(), RestrictTarget{nullptr, nullptr, -1, -1});
+    for (int l = D->L - 1; l >= D->ld; l--)
+        CHK(dist_down_leg(D, c, l, tgt.data(), none.data()));
+    CHK(dist_replicated_levels(D));
+    for (int l = D->ld; l < D->L; l++)
+        CHK(dist_up_leg(D, c, l));
+    if (!c.legs_out)
         CHK(reduce_norm(D, slot));
     /* a whole V(2,2) cycle has ended the ordinary way: its last pass was red, the exchange behind it leaves all H halo planes
      * of u exact (plain plan: planes 2..H by exchange, plane 1 as the post-smoother made it) */
-    if (!legs_out && !carry_out && D->nu == 2 && !D->coef)
+    if (!c.legs_out && !c.carry_out && D->nu == 2 && !D->coef)
         D->red_tail = true;
     if (D->phase != (int)(*D->cur)[0].kind.size())
         return fail(MG3D_ERR_STATE, "slab schedule ended after %d of the plan's %d phases", D->phase, (int)(*D->cur)[0].kind.size());
@@ -1547,9 +1551,6 @@ static int dist_enqueue_vcycle(mg3d_dist *D, int slot, bool carry_out = false, b
         return fail(MG3D_ERR_HIP, "mg3d_dist_vcycles: kernel launch failed: %s", hipGetErrorString(e));
     return MG3D_OK;
 }
-
-/* after the last cycle the compute stream joins the exchange of the finest u halos that the cycle started */
-static int dist_finish(mg3d_dist *D) { return await_u(D, D->L - 1); }
 
 extern "C" int mg3d_dist_vcycles(mg3d_dist *D, int count, double *norms)
 {
@@ -1577,20 +1578,19 @@ extern "C" int mg3d_dist_vcycles(mg3d_dist *D, int count, double *norms)
             /* every cycle but the last of a call ends ahead into the next one (a call never ends in the carried state) */
             CHK(dist_enqueue_vcycle(D, c, done + c + 1 < count, c + 1 < nb));
         }
-        CHK(dist_finish(D));
+        CHK(await_u(D, D->L - 1)); /* the compute stream joins the exchange of the finest u halos that the last cycle started */
         HIPCHK(hipMemcpyAsync(D->h_norms, D->d_norms, nb * sizeof(double), hipMemcpyDeviceToHost, D->stream));
         HIPCHK(hipStreamSynchronize(D->stream));
         HIPCHK(hipStreamSynchronize(D->comm_stream));
         dist_resolve_timers(D);
         /* an RCCL failure that surfaced asynchronously (a peer died, a transport error): an error here, not a hang or a
          * wrong number later */
-        for (ncclComm_t cm : {D->have_comm ? D->comm : nullptr})
-            if (cm) {
-                ncclResult_t ae = ncclSuccess;
-                NCCLCHK(ncclCommGetAsyncError(cm, &ae));
-                if (ae != ncclSuccess)
-                    return fail(MG3D_ERR_HIP, "RCCL reported an asynchronous error: %s", ncclGetErrorString(ae));
-            }
+        if (D->have_comm && D->comm) {
+            ncclResult_t ae = ncclSuccess;
+            NCCLCHK(ncclCommGetAsyncError(D->comm, &ae));
+            if (ae != ncclSuccess)
+                return fail(MG3D_ERR_HIP, "RCCL reported an asynchronous error: %s", ncclGetErrorString(ae));
+        }
         if (norms)
             for (int c = 0; c < nb; c++)
                 norms[done + c] = sqrt(D->h_norms[c]);

@@ -104,7 +104,7 @@ def worker(r, P, port, c, L, nu, sigma, field, cycles, out_path, policy):
 
     for _ in range(cycles):
         plan.start_cycle()  # the plain plan: never carried, never legs
-        for l in range(L - 1, ld - 1, -1):  # ---- down
+        for l in range(L - 1, ld - 1, -1):  # ---- down (dist_down_leg, its coefficient form)
             sl = lv[l]
             if l < L - 1:
                 sl.u[:] = 0.0
@@ -123,14 +123,14 @@ def worker(r, P, port, c, L, nu, sigma, field, cycles, out_path, policy):
                 plan.run(PL.RHS_GATHER if policy else PL.RHS_ALLGATHER, ld - 1, array_of)
             plan.run(PL.HALO_U_DOWN, l, array_of)  # every halo plane of u, poisoned ones included
             assert not np.isnan(sl.u).any()
-        if not policy or r == 0:  # ---- replicated levels
+        if not policy or r == 0:  # ---- replicated levels (dist_replicated_levels)
             rep.u[ld - 1][...] = 0.0
             rep.vcycle(ld - 1, hs[ld - 1])
         else:
             rep.u[ld - 1][...] = np.nan  # must be overwritten by the broadcast
         if policy:
             plan.run(PL.CORR_BCAST, ld - 1, array_of)
-        for l in range(ld, L):  # ---- up
+        for l in range(ld, L):  # ---- up (dist_up_leg, its coefficient form)
             sl = lv[l]
             if l - 1 >= ld:
                 sc = lv[l - 1]

@@ -4,7 +4,9 @@ send/recv for the halo planes, broadcast for the replicated right-hand side, all
 What is under test is the host logic the multi-GPU path rests on: the partition (`mg3d_slab_*` from libmg3d.so,
 pure host arithmetic), the halo depth H = 2*nu+2, and the EXCHANGE PLAN of csrc/mg3d_dist.hip (`mg3d_dist_plan`: the
 very list of sends / receives / broadcasts its RCCL transport issues, phase by phase) -- every transfer below is read
-from that plan, none is computed here; the order of the compute steps mirrors dist_enqueue_vcycle.  The per-slab arithmetic is the numpy statement of the
+from that plan, none is computed here; the order of the compute steps mirrors dist_enqueue_vcycle (dist_down_leg per
+level, dist_replicated_levels, dist_up_leg per level; the finest level's last launch and the exchange behind it:
+edge_first).  The per-slab arithmetic is the numpy statement of the
 operators (tests/_slab_numpy.py, pinned to the oracle); the replicated levels run the oracle's V-cycle.  The
 assembled solution must equal the single-domain oracle bit for bit.  No GPU, no HIP compute."""
 import ctypes as C
@@ -133,12 +135,12 @@ def worker(r, P, port, c, L, nu, cycles, out_path, policy=0, carry=False, legs=F
     carried = False  # u of the top level already holds the next cycle's first three pre-smoothing passes
     pending = None   # one launch per leg: the previous cycle's sum of squares, reduced behind this cycle's down-leg
     for cyc in range(cycles):
-        # carried cycles (V(2,2); csrc/mg3d_dist.hip dist_enqueue_vcycle): every cycle but the last ends ahead
+        # carried cycles (V(2,2); csrc/mg3d_dist.hip dist_begin_cycle, dist_up_leg_carried): every cycle but the last ends ahead
         carry_in, carry_out = carried, carry and nu == 2 and cyc + 1 < cycles
         # one launch per leg: every cycle but the last ends with the one-launch up-leg, whose norm the next cycle completes
         legs_in, legs_out = pending is not None, legs and nu == 2 and cyc + 1 < cycles
         plan.start_cycle(carry_out, legs_in, legs_out)
-        for l in range(L - 1, ld - 1, -1):  # ---- down
+        for l in range(L - 1, ld - 1, -1):  # ---- down (dist_down_leg)
             sl = lv[l]
             if l < L - 1:
                 sl.u[:] = 0.0
@@ -175,7 +177,7 @@ def worker(r, P, port, c, L, nu, cycles, out_path, policy=0, carry=False, legs=F
             # ... then the halos of u, final on this level until the way up (on the GPU: issued behind the exchange above on
             # the one communication stream, running underneath the coarser levels)
             plan.run(PL.HALO_U_DOWN, l, array_of)
-        # ---- coarse levels: identical on every rank -- or on rank 0 alone, whose correction is then broadcast
+        # ---- coarse levels (dist_replicated_levels): identical on every rank -- or on rank 0 alone, whose correction is then broadcast
         if not policy or r == 0:
             Hc.u[ld - 1][:] = 0.0
             O.lib().orc_vcycle(Hc.ptrs(Hc.u), Hc.ptrs(Hc.d), Hc.ptrs(Hc.r), hs[ld - 1], ld - 1, L, nu, Hc.N[ld - 1], O.P(LU))
@@ -183,7 +185,7 @@ def worker(r, P, port, c, L, nu, cycles, out_path, policy=0, carry=False, legs=F
             Hc.u[ld - 1][:] = np.nan  # must be overwritten by the broadcast
         if policy:
             plan.run(PL.CORR_BCAST, ld - 1, array_of)
-        for l in range(ld, L):  # ---- up
+        for l in range(ld, L):  # ---- up (dist_up_leg)
             sl = lv[l]
             # the correction is applied to every local plane, halos included: both operands have exact halos
             if l - 1 >= ld:

@@ -108,10 +108,11 @@ def test_every_send_has_its_receive(c, L, nu, P, overlap, policy):
 
 @pytest.mark.parametrize("c,L,nu,P", [(9, 7, 2, 8), (5, 6, 3, 3)])
 def test_phase_sequence_of_a_cycle(c, L, nu, P):
-    """the order dist_enqueue_vcycle walks: per distributed level the coarser right-hand side (what the next level waits
-    for), then the level's u halos (for the way up: they travel underneath the coarser levels -- one communicator, one
-    in-order stream, so the critical exchange is issued first); the coarse levels; per level the correction's halos; the
-    finest u for the next cycle; the norm"""
+    """the order dist_enqueue_vcycle walks: per distributed level (dist_down_leg) the coarser right-hand side (what the
+    next level waits for), then the level's u halos (for the way up: they travel underneath the coarser levels -- one
+    communicator, one in-order stream, so the critical exchange is issued first); the coarse levels
+    (dist_replicated_levels); per level the correction's halos (dist_up_leg); the finest u for the next cycle
+    (edge_first); the norm"""
     lib = M.lib()
     H = lib.mg3d_slab_halo(nu)
     ld = lib.mg3d_slab_first_level(c, L, P, H)

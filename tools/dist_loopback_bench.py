@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import multigrid_parallel_amd as M
 
 c, L, nu = 9, 7, 2
-steps = 10
+steps = int(os.environ.get("MG3D_LOOPBACK_STEPS", "10"))  # timed cycles per figure
 with M.Solver(c, L, nu) as s:
     s.setup_test_problem(); s.vcycles(2); s.sync()
     t0 = time.perf_counter(); ref = s.vcycles(steps); t1 = time.perf_counter()
