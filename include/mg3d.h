@@ -202,6 +202,53 @@ int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on);
 int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host); /* the injected mask, dense n^3; MG3D_ERR_STATE without one */
 /* (mg3d_ctx_set_mask_device is declared with the other device-array calls, behind mg3d_array) */
 
+/* Screening field: sigma per grid point.  s is one double per point of the finest level, a dense N^3 host array, every entry
+ * finite and >= 0.  Every operator of the context becomes the one of
+ *     div(eps grad u) - (sigma + s_p) u = d        (sigma the scalar of mg3d_ctx_set_shift, added per point; eps as set, or 1)
+ * with the arithmetic of the variable-coefficient kernels and one change: s(um) and D, the sum of the six face means --
+ * exactly 6.0 without eps --, stay, and  dg = D + (sigma + s_p)*h^2, formed per point in this order;  smoother
+ * v = (sum - h^2 d)/dg, an IEEE division also without eps;  residual  d - (sum - dg*v)/h^2;  A p of the CG solvers and q of the
+ * stepper likewise;  coarse matrix mg3d_coarse_matrix_field, diagonal -((D + (sigma + s_p)*h^2)/h^2).  So an all-zero field
+ * on a context with eps gives every grid value and norm of the context without a field, bit for bit; and a field without eps
+ * gives what eps = 1.0 at every point gives with the same field -- the library runs that case on the eps kernels over an
+ * internal array of ones (mg3d_ctx_has_coefficient still reports 0, mg3d_ctx_get_coefficient still MG3D_ERR_STATE;
+ * INTEGRATION.md, "Screening field", has the cost).
+ * Uses: a Newton step of Poisson-Boltzmann, Delta u - kappa^2 sinh u = f, is a solve with s = kappa^2 cosh u_k; decay or
+ * reaction rates that vary in space under mg3d_step_advance; sponge layers.  A huge penalty inside a body is the job of
+ * mg3d_ctx_set_mask, not of this field (below).  A Robin face is NOT offered as a helper: its term scales with 1/h per
+ * level, which no coarsening of a stored field reproduces.
+ * Hierarchy: s of a coarser level is the context's own restriction of the finer one -- FULL WEIGHTING at every coarse
+ * unknown, with the wrapped (periodic) or reflected (Neumann) taps the operator has, injection at the points of Dirichlet
+ * faces (never used), periodic duplicates copies of their sources.  Not injection, which loses a feature thinner than the
+ * coarse spacing from every coarse level; with full weighting a thin feature is smeared, not lost, and plain cycles keep
+ * converging (INTEGRATION.md has the measurements, and the one case injection wins: a penalty of 1e6 inside a ball).
+ * When the boundary masks change, the coarser levels are restricted again.  On a periodic axis the duplicates of the
+ * finest level are neither checked nor kept, for good, as for the mask.
+ * Singular cases, as the mask's: the pin of unknown (0,0,0) of level 0 applies iff the condition of mg3d_ctx_set_neumann
+ * holds AND level 0's mask has no fixed unknown AND level 0's field is > 0 at no unknown; mg3d_wpcg_solve projects iff that
+ * holds and the FINEST mask has no fixed unknown and the finest field is > 0 at no unknown.
+ * The contract is mg3d_ctx_set_coefficient's: the array is checked before anything changes (periodic duplicates skipped);
+ * an entry that is not finite or is < 0 is MG3D_ERR_ARG and changes nothing, the message naming the lowest dense index
+ * among them and its value.  Otherwise a cycle that has run ahead is finished first with the operator it started with, a
+ * factor of mg3d_ctx_build_coarse is rebuilt and one of mg3d_ctx_set_lu / mg3d_es_setup dropped.  Another array replaces the
+ * field on every level; NULL returns to the context as it was, bit for bit and with its fused schedules.  The setters
+ * (shift, coefficient, periodic, neumann, mask, field) work in every order.  With a field the context runs the unfused
+ * kernels, as with eps: the fused, carried, per-leg and single-workgroup options keep their values and do not apply, the
+ * zero map of d is unused.  The field holds under mg3d_smooth, mg3d_residual, mg3d_vcycle(s), mg3d_pcg_solve /
+ * mg3d_wpcg_solve (a non-negative diagonal keeps operator and cycle self-adjoint in the same inner products),
+ * mg3d_fmg_solve (where no mask forbids it) and mg3d_step_*: mg3d_step_setup keeps setting the scalar, the equation stepped
+ * is u_t = div(eps grad u) - (kappa + s_p) u + source, the field enters d through q and the stepper's formulas stand.
+ * mg3d_field_*, mg3d_field_sample* and mg3d_deposit* ignore the field, as they ignore sigma.  mg3d_es_* and
+ * mg3d_fmg_initialize return MG3D_ERR_STATE.  The slab, fp32 and mg3d_host_* forms and the drop-in header have no field.
+ * mg3d_ctx_set_shift_field_device: the same from a device array (mg3d_array below), MG3D_F64 or MG3D_F32, any strides >= 0,
+ * checked on the device before anything changes, with the stream ordering and the two host synchronisations of
+ * mg3d_ctx_set_coefficient_device; MG3D_F64 stores the same bytes as the host form.
+ * mg3d_ctx_get_shift_field: the restricted field of a level, dense n^3. */
+int mg3d_ctx_set_shift_field(mg3d_ctx *ctx, const double *s); /* finest level, dense N^3 host array; NULL: no field */
+int mg3d_ctx_has_shift_field(const mg3d_ctx *ctx, int *on);
+int mg3d_ctx_get_shift_field(mg3d_ctx *ctx, int level, double *host); /* the restricted field of a level, dense n^3; MG3D_ERR_STATE without one */
+/* (mg3d_ctx_set_shift_field_device is declared with the other device-array calls, behind mg3d_array) */
+
 /* ------------------------------------------------------------ data movement
  * Host arrays are dense N^3 (reference layout). */
 int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host);
@@ -260,6 +307,7 @@ int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *
 int mg3d_step_set_source_device(mg3d_ctx *ctx, const mg3d_array *s /* NULL: no source */, void *stream);
 int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps /* NULL: constant operator */, void *stream);
 int mg3d_ctx_set_mask_device(mg3d_ctx *ctx, const mg3d_array *mask /* dtype MG3D_U8 only; NULL: no mask */, void *stream);
+int mg3d_ctx_set_shift_field_device(mg3d_ctx *ctx, const mg3d_array *s /* MG3D_F64 or MG3D_F32; NULL: no field */, void *stream);
 
 /* ------------------------------------------------------------ field output
  * What is wanted of a solved potential u of div(eps grad u) - sigma u = f: the field E = -grad u, the charge u induces on
@@ -840,7 +888,10 @@ int mg3d_host_vcycle(double **u, double **f, double **res, double h, int q, int 
  *   mg3d_coarse_matrix_periodic: + periodic axes (mg3d_ctx_set_periodic; eps NULL for the constant operator)
  *   mg3d_coarse_matrix_bc      : + Neumann faces (mg3d_ctx_set_neumann): reflected rows for the Neumann face unknowns
  *   mg3d_coarse_matrix_mask    : + fixed points (mg3d_ctx_set_mask; mask dense N^3 bytes): identity rows at the fixed
- *                                unknowns, and the pin only without one -- the form mg3d_ctx_build_coarse calls
+ *                                unknowns, and the pin only without one
+ *   mg3d_coarse_matrix_field   : + the screening field (mg3d_ctx_set_shift_field; s dense N^3, >= 0, NULL for none): the
+ *                                diagonal -((D + (sigma + s[p])*h^2)/h^2), D the sum of the six face means or exactly 6.0,
+ *                                and the pin only where s is > 0 at no unknown -- the form mg3d_ctx_build_coarse calls
  * mg3d_neumann_fold_flux  : a prescribed outward normal derivative g folded into the right-hand side d (dense N^3) of the
  *                           homogeneous Neumann operator: d -= 2*a*g/h at each point of each Neumann face in `faces`, a = 1
  *                           (eps NULL) or 0.5*(eps_face + eps_inner), summed over the faces an edge or corner point lies
@@ -862,6 +913,9 @@ void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps /* NULL
                            int periodic_axes, int neumann_faces); /* host only, A zeroed by caller */
 void mg3d_coarse_matrix_mask(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
                              int periodic_axes, int neumann_faces, const unsigned char *mask /* NULL: none */);
+void mg3d_coarse_matrix_field(double *A, int N, double h, const double *eps /* NULL: constant */, double sigma,
+                              int periodic_axes, int neumann_faces, const unsigned char *mask /* NULL: none */,
+                              const double *s /* NULL: none */);
 int mg3d_neumann_fold_flux(double *d, const double *eps /* NULL: constant */, int N, double h, int faces,
                            const double *const *g);
 void mg3d_lu_factor(double *a, int n);

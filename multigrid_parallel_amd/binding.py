@@ -82,6 +82,10 @@ SIGNATURES = {
     "mg3d_download_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ap, C.c_void_p]),
     "mg3d_step_set_source_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
     "mg3d_ctx_set_coefficient_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_ctx_set_shift_field": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_ctx_set_shift_field_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_ctx_has_shift_field": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mg3d_ctx_get_shift_field": (C.c_int, [C.c_void_p, C.c_int, dp]),
     "mg3d_ctx_set_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte)]),
     "mg3d_ctx_set_mask_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
     "mg3d_ctx_has_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
@@ -172,6 +176,7 @@ SIGNATURES = {
     "mg3d_coarse_matrix_periodic": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int]),
     "mg3d_coarse_matrix_bc": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int]),
     "mg3d_coarse_matrix_mask": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_ubyte)]),
+    "mg3d_coarse_matrix_field": (None, [dp, C.c_int, C.c_double, dp, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_ubyte), dp]),
     "mg3d_neumann_fold_flux": (C.c_int, [dp, dp, C.c_int, C.c_double, C.c_int, C.POINTER(dp)]),
     "mg3d_lu_factor": (None, [dp, C.c_int]),
     "mg3d_l2norm_host": (C.c_double, [dp, C.c_long]),
@@ -518,6 +523,34 @@ class Solver:
         check(self.L.mg3d_ctx_get_mask(self._h, level, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out.reshape(n, n, n)
 
+    def set_shift_field(self, s):
+        """mg3d_ctx_set_shift_field: solve  div(eps grad u) - (sigma + s)*u = d  with s >= 0 given at every point of the
+        finest level ((N, N, N) or flat float64; coarser levels take it by the context's own restriction, full weighting).
+        sigma is set_shift's scalar, eps set_coefficient's or 1.  None: no field again.  Rebuilds a coarse factor of
+        get_details(); drops one given to set_lu."""
+        if s is None:
+            check(self.L.mg3d_ctx_set_shift_field(self._h, None))
+            return
+        s = np.asarray(s)
+        if s.dtype != np.float64:
+            raise TypeError(f"set_shift_field: need float64, got {s.dtype}")
+        if s.size != self.N ** 3 or s.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"set_shift_field: need shape ({self.N},)*3 or ({self.N ** 3},), got {s.shape}")
+        check(self.L.mg3d_ctx_set_shift_field(self._h, P(np.ascontiguousarray(s).reshape(-1))))
+
+    def has_shift_field(self):
+        on = C.c_int(0)
+        check(self.L.mg3d_ctx_has_shift_field(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def get_shift_field(self, level=None):
+        """the restricted field of a level as the kernels use it, (n, n, n)"""
+        level = self.num_levels - 1 if level is None else level
+        n = self.level_n(level)
+        out = np.empty(n ** 3)
+        check(self.L.mg3d_ctx_get_shift_field(self._h, level, P(out)))
+        return out.reshape(n, n, n)
+
     def set_periodic(self, axes):
         """mg3d_ctx_set_periodic: periodic boundaries on the axes given as a mask (MG3D_PERIODIC_I = 1, _J = 2, _K = 4) or
         as an iterable of axis indices 0, 1, 2; 0 or () gives Dirichlet faces everywhere again.  On a periodic axis index
@@ -708,6 +741,16 @@ class Solver:
             return
         a, stream = _device_args(t, "set_coefficient_tensor", (self.N,) * 3)
         check(self.L.mg3d_ctx_set_coefficient_device(self._h, C.byref(a), stream))
+
+    def set_shift_field_tensor(self, t):
+        """mg3d_ctx_set_shift_field_device: set_shift_field from an (N, N, N) float64 or float32 tensor on the GPU, any
+        view; checked on the device (Mg3dError code 1 names the lowest bad dense index), synchronises with the host.
+        None: no field."""
+        if t is None:
+            check(self.L.mg3d_ctx_set_shift_field_device(self._h, None, None))
+            return
+        a, stream = _device_args(t, "set_shift_field_tensor", (self.N,) * 3)
+        check(self.L.mg3d_ctx_set_shift_field_device(self._h, C.byref(a), stream))
 
     # -- field output (include/mg3d.h, "Field output"): read-only, the finest level
     def gradient(self, scale=1.0):

@@ -45,6 +45,16 @@ struct mg3d_ctx {
     std::vector<unsigned char *> mask;
     std::vector<unsigned char> mask0;
     unsigned long long mask_fixed0 = 0, mask_fixed_top = 0;
+    /* the screening field of div(eps grad u) - (sigma + s) u (mg3d_ctx_set_shift_field): s of every level in the padded
+     * layout, the finest level's as given and each coarser one's by the context's own restriction (empty: no field); level
+     * 0's, dense, for the coarse matrix; how many UNKNOWNS of level 0 and of the finest level have s > 0 under the present
+     * boundary masks (retaken, with the coarser levels, when those change); and, while the context has a field and no eps,
+     * eps = 1 at every point of every level for the eps kernels, which alone have the field form (empty otherwise; the
+     * context still has no coefficient: mg3d_ctx_has_coefficient) */
+    std::vector<double *> sfield;
+    std::vector<double> sfield0;
+    unsigned long long sfield_pos0 = 0, sfield_pos_top = 0;
+    std::vector<double *> ones;
     /* periodic axes (mg3d_ctx_set_periodic; MG3D_PERIODIC_* mask, 0: Dirichlet faces everywhere) and the padded level-0
      * right-hand side of the direct solve that k_per_coarse_rhs builds from d (allocated with the first nonzero mask) */
     int periodic;
@@ -140,10 +150,12 @@ static inline void swap_u(Level &l)
 /* the fused schedules (sweep, tiny, carried cycles, legs) apply: not with a variable coefficient, whose levels run colour
  * passes and residual of k_smooth_color / k_residual with the plain restriction, prolongation and coarse solve between
  * them, nor with a periodic axis or a Neumann face, whose levels run those with wrapped or reflected neighbours and the
- * transfers k_restrict / k_prolong launch for a boundary word, nor with fixed points, whose levels run the MASK forms */
+ * transfers k_restrict / k_prolong launch for a boundary word, nor with fixed points, whose levels run the MASK forms, nor
+ * with a screening field, whose levels run the SFIELD forms of the eps kernels */
 static inline bool mg3d_fused(const mg3d_ctx *ctx)
 {
-    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty();
+    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty() &&
+           ctx->sfield.empty();
 }
 /* a sweep launch on a level of this context, u -> alt: the caller adds what the launch does (SweepLaunch) */
 static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
@@ -169,23 +181,33 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
 /* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */
 static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodic, ctx->neumann); }
 /* the operator of a level of this context for the stencil launchers: the constants of its spacing and the context's sigma,
- * its eps (NULL: constant), the boundary word and its fixed-point bytes (NULL: the context has no mask) */
-static inline LevelOperator mg3d_level_operator(const mg3d_ctx *ctx, int level)
+ * its eps (NULL: constant), the boundary word, its fixed-point bytes (NULL: the context has no mask) and its screening field
+ * (NULL: none; with one and no eps, e is eps = 1 at every point).  screened = false: the operator without the field -- the
+ * field output, which ignores s as it ignores sigma */
+static inline LevelOperator mg3d_level_operator(const mg3d_ctx *ctx, int level, bool screened = true)
 {
-    return {mg3d_level_op(ctx->lv[level].h, ctx->sigma), ctx->sigma, ctx->eps.empty() ? nullptr : ctx->eps[level],
-            mg3d_ctx_bc(ctx), ctx->mask.empty() ? nullptr : ctx->mask[level]};
+    const bool field = screened && !ctx->sfield.empty();
+    return {mg3d_level_op(ctx->lv[level].h, ctx->sigma),
+            ctx->sigma,
+            !ctx->eps.empty() ? ctx->eps[level] : (field ? ctx->ones[level] : nullptr),
+            mg3d_ctx_bc(ctx),
+            ctx->mask.empty() ? nullptr : ctx->mask[level],
+            field ? ctx->sfield[level] : nullptr};
 }
-/* sigma = 0, every axis periodic or Neumann on both faces and no fixed unknown on level 0: constants are in the kernel of
- * the coarsest operator, unknown (0,0,0) of level 0 is pinned */
+/* sigma = 0, every axis periodic or Neumann on both faces, no fixed unknown on level 0 and no unknown of level 0 at which
+ * its screening field is > 0: constants are in the kernel of the coarsest operator, unknown (0,0,0) of level 0 is pinned */
 static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
 {
     bool closed = true;
     for (int ax = 0; ax < 3; ax++)
         closed = closed && ((ctx->periodic >> ax & 1) || (ctx->neumann >> (2 * ax) & 3) == 3);
-    return closed && ctx->sigma == 0. && ctx->mask_fixed0 == 0;
+    return closed && ctx->sigma == 0. && ctx->mask_fixed0 == 0 && ctx->sfield_pos0 == 0;
 }
 /* ... and none on the finest level either: the system itself is singular (mg3d_wpcg_solve projects) */
-static inline bool mg3d_ctx_singular(const mg3d_ctx *ctx) { return mg3d_ctx_pinned(ctx) && ctx->mask_fixed_top == 0; }
+static inline bool mg3d_ctx_singular(const mg3d_ctx *ctx)
+{
+    return mg3d_ctx_pinned(ctx) && ctx->mask_fixed_top == 0 && ctx->sfield_pos_top == 0;
+}
 /* field `field` of `level` was written from outside the cycle (see faces_dirty), and how -- what the zero map of the top
  * level's d (dz_state) makes of it: MG3D_WROTE_DEVICE a kernel of the library wrote values nobody has looked at (NONE),
  * MG3D_WROTE_CALLER the caller's values arrived (UNKNOWN: scanned before the next cycle), MG3D_WROTE_ZERO the field was

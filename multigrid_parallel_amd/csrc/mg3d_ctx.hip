@@ -188,6 +188,10 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
         (void)hipFree(e);
     for (unsigned char *m : ctx->mask)
         (void)hipFree(m);
+    for (double *f : ctx->sfield)
+        (void)hipFree(f);
+    for (double *e : ctx->ones)
+        (void)hipFree(e);
     if (ctx->per_b)
         (void)hipFree(ctx->per_b);
     for (double *v : ctx->pcg_v)
@@ -680,8 +684,9 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    mg3d_coarse_matrix_mask(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
-                            ctx->neumann, ctx->mask.empty() ? nullptr : ctx->mask0.data()); /* mg_3d.h:288 */
+    mg3d_coarse_matrix_field(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
+                             ctx->neumann, ctx->mask.empty() ? nullptr : ctx->mask0.data(),
+                             ctx->sfield.empty() ? nullptr : ctx->sfield0.data()); /* mg_3d.h:288 */
     mg3d_lu_factor(A, (int)n);                             /* mg_3d.h:289 */
     const int rc = mg3d_ctx_set_lu(ctx, A);
     free(A);
@@ -697,6 +702,8 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
  * sigma rebuilds a factor of mg3d_ctx_build_coarse for the spacing it was built with, or drops one installed by
  * mg3d_ctx_set_lu (or mg3d_es_setup): the next cycle returns MG3D_ERR_STATE until a factor is set again. */
 static int operator_changed(mg3d_ctx *ctx);
+static int ensure_ones(mg3d_ctx *ctx, const char *who);
+static void free_ones(mg3d_ctx *ctx);
 static int launch_ok(const char *who);
 static int check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who);
 extern "C" int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma)
@@ -795,6 +802,7 @@ static int coefficient_written(mg3d_ctx *ctx, const char *who)
                             (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     CHK(launch_ok(who));
+    free_ones(ctx); /* (a screening field ran the eps kernels over eps = 1 until now; nothing in flight reads it any more) */
     return operator_changed(ctx);
 }
 
@@ -824,6 +832,10 @@ extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
     if (!eps) {
         if (ctx->eps.empty())
             return MG3D_OK;
+        if (!ctx->sfield.empty()) { /* a screening field stays: its eps kernels go on over eps = 1 */
+            CHK(ensure_io_chk(ctx, "mg3d_ctx_set_coefficient"));
+            CHK(ensure_ones(ctx, "mg3d_ctx_set_coefficient"));
+        }
         HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read eps */
         free_eps(ctx);
         return operator_changed(ctx);
@@ -1096,11 +1108,237 @@ extern "C" int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host)
     return MG3D_OK;
 }
 
+/* The screening field (mg3d_ctx_set_shift_field, mg3d_kernels.hip): one double >= 0 per point of every level,
+ * div(eps grad u) - (sigma + s) u. */
+static void free_ones(mg3d_ctx *ctx)
+{
+    for (double *e : ctx->ones)
+        (void)hipFree(e);
+    ctx->ones.clear();
+}
+
+static void free_sfield(mg3d_ctx *ctx)
+{
+    for (double *f : ctx->sfield)
+        (void)hipFree(f);
+    ctx->sfield.clear();
+    ctx->sfield0.clear();
+    ctx->sfield_pos0 = ctx->sfield_pos_top = 0;
+    free_ones(ctx);
+}
+
+/* one array of doubles per level in the padded layout; v is untouched when an allocation fails */
+static int alloc_level_doubles(mg3d_ctx *ctx, std::vector<double *> &v, const char *who)
+{
+    std::vector<double *> a(ctx->L, nullptr);
+    for (int l = 0; l < ctx->L; l++) {
+        const int rc = mg3d_device_alloc((void **)&a[l], ctx->lv[l].elems * sizeof(double), who);
+        if (rc == MG3D_OK)
+            continue;
+        for (double *q : a)
+            if (q)
+                (void)hipFree(q);
+        return rc;
+    }
+    v = a;
+    return MG3D_OK;
+}
+
+/* eps = 1 at the N^3 points of every level, for a context with a field and no coefficient: the eps kernels alone have the
+ * field form.  Written by k_pack from one double (every stride 0), which io_chk holds for the length of these launches --
+ * whoever uses io_chk next on the stream sets it first.  (The context has io_chk.) */
+static int ensure_ones(mg3d_ctx *ctx, const char *who)
+{
+    if (!ctx->ones.empty())
+        return MG3D_OK;
+    static const double one = 1.;
+    CHK(alloc_level_doubles(ctx, ctx->ones, who));
+    HIPCHK(hipMemcpyAsync(ctx->io_chk, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
+    const mg3d_array src = {ctx->io_chk, MG3D_F64, {0, 0, 0}};
+    for (int l = 0; l < ctx->L; l++)
+        k_pack(ctx->lv[l].g, ctx->ones[l], src, ctx->stream);
+    return MG3D_OK;
+}
+
+/* a field that could not be brought up to date (a HIP error): the context is left without one, and without a factor of the
+ * operator that had it -- as mask_abandon.  The first error is the one reported. */
+static int sfield_abandon(mg3d_ctx *ctx, int rc)
+{
+    (void)hipStreamSynchronize(ctx->stream);
+    free_sfield(ctx);
+    (void)operator_changed(ctx);
+    return rc;
+}
+
+/* Everything below the finest level's field, under the present boundary masks: its periodic duplicates from their sources,
+ * each coarser level by the context's own restriction (k_restrict with the boundary word: full weighting at every coarse
+ * unknown with the operator's wrapped or reflected taps, injection on Dirichlet faces, duplicates written), the unknowns with
+ * s > 0 on level 0 and on the finest level, level 0's field on the host for the coarse matrix.  One host synchronisation --
+ * behind it a caller's array has been read.  (The context has a field and io_chk.) */
+static int sfield_rebuild(mg3d_ctx *ctx, const char *who)
+{
+    const int L = ctx->L, bc = mg3d_ctx_bc(ctx);
+    const Level &l0 = ctx->lv[0], &top = ctx->lv[L - 1];
+    const int N0 = l0.g.N;
+    k_per_refresh(top.g, ctx->sfield[L - 1], bc, ctx->stream);
+    for (int l = L - 1; l >= 1; l--)
+        k_restrict(ctx->lv[l].g, ctx->sfield[l], ctx->lv[l - 1].g, ctx->sfield[l - 1], bc, ctx->stream);
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof cnt, ctx->stream));
+    k_field_count(l0.g, ctx->sfield[0], bc, ctx->io_chk, ctx->stream);
+    k_field_count(top.g, ctx->sfield[L - 1], bc, ctx->io_chk + 1, ctx->stream);
+    HIPCHK(hipMemcpyAsync(cnt, ctx->io_chk, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sfield0.resize((size_t)N0 * N0 * N0);
+    HIPCHK(hipMemcpy2DAsync(ctx->sfield0.data(), N0 * sizeof(double), ctx->sfield[0], l0.g.pitch * sizeof(double),
+                            N0 * sizeof(double), (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
+    ctx->sfield_pos0 = cnt[0];
+    ctx->sfield_pos_top = cnt[1];
+    return MG3D_OK;
+}
+
+/* what both forms of mg3d_ctx_set_shift_field do before the finest level's field is written -- everything that can fail for
+ * want of memory, nothing has changed when it does -- and behind it */
+static int sfield_prepare(mg3d_ctx *ctx, const char *who)
+{
+    CHK(ensure_io_chk(ctx, who));
+    CHK(ensure_per_b(ctx, who)); /* (a positive entry may lift the pin of a context whose boundaries are set later) */
+    if (ctx->eps.empty())
+        CHK(ensure_ones(ctx, who));
+    if (ctx->sfield.empty())
+        CHK(alloc_level_doubles(ctx, ctx->sfield, who));
+    return MG3D_OK;
+}
+static int sfield_written(mg3d_ctx *ctx, const char *who)
+{
+    const int rc = sfield_rebuild(ctx, who);
+    if (rc != MG3D_OK)
+        return sfield_abandon(ctx, rc);
+    return operator_changed(ctx);
+}
+
+static int sfield_clear(mg3d_ctx *ctx)
+{
+    CHK(mg3d_drop_carry(ctx));
+    if (ctx->sfield.empty())
+        return MG3D_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read the field */
+    free_sfield(ctx);
+    return operator_changed(ctx);
+}
+
+/* The operator div(eps grad u) - (sigma + s) u = d on every level: s of the finest level as given, of each coarser one by
+ * restriction.  The contract of mg3d_ctx_set_coefficient: the array is checked before anything changes (periodic duplicates
+ * are skipped); then a cycle that has run ahead is finished with the operator it started with and the coarse factor is
+ * rebuilt or dropped.  NULL: back to the context as it was, its fused schedules included. */
+extern "C" int mg3d_ctx_set_shift_field(mg3d_ctx *ctx, const double *s)
+{
+    static const char who[] = "mg3d_ctx_set_shift_field";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!s)
+        return sfield_clear(ctx);
+    const int L = ctx->L;
+    const Level &top = ctx->lv[L - 1];
+    const int N = top.g.N;
+    const long long n = (long long)N * N * N;
+    const int ax = ctx->periodic;
+    auto dup = [&](long long q) {
+        return ((ax & 1) && q / ((long long)N * N) == N - 1) || ((ax & 2) && (q / N) % N == N - 1) || ((ax & 4) && q % N == N - 1);
+    };
+    for (long long p = 0; p < n; p++)
+        if ((!(s[p] >= 0.) || !isfinite(s[p])) && !(ax && dup(p)))
+            return fail(MG3D_ERR_ARG, "%s: s[%lld] = %g (every entry must be finite and >= 0)", who, p, s[p]);
+    CHK(mg3d_drop_carry(ctx));
+    CHK(sfield_prepare(ctx, who));
+    HIPCHK(hipMemcpy2DAsync(ctx->sfield[L - 1], top.g.pitch * sizeof(double), s, N * sizeof(double), N * sizeof(double),
+                            (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
+    return sfield_written(ctx, who); /* (the host array may go once the call returns) */
+}
+
+/* the device form, step for step that of mg3d_ctx_set_coefficient_device: the check (a launch that reads the array as
+ * given; its two integers cross to the host), then the carried cycle, the pack into the finest level's field, the
+ * duplicates, the restrictions and the counts (sfield_written).  Two host synchronisations; behind the second one the array
+ * has been read, so the caller's stream needs no event of ours. */
+extern "C" int mg3d_ctx_set_shift_field_device(mg3d_ctx *ctx, const mg3d_array *s, void *stream)
+{
+    static const char who[] = "mg3d_ctx_set_shift_field_device";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (!s)
+        return sfield_clear(ctx);
+    CHK(mg3d_array_check(ctx, s, false, who));
+    const int L = ctx->L;
+    const Level &top = ctx->lv[L - 1];
+    const int N = top.g.N;
+    CHK(ensure_io_chk(ctx, who));
+    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
+    unsigned long long chk[2] = {0, 0};
+    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof(unsigned long long), ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->io_chk + 1, 0xff, sizeof(unsigned long long), ctx->stream));
+    k_field_check(top.g, *s, ctx->periodic, ctx->io_chk, ctx->stream);
+    HIPCHK(hipMemcpyAsync(chk, ctx->io_chk, sizeof chk, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(launch_ok(who));
+    if (chk[0] != 0) {
+        const long long p = (long long)chk[1];
+        const long long off = s->stride[0] * (p / ((long long)N * N)) + s->stride[1] * ((p / N) % N) + s->stride[2] * (p % N);
+        double v = 0.;
+        float v32 = 0.f;
+        if (s->dtype == MG3D_F32) {
+            HIPCHK(hipMemcpy(&v32, (const float *)s->ptr + off, sizeof v32, hipMemcpyDeviceToHost));
+            v = (double)v32;
+        } else {
+            HIPCHK(hipMemcpy(&v, (const double *)s->ptr + off, sizeof v, hipMemcpyDeviceToHost));
+        }
+        return fail(MG3D_ERR_ARG, "%s: s[%lld] = %g (every entry must be finite and >= 0; %llu entries are not)", who, p, v,
+                    chk[0]);
+    }
+    CHK(mg3d_drop_carry(ctx));
+    CHK(sfield_prepare(ctx, who));
+    {
+        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
+        k_pack(top.g, ctx->sfield[L - 1], *s, ctx->stream);
+    }
+    return sfield_written(ctx, who);
+}
+
+extern "C" int mg3d_ctx_has_shift_field(const mg3d_ctx *ctx, int *on)
+{
+    if (!ctx || !on)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_shift_field: NULL argument");
+    *on = ctx->sfield.empty() ? 0 : 1;
+    return MG3D_OK;
+}
+
+extern "C" int mg3d_ctx_get_shift_field(mg3d_ctx *ctx, int level, double *host)
+{
+    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_shift_field"));
+    if (!host)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_shift_field: NULL host pointer");
+    if (ctx->sfield.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_shift_field: no field set");
+    const Level &l = ctx->lv[level];
+    const int N = l.g.N;
+    HIPCHK(hipMemcpy2DAsync(host, N * sizeof(double), ctx->sfield[level], l.g.pitch * sizeof(double), N * sizeof(double),
+                            (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MG3D_OK;
+}
+
 /* the boundary masks changed under a mask: the duplicates of a periodic axis take their sources' bytes -- for good: the
  * caller's bytes there are not kept, an axis that stops being periodic finds its plane N-1 with plane 0's bytes -- and which
- * fixed points are unknowns is counted again; then the coarse factor, as for every change of the operator */
+ * fixed points are unknowns is counted again; under a screening field: the finest level's duplicates likewise, and the
+ * coarser levels and the counts are taken again, for the restriction is the boundary word's; then the coarse factor, as
+ * for every change of the operator */
 static int mask_boundary_changed(mg3d_ctx *ctx, const char *who)
 {
+    if (!ctx->sfield.empty()) {
+        const int rc = sfield_rebuild(ctx, who);
+        if (rc != MG3D_OK)
+            return sfield_abandon(ctx, rc);
+    }
     if (ctx->mask.empty())
         return operator_changed(ctx);
     for (int l = 0; l < ctx->L; l++)
@@ -2075,6 +2313,8 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (!ctx->mask.empty())
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
+    if (!ctx->sfield.empty()) /* the F-cycle start is the reference's, whose operator has no field */
+        return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: no coarse LU set");
     if (ctx->have_es)

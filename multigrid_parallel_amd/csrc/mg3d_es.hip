@@ -177,6 +177,8 @@ extern "C" int mg3d_es_setup(mg3d_ctx *ctx, const mg3d_es_params *p)
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (ctx && !ctx->mask.empty())
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
+    if (ctx && !ctx->sfield.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || !p || !(p->length > 0.))
         return fail(MG3D_ERR_ARG, "mg3d_es_setup: bad arguments");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
@@ -223,6 +225,8 @@ extern "C" int mg3d_es_smooth(mg3d_ctx *ctx, int level, int post, int iters)
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (ctx && !ctx->mask.empty())
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
+    if (ctx && !ctx->sfield.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || !ctx->have_es || level < 0 || level >= ctx->L || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_es_smooth: bad arguments (mg3d_es_setup first)");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */
@@ -279,6 +283,8 @@ extern "C" int mg3d_es_vcycles(mg3d_ctx *ctx, int count, double *norms)
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     if (ctx && !ctx->mask.empty())
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
+    if (ctx && !ctx->sfield.empty())
+        return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || count < 0 || !ctx->have_es)
         return fail(MG3D_ERR_ARG, "mg3d_es_vcycles: bad arguments (mg3d_es_setup first)");
     if (ctx->sigma != 0.) /* the mixed-boundary problem keeps the reference's operator */

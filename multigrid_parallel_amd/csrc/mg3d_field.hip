@@ -152,7 +152,7 @@ extern "C" int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux)
         return rc;
     const int q = ctx->L - 1, slot = ctx->sumsq_slots - 1;
     const Level &top = ctx->lv[q];
-    if (k_field_flux(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q), label, ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
+    if (k_field_flux(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q, false), label, ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
         return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", who);
     rc = field_launch_ok(who);
     double sum = 0.;
@@ -178,7 +178,7 @@ extern "C" int mg3d_field_energy(mg3d_ctx *ctx, double *energy)
         return rc;
     const int q = ctx->L - 1, slot = ctx->sumsq_slots - 1;
     const Level &top = ctx->lv[q];
-    if (k_field_energy(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q), ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
+    if (k_field_energy(top.g, top.f[MG3D_U], mg3d_level_operator(ctx, q, false), ctx->partials, ctx->sumsq + slot, ctx->stream) < 0)
         return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", who);
     rc = field_launch_ok(who);
     double sum = 0.;

@@ -36,21 +36,23 @@ void mg3d_fill_boundary_host(double *v, int N, double h)
 }
 
 /* The coarsest matrix, every form of it: constructCoarseMatrixA, mg_3d.h:147-273, for the operator
- * div(eps grad u) - sigma u with periodic axes, Neumann faces and fixed points.  Dense n x n, n = N^3; A must be zero on
- * entry (calloc, mg_3d.h:283).  eps: dense N^3, NULL for the constant operator; axes a MG3D_PERIODIC_* mask; faces a
- * MG3D_NEUMANN_* mask with no bit on a periodic axis; mask: dense N^3 bytes, NULL for none.
+ * div(eps grad u) - (sigma + s) u with periodic axes, Neumann faces and fixed points.  Dense n x n, n = N^3; A must be zero
+ * on entry (calloc, mg_3d.h:283).  eps: dense N^3, NULL for the constant operator; axes a MG3D_PERIODIC_* mask; faces a
+ * MG3D_NEUMANN_* mask with no bit on a periodic axis; mask: dense N^3 bytes, NULL for none; s: the screening field, dense
+ * N^3, every entry >= 0, NULL for none.
  * Identity rows (mg_3d.h:179-185) on the Dirichlet faces (index 0 or N-1 of an axis that is not periodic, unless that face
  * is a Neumann face), on the duplicates (index N-1 of a periodic axis), at the fixed unknowns -- nonzero bytes of mask on
  * points that are neither; the other bytes change nothing -- and on the pinned point (0,0,0): the pin applies when
- * sigma = 0, every axis is periodic or Neumann on both faces and there is no fixed unknown, for the operator then
- * annihilates constants.  The columns of a fixed point stay: its value is the right-hand side of its row, 0 in a cycle.
+ * sigma = 0, every axis is periodic or Neumann on both faces, there is no fixed unknown and s is > 0 at no unknown, for
+ * the operator then annihilates constants.  The columns of a fixed point stay: its value is the right-hand side of its row, 0 in a cycle.
  * Every other row is the row of the kernels of mg3d_kernels.hip: its six neighbours q in the order i-, i+, j-, j+, k-, k+,
  * wrapped on a periodic axis (i-1 at 0 is N-2, i+1 at N-2 is 0; needs N - 1 >= 4 there) and reflected across a Neumann
  * face (i-1 at 0 is 1, i+1 at N-1 is N-2: the two coincide, so that column receives the sum of both entries, added in
  * that order; reflection does not widen the band).  Off the diagonal a_q/h^2 with the face mean a_q = 0.5*(eps[p] + eps[q]),
  * on it -dg/h^2, dg = (((((a_im + a_ip) + a_jm) + a_jp) + a_km) + a_kp) + sigma*h^2; the constant operator writes
  * (1,1,1,1,1,1,-dg)/h^2 with dg = 6 + sigma*h^2 (mg_3d.h:257-268; sigma = 0: the reference's 6, bit for bit).  Where the
- * six neighbours are distinct, += on the zeroed row stores the entry itself. */
+ * six neighbours are distinct, += on the zeroed row stores the entry itself.  With s the diagonal is
+ * -((D + (sigma + s[p])*h^2)/h^2), D the sum of the six face means or exactly 6.0 without eps -- the kernels' per-point dg. */
 struct bc_axes {
     int per[3], rlo[3], rhi[3];
 };
@@ -63,7 +65,7 @@ static int bc_bound(const struct bc_axes *b, int N, const int x[3])
     return bound;
 }
 static void coarse_rows(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
-                        const unsigned char *mask)
+                        const unsigned char *mask, const double *s)
 {
     const long NN = (long)N * N, n = NN * N;
     const double hSq = h * h;
@@ -90,6 +92,15 @@ static void coarse_rows(double *A, int N, double h, const double *eps, double si
                         pin = 0;
                 }
     p = 0;
+    if (pin && s) /* so does an unknown with s > 0 */
+        for (int i = 0; i < N; i++)
+            for (int j = 0; j < N; j++)
+                for (int k = 0; k < N; k++, p++) {
+                    const int x[3] = {i, j, k};
+                    if (s[p] > 0. && !bc_bound(&b, N, x))
+                        pin = 0;
+                }
+    p = 0;
     for (int i = 0; i < N; i++)
         for (int j = 0; j < N; j++)
             for (int k = 0; k < N; k++, p++) {
@@ -109,14 +120,14 @@ static void coarse_rows(double *A, int N, double h, const double *eps, double si
                 if (!eps) {
                     for (int t = 0; t < 6; t++)
                         row[q[t]] += off;
-                    row[p] = -diag;
+                    row[p] = s ? -((6. + (sigma + s[p]) * hSq) * invHsq) : -diag;
                     continue;
                 }
                 const double e = eps[p];
                 double a[6];
                 for (int t = 0; t < 6; t++)
                     a[t] = 0.5 * (e + eps[q[t]]);
-                const double dg = ((((a[0] + a[1]) + a[2]) + a[3]) + a[4]) + a[5] + shift;
+                const double dg = ((((a[0] + a[1]) + a[2]) + a[3]) + a[4]) + a[5] + (s ? (sigma + s[p]) * hSq : shift);
                 for (int t = 0; t < 6; t++)
                     row[q[t]] += a[t] * invHsq;
                 row[p] = -(dg * invHsq);
@@ -124,24 +135,29 @@ static void coarse_rows(double *A, int N, double h, const double *eps, double si
 }
 
 /* the exported forms (include/mg3d.h): coarse_rows at the arguments each one names */
-void mg3d_coarse_matrix(double *A, int N, double h) { coarse_rows(A, N, h, NULL, 0., 0, 0, NULL); }
-void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma) { coarse_rows(A, N, h, NULL, sigma, 0, 0, NULL); }
+void mg3d_coarse_matrix(double *A, int N, double h) { coarse_rows(A, N, h, NULL, 0., 0, 0, NULL, NULL); }
+void mg3d_coarse_matrix_shift(double *A, int N, double h, double sigma) { coarse_rows(A, N, h, NULL, sigma, 0, 0, NULL, NULL); }
 void mg3d_coarse_matrix_coef(double *A, int N, double h, const double *eps, double sigma)
 {
-    coarse_rows(A, N, h, eps, sigma, 0, 0, NULL);
+    coarse_rows(A, N, h, eps, sigma, 0, 0, NULL, NULL);
 }
 void mg3d_coarse_matrix_periodic(double *A, int N, double h, const double *eps, double sigma, int axes)
 {
-    coarse_rows(A, N, h, eps, sigma, axes, 0, NULL);
+    coarse_rows(A, N, h, eps, sigma, axes, 0, NULL, NULL);
 }
 void mg3d_coarse_matrix_bc(double *A, int N, double h, const double *eps, double sigma, int axes, int faces)
 {
-    coarse_rows(A, N, h, eps, sigma, axes, faces, NULL);
+    coarse_rows(A, N, h, eps, sigma, axes, faces, NULL, NULL);
 }
 void mg3d_coarse_matrix_mask(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
                              const unsigned char *mask)
 {
-    coarse_rows(A, N, h, eps, sigma, axes, faces, mask);
+    coarse_rows(A, N, h, eps, sigma, axes, faces, mask, NULL);
+}
+void mg3d_coarse_matrix_field(double *A, int N, double h, const double *eps, double sigma, int axes, int faces,
+                              const unsigned char *mask, const double *s)
+{
+    coarse_rows(A, N, h, eps, sigma, axes, faces, mask, s);
 }
 
 /* A prescribed outward normal derivative folded into the right-hand side of the homogeneous Neumann operator (mg3d.h) */

@@ -104,13 +104,17 @@ const char *mg3d_option_key(int index);           /* NULL past the end */
  * duplicate points receive copies, and above it the MG3D_NEUMANN_* mask of reflected faces (mg3d_ctx_set_neumann), whose
  * points are unknowns; m, the level's fixed-point bytes in the padded layout (mg3d_ctx_set_mask), NULL for none -- the
  * colour pass skips a fixed point, the residual is 0. there, apply_dot's q is 0. there.  bc and m are nonzero on
- * single-domain levels only, which take no windows.  A context's level: mg3d_level_operator (mg3d_ctx.h). */
+ * single-domain levels only, which take no windows; s, the level's screening field in the padded layout
+ * (mg3d_ctx_set_shift_field), NULL for none -- div(eps grad u) - (sigma + s) u, with e set (the eps kernels alone have the
+ * form: a context without eps gives them eps = 1 at every point); k_smooth_color, k_residual, k_pcg_apply_dot and k_step_rhs
+ * take it, the field output does not look at it.  A context's level: mg3d_level_operator (mg3d_ctx.h). */
 struct LevelOperator {
     LevelOp op;
     double sigma;
     const double *e;
     int bc;
     const unsigned char *m;
+    const double *s;
 };
 static inline int mg3d_bc(int periodic, int neumann) { return periodic | neumann << 3; }
 
@@ -379,6 +383,10 @@ void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);
 void k_pack(const Geom &g, double *v, const mg3d_array &a, hipStream_t s);
 void k_unpack(const Geom &g, const double *v, const mg3d_array &a, hipStream_t s);
 void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s);
+/* the screening field (mg3d_ctx_set_shift_field).  k_field_check: k_coef_check with "finite and >= 0".  k_field_count:
+ * *out += the number of UNKNOWNS (k_mask_count's) at which the level's field f, in the padded layout, is > 0 */
+void k_field_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s);
+void k_field_count(const Geom &g, const double *f, int bc, unsigned long long *out, hipStream_t s);
 /* field output (mg3d_field.hip; single-domain levels, bc the boundary word; include/mg3d.h "Field output" has the formulas).
  * k_gradient: cs * (the central / wrapped / reflected / one-sided difference of u) per axis at all N^3 points into the
  * caller's arrays out[0..2] (NULL: not wanted; at least one; float or double each, any strides >= 1), one launch.

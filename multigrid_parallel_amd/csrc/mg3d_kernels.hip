@@ -54,6 +54,12 @@
  * ordinary stencil.  Bytes on Dirichlet faces lie outside every launch; bytes on periodic duplicates are never read.
  * Coarse levels take the mask by injection.  tests/_mask_ref.py states the same in numpy.
  *
+ * Screening field (mg3d_ctx_set_shift_field): a level may carry one double s >= 0 per point in its padded layout, and its
+ * operator is div(eps grad u) - (sigma + s) u: s, D and every expression above stay, with dg = D + (sigma + s[p])*hSq formed
+ * per point in this order.  Only the eps kernels have the form (SFIELD); a context without eps runs them over eps = 1 at
+ * every point, where 0.5*(1 + 1) is 1, 1*v is v and D is 6.  Coarse levels take s by the restriction below (full weighting
+ * at the unknowns, injection on Dirichlet faces).  tests/_shift_field_ref.py states the same in numpy.
+ *
  * The launchers take both masks as one boundary word bc = periodic axes | Neumann faces << 3 (mg3d_bc); the stencil
  * kernels are instantiated per boundary mode: BC_PLAIN (bc = 0), BC_WRAP (periodic axes only), BC_REFLECT (a Neumann
  * face, with or without periodic axes).
@@ -79,7 +85,8 @@ enum { BC_PLAIN = 0, BC_WRAP = 1, BC_REFLECT = 2 };
 static inline int bc_mode(int bc) { return (bc >> 3) ? BC_REFLECT : (bc ? BC_WRAP : BC_PLAIN); }
 /* the one launch ladder: f(coef, mode, mask) with eps set or not, the boundary mode of bc and whether the level has fixed
  * points (m) as compile-time constants --
- * dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) { launch_op(mask, OP_KERNELS(kernel, coef(), mode()), ...); }) */
+ * dispatch_op(e, bc, m, [&](auto coef, auto mode, auto mask) { launch_op(mask, OP_KERNELS(kernel, coef(), mode(), false), ...); })
+ * (the `false`: no screening field; a launcher of the eps side asks for A.s itself and takes OP_KERNELS_FIELD, below) */
 template <class F>
 static void dispatch_op(const double *e, int bc, const unsigned char *m, F f)
 {
@@ -120,6 +127,24 @@ static void launch_op(Mask, void (*plain)(P0...), void (*masked)(P1...), dim3 gr
     else
         hipLaunchKernelGGL(plain, grid, block, 0, s, args...);
 }
+/* SFIELD, the fourth constant, on the eps side of the family only: the level has a screening field s (mg3d_ctx_set_shift_field)
+ * and the diagonal is dg = D + (sigma + s[p])*hSq, formed per point in this order.  The kernel takes the field and hSq as
+ * one more trailing argument, in front of the mask; the argument every kernel has for sigma*hSq carries sigma itself.  s is
+ * read at the point's own offset, lanes contiguous in k, as d is.  As with MASK, the SFIELD = false instantiations have no
+ * such argument: their argument lists and their code are what they were. */
+struct FieldArg {
+    const double *__restrict__ s;
+    double hSq;
+};
+#define OP_KERNELS_FIELD(kernel, ...) kernel<__VA_ARGS__, true, false, FieldArg>, kernel<__VA_ARGS__, true, true, FieldArg, MaskPtr>
+/* the trailing arguments of an instantiation are (), (m), (f) or (f, m): the point's diagonal term beside D, and is it fixed */
+__device__ __forceinline__ double point_dg0(double dg0, long long) { return dg0; }
+__device__ __forceinline__ double point_dg0(double dg0, long long, const unsigned char *) { return dg0; }
+template <class... M> __device__ __forceinline__ double point_dg0(double sigma, long long p, FieldArg f, M...)
+{
+    return (sigma + f.s[p]) * f.hSq;
+}
+__device__ __forceinline__ bool mask_fixed(long long p, FieldArg, const unsigned char *m) { return m[p] != 0; }
 /* is the low / high face of axis ax (0 i, 1 j, 2 k) a Neumann face */
 __host__ __device__ __forceinline__ bool bc_ref_lo(int bc, int ax) { return (bc >> (3 + 2 * ax)) & 1; }
 __host__ __device__ __forceinline__ bool bc_ref_hi(int bc, int ax) { return (bc >> (4 + 2 * ax)) & 1; }
@@ -169,6 +194,8 @@ __device__ __forceinline__ void store_dup(const Geom &g, double *__restrict__ a,
  *         [lo, hi], and whatever axis is periodic beside it wraps as in BC_WRAP
  *   MASK  the level has fixed points: one byte per point and pass, read where the point's own d would be (lanes
  *         contiguous in k, as the walk has them); the bytes are the pack M of one trailing argument
+ *   SFIELD (with COEF only) the level has a screening field: dg = D + (sigma + s[p])*hSq, one more double per point and pass,
+ *         read where the point's own d is (FieldArg)
  * The residual and the colour pass with eps give each thread one (j, k) column of `chunk` planes, lanes contiguous in
  * k, and keep the i-1 / i / i+1 values of v (and eps) of the column in registers; the constant colour pass gives a lane
  * one k-pair of a row (measured at 513^3 the column form of that pass took 0.76 ms against 0.64 ms).
@@ -364,12 +391,12 @@ __global__ void __launch_bounds__(256) smooth_color_kernel(Geom g, double *__res
 }
 
 /* eps set: a thread updates the points of its column that have colour `color` (every other plane) */
-template <int BC, bool MASK, class... M>
+template <int BC, bool SFIELD, bool MASK, class... M>
 __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restrict__ v, const double *__restrict__ e,
                                                          const double *__restrict__ d, double hSq, double shift,
                                                          int color, int bc, int chunk, int i_lo, int i_hi, M... fixed)
 {
-    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
+    static_assert(sizeof...(M) == (SFIELD ? 1 : 0) + (MASK ? 1 : 0), "SFIELD, MASK: the field, then the mask, trail");
     Column c;
     if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
@@ -382,7 +409,7 @@ __global__ void __launch_bounds__(256) coef_color_kernel(Geom g, double *__restr
             if (mask_fixed(pt.p, fixed...))
                 return;
         double s, dg;
-        pt.sum(shift, s, dg);
+        pt.sum(point_dg0(shift, pt.p, fixed...), s, dg);
         store_dup(g, v, pt.p, (s - hSq * d[pt.p]) / dg, pt.di(), c.dj, c.dk);
     });
 }
@@ -397,8 +424,12 @@ void k_smooth_color(const Geom &g, double *v, const double *d, const LevelOperat
         if constexpr (coef()) {
             int chunk;
             const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk);
-            launch_op(mask, OP_KERNELS(coef_color_kernel, mode()), grid, block, s, A.m, g, v, A.e, d, A.op.hSq,
-                      A.sigma * A.op.hSq, color, A.bc, chunk, i_lo, i_hi);
+            if (A.s)
+                launch_op(mask, OP_KERNELS_FIELD(coef_color_kernel, mode()), grid, block, s, A.m, g, v, A.e, d, A.op.hSq, A.sigma,
+                          color, A.bc, chunk, i_lo, i_hi, FieldArg{A.s, A.op.hSq});
+            else
+                launch_op(mask, OP_KERNELS(coef_color_kernel, mode(), false), grid, block, s, A.m, g, v, A.e, d, A.op.hSq,
+                          A.sigma * A.op.hSq, color, A.bc, chunk, i_lo, i_hi);
         } else {
             const int pairs = (g.nk + 1) / 2;
             const dim3 grid((pairs + WAVE - 1) / WAVE, (g.nj - 2 + bc_extra(A.bc, 1) + 3) / 4, i_hi - i_lo);
@@ -468,13 +499,14 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const double *__rest
  * diff at every unique interior point; res (optional) receives it there and at the duplicates (mg_3d.h:824-825), partials
  * one sum of diff^2 per block (lanes by shuffle tree, waves 0..3 in order), folded by k_fold: the norm counts every
  * unknown once. */
-template <bool COEF, int BC, bool MASK, class... M>
+template <bool COEF, int BC, bool SFIELD, bool MASK, class... M>
 __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                        const double *__restrict__ d, double invHsq, double dg0,
                                                        double *__restrict__ res, double *__restrict__ partials, int bc,
                                                        int chunk, int i_lo, int i_hi, int acc_lo, int acc_hi, M... fixed)
 {
-    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
+    static_assert(sizeof...(M) == (SFIELD ? 1 : 0) + (MASK ? 1 : 0), "SFIELD, MASK: the field, then the mask, trail");
+    static_assert(COEF || !SFIELD, "SFIELD: the eps side only");
     __shared__ double lds4[4];
     double acc = 0.;
     Column c;
@@ -497,7 +529,7 @@ __global__ void __launch_bounds__(256) residual_kernel(Geom g, const double *__r
             if constexpr (COEF)
                 ea = e[pa];
             double s, dg;
-            stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, dg0, s, dg);
+            stencil<COEF>(v, e, p, c.ojm, c.ojp, c.okm, c.okp, vb, va, eb, eh, ea, point_dg0(dg0, p, fixed...), s, dg);
             double diff;
             if constexpr (MASK) /* a fixed point: 0., whatever d and the sums hold */
                 diff = mask_fixed(p, fixed...) ? 0. : d[p] - invHsq * (s - dg * vh);
@@ -562,8 +594,14 @@ void k_residual(const Geom &g, const double *v, const double *d, const LevelOper
     int chunk;
     const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
-        launch_op(mask, OP_KERNELS(residual_kernel, coef(), mode()), grid, block, s, A.m, g, v, A.e, d, A.op.invHsq, op_dg0(A),
-                  res, partials, A.bc, chunk, i_lo, i_hi, acc_lo, acc_hi);
+        if constexpr (coef())
+            if (A.s) {
+                launch_op(mask, OP_KERNELS_FIELD(residual_kernel, true, mode()), grid, block, s, A.m, g, v, A.e, d, A.op.invHsq,
+                          A.sigma, res, partials, A.bc, chunk, i_lo, i_hi, acc_lo, acc_hi, FieldArg{A.s, A.op.hSq});
+                return;
+            }
+        launch_op(mask, OP_KERNELS(residual_kernel, coef(), mode(), false), grid, block, s, A.m, g, v, A.e, d, A.op.invHsq,
+                  op_dg0(A), res, partials, A.bc, chunk, i_lo, i_hi, acc_lo, acc_hi);
     });
     k_fold(partials, (int)(grid.x * grid.y * grid.z), sumsq_out, s);
 }
@@ -583,13 +621,14 @@ __device__ __forceinline__ double bc_weight(int bc, int ax, int x, int N)
 {
     return ((x == 0 && bc_ref_lo(bc, ax)) || (x == N - 1 && bc_ref_hi(bc, ax))) ? 0.5 : 1.;
 }
-template <bool COEF, int BC, bool MASK, class... M>
+template <bool COEF, int BC, bool SFIELD, bool MASK, class... M>
 __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                         double invHsq, double dg0, double *__restrict__ q,
                                                         double *__restrict__ partials, int bc, int chunk, int i_lo,
                                                         int i_hi, M... fixed)
 {
-    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask is the one trailing argument");
+    static_assert(sizeof...(M) == (SFIELD ? 1 : 0) + (MASK ? 1 : 0), "SFIELD, MASK: the field, then the mask, trail");
+    static_assert(COEF || !SFIELD, "SFIELD: the eps side only");
     __shared__ double lds4[4];
     double acc = 0.;
     Column c;
@@ -599,7 +638,7 @@ __global__ void __launch_bounds__(256) pcg_apply_kernel(Geom g, const double *__
             wjk = bc_weight(bc, 1, c.j, g.N) * bc_weight(bc, 2, c.k, g.N);
         walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
             double s, dg;
-            pt.sum(dg0, s, dg);
+            pt.sum(point_dg0(dg0, pt.p, fixed...), s, dg);
             double ap;
             if constexpr (MASK) /* a fixed point: q = 0. (p is 0. there, so nothing enters the dot) */
                 ap = mask_fixed(pt.p, fixed...) ? 0. : invHsq * (s - dg * pt.vh);
@@ -628,8 +667,14 @@ int k_pcg_apply_dot(const Geom &g, const double *p, const LevelOperator &A, doub
     int chunk;
     const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
-        launch_op(mask, OP_KERNELS(pcg_apply_kernel, coef(), mode()), grid, block, s, A.m, g, p, A.e, A.op.invHsq, op_dg0(A), q,
-                  partials, A.bc, chunk, i_lo, i_hi);
+        if constexpr (coef())
+            if (A.s) {
+                launch_op(mask, OP_KERNELS_FIELD(pcg_apply_kernel, true, mode()), grid, block, s, A.m, g, p, A.e, A.op.invHsq,
+                          A.sigma, q, partials, A.bc, chunk, i_lo, i_hi, FieldArg{A.s, A.op.hSq});
+                return;
+            }
+        launch_op(mask, OP_KERNELS(pcg_apply_kernel, coef(), mode(), false), grid, block, s, A.m, g, p, A.e, A.op.invHsq,
+                  op_dg0(A), q, partials, A.bc, chunk, i_lo, i_hi);
     });
     const int np = (int)(grid.x * grid.y * grid.z);
     k_fold(partials, np, dot_out, s);
@@ -935,18 +980,19 @@ double k_wpcg_weight_sum(const Geom &g, int bc)
  * theta < 1: pcg_apply_kernel's body on the column walk with one more operand and neither a sum nor partials.  src is a
  * uniform branch: the six instantiations stay six.  Both launches take the grids of the passes they are modelled on (column_grid,
  * pair_grid) as they are: the cap on blocks those keep for the partial sums means nothing here and does no harm. */
-template <bool COEF, int BC>
+template <bool COEF, int BC, bool SFIELD, class... M>
 __global__ void __launch_bounds__(256) step_rhs_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
                                                        const double *__restrict__ src, double invHsq, double dg0, double a,
                                                        double c1, double b, double *__restrict__ d, int bc, int chunk,
-                                                       int i_lo, int i_hi)
+                                                       int i_lo, int i_hi, M... field)
 {
+    static_assert(sizeof...(M) == (SFIELD ? 1 : 0) && (COEF || !SFIELD), "SFIELD: the field trails, on the eps side only");
     Column c;
     if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
         return;
     walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
         double s, dg;
-        pt.sum(dg0, s, dg);
+        pt.sum(point_dg0(dg0, pt.p, field...), s, dg);
         const double q = invHsq * (s - dg * pt.vh);
         double t = a * pt.vh + c1 * q;
         if (src)
@@ -995,8 +1041,14 @@ int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOp
     const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
     /* (no MASK form: d at a fixed point is never read, what the pass writes there is unspecified) */
     dispatch_op(A.e, A.bc, nullptr, [&](auto coef, auto mode, auto) {
-        hipLaunchKernelGGL((step_rhs_kernel<coef(), mode()>), grid, block, 0, s, g, u0, A.e, src, A.op.invHsq, op_dg0(A), a, c1, b,
-                           d, A.bc, chunk, i_lo, i_hi);
+        if constexpr (coef())
+            if (A.s) {
+                hipLaunchKernelGGL((step_rhs_kernel<true, mode(), true, FieldArg>), grid, block, 0, s, g, u0, A.e, src,
+                                   A.op.invHsq, A.sigma, a, c1, b, d, A.bc, chunk, i_lo, i_hi, FieldArg{A.s, A.op.hSq});
+                return;
+            }
+        hipLaunchKernelGGL((step_rhs_kernel<coef(), mode(), false>), grid, block, 0, s, g, u0, A.e, src, A.op.invHsq, op_dg0(A), a,
+                           c1, b, d, A.bc, chunk, i_lo, i_hi);
     });
     return 0;
 }
@@ -1734,15 +1786,17 @@ void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s)
 
 /* ------------------------------------------------------------- fixed points */
 
-/* the fixed UNKNOWNS of a level, counted: one 64-bit atomic add per block that found any */
-__global__ void __launch_bounds__(256) mask_count_kernel(Geom g, const unsigned char *__restrict__ m, int bc,
+/* the fixed UNKNOWNS of a level, counted: one 64-bit atomic add per block that found any.  T = double: the unknowns at
+ * which a screening field is > 0 (k_field_count) */
+template <class T>
+__global__ void __launch_bounds__(256) mask_count_kernel(Geom g, const T *__restrict__ m, int bc,
                                                          unsigned long long *__restrict__ out)
 {
     const int k = blockIdx.x * WAVE + threadIdx.x;
     const int j = blockIdx.y * 4 + threadIdx.y;
     const int i = blockIdx.z;
     const int N = g.N;
-    const bool fixed = k < N && j < N && bc_unknown(bc, N, i, j, k) && m[gidx(g, i, j, k)] != 0;
+    const bool fixed = k < N && j < N && bc_unknown(bc, N, i, j, k) && m[gidx(g, i, j, k)] > (T)0;
     __shared__ unsigned int row_cnt[4];
     const unsigned long long bal = __ballot(fixed);
     if (threadIdx.x == 0)
@@ -1758,7 +1812,13 @@ __global__ void __launch_bounds__(256) mask_count_kernel(Geom g, const unsigned 
 void k_mask_count(const Geom &g, const unsigned char *m, int bc, unsigned long long *out, hipStream_t s)
 {
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
-    hipLaunchKernelGGL(mask_count_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, m, bc, out);
+    hipLaunchKernelGGL(mask_count_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, g, m, bc, out);
+}
+
+void k_field_count(const Geom &g, const double *f, int bc, unsigned long long *out, hipStream_t s)
+{
+    dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
+    hipLaunchKernelGGL(mask_count_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, f, bc, out);
 }
 
 /* the caller's bytes (any element strides) into the level's padded layout; a periodic duplicate takes its source's byte */
@@ -1834,8 +1894,9 @@ __global__ void __launch_bounds__(256) unpack_kernel(Geom g, const double *__res
 }
 
 /* A wave is one row of 64 k: its bad entries as a ballot, the lowest bad lane is the lowest dense index of the row; the
- * block's four rows meet in LDS and thread (0,0) issues the two atomics, only when the block found anything. */
-template <class T>
+ * block's four rows meet in LDS and thread (0,0) issues the two atomics, only when the block found anything.
+ * ZERO_OK: a screening field (k_field_check) -- finite and >= 0 instead of > 0. */
+template <class T, bool ZERO_OK>
 __global__ void __launch_bounds__(256) coef_check_kernel(Geom g, const T *__restrict__ a, long long si, long long sj,
                                                          long long sk, int axes, unsigned long long *__restrict__ out)
 {
@@ -1848,7 +1909,7 @@ __global__ void __launch_bounds__(256) coef_check_kernel(Geom g, const T *__rest
         const bool dup = ((axes & 1) && i == N - 1) || ((axes & 2) && j == N - 1) || ((axes & 4) && k == N - 1);
         if (!dup) {
             const double e = (double)a[si * i + sj * j + sk * k];
-            bad = !(e > 0.) || !(e <= 1.7976931348623157e308); /* NaN, <= 0, +inf */
+            bad = !(ZERO_OK ? e >= 0. : e > 0.) || !(e <= 1.7976931348623157e308); /* NaN, <= 0 (ZERO_OK: < 0), +inf */
         }
     }
     __shared__ unsigned long long row_min[4];
@@ -1894,15 +1955,26 @@ void k_unpack(const Geom &g, const double *v, const mg3d_array &a, hipStream_t s
                            a.stride[1], a.stride[2]);
 }
 
-void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s)
+template <bool ZERO_OK>
+static void launch_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s)
 {
     dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
     if (a.dtype == MG3D_F32)
-        hipLaunchKernelGGL(coef_check_kernel<float>, grid, dim3(WAVE, 4, 1), 0, s, g, (const float *)a.ptr, a.stride[0],
-                           a.stride[1], a.stride[2], bc & 7, out);
+        hipLaunchKernelGGL((coef_check_kernel<float, ZERO_OK>), grid, dim3(WAVE, 4, 1), 0, s, g, (const float *)a.ptr,
+                           a.stride[0], a.stride[1], a.stride[2], bc & 7, out);
     else
-        hipLaunchKernelGGL(coef_check_kernel<double>, grid, dim3(WAVE, 4, 1), 0, s, g, (const double *)a.ptr, a.stride[0],
-                           a.stride[1], a.stride[2], bc & 7, out);
+        hipLaunchKernelGGL((coef_check_kernel<double, ZERO_OK>), grid, dim3(WAVE, 4, 1), 0, s, g, (const double *)a.ptr,
+                           a.stride[0], a.stride[1], a.stride[2], bc & 7, out);
+}
+
+void k_coef_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s)
+{
+    launch_check<false>(g, a, bc, out, s);
+}
+
+void k_field_check(const Geom &g, const mg3d_array &a, int bc, unsigned long long *out, hipStream_t s)
+{
+    launch_check<true>(g, a, bc, out, s);
 }
 
 /* --------------------------------------------------------------- field output
