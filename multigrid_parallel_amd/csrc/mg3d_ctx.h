@@ -1,4 +1,5 @@
-/* mg3d_ctx.h -- solver context internals shared by mg3d_ctx.hip and mg3d_dist.hip (not installed). */
+/* mg3d_ctx.h -- solver context internals shared by mg3d_ctx.hip, mg3d_operator.hip and the other files that work on a
+ * context (not installed). */
 #ifndef MG3D_CTX_H
 #define MG3D_CTX_H
 
@@ -21,6 +22,26 @@ struct StageTimer {
     double seconds;
 };
 
+/* One per-level field of the operator (mg3d_operator.hip): eps, the fixed-point bytes, the screening field.  lv: one device
+ * array per level in the padded layout of the level's doubles (empty: the context has no such field); host0: level 0's,
+ * dense, for the coarse matrix; count: unknowns of level 0 ([0]) and of the finest level ([1]) that the field singles out
+ * under the present boundary masks -- what is counted is the field's own business, mg3d_ctx says it for each */
+template <class T> struct OperatorField {
+    std::vector<T *> lv;
+    std::vector<T> host0;
+    unsigned long long count[2] = {0, 0};
+    bool set() const { return !lv.empty(); }
+    T *at(int level) const { return lv.empty() ? nullptr : lv[level]; }
+};
+/* frees the levels and forgets the host copy and the counts (every way a field leaves a context, mg3d_ctx_destroy too;
+ * nothing in flight may read it any more) */
+template <class T> static inline void mg3d_field_free(OperatorField<T> &f)
+{
+    for (T *p : f.lv)
+        (void)hipFree(p);
+    f = OperatorField<T>();
+}
+
 struct mg3d_ctx {
     int c, L, iters;
     double length;
@@ -36,25 +57,21 @@ struct mg3d_ctx {
     bool lu_built;
     double lu_h;
     /* the variable coefficient of div(eps grad u) - sigma u (mg3d_ctx_set_coefficient): eps of every level in the padded
-     * layout (empty: the constant-coefficient operator) and level 0's, dense, for the coarse matrix */
-    std::vector<double *> eps;
-    std::vector<double> eps0;
+     * layout (not set: the constant-coefficient operator) and level 0's, dense, for the coarse matrix; no counts */
+    OperatorField<double> eps;
     /* fixed points (mg3d_ctx_set_mask): one byte per point of every level in the padded layout, the finest level's as given
-     * and the others' by injection (empty: no mask); level 0's, dense, for the coarse matrix; and how many fixed UNKNOWNS
+     * and the others' by injection (not set: no mask); level 0's, dense, for the coarse matrix; and how many fixed UNKNOWNS
      * level 0 and the finest level have under the present boundary masks (recounted when those change) */
-    std::vector<unsigned char *> mask;
-    std::vector<unsigned char> mask0;
-    unsigned long long mask_fixed0 = 0, mask_fixed_top = 0;
+    OperatorField<unsigned char> mask;
     /* the screening field of div(eps grad u) - (sigma + s) u (mg3d_ctx_set_shift_field): s of every level in the padded
-     * layout, the finest level's as given and each coarser one's by the context's own restriction (empty: no field); level
+     * layout, the finest level's as given and each coarser one's by the context's own restriction (not set: no field); level
      * 0's, dense, for the coarse matrix; how many UNKNOWNS of level 0 and of the finest level have s > 0 under the present
-     * boundary masks (retaken, with the coarser levels, when those change); and, while the context has a field and no eps,
-     * eps = 1 at every point of every level for the eps kernels, which alone have the field form (empty otherwise; the
-     * context still has no coefficient: mg3d_ctx_has_coefficient) */
-    std::vector<double *> sfield;
-    std::vector<double> sfield0;
-    unsigned long long sfield_pos0 = 0, sfield_pos_top = 0;
-    std::vector<double *> ones;
+     * boundary masks (retaken, with the coarser levels, when those change) */
+    OperatorField<double> sfield;
+    /* while the context has a field and no eps, eps = 1 at every point of every level for the eps kernels, which alone
+     * have the field form (not set otherwise; the context still has no coefficient: mg3d_ctx_has_coefficient); neither a
+     * host copy nor counts */
+    OperatorField<double> ones;
     /* periodic axes (mg3d_ctx_set_periodic; MG3D_PERIODIC_* mask, 0: Dirichlet faces everywhere) and the padded level-0
      * right-hand side of the direct solve that k_per_coarse_rhs builds from d (allocated with the first nonzero mask) */
     int periodic;
@@ -154,8 +171,8 @@ static inline void swap_u(Level &l)
  * with a screening field, whose levels run the SFIELD forms of the eps kernels */
 static inline bool mg3d_fused(const mg3d_ctx *ctx)
 {
-    return ctx->fused && ctx->eps.empty() && ctx->periodic == 0 && ctx->neumann == 0 && ctx->mask.empty() &&
-           ctx->sfield.empty();
+    return ctx->fused && !ctx->eps.set() && ctx->periodic == 0 && ctx->neumann == 0 && !ctx->mask.set() &&
+           !ctx->sfield.set();
 }
 /* a sweep launch on a level of this context, u -> alt: the caller adds what the launch does (SweepLaunch) */
 static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
@@ -186,13 +203,13 @@ static inline int mg3d_ctx_bc(const mg3d_ctx *ctx) { return mg3d_bc(ctx->periodi
  * field output, which ignores s as it ignores sigma */
 static inline LevelOperator mg3d_level_operator(const mg3d_ctx *ctx, int level, bool screened = true)
 {
-    const bool field = screened && !ctx->sfield.empty();
+    const bool field = screened && ctx->sfield.set();
     return {mg3d_level_op(ctx->lv[level].h, ctx->sigma),
             ctx->sigma,
-            !ctx->eps.empty() ? ctx->eps[level] : (field ? ctx->ones[level] : nullptr),
+            ctx->eps.set() ? ctx->eps.at(level) : (field ? ctx->ones.at(level) : nullptr),
             mg3d_ctx_bc(ctx),
-            ctx->mask.empty() ? nullptr : ctx->mask[level],
-            field ? ctx->sfield[level] : nullptr};
+            ctx->mask.at(level),
+            field ? ctx->sfield.at(level) : nullptr};
 }
 /* sigma = 0, every axis periodic or Neumann on both faces, no fixed unknown on level 0 and no unknown of level 0 at which
  * its screening field is > 0: constants are in the kernel of the coarsest operator, unknown (0,0,0) of level 0 is pinned */
@@ -201,12 +218,12 @@ static inline bool mg3d_ctx_pinned(const mg3d_ctx *ctx)
     bool closed = true;
     for (int ax = 0; ax < 3; ax++)
         closed = closed && ((ctx->periodic >> ax & 1) || (ctx->neumann >> (2 * ax) & 3) == 3);
-    return closed && ctx->sigma == 0. && ctx->mask_fixed0 == 0 && ctx->sfield_pos0 == 0;
+    return closed && ctx->sigma == 0. && ctx->mask.count[0] == 0 && ctx->sfield.count[0] == 0;
 }
 /* ... and none on the finest level either: the system itself is singular (mg3d_wpcg_solve projects) */
 static inline bool mg3d_ctx_singular(const mg3d_ctx *ctx)
 {
-    return mg3d_ctx_pinned(ctx) && ctx->mask_fixed_top == 0 && ctx->sfield_pos_top == 0;
+    return mg3d_ctx_pinned(ctx) && ctx->mask.count[1] == 0 && ctx->sfield.count[1] == 0;
 }
 /* field `field` of `level` was written from outside the cycle (see faces_dirty), and how -- what the zero map of the top
  * level's d (dz_state) makes of it: MG3D_WROTE_DEVICE a kernel of the library wrote values nobody has looked at (NONE),
@@ -244,6 +261,13 @@ bool mg3d_can_legs(const mg3d_ctx *ctx, int q);
 /* carried state -> the finished cycle's own u; a no-op (MG3D_OK) otherwise.  An error leaves the carried state in place. */
 int mg3d_drop_carry(mg3d_ctx *ctx);
 int mg3d_drop_carry_keep(mg3d_ctx *ctx); /* the same without clearing red_tail: mg3d_vcycle(s) themselves */
+/* what mg3d_ctx.hip and mg3d_operator.hip both need of mg3d_ctx.hip: */
+/* MG3D_ERR_HIP "<who>: kernel launch failed: ..." when a launch since the last look left an error */
+int mg3d_launch_ok(const char *who);
+/* MG3D_ERR_ARG unless ctx is a context, field one of MG3D_U / _D / _R and level one of its levels */
+int mg3d_check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who);
+/* frees the coarse factor and its work space (nothing in flight may read them any more) */
+void mg3d_free_lu(mg3d_ctx *ctx);
 /* device arrays (mg3d_ctx.hip; mg3d_step.hip uses them for the source).  mg3d_array_check: MG3D_ERR_ARG unless `a` is a
  * usable descriptor of device memory of the context's device (`writable`: every stride >= 1).  mg3d_stream_join: the
  * two-way join of the caller's stream with the context's -- out = false, before the kernel: the context's stream waits for

@@ -159,7 +159,7 @@ static void free_band(LuBand &b)
     memset(&b, 0, sizeof b);
 }
 
-static void free_lu(mg3d_ctx *ctx)
+void mg3d_free_lu(mg3d_ctx *ctx)
 {
     free_band(ctx->lu);
     free_band(ctx->lu_in);
@@ -183,15 +183,11 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
         if (l.alt)
             (void)hipFree(l.alt);
     }
-    free_lu(ctx);
-    for (double *e : ctx->eps)
-        (void)hipFree(e);
-    for (unsigned char *m : ctx->mask)
-        (void)hipFree(m);
-    for (double *f : ctx->sfield)
-        (void)hipFree(f);
-    for (double *e : ctx->ones)
-        (void)hipFree(e);
+    mg3d_free_lu(ctx);
+    mg3d_field_free(ctx->eps);
+    mg3d_field_free(ctx->mask);
+    mg3d_field_free(ctx->sfield);
+    mg3d_field_free(ctx->ones);
     if (ctx->per_b)
         (void)hipFree(ctx->per_b);
     for (double *v : ctx->pcg_v)
@@ -618,7 +614,7 @@ template <class At> static int build_band(LuBand &out, long long n, At at)
 
 static int install_lu(mg3d_ctx *ctx, const double *LU, long long n, size_t work_doubles)
 {
-    free_lu(ctx);
+    mg3d_free_lu(ctx);
     CHK(build_band(ctx->lu, n, [&](long long i, long long j) { return LU[i * n + j]; }));
     HIPCHK(hipMalloc(&ctx->lu_work, work_doubles * sizeof(double)));
     /* The reduced system.  A row of the factor that is the identity row (constructCoarseMatrixA's boundary rows,
@@ -684,9 +680,9 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
     double *A = (double *)calloc((size_t)(n * n), sizeof(double)); /* mg_3d.h:283 */
     if (!A)
         return fail(MG3D_ERR_ALLOC, "mg3d_ctx_build_coarse: out of host memory");
-    mg3d_coarse_matrix_field(A, N0, h_coarse, ctx->eps.empty() ? nullptr : ctx->eps0.data(), ctx->sigma, ctx->periodic,
-                             ctx->neumann, ctx->mask.empty() ? nullptr : ctx->mask0.data(),
-                             ctx->sfield.empty() ? nullptr : ctx->sfield0.data()); /* mg_3d.h:288 */
+    mg3d_coarse_matrix_field(A, N0, h_coarse, ctx->eps.set() ? ctx->eps.host0.data() : nullptr, ctx->sigma, ctx->periodic,
+                             ctx->neumann, ctx->mask.set() ? ctx->mask.host0.data() : nullptr,
+                             ctx->sfield.set() ? ctx->sfield.host0.data() : nullptr); /* mg_3d.h:288 */
     mg3d_lu_factor(A, (int)n);                             /* mg_3d.h:289 */
     const int rc = mg3d_ctx_set_lu(ctx, A);
     free(A);
@@ -695,155 +691,6 @@ extern "C" int mg3d_ctx_build_coarse(mg3d_ctx *ctx, double h_coarse)
         ctx->lu_h = h_coarse;
     }
     return rc;
-}
-
-/* The screened operator Delta_h u - sigma u = d on every level (LevelOp).  The argument is checked before anything
- * changes.  Then: a cycle that has run ahead is finished with the operator it started with (mg3d_drop_carry), and a new
- * sigma rebuilds a factor of mg3d_ctx_build_coarse for the spacing it was built with, or drops one installed by
- * mg3d_ctx_set_lu (or mg3d_es_setup): the next cycle returns MG3D_ERR_STATE until a factor is set again. */
-static int operator_changed(mg3d_ctx *ctx);
-static int ensure_ones(mg3d_ctx *ctx, const char *who);
-static void free_ones(mg3d_ctx *ctx);
-static int launch_ok(const char *who);
-static int check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who);
-extern "C" int mg3d_ctx_set_shift(mg3d_ctx *ctx, double sigma)
-{
-    if (!ctx || !(sigma >= 0.) || !isfinite(sigma))
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_shift: %s", ctx ? "sigma must be finite and >= 0" : "NULL context");
-    CHK(mg3d_drop_carry(ctx));
-    if (sigma == ctx->sigma)
-        return MG3D_OK;
-    ctx->sigma = sigma == 0. ? 0. : sigma; /* (-0 is stored as +0) */
-    return operator_changed(ctx);
-}
-
-/* the operator of the context changed (sigma, the coefficient): a factor of mg3d_ctx_build_coarse is built again for the
- * spacing it was built with, one installed by mg3d_ctx_set_lu (or mg3d_es_setup) is dropped */
-static int operator_changed(mg3d_ctx *ctx)
-{
-    if (!ctx->have_lu)
-        return MG3D_OK;
-    if (ctx->lu_built) {
-        const int rc = mg3d_ctx_build_coarse(ctx, ctx->lu_h);
-        if (rc == MG3D_OK)
-            return MG3D_OK;
-        /* no factor of the old operator may survive next to the new one */
-        (void)hipStreamSynchronize(ctx->stream);
-        free_lu(ctx);
-        ctx->lu_built = false;
-        return rc;
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream)); /* a solve still in flight reads the factor */
-    free_lu(ctx);
-    ctx->have_es = false;
-    return MG3D_OK;
-}
-
-extern "C" int mg3d_ctx_get_shift(const mg3d_ctx *ctx, double *sigma)
-{
-    if (!ctx || !sigma)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_shift: NULL argument");
-    *sigma = ctx->sigma;
-    return MG3D_OK;
-}
-
-static void free_eps(mg3d_ctx *ctx)
-{
-    for (double *e : ctx->eps)
-        (void)hipFree(e);
-    ctx->eps.clear();
-    ctx->eps0.clear();
-}
-
-/* eps of every level in the padded layout, unless the context has them already */
-static int alloc_eps(mg3d_ctx *ctx)
-{
-    if (!ctx->eps.empty())
-        return MG3D_OK;
-    const int L = ctx->L;
-    std::vector<double *> e(L, nullptr);
-    for (int l = 0; l < L; l++) {
-        const int rc = mg3d_device_alloc((void **)&e[l], ctx->lv[l].elems * sizeof(double), "mg3d_ctx_set_coefficient");
-        if (rc == MG3D_OK)
-            continue;
-        for (double *q : e)
-            if (q)
-                (void)hipFree(q);
-        return rc;
-    }
-    ctx->eps = e;
-    return MG3D_OK;
-}
-
-/* the two 64-bit device words of k_coef_check and k_mask_count, and the padded level-0 right-hand side of the direct solve
- * (k_coarse_rhs): allocated on first use, freed with the context */
-static int ensure_io_chk(mg3d_ctx *ctx, const char *who)
-{
-    return ctx->io_chk ? MG3D_OK : mg3d_device_alloc((void **)&ctx->io_chk, 2 * sizeof(unsigned long long), who);
-}
-static int ensure_per_b(mg3d_ctx *ctx, const char *who)
-{
-    return ctx->per_b ? MG3D_OK : mg3d_device_alloc((void **)&ctx->per_b, ctx->lv[0].elems * sizeof(double), who);
-}
-
-/* what both forms of mg3d_ctx_set_coefficient do once the finest level's eps is written: its duplicates, the injections,
- * level 0's eps back on the host for the coarse matrix, one host synchronisation -- behind it the caller's array has been
- * read --, the coarse factor */
-static int coefficient_written(mg3d_ctx *ctx, const char *who)
-{
-    const int L = ctx->L;
-    k_per_refresh(ctx->lv[L - 1].g, ctx->eps[L - 1], ctx->periodic, ctx->stream);
-    for (int l = L - 1; l >= 1; l--)
-        k_coef_inject(ctx->lv[l].g, ctx->eps[l], ctx->lv[l - 1].g, ctx->eps[l - 1], ctx->stream);
-    const Level &l0 = ctx->lv[0];
-    const int N0 = l0.g.N;
-    ctx->eps0.resize((size_t)N0 * N0 * N0);
-    HIPCHK(hipMemcpy2DAsync(ctx->eps0.data(), N0 * sizeof(double), ctx->eps[0], l0.g.pitch * sizeof(double), N0 * sizeof(double),
-                            (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    free_ones(ctx); /* (a screening field ran the eps kernels over eps = 1 until now; nothing in flight reads it any more) */
-    return operator_changed(ctx);
-}
-
-/* The variable-coefficient operator div(eps grad u) - sigma u = d (mg3d_kernels.hip) on every level: eps of the finest level
- * as given, of each coarser one by injection.  The array is checked before anything changes; then, as for a new sigma, a
- * cycle that has run ahead is finished with the operator it started with and the coarse factor is rebuilt or dropped.
- * NULL: back to the constant-coefficient operator and its fused schedules. */
-extern "C" int mg3d_ctx_set_coefficient(mg3d_ctx *ctx, const double *eps)
-{
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_coefficient: NULL context");
-    const int L = ctx->L;
-    const Level &top = ctx->lv[L - 1];
-    const int N = top.g.N;
-    const long long n = (long long)N * N * N;
-    /* with periodic axes the duplicates are not read: neither checked nor kept (their sources are copied over them) */
-    const int ax = ctx->periodic;
-    auto dup = [&](long long q) {
-        return ((ax & 1) && q / ((long long)N * N) == N - 1) || ((ax & 2) && (q / N) % N == N - 1) || ((ax & 4) && q % N == N - 1);
-    };
-    if (eps)
-        for (long long p = 0; p < n; p++)
-            if ((!(eps[p] > 0.) || !isfinite(eps[p])) && !(ax && dup(p)))
-                return fail(MG3D_ERR_ARG, "mg3d_ctx_set_coefficient: eps[%lld] = %g (every entry must be finite and > 0)", p,
-                            eps[p]);
-    CHK(mg3d_drop_carry(ctx));
-    if (!eps) {
-        if (ctx->eps.empty())
-            return MG3D_OK;
-        if (!ctx->sfield.empty()) { /* a screening field stays: its eps kernels go on over eps = 1 */
-            CHK(ensure_io_chk(ctx, "mg3d_ctx_set_coefficient"));
-            CHK(ensure_ones(ctx, "mg3d_ctx_set_coefficient"));
-        }
-        HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read eps */
-        free_eps(ctx);
-        return operator_changed(ctx);
-    }
-    CHK(alloc_eps(ctx));
-    HIPCHK(hipMemcpy2DAsync(ctx->eps[L - 1], top.g.pitch * sizeof(double), eps, N * sizeof(double), N * sizeof(double),
-                            (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
-    return coefficient_written(ctx, "mg3d_ctx_set_coefficient"); /* (the host array may go once the call returns) */
 }
 
 /* Device arrays (mg3d_array, include/mg3d.h): the descriptor checks and the stream join of every mg3d_*_device entry point. */
@@ -887,557 +734,8 @@ int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *wh
     return MG3D_OK;
 }
 
-/* mg3d_ctx_set_coefficient from a device array, step for step: the check (a launch that reads the array as given; its two
- * integers cross to the host), then the carried cycle, the pack into the finest level's eps, the duplicates, the
- * injections (coefficient_written).  Two host synchronisations; behind the second one the array has been read, so the
- * caller's stream needs no event of ours. */
-extern "C" int mg3d_ctx_set_coefficient_device(mg3d_ctx *ctx, const mg3d_array *eps, void *stream)
-{
-    static const char who[] = "mg3d_ctx_set_coefficient_device";
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!eps)
-        return mg3d_ctx_set_coefficient(ctx, nullptr);
-    CHK(mg3d_array_check(ctx, eps, false, who));
-    const int L = ctx->L;
-    const Level &top = ctx->lv[L - 1];
-    const int N = top.g.N;
-    const int ax = ctx->periodic;
-    CHK(ensure_io_chk(ctx, who));
-    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
-    unsigned long long chk[2] = {0, 0};
-    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->io_chk + 1, 0xff, sizeof(unsigned long long), ctx->stream));
-    k_coef_check(top.g, *eps, ax, ctx->io_chk, ctx->stream);
-    HIPCHK(hipMemcpyAsync(chk, ctx->io_chk, sizeof chk, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    if (chk[0] != 0) {
-        const long long p = (long long)chk[1];
-        const long long off = eps->stride[0] * (p / ((long long)N * N)) + eps->stride[1] * ((p / N) % N) + eps->stride[2] * (p % N);
-        double v = 0.;
-        float v32 = 0.f;
-        if (eps->dtype == MG3D_F32) {
-            HIPCHK(hipMemcpy(&v32, (const float *)eps->ptr + off, sizeof v32, hipMemcpyDeviceToHost));
-            v = (double)v32;
-        } else {
-            HIPCHK(hipMemcpy(&v, (const double *)eps->ptr + off, sizeof v, hipMemcpyDeviceToHost));
-        }
-        return fail(MG3D_ERR_ARG, "%s: eps[%lld] = %g (every entry must be finite and > 0; %llu entries are not)", who, p, v,
-                    chk[0]);
-    }
-    CHK(mg3d_drop_carry(ctx));
-    CHK(alloc_eps(ctx));
-    {
-        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
-        k_pack(top.g, ctx->eps[L - 1], *eps, ctx->stream);
-    }
-    return coefficient_written(ctx, who);
-}
-
-extern "C" int mg3d_ctx_has_coefficient(const mg3d_ctx *ctx, int *on)
-{
-    if (!ctx || !on)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_coefficient: NULL argument");
-    *on = ctx->eps.empty() ? 0 : 1;
-    return MG3D_OK;
-}
-
-extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
-{
-    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_coefficient"));
-    if (!host)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_coefficient: NULL host pointer");
-    if (ctx->eps.empty())
-        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_coefficient: no coefficient set");
-    const Level &l = ctx->lv[level];
-    const int N = l.g.N;
-    HIPCHK(hipMemcpy2DAsync(host, N * sizeof(double), ctx->eps[level], l.g.pitch * sizeof(double), N * sizeof(double),
-                            (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MG3D_OK;
-}
-
-/* Fixed points (mg3d_ctx_set_mask, mg3d_kernels.hip): one byte per point of every level. */
-static void free_mask(mg3d_ctx *ctx)
-{
-    for (unsigned char *m : ctx->mask)
-        (void)hipFree(m);
-    ctx->mask.clear();
-    ctx->mask0.clear();
-    ctx->mask_fixed0 = ctx->mask_fixed_top = 0;
-}
-
-/* The fixed UNKNOWNS of level 0 and of the finest level under the present boundary masks, and level 0's bytes on the host
- * for the coarse matrix.  One host synchronisation.  (The context has a mask and io_chk.) */
-static int mask_recount(mg3d_ctx *ctx, const char *who)
-{
-    const Level &l0 = ctx->lv[0], &top = ctx->lv[ctx->L - 1];
-    const int N0 = l0.g.N, bc = mg3d_ctx_bc(ctx);
-    unsigned long long cnt[2] = {0, 0};
-    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof cnt, ctx->stream));
-    k_mask_count(l0.g, ctx->mask[0], bc, ctx->io_chk, ctx->stream);
-    k_mask_count(top.g, ctx->mask[ctx->L - 1], bc, ctx->io_chk + 1, ctx->stream);
-    HIPCHK(hipMemcpyAsync(cnt, ctx->io_chk, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->mask0.resize((size_t)N0 * N0 * N0);
-    HIPCHK(hipMemcpy2DAsync(ctx->mask0.data(), N0, ctx->mask[0], l0.g.pitch, N0, (size_t)N0 * N0, hipMemcpyDeviceToHost,
-                            ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    ctx->mask_fixed0 = cnt[0];
-    ctx->mask_fixed_top = cnt[1];
-    return MG3D_OK;
-}
-
-/* a mask whose bytes or counts could not be brought up to date (a HIP error): no half-installed mask stays behind -- the
- * context is left without one, and without a factor of the operator that had it.  The first error is the one reported. */
-static int mask_abandon(mg3d_ctx *ctx, int rc)
-{
-    (void)hipStreamSynchronize(ctx->stream);
-    free_mask(ctx);
-    (void)operator_changed(ctx);
-    return rc;
-}
-
-/* the mask from a checked device array: the cycle that has run ahead, then everything that can fail for want of memory
- * (nothing has changed when it does), the pack into the finest level (duplicates from their sources), the injections, the
- * counts, the coarse factor */
-static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
-{
-    const int L = ctx->L;
-    CHK(mg3d_drop_carry(ctx));
-    CHK(ensure_io_chk(ctx, who));
-    CHK(ensure_per_b(ctx, who));
-    std::vector<unsigned char *> m = ctx->mask;
-    if (m.empty()) {
-        m.assign(L, nullptr);
-        for (int l = 0; l < L; l++) {
-            hipError_t rc = hipMalloc(&m[l], ctx->lv[l].elems);
-            if (rc == hipSuccess)
-                rc = hipMemsetAsync(m[l], 0, ctx->lv[l].elems, ctx->stream); /* (the row padding) */
-            if (rc == hipSuccess)
-                continue;
-            (void)hipStreamSynchronize(ctx->stream);
-            for (unsigned char *q : m)
-                if (q)
-                    (void)hipFree(q);
-            return mg3d_alloc_fail(rc, who, "hipMalloc");
-        }
-    }
-    ctx->mask = m;
-    const int bc = mg3d_ctx_bc(ctx);
-    {
-        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
-        k_mask_pack(ctx->lv[L - 1].g, ctx->mask[L - 1], a, bc, ctx->stream);
-    }
-    for (int l = L - 1; l >= 1; l--)
-        k_mask_inject(ctx->lv[l].g, ctx->mask[l], ctx->lv[l - 1].g, ctx->mask[l - 1], ctx->stream);
-    const int rc = mask_recount(ctx, who);
-    if (rc != MG3D_OK)
-        return mask_abandon(ctx, rc);
-    return operator_changed(ctx);
-}
-
-static int mask_clear(mg3d_ctx *ctx)
-{
-    CHK(mg3d_drop_carry(ctx));
-    if (ctx->mask.empty())
-        return MG3D_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read the bytes */
-    free_mask(ctx);
-    return operator_changed(ctx);
-}
-
-extern "C" int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask)
-{
-    static const char who[] = "mg3d_ctx_set_mask";
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!mask)
-        return mask_clear(ctx);
-    /* through a dense device copy and the pack of the device form: one code path writes the levels */
-    const long long N = ctx->lv[ctx->L - 1].g.N, n = N * N * N;
-    unsigned char *tmp = nullptr;
-    CHK(mg3d_device_alloc((void **)&tmp, (size_t)n, who));
-    int out = MG3D_OK;
-    const hipError_t cp = hipMemcpyAsync(tmp, mask, (size_t)n, hipMemcpyHostToDevice, ctx->stream);
-    if (cp != hipSuccess)
-        out = fail(MG3D_ERR_HIP, "%s: hipMemcpyAsync: %s", who, hipGetErrorString(cp));
-    else {
-        const mg3d_array a = {tmp, MG3D_U8, {N * N, N, 1}};
-        out = mask_install(ctx, a, who);
-    }
-    (void)hipStreamSynchronize(ctx->stream); /* (the host array and the copy may go once the call returns) */
-    (void)hipFree(tmp);
-    return out;
-}
-
-/* the device form: the descriptor is checked before anything happens; every byte value is valid, so there is no check on
- * the device; the one host synchronisation is mask_recount's, behind which the array has been read */
-extern "C" int mg3d_ctx_set_mask_device(mg3d_ctx *ctx, const mg3d_array *mask, void *stream)
-{
-    static const char who[] = "mg3d_ctx_set_mask_device";
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!mask)
-        return mask_clear(ctx);
-    CHK(mg3d_array_check(ctx, mask, false, who, true));
-    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
-    return mask_install(ctx, *mask, who);
-}
-
-extern "C" int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on)
-{
-    if (!ctx || !on)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_mask: NULL argument");
-    *on = ctx->mask.empty() ? 0 : 1;
-    return MG3D_OK;
-}
-
-extern "C" int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host)
-{
-    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_mask"));
-    if (!host)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_mask: NULL host pointer");
-    if (ctx->mask.empty())
-        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_mask: no mask set");
-    const Level &l = ctx->lv[level];
-    const int N = l.g.N;
-    HIPCHK(hipMemcpy2DAsync(host, N, ctx->mask[level], l.g.pitch, N, (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MG3D_OK;
-}
-
-/* The screening field (mg3d_ctx_set_shift_field, mg3d_kernels.hip): one double >= 0 per point of every level,
- * div(eps grad u) - (sigma + s) u. */
-static void free_ones(mg3d_ctx *ctx)
-{
-    for (double *e : ctx->ones)
-        (void)hipFree(e);
-    ctx->ones.clear();
-}
-
-static void free_sfield(mg3d_ctx *ctx)
-{
-    for (double *f : ctx->sfield)
-        (void)hipFree(f);
-    ctx->sfield.clear();
-    ctx->sfield0.clear();
-    ctx->sfield_pos0 = ctx->sfield_pos_top = 0;
-    free_ones(ctx);
-}
-
-/* one array of doubles per level in the padded layout; v is untouched when an allocation fails */
-static int alloc_level_doubles(mg3d_ctx *ctx, std::vector<double *> &v, const char *who)
-{
-    std::vector<double *> a(ctx->L, nullptr);
-    for (int l = 0; l < ctx->L; l++) {
-        const int rc = mg3d_device_alloc((void **)&a[l], ctx->lv[l].elems * sizeof(double), who);
-        if (rc == MG3D_OK)
-            continue;
-        for (double *q : a)
-            if (q)
-                (void)hipFree(q);
-        return rc;
-    }
-    v = a;
-    return MG3D_OK;
-}
-
-/* eps = 1 at the N^3 points of every level, for a context with a field and no coefficient: the eps kernels alone have the
- * field form.  Written by k_pack from one double (every stride 0), which io_chk holds for the length of these launches --
- * whoever uses io_chk next on the stream sets it first.  (The context has io_chk.) */
-static int ensure_ones(mg3d_ctx *ctx, const char *who)
-{
-    if (!ctx->ones.empty())
-        return MG3D_OK;
-    static const double one = 1.;
-    CHK(alloc_level_doubles(ctx, ctx->ones, who));
-    HIPCHK(hipMemcpyAsync(ctx->io_chk, &one, sizeof one, hipMemcpyHostToDevice, ctx->stream));
-    const mg3d_array src = {ctx->io_chk, MG3D_F64, {0, 0, 0}};
-    for (int l = 0; l < ctx->L; l++)
-        k_pack(ctx->lv[l].g, ctx->ones[l], src, ctx->stream);
-    return MG3D_OK;
-}
-
-/* a field that could not be brought up to date (a HIP error): the context is left without one, and without a factor of the
- * operator that had it -- as mask_abandon.  The first error is the one reported. */
-static int sfield_abandon(mg3d_ctx *ctx, int rc)
-{
-    (void)hipStreamSynchronize(ctx->stream);
-    free_sfield(ctx);
-    (void)operator_changed(ctx);
-    return rc;
-}
-
-/* Everything below the finest level's field, under the present boundary masks: its periodic duplicates from their sources,
- * each coarser level by the context's own restriction (k_restrict with the boundary word: full weighting at every coarse
- * unknown with the operator's wrapped or reflected taps, injection on Dirichlet faces, duplicates written), the unknowns with
- * s > 0 on level 0 and on the finest level, level 0's field on the host for the coarse matrix.  One host synchronisation --
- * behind it a caller's array has been read.  (The context has a field and io_chk.) */
-static int sfield_rebuild(mg3d_ctx *ctx, const char *who)
-{
-    const int L = ctx->L, bc = mg3d_ctx_bc(ctx);
-    const Level &l0 = ctx->lv[0], &top = ctx->lv[L - 1];
-    const int N0 = l0.g.N;
-    k_per_refresh(top.g, ctx->sfield[L - 1], bc, ctx->stream);
-    for (int l = L - 1; l >= 1; l--)
-        k_restrict(ctx->lv[l].g, ctx->sfield[l], ctx->lv[l - 1].g, ctx->sfield[l - 1], bc, ctx->stream);
-    unsigned long long cnt[2] = {0, 0};
-    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof cnt, ctx->stream));
-    k_field_count(l0.g, ctx->sfield[0], bc, ctx->io_chk, ctx->stream);
-    k_field_count(top.g, ctx->sfield[L - 1], bc, ctx->io_chk + 1, ctx->stream);
-    HIPCHK(hipMemcpyAsync(cnt, ctx->io_chk, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->sfield0.resize((size_t)N0 * N0 * N0);
-    HIPCHK(hipMemcpy2DAsync(ctx->sfield0.data(), N0 * sizeof(double), ctx->sfield[0], l0.g.pitch * sizeof(double),
-                            N0 * sizeof(double), (size_t)N0 * N0, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    ctx->sfield_pos0 = cnt[0];
-    ctx->sfield_pos_top = cnt[1];
-    return MG3D_OK;
-}
-
-/* what both forms of mg3d_ctx_set_shift_field do before the finest level's field is written -- everything that can fail for
- * want of memory, nothing has changed when it does -- and behind it */
-static int sfield_prepare(mg3d_ctx *ctx, const char *who)
-{
-    CHK(ensure_io_chk(ctx, who));
-    CHK(ensure_per_b(ctx, who)); /* (a positive entry may lift the pin of a context whose boundaries are set later) */
-    if (ctx->eps.empty())
-        CHK(ensure_ones(ctx, who));
-    if (ctx->sfield.empty())
-        CHK(alloc_level_doubles(ctx, ctx->sfield, who));
-    return MG3D_OK;
-}
-static int sfield_written(mg3d_ctx *ctx, const char *who)
-{
-    const int rc = sfield_rebuild(ctx, who);
-    if (rc != MG3D_OK)
-        return sfield_abandon(ctx, rc);
-    return operator_changed(ctx);
-}
-
-static int sfield_clear(mg3d_ctx *ctx)
-{
-    CHK(mg3d_drop_carry(ctx));
-    if (ctx->sfield.empty())
-        return MG3D_OK;
-    HIPCHK(hipStreamSynchronize(ctx->stream)); /* launches in flight read the field */
-    free_sfield(ctx);
-    return operator_changed(ctx);
-}
-
-/* The operator div(eps grad u) - (sigma + s) u = d on every level: s of the finest level as given, of each coarser one by
- * restriction.  The contract of mg3d_ctx_set_coefficient: the array is checked before anything changes (periodic duplicates
- * are skipped); then a cycle that has run ahead is finished with the operator it started with and the coarse factor is
- * rebuilt or dropped.  NULL: back to the context as it was, its fused schedules included. */
-extern "C" int mg3d_ctx_set_shift_field(mg3d_ctx *ctx, const double *s)
-{
-    static const char who[] = "mg3d_ctx_set_shift_field";
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!s)
-        return sfield_clear(ctx);
-    const int L = ctx->L;
-    const Level &top = ctx->lv[L - 1];
-    const int N = top.g.N;
-    const long long n = (long long)N * N * N;
-    const int ax = ctx->periodic;
-    auto dup = [&](long long q) {
-        return ((ax & 1) && q / ((long long)N * N) == N - 1) || ((ax & 2) && (q / N) % N == N - 1) || ((ax & 4) && q % N == N - 1);
-    };
-    for (long long p = 0; p < n; p++)
-        if ((!(s[p] >= 0.) || !isfinite(s[p])) && !(ax && dup(p)))
-            return fail(MG3D_ERR_ARG, "%s: s[%lld] = %g (every entry must be finite and >= 0)", who, p, s[p]);
-    CHK(mg3d_drop_carry(ctx));
-    CHK(sfield_prepare(ctx, who));
-    HIPCHK(hipMemcpy2DAsync(ctx->sfield[L - 1], top.g.pitch * sizeof(double), s, N * sizeof(double), N * sizeof(double),
-                            (size_t)N * N, hipMemcpyHostToDevice, ctx->stream));
-    return sfield_written(ctx, who); /* (the host array may go once the call returns) */
-}
-
-/* the device form, step for step that of mg3d_ctx_set_coefficient_device: the check (a launch that reads the array as
- * given; its two integers cross to the host), then the carried cycle, the pack into the finest level's field, the
- * duplicates, the restrictions and the counts (sfield_written).  Two host synchronisations; behind the second one the array
- * has been read, so the caller's stream needs no event of ours. */
-extern "C" int mg3d_ctx_set_shift_field_device(mg3d_ctx *ctx, const mg3d_array *s, void *stream)
-{
-    static const char who[] = "mg3d_ctx_set_shift_field_device";
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!s)
-        return sfield_clear(ctx);
-    CHK(mg3d_array_check(ctx, s, false, who));
-    const int L = ctx->L;
-    const Level &top = ctx->lv[L - 1];
-    const int N = top.g.N;
-    CHK(ensure_io_chk(ctx, who));
-    CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
-    unsigned long long chk[2] = {0, 0};
-    HIPCHK(hipMemsetAsync(ctx->io_chk, 0, sizeof(unsigned long long), ctx->stream));
-    HIPCHK(hipMemsetAsync(ctx->io_chk + 1, 0xff, sizeof(unsigned long long), ctx->stream));
-    k_field_check(top.g, *s, ctx->periodic, ctx->io_chk, ctx->stream);
-    HIPCHK(hipMemcpyAsync(chk, ctx->io_chk, sizeof chk, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    CHK(launch_ok(who));
-    if (chk[0] != 0) {
-        const long long p = (long long)chk[1];
-        const long long off = s->stride[0] * (p / ((long long)N * N)) + s->stride[1] * ((p / N) % N) + s->stride[2] * (p % N);
-        double v = 0.;
-        float v32 = 0.f;
-        if (s->dtype == MG3D_F32) {
-            HIPCHK(hipMemcpy(&v32, (const float *)s->ptr + off, sizeof v32, hipMemcpyDeviceToHost));
-            v = (double)v32;
-        } else {
-            HIPCHK(hipMemcpy(&v, (const double *)s->ptr + off, sizeof v, hipMemcpyDeviceToHost));
-        }
-        return fail(MG3D_ERR_ARG, "%s: s[%lld] = %g (every entry must be finite and >= 0; %llu entries are not)", who, p, v,
-                    chk[0]);
-    }
-    CHK(mg3d_drop_carry(ctx));
-    CHK(sfield_prepare(ctx, who));
-    {
-        StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
-        k_pack(top.g, ctx->sfield[L - 1], *s, ctx->stream);
-    }
-    return sfield_written(ctx, who);
-}
-
-extern "C" int mg3d_ctx_has_shift_field(const mg3d_ctx *ctx, int *on)
-{
-    if (!ctx || !on)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_has_shift_field: NULL argument");
-    *on = ctx->sfield.empty() ? 0 : 1;
-    return MG3D_OK;
-}
-
-extern "C" int mg3d_ctx_get_shift_field(mg3d_ctx *ctx, int level, double *host)
-{
-    CHK(check_field_level(ctx, 0, level, "mg3d_ctx_get_shift_field"));
-    if (!host)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_shift_field: NULL host pointer");
-    if (ctx->sfield.empty())
-        return fail(MG3D_ERR_STATE, "mg3d_ctx_get_shift_field: no field set");
-    const Level &l = ctx->lv[level];
-    const int N = l.g.N;
-    HIPCHK(hipMemcpy2DAsync(host, N * sizeof(double), ctx->sfield[level], l.g.pitch * sizeof(double), N * sizeof(double),
-                            (size_t)N * N, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MG3D_OK;
-}
-
-/* the boundary masks changed under a mask: the duplicates of a periodic axis take their sources' bytes -- for good: the
- * caller's bytes there are not kept, an axis that stops being periodic finds its plane N-1 with plane 0's bytes -- and which
- * fixed points are unknowns is counted again; under a screening field: the finest level's duplicates likewise, and the
- * coarser levels and the counts are taken again, for the restriction is the boundary word's; then the coarse factor, as
- * for every change of the operator */
-static int mask_boundary_changed(mg3d_ctx *ctx, const char *who)
-{
-    if (!ctx->sfield.empty()) {
-        const int rc = sfield_rebuild(ctx, who);
-        if (rc != MG3D_OK)
-            return sfield_abandon(ctx, rc);
-    }
-    if (ctx->mask.empty())
-        return operator_changed(ctx);
-    for (int l = 0; l < ctx->L; l++)
-        k_mask_refresh(ctx->lv[l].g, ctx->mask[l], mg3d_ctx_bc(ctx), ctx->stream);
-    const int rc = mask_recount(ctx, who);
-    if (rc != MG3D_OK)
-        return mask_abandon(ctx, rc);
-    return operator_changed(ctx);
-}
-
-/* The tail of mg3d_ctx_set_periodic and mg3d_ctx_set_neumann: the boundary masks become (per, neu).  The coarse faces that
- * the restriction weighted are injections again (and vice versa), so every level's are redone; and on a face that was a
- * face of unknowns and is a Dirichlet face now, r of every level still holds the residuals of the other operator where a
- * Dirichlet cycle never writes and the injection reads -- zeroed, as in a context that never had the mask.  Then the mask's
- * bytes and the coarse factor (mask_boundary_changed). */
-static int set_boundaries(mg3d_ctx *ctx, int per, int neu, const char *who)
-{
-    if (per || neu)
-        CHK(ensure_per_b(ctx, who));
-    const int per0 = ctx->periodic, neu0 = ctx->neumann;
-    ctx->periodic = per;
-    ctx->neumann = neu;
-    auto unknown_faces = [](int periodic, int neumann) {
-        int m = neumann;
-        for (int ax = 0; ax < 3; ax++)
-            if (periodic >> ax & 1)
-                m |= 3 << (2 * ax);
-        return m;
-    };
-    const int back = unknown_faces(per0, neu0) & ~unknown_faces(ctx->periodic, ctx->neumann);
-    for (int l = 0; l < ctx->L; l++)
-        k_zero_faces(ctx->lv[l].g, ctx->lv[l].f[MG3D_R], back, ctx->stream);
-    std::fill(ctx->faces_dirty.begin(), ctx->faces_dirty.end(), 1);
-    return mask_boundary_changed(ctx, who);
-}
-
-/* Periodic axes (mg3d_kernels.hip): a mask of MG3D_PERIODIC_I / _J / _K.  The argument is checked before anything
- * changes -- a mask outside 0..7, or a nonzero one on a hierarchy whose coarsest level has fewer than 4 or an odd number
- * of unique points per side, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that has run ahead is finished with the
- * operator it started with and the coarse factor is rebuilt (mg3d_ctx_build_coarse) or dropped.  0: Dirichlet faces
- * everywhere again, the fused schedules included. */
-extern "C" int mg3d_ctx_set_periodic(mg3d_ctx *ctx, int axes)
-{
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: NULL context");
-    if (axes < 0 || axes > 7)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: axes = %d (a mask of MG3D_PERIODIC_I | _J | _K, 0..7)", axes);
-    const int N0 = ctx->lv[0].g.N;
-    if (axes && ((N0 - 1) % 2 != 0 || N0 - 1 < 4))
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: the coarsest level has %d points per side (c - 1 must be even and >= 4)",
-                    N0);
-    for (int ax = 0; ax < 3; ax++)
-        if ((axes >> ax & 1) && (ctx->neumann >> (2 * ax) & 3))
-            return fail(MG3D_ERR_ARG, "mg3d_ctx_set_periodic: axis %d has a Neumann face (mg3d_ctx_set_neumann: mask %d)", ax,
-                        ctx->neumann);
-    CHK(mg3d_drop_carry(ctx));
-    if (axes == ctx->periodic)
-        return MG3D_OK;
-    return set_boundaries(ctx, axes, ctx->neumann, "mg3d_ctx_set_periodic");
-}
-
-extern "C" int mg3d_ctx_get_periodic(const mg3d_ctx *ctx, int *axes)
-{
-    if (!ctx || !axes)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_periodic: NULL argument");
-    *axes = ctx->periodic;
-    return MG3D_OK;
-}
-
-/* Neumann faces (mg3d_kernels.hip): a mask of MG3D_NEUMANN_ILO ... _KHI.  The argument is checked before anything changes
- * -- a mask outside 0..63, or one with a bit on a periodic axis, is MG3D_ERR_ARG.  Then, as for a new sigma, a cycle that
- * has run ahead is finished with the operator it started with and the coarse factor is rebuilt (mg3d_ctx_build_coarse) or
- * dropped.  0: no Neumann face again, the fused schedules included (when no axis is periodic). */
-extern "C" int mg3d_ctx_set_neumann(mg3d_ctx *ctx, int faces)
-{
-    if (!ctx)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: NULL context");
-    if (faces < 0 || faces > 63)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: faces = %d (a mask of MG3D_NEUMANN_ILO ... _KHI, 0..63)", faces);
-    for (int ax = 0; ax < 3; ax++)
-        if ((ctx->periodic >> ax & 1) && (faces >> (2 * ax) & 3))
-            return fail(MG3D_ERR_ARG, "mg3d_ctx_set_neumann: faces = %d has a bit on periodic axis %d (mg3d_ctx_set_periodic: mask %d)",
-                        faces, ax, ctx->periodic);
-    CHK(mg3d_drop_carry(ctx));
-    if (faces == ctx->neumann)
-        return MG3D_OK;
-    return set_boundaries(ctx, ctx->periodic, faces, "mg3d_ctx_set_neumann");
-}
-
-extern "C" int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces)
-{
-    if (!ctx || !faces)
-        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_neumann: NULL argument");
-    *faces = ctx->neumann;
-    return MG3D_OK;
-}
-
 /* ----------------------------------------------------------- data movement */
-static int check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who)
+int mg3d_check_field_level(const mg3d_ctx *ctx, int field, int level, const char *who)
 {
     if (!ctx || field < 0 || field > 2 || level < 0 || level >= ctx->L)
         return fail(MG3D_ERR_ARG, "%s: bad field/level (%d, %d)", who, field, level);
@@ -1447,7 +745,7 @@ static int check_field_level(const mg3d_ctx *ctx, int field, int level, const ch
 extern "C" int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *host)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, field, level, "mg3d_upload"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_upload"));
     if (!host)
         return fail(MG3D_ERR_ARG, "mg3d_upload: NULL host pointer");
     const Level &l = ctx->lv[level];
@@ -1462,7 +760,7 @@ extern "C" int mg3d_upload(mg3d_ctx *ctx, int field, int level, const double *ho
 extern "C" int mg3d_download(mg3d_ctx *ctx, int field, int level, double *host)
 {
     CHK(mg3d_drop_carry_keep(ctx)); /* (reads only: the next cycle may still continue behind the last one, see red_tail) */
-    CHK(check_field_level(ctx, field, level, "mg3d_download"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_download"));
     if (!host)
         return fail(MG3D_ERR_ARG, "mg3d_download: NULL host pointer");
     const Level &l = ctx->lv[level];
@@ -1478,7 +776,7 @@ extern "C" int mg3d_download(mg3d_ctx *ctx, int field, int level, double *host)
 extern "C" int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *src, void *stream)
 {
     static const char who[] = "mg3d_upload_device";
-    CHK(check_field_level(ctx, field, level, who));
+    CHK(mg3d_check_field_level(ctx, field, level, who));
     CHK(mg3d_array_check(ctx, src, false, who));
     CHK(mg3d_drop_carry(ctx));
     const Level &l = ctx->lv[level];
@@ -1488,14 +786,14 @@ extern "C" int mg3d_upload_device(mg3d_ctx *ctx, int field, int level, const mg3
         k_pack(l.g, l.f[field], *src, ctx->stream);
     }
     mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_CALLER);
-    CHK(launch_ok(who));
+    CHK(mg3d_launch_ok(who));
     return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
 }
 
 extern "C" int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const mg3d_array *dst, void *stream)
 {
     static const char who[] = "mg3d_download_device";
-    CHK(check_field_level(ctx, field, level, who));
+    CHK(mg3d_check_field_level(ctx, field, level, who));
     CHK(mg3d_array_check(ctx, dst, true, who));
     CHK(mg3d_drop_carry_keep(ctx)); /* (reads only, as mg3d_download) */
     const Level &l = ctx->lv[level];
@@ -1504,14 +802,14 @@ extern "C" int mg3d_download_device(mg3d_ctx *ctx, int field, int level, const m
         StageScope kt(ctx, level, MG3D_K_PACK, true);
         k_unpack(l.g, l.f[field], *dst, ctx->stream);
     }
-    CHK(launch_ok(who));
+    CHK(mg3d_launch_ok(who));
     return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
 }
 
 extern "C" int mg3d_zero(mg3d_ctx *ctx, int field, int level)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, field, level, "mg3d_zero"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_zero"));
     const Level &l = ctx->lv[level];
     HIPCHK(hipMemsetAsync(l.f[field], 0, l.elems * sizeof(double), ctx->stream));
     mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_ZERO);
@@ -1531,7 +829,7 @@ extern "C" int mg3d_device_view(mg3d_ctx *ctx, int field, int level, void **dev_
                                 long *plane_doubles)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, field, level, "mg3d_device_view"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_device_view"));
     const Level &l = ctx->lv[level];
     mg3d_ctx_touched(ctx, field, level, true);
     if (dev_ptr)
@@ -1566,7 +864,7 @@ extern "C" int mg3d_ctx_dnone_launches(const mg3d_ctx *ctx, unsigned long long *
 }
 
 /* ----------------------------------------------------------------- operators */
-static int launch_ok(const char *who)
+int mg3d_launch_ok(const char *who)
 {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -1725,64 +1023,64 @@ static int enqueue_residual(mg3d_ctx *ctx, int level, int store, int slot)
 extern "C" int mg3d_smooth(mg3d_ctx *ctx, int level, int post, int iters)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_smooth"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_smooth"));
     if (iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_smooth: negative iteration count");
     CHK(enqueue_smooth(ctx, level, post, iters));
-    return launch_ok("mg3d_smooth");
+    return mg3d_launch_ok("mg3d_smooth");
 }
 
 extern "C" int mg3d_residual(mg3d_ctx *ctx, int level, int store, double *norm)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_residual"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_residual"));
     CHK(enqueue_residual(ctx, level, store, 0));
-    CHK(launch_ok("mg3d_residual"));
+    CHK(mg3d_launch_ok("mg3d_residual"));
     return read_norm(ctx, 0, norm);
 }
 
 extern "C" int mg3d_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters, int store, double *norm)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_smooth_residual"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_smooth_residual"));
     if (iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_smooth_residual: negative iteration count");
     CHK(enqueue_smooth_residual(ctx, level, post, iters, store ? 2 : 1, 0));
-    CHK(launch_ok("mg3d_smooth_residual"));
+    CHK(mg3d_launch_ok("mg3d_smooth_residual"));
     return read_norm(ctx, 0, norm);
 }
 
 extern "C" int mg3d_smooth_restrict(mg3d_ctx *ctx, int level, int iters)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_smooth_restrict"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_smooth_restrict"));
     if (level < 1 || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_smooth_restrict: bad level/iteration count");
     Level &lc = ctx->lv[level - 1];
     CHK(enqueue_smooth_residual(ctx, level, 0, iters, 2, ctx->sumsq_slots - 1, mg3d_fused(ctx) ? &lc : nullptr, nullptr, false,
                                 /* need_norm: only without the fused restriction, whose shapes have no norm */ !mg3d_fused(ctx)));
     enqueue_restrict(ctx, level, mg3d_fused(ctx));
-    return launch_ok("mg3d_smooth_restrict");
+    return mg3d_launch_ok("mg3d_smooth_restrict");
 }
 
 extern "C" int mg3d_restrict(mg3d_ctx *ctx, int level)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_restrict"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_restrict"));
     if (level < 1)
         return fail(MG3D_ERR_ARG, "mg3d_restrict: level 0 has no coarser level");
     enqueue_restrict(ctx, level);
-    return launch_ok("mg3d_restrict");
+    return mg3d_launch_ok("mg3d_restrict");
 }
 
 extern "C" int mg3d_prolong(mg3d_ctx *ctx, int level)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, 0, level, "mg3d_prolong"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_prolong"));
     if (level < 1)
         return fail(MG3D_ERR_ARG, "mg3d_prolong: level 0 has no coarser level");
     enqueue_prolong(ctx, level);
-    return launch_ok("mg3d_prolong");
+    return mg3d_launch_ok("mg3d_prolong");
 }
 
 extern "C" int mg3d_coarse_solve(mg3d_ctx *ctx)
@@ -1795,15 +1093,15 @@ extern "C" int mg3d_coarse_solve(mg3d_ctx *ctx)
     if (ctx->have_es)
         return fail(MG3D_ERR_STATE, "mg3d_coarse_solve: the context holds the mixed-boundary factor of mg3d_es_setup");
     enqueue_coarse_solve(ctx);
-    return launch_ok("mg3d_coarse_solve");
+    return mg3d_launch_ok("mg3d_coarse_solve");
 }
 
 extern "C" int mg3d_l2norm(mg3d_ctx *ctx, int field, int level, double *norm)
 {
     CHK(mg3d_drop_carry_keep(ctx)); /* (reads only) */
-    CHK(check_field_level(ctx, field, level, "mg3d_l2norm"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_l2norm"));
     k_sumsq(ctx->lv[level].g, ctx->lv[level].f[field], ctx->partials, ctx->sumsq, ctx->stream);
-    CHK(launch_ok("mg3d_l2norm"));
+    CHK(mg3d_launch_ok("mg3d_l2norm"));
     return read_norm(ctx, 0, norm);
 }
 
@@ -2152,7 +1450,7 @@ static int dzero_scan(mg3d_ctx *ctx)
     const Level &top = ctx->lv[ctx->L - 1];
     std::vector<unsigned> words((size_t)mg3d_dzero_words(top.g.ni));
     k_dzero_scan(top.g, top.f[MG3D_D], ctx->dz_map, ctx->stream);
-    CHK(launch_ok("mg3d_vcycle: zero map of d"));
+    CHK(mg3d_launch_ok("mg3d_vcycle: zero map of d"));
     HIPCHK(hipMemcpyAsync(words.data(), ctx->dz_map, words.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->dz_planes = 0;
@@ -2225,12 +1523,12 @@ int mg3d_enqueue_vcycle(mg3d_ctx *ctx, int q, int slot, int carry_out, bool keep
     /* a whole V(2,2) cycle from the top level has ended with its last red pass and nothing runs ahead: see red_in */
     if (q == L - 1 && ctx->legs_state == 0 && !ctx->carried && ctx->iters == 2 && mg3d_fused(ctx))
         ctx->red_tail = true;
-    return launch_ok("mg3d_vcycle");
+    return mg3d_launch_ok("mg3d_vcycle");
 }
 
 extern "C" int mg3d_vcycle(mg3d_ctx *ctx, int level, double *norm)
 {
-    CHK(check_field_level(ctx, 0, level, "mg3d_vcycle"));
+    CHK(mg3d_check_field_level(ctx, 0, level, "mg3d_vcycle"));
     if (level == 0) { /* q == 0: direct solve, returns 0 (mg_3d.h:1262-1277) */
         CHK(mg3d_coarse_solve(ctx));
         if (norm)
@@ -2291,14 +1589,14 @@ extern "C" int mg3d_vcycles(mg3d_ctx *ctx, int count, double *norms)
 extern "C" int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level)
 {
     CHK(mg3d_drop_carry(ctx));
-    CHK(check_field_level(ctx, field, level, "mg3d_fill_boundary"));
+    CHK(mg3d_check_field_level(ctx, field, level, "mg3d_fill_boundary"));
     if (ctx->periodic) /* BCFunc is defined on all six faces */
         return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_fill_boundary: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
     k_fill_boundary(ctx->lv[level].g, ctx->lv[level].f[field], ctx->lv[level].h, ctx->stream);
     mg3d_ctx_touched(ctx, field, level, false, MG3D_WROTE_FACES);
-    return launch_ok("mg3d_fill_boundary");
+    return mg3d_launch_ok("mg3d_fill_boundary");
 }
 
 /* SolverFMGInitialize, mg_dirichlet_analytic.c:771-806 */
@@ -2311,9 +1609,9 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
-    if (!ctx->mask.empty())
+    if (ctx->mask.set())
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
-    if (!ctx->sfield.empty()) /* the F-cycle start is the reference's, whose operator has no field */
+    if (ctx->sfield.set()) /* the F-cycle start is the reference's, whose operator has no field */
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "mg3d_fmg_initialize: no coarse LU set");
@@ -2329,7 +1627,7 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
         (void)hipMemsetAsync(lc.f[MG3D_U], 0, lc.elems * sizeof(double), s);                                 /* :801 */
         CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1));                                              /* :804 */
     }
-    return launch_ok("mg3d_fmg_initialize");
+    return mg3d_launch_ok("mg3d_fmg_initialize");
 }
 
 /* Full multigrid for the caller's problem (include/mg3d.h): what mg3d_fmg_initialize cannot be while it is pinned to the
@@ -2337,7 +1635,7 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
  * that keep the interpolated guess (keep_guess of mg3d_enqueue_vcycle). */
 static int fmg_check(mg3d_ctx *ctx, const char *who)
 {
-    if (!ctx->mask.empty()) /* (full multigrid would need a mask-aware restriction of d and interpolation) */
+    if (ctx->mask.set()) /* (full multigrid would need a mask-aware restriction of d and interpolation) */
         return fail(MG3D_ERR_STATE, "%s: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL", who);
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "%s: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)", who);
@@ -2354,7 +1652,7 @@ extern "C" int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level)
     CHK(mg3d_drop_carry(ctx));
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
     k_fmg_interp(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
-    return launch_ok("mg3d_fmg_interpolate");
+    return mg3d_launch_ok("mg3d_fmg_interpolate");
 }
 
 extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
@@ -2382,7 +1680,7 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
     }
     k_dirichlet_rhs(l0.g, l0.f[MG3D_U], rhs, bc, s);
     enqueue_coarse_solve(ctx, rhs);
-    CHK(launch_ok("mg3d_fmg_solve"));
+    CHK(mg3d_launch_ok("mg3d_fmg_solve"));
     if (L == 1) {
         if (norm)
             *norm = 0.;
@@ -2396,7 +1694,7 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
             CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1, 0, true));
     }
     k_fmg_interp(ctx->lv[L - 2].g, ctx->lv[L - 2].f[MG3D_U], ctx->lv[L - 1].g, ctx->lv[L - 1].f[MG3D_U], bc, s);
-    CHK(launch_ok("mg3d_fmg_solve"));
+    CHK(mg3d_launch_ok("mg3d_fmg_solve"));
     std::vector<double> norms((size_t)cycles);
     CHK(mg3d_vcycles(ctx, cycles, norms.data())); /* the finest level: its schedules, its guard */
     if (norm)
@@ -2571,7 +1869,7 @@ extern "C" int mg3d_host_lu_solve(const double *LU, int n, const double *b, doub
     g.plane = 1;
     g.ig0 = 0;
     k_lu_solve(ctx->lu, ctx->lu_in, g, db, dx, ctx->lu_work, ctx->stream);
-    CHK(launch_ok("mg3d_host_lu_solve"));
+    CHK(mg3d_launch_ok("mg3d_host_lu_solve"));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(x, dx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return MG3D_OK;

@@ -169,15 +169,15 @@ static int launch_ok_es(const char *who)
 extern "C" int mg3d_es_setup(mg3d_ctx *ctx, const mg3d_es_params *p)
 {
     CHK(mg3d_drop_carry(ctx));
-    if (ctx && !ctx->eps.empty()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
+    if (ctx && ctx->eps.set()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx && ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
-    if (ctx && !ctx->mask.empty())
+    if (ctx && ctx->mask.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
-    if (ctx && !ctx->sfield.empty())
+    if (ctx && ctx->sfield.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_setup: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || !p || !(p->length > 0.))
         return fail(MG3D_ERR_ARG, "mg3d_es_setup: bad arguments");
@@ -217,15 +217,15 @@ extern "C" int mg3d_es_setup(mg3d_ctx *ctx, const mg3d_es_params *p)
 extern "C" int mg3d_es_smooth(mg3d_ctx *ctx, int level, int post, int iters)
 {
     CHK(mg3d_drop_carry(ctx));
-    if (ctx && !ctx->eps.empty()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
+    if (ctx && ctx->eps.set()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx && ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
-    if (ctx && !ctx->mask.empty())
+    if (ctx && ctx->mask.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
-    if (ctx && !ctx->sfield.empty())
+    if (ctx && ctx->sfield.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_smooth: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || !ctx->have_es || level < 0 || level >= ctx->L || iters < 0)
         return fail(MG3D_ERR_ARG, "mg3d_es_smooth: bad arguments (mg3d_es_setup first)");
@@ -275,15 +275,15 @@ static int es_vcycle(mg3d_ctx *ctx, int q, int slot)
 extern "C" int mg3d_es_vcycles(mg3d_ctx *ctx, int count, double *norms)
 {
     CHK(mg3d_drop_carry(ctx));
-    if (ctx && !ctx->eps.empty()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
+    if (ctx && ctx->eps.set()) /* the mixed-boundary problem has a constant coefficient (checked before its own state) */
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has a variable coefficient (mg3d_ctx_set_coefficient); set it to NULL");
     if (ctx && ctx->periodic) /* the mixed-boundary problem is defined on six faces */
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has periodic axes (mg3d_ctx_set_periodic); set them to 0");
     if (ctx && ctx->neumann)
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has Neumann faces (mg3d_ctx_set_neumann); set them to 0");
-    if (ctx && !ctx->mask.empty())
+    if (ctx && ctx->mask.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL");
-    if (ctx && !ctx->sfield.empty())
+    if (ctx && ctx->sfield.set())
         return fail(MG3D_ERR_STATE, "mg3d_es_vcycles: the context has a screening field (mg3d_ctx_set_shift_field); set it to NULL");
     if (!ctx || count < 0 || !ctx->have_es)
         return fail(MG3D_ERR_ARG, "mg3d_es_vcycles: bad arguments (mg3d_es_setup first)");

@@ -143,7 +143,7 @@ extern "C" int mg3d_field_flux(mg3d_ctx *ctx, int label, double *flux)
         return fail(MG3D_ERR_ARG, "%s: NULL result pointer", who);
     if (label < 0 || label > 255)
         return fail(MG3D_ERR_ARG, "%s: label %d (0: every fixed point, 1..255: the points with that byte)", who, label);
-    if (ctx->mask.empty())
+    if (!ctx->mask.set())
         return fail(MG3D_ERR_STATE, "%s: the context has no mask (mg3d_ctx_set_mask)", who);
     int rc = mg3d_field_level(ctx, who);
     if (rc == MG3D_OK)
