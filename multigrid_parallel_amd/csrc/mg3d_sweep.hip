@@ -529,7 +529,13 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
  * of its wave-edge rows and one barrier a step.  Planes of u in flight, 1 or 2: the registers the window gave back hold a
  * second one without scratch (profiles/dnone_kernel_resources.txt); both are compiled, option sweep_pf picks the one that
  * is not the default for a same-box A/B.  Measured at 513^3 (profiles/dnone_ab.txt; the kernels with the map: down 0.698,
- * up 0.647 ms): down-leg 0.599 ms with one plane, 0.609 with two; up-leg 0.507 ms with one, 0.498 with two */
+ * up 0.647 ms): down-leg 0.599 ms with one plane, 0.609 with two; up-leg 0.507 ms with one, 0.498 with two.
+ * The down-leg (NDR in the kernel) has since spent the registers and the LDS the window freed: the r pairs of the restriction
+ * stay in registers (224 VGPRs, no scratch, 82 KB of LDS instead of 131), its update and its tap test lane masks formed once
+ * a step, and its plane load carries no test for an absent input -- sweep_leg_down takes these kernels only with an input
+ * field.  513^3, same box (profiles/dnone_down_ab.txt): 0.597 -> 0.509 ms; with two planes in flight 0.502, inside each other's ranges: one stays.
+ * Its chunks stay the model's two layers of 257 planes: the tail chunk (247 + 247 + 19 planes, eight turns on the 16
+ * left-over CUs) measured 0.616 against 0.581 ms */
 #ifndef MG3D_LEG_ND_PF_DOWN
 #define MG3D_LEG_ND_PF_DOWN 1
 #endif
@@ -555,7 +561,7 @@ static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch
     const mg3d_options oq = leg_options(o);
     const int S = w.S, max_partials = w.max_partials;
     a.c1 = S == 4 ? 1 : 0;
-    if (a.d_none && S == 3) { /* d is +0.0 at every interior point: the kernels without a d window, nothing parked (DP = 0) */
+    if (a.d_none && S == 3 && a.vin) { /* d is +0.0 at every interior point: the kernels without a d window, nothing parked (DP = 0) */
         constexpr int PFD = MG3D_LEG_ND_PF_DOWN, PFA = 3 - PFD;
         if (o.v[MG3D_OPT_SWEEP_PF] == PFA) /* the other candidate of the choice (measurement only) */
             return w.partials ? launch_sweep<3, 2, 4, 8, PFA, false, true, 0, 0, -1, true>(oq, a, max_partials, s)

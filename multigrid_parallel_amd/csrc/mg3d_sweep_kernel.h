@@ -196,6 +196,11 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
     static_assert(RJ % 2 == 0, "RJ must be even (row parity of a wave's first row)");
     static_assert(VJ > 0 && ST >= 1, "tile too small");
     constexpr int STX = ST > 0 ? ST : 1;
+    /* NDR: the restricting shape without d (the down-leg of the one-launch-per-leg schedule on a source-free problem).  The d
+     * window it does not hold leaves it 30-odd VGPRs below the limit the restricting shapes were written against, so three of
+     * their economies are off in it: the r pairs stay in registers (RPARK), the update and the tap test lane masks formed once a
+     * step, and the plane load carries no test for an absent input (load_plane).  profiles/dnone_down_ab.txt */
+    constexpr bool NDR = ND && RES == 2;
 
     /* edge rows exchanged between waves: [parity][wave][top/bottom][stage][lane].  Two copies, written at the end of a step
      * and read at the top of the next, cost one barrier a step.  EXS: ONE copy and a second barrier behind the reads at the top
@@ -217,8 +222,10 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
     __shared__ double cpl[PRO ? 3 : 1][CRW][CCW];
     /* RES == 2 behind colour passes: the r pairs a thread hands from one step's rows to the next step's restriction are
      * written once and read once a whole step later -- parked in LDS (own rows only: no hazard, no second buffer) they
-     * free 4 x RJ VGPRs of a shape that otherwise spills inside the plane loop */
-    constexpr bool RPARK = RES == 2 && S > 0 && RJ >= 4;
+     * free 4 x RJ VGPRs of a shape that otherwise spills inside the plane loop.  Not without a d window (ND): there the pairs
+     * and the kept diff fit the registers (rlag, rkeep; 212 -> 220 VGPRs, no scratch), the arrays shrink to one element
+     * (131 -> 82 KB of LDS) and the step loses 34 LDS instructions and 14 waits in two steps (513^3: 0.599 -> 0.581 ms) */
+    constexpr bool RPARK = RES == 2 && S > 0 && RJ >= 4 && !ND;
     __shared__ double2 rpark[RPARK ? NW * RJ : 1][RPARK ? WAVE : 1];
     __shared__ double rkpark[RPARK ? NW * RJ : 1][RPARK ? WAVE : 1]; /* likewise the diff a row keeps for one step (rkeep) */
     /* DP > 0: ring of the DP oldest planes of the d window, [ring slot][row][column][lane] */
@@ -447,8 +454,10 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         }
         const gcbytes ubase = reinterpret_cast<gcbytes>(ub_), dbase = reinterpret_cast<gcbytes>(db_);
         /* vin == NULL: the input field is identically zero (a coarse level's initial guess, mg_3d.h:1258-1259) --
-         * neither zeroed in memory beforehand nor read */
-        const bool have_u = a.vin != nullptr; /* uniform */
+         * neither zeroed in memory beforehand nor read.  NDR: the launcher passes an input (sweep_leg_down), no test: the test
+         * is a branch around the loads at the top of every step and eight 64-bit moves that zero their destinations in front
+         * of it, and the loads cannot be issued before either (513^3: 0.563 -> 0.511 ms) */
+        const bool have_u = NDR ? true : a.vin != nullptr; /* uniform */
         /* (one uniform test for the whole plane, not one per row: the rows' loads stay a straight line) */
         if (have_u) {
 #pragma unroll
@@ -611,8 +620,11 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         unsigned lm = lmask;
         asm volatile("" : "+v"(lm));
         /* "this column is updatable" as two lane masks formed once a step (the other flags are tested where they are used: as
-         * step-wide masks they cost more scalar registers than the shapes at the limit have): up-leg -1 % */
+         * step-wide masks they cost more scalar registers than the shapes at the limit have): up-leg -1 %.  NDR has the
+         * registers for "this column is owned and updatable" as well (the tap: 12 VALU fewer in two steps); LM_PAIR
+         * formed once a step compiles to the same loop and stays a test at its uses, as does LM_CCOL (every other step) */
         const bool upd_col[2] = {(lm & (unsigned)LM_UPD0) != 0u, (lm & (unsigned)LM_UPD1) != 0u};
+        const bool own_col[2] = {(lm & (unsigned)LM_OWN0) != 0u, (lm & (unsigned)LM_OWN1) != 0u}; /* (NDR only) */
         /* current plane <- head of the prefetch queue, then request plane i+PF */
         if constexpr (PF == 2) {
             /* two planes in flight as a RING indexed by the step's parity (a template argument), not a queue that shifts:
@@ -840,7 +852,7 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                             else
                                 val = a.sixth * (sum - a.hSq * dd); /* mg_3d.h:438-443 */
         #endif
-                            if constexpr (RES == 2) /* (the restricting shapes sit at the register limit: the step-wide lane masks push them into scratch) */
+                            if constexpr (RES == 2 && !NDR) /* (the restricting shapes with a d window sit at the register limit: the step-wide lane masks push them into scratch) */
                                 nwG[g][s] = LM(updu ? (X ? LM_UPD1 : LM_UPD0) : 0) ? val : center;
                             else
                                 nwG[g][s] = (updu & upd_col[X]) ? val : center;
@@ -853,7 +865,9 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                                  * TAPQ = S has only the first half, TAPQ = 0 only the second: two launches, one norm. */
                                 if (s == TAPQ || s == TAPQ + 1) {
                                     const double diff = dd - a.invHsq * (sum - a.dg * (s == TAPQ ? nwG[g][s] : center));
-                                    if ((updu & row_own[rr]) & acc_ok[s])
+                                    if constexpr (NDR) /* one select on the joined mask: adding +0 leaves the sum unchanged */
+                                        acc += (((updu & row_own[rr]) & acc_ok[s]) & own_col[X]) ? diff * diff : 0.;
+                                    else if ((updu & row_own[rr]) & acc_ok[s])
                                         acc += LM(X ? LM_OWN1 : LM_OWN0) ? diff * diff : 0.;
                                 }
                             }
