@@ -712,6 +712,31 @@ int mg3d_ctx_dzero_planes(const mg3d_ctx *ctx, int *planes, int *state);
  * (d_zero_skip = 1, d +0.0 at every interior point of the finest level: the flagship problem, every source-free one).  The
  * same bits as with the map alone or without it: h^2 * (+0.0) is +0.0, x - (+0.0) is x.  For tests and tools. */
 int mg3d_ctx_dnone_launches(const mg3d_ctx *ctx, unsigned long long *launches);
+/* mg3d_ctx_sweep_taken: which fused sweep launches this context has taken -- a record the launcher writes on the host when
+ * it launches; no kernel knows of it.  Grid values never depend on the chunk length or on the tile shape (options sweep_ci,
+ * sweep_rj/nw/pf), and a request that names no compiled shape runs the default one: this is how a test or an A/B tool sees
+ * what ran.  Per kind of launch the context keeps the DISTINCT records, the most recent first (at most 32 of a kind; the one
+ * used longest ago is dropped): `which` = 0 is the kind's last launch, 1 the distinct one before it, ...  out receives the
+ * MG3D_SWEEP_TAKEN_FIELDS ints named below, *count how many launches had exactly this record, *launches every launch of the
+ * kind (either may be NULL).  Past the end of the list out is zeroed and *count is 0.  MG3D_ERR_ARG: no such kind, a
+ * negative index, NULL ctx or out.  The slab path (mg3d_dist_*) and the fp32 solver keep no records.  For tests and tools.
+ *   kinds:  PASSES colour passes alone; PASSES_RES ... with the residual (norm, r, or its restriction); TAP the launch two
+ *           carried cycles share; LEG_DOWN / LEG_UP the one-launch legs
+ *   fields: S colour passes, RES 0 none / 1 residual / 2 residual restricted / 3 norm tapped after the second pass, RJ rows a
+ *           thread, NW waves, PF planes in flight, ND the kernel without d, DZ the kernel that reads d through its zero
+ *           map, CI planes per chunk, BLOCKS of the grid, XCD_REMAP 0 blocks as numbered / 1 the whole grid regrouped / 2
+ *           every chunk's layer regrouped, NTJ x NTK tiles, PRO prolongation in the loads, RST 0 the norm-only residual,
+ *           DP slots of the d window parked in LDS, TAP the colour pass behind which a half of the norm is formed (-1 none), N points per side
+ *           of the level */
+enum { MG3D_SWEEP_KIND_PASSES = 0, MG3D_SWEEP_KIND_PASSES_RES, MG3D_SWEEP_KIND_TAP, MG3D_SWEEP_KIND_LEG_DOWN, MG3D_SWEEP_KIND_LEG_UP };
+enum {
+    MG3D_SWEEP_TAKEN_S = 0, MG3D_SWEEP_TAKEN_RES, MG3D_SWEEP_TAKEN_RJ, MG3D_SWEEP_TAKEN_NW, MG3D_SWEEP_TAKEN_PF,
+    MG3D_SWEEP_TAKEN_ND, MG3D_SWEEP_TAKEN_DZ, MG3D_SWEEP_TAKEN_CI, MG3D_SWEEP_TAKEN_BLOCKS, MG3D_SWEEP_TAKEN_XCD_REMAP,
+    MG3D_SWEEP_TAKEN_NTJ, MG3D_SWEEP_TAKEN_NTK, MG3D_SWEEP_TAKEN_PRO, MG3D_SWEEP_TAKEN_RST, MG3D_SWEEP_TAKEN_DP,
+    MG3D_SWEEP_TAKEN_TAP, MG3D_SWEEP_TAKEN_N, MG3D_SWEEP_TAKEN_FIELDS
+};
+int mg3d_ctx_sweep_taken(const mg3d_ctx *ctx, int kind, int which, int out[MG3D_SWEEP_TAKEN_FIELDS],
+                         unsigned long long *count, unsigned long long *launches);
 
 /* per-stage timers (timing_info.h:6-47), filled from hipEvent pairs recorded in-stream (no stall).
  * on: 0 = off, 1 = every level, 2 = finest level only, 3 = the kernel timers of the finest level only (no stage

@@ -13,6 +13,10 @@ fp = C.POINTER(C.c_float)
 MG3D_U, MG3D_D, MG3D_R = 0, 1, 2
 MG3D_PERIODIC_I, MG3D_PERIODIC_J, MG3D_PERIODIC_K = 1, 2, 4
 STAGES = 7
+# mg3d_ctx_sweep_taken: MG3D_SWEEP_KIND_* and the MG3D_SWEEP_TAKEN_* fields in order
+SWEEP_KINDS = {"passes": 0, "passes_res": 1, "tap": 2, "leg_down": 3, "leg_up": 4}
+SWEEP_TAKEN_FIELDS = ("S", "RES", "RJ", "NW", "PF", "ND", "DZ", "CI", "blocks", "xcd_remap", "ntj", "ntk", "PRO", "RST", "DP",
+                      "TAP", "N")
 _ERR = {1: "bad argument", 2: "no device", 3: "HIP error", 4: "allocation failed", 5: "bad state"}
 
 
@@ -139,6 +143,8 @@ SIGNATURES = {
     "mg3d_option_name": (C.c_char_p, [C.c_int]),
     "mg3d_ctx_dzero_planes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mg3d_ctx_dnone_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "mg3d_ctx_sweep_taken": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong),
+                                       C.POINTER(C.c_ulonglong)]),
     "mg3d32_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mg3d32_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d32_kernel_name": (C.c_char_p, [C.c_int]),
@@ -437,6 +443,18 @@ class Solver:
         n = C.c_ulonglong(0)
         check(self.L.mg3d_ctx_dnone_launches(self._h, C.byref(n)))
         return n.value
+
+    def sweep_taken(self, kind):
+        """mg3d_ctx_sweep_taken: the fused sweep launches of one kind (a key of SWEEP_KINDS) this context has taken, as
+        (launches of the kind, the distinct records as dicts over SWEEP_TAKEN_FIELDS plus "count", most recent first)."""
+        out, recs, which = (C.c_int * len(SWEEP_TAKEN_FIELDS))(), [], 0
+        count, launches = C.c_ulonglong(0), C.c_ulonglong(0)
+        while True:
+            check(self.L.mg3d_ctx_sweep_taken(self._h, SWEEP_KINDS[kind], which, out, C.byref(count), C.byref(launches)))
+            if count.value == 0:
+                return launches.value, recs
+            recs.append(dict(zip(SWEEP_TAKEN_FIELDS, out), count=count.value))
+            which += 1
 
     # -- geometry
     def level_n(self, level):

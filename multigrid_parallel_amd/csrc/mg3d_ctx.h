@@ -142,6 +142,9 @@ struct mg3d_ctx {
     /* launches that took a kernel without d because the map was full (SweepLaunch::d_none; mg3d_ctx_dnone_launches).
      * Counted where the launch is described, through the const context of mg3d_level_sweep */
     mutable unsigned long long dnone_launches = 0;
+    /* what the sweep launches of this context were: kernel, chunk length, grid (SweepLaunch::taken; mg3d_ctx_sweep_taken),
+     * written by k_sweep on the host through the const context of mg3d_level_sweep */
+    mutable SweepTakenLog sweep_taken = {};
     mg3d_options opt; /* launch / schedule policy (mg3d_options_init at creation, mg3d_ctx_set_option afterwards) */
     bool fused; /* fused sweep kernel (default) or one launch per colour pass (MG3D_NO_FUSE=1) */
     int timing; /* 0 off, 1 every level, 2 finest level only, 3 finest level's kernel timers only, 4 + k: 3 on every (k+2)-th cycle */
@@ -193,6 +196,7 @@ static inline SweepLaunch mg3d_level_sweep(const mg3d_ctx *ctx, const Level &l)
         }
     }
     w.vout = l.alt;
+    w.taken = &ctx->sweep_taken;
     return w;
 }
 /* the boundary word of the context's levels for the launchers of mg3d_kernels.hip */

@@ -863,6 +863,32 @@ extern "C" int mg3d_ctx_dnone_launches(const mg3d_ctx *ctx, unsigned long long *
     return MG3D_OK;
 }
 
+/* the sweep launches this context has taken, by kind (mg3d_ctx.h, sweep_taken; SweepTakenLog): host bookkeeping only */
+extern "C" int mg3d_ctx_sweep_taken(const mg3d_ctx *ctx, int kind, int which, int out[MG3D_SWEEP_TAKEN_FIELDS],
+                                    unsigned long long *count, unsigned long long *launches)
+{
+    static_assert(sizeof(SweepTaken) == MG3D_SWEEP_TAKEN_FIELDS * sizeof(int), "SweepTaken is the MG3D_SWEEP_TAKEN_* fields in order");
+    static_assert(MG3D_SWEEP_KIND_LEG_UP + 1 == MG3D_SWEEP_KINDS && MG3D_SWEEP_KIND_PASSES == SWEEP_PASSES &&
+                      MG3D_SWEEP_KIND_PASSES_RES == SWEEP_PASSES_RES && MG3D_SWEEP_KIND_TAP == SWEEP_TAP &&
+                      MG3D_SWEEP_KIND_LEG_DOWN == SWEEP_LEG_DOWN && MG3D_SWEEP_KIND_LEG_UP == SWEEP_LEG_UP,
+                  "MG3D_SWEEP_KIND_* are SweepKind");
+    if (!ctx || !out)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_sweep_taken: NULL argument");
+    if (kind < 0 || kind >= MG3D_SWEEP_KINDS || which < 0)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_sweep_taken: no such kind, or a negative index");
+    const SweepTakenLog &log = ctx->sweep_taken;
+    const bool have = which < log.n[kind];
+    if (have)
+        memcpy(out, &log.e[kind][which].t, sizeof(SweepTaken));
+    else
+        memset(out, 0, sizeof(SweepTaken));
+    if (count)
+        *count = have ? log.e[kind][which].count : 0;
+    if (launches)
+        *launches = log.launches[kind];
+    return MG3D_OK;
+}
+
 /* ----------------------------------------------------------------- operators */
 int mg3d_launch_ok(const char *who)
 {

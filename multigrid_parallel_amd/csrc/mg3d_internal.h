@@ -199,7 +199,28 @@ enum SweepKind {
     SWEEP_LEG_UP      /* ... the input is vin + P(ec), four passes black first; partials: the sum of diff^2 of the RESULT over
                          the colour the last pass updated.  (The legs set c1 themselves and never measure chunk lengths.) */
 };
+/* What k_sweep launched, written on the host when it launches (mg3d_ctx_sweep_taken, include/mg3d.h: the same order as
+ * MG3D_SWEEP_TAKEN_*): the template arguments of the kernel, whether the instantiation that reads d through its zero map
+ * ran (DZ), the chunk length, the grid and its block numbering, the tiling, and the level's points per side. */
+struct SweepTaken {
+    int S, RES, RJ, NW, PF, ND, DZ, CI, blocks, xcd_remap, ntj, ntk, PRO, RST, DP, TAP, N;
+};
+/* the launches of one context, by kind: the distinct records, the most recent one first, each with the number of launches
+ * it stands for; at most MG3D_SWEEP_TAKEN_KEEP of a kind (the one used longest ago goes), `launches` counts them all */
+#define MG3D_SWEEP_KINDS 5
+#define MG3D_SWEEP_TAKEN_KEEP 32
+struct SweepTakenLog {
+    struct Entry {
+        SweepTaken t;
+        unsigned long long count;
+    };
+    Entry e[MG3D_SWEEP_KINDS][MG3D_SWEEP_TAKEN_KEEP];
+    int n[MG3D_SWEEP_KINDS];
+    unsigned long long launches[MG3D_SWEEP_KINDS];
+};
 struct SweepLaunch {
+    /* optional: where k_sweep records the launch it takes (nothing when it launches nothing); host side only */
+    SweepTakenLog *taken = nullptr;
     /* the level: its local geometry, operator constants and arrays */
     const Geom *g = nullptr;
     LevelOp op = {};

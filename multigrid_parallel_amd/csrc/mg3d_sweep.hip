@@ -94,7 +94,7 @@ static int device_cus() /* of the CURRENT device (a process may drive several: m
  * the default schedules use; the shapes only the options sweep_rj / nw / pf reach read every plane.
  * ND: the launcher has chosen the kernel without d (SweepArgs::d_none, the leg launches): neither a.d nor a.dz is looked at. */
 template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND>
-static void launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s)
+static bool launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s) /* true: the instantiation with the zero map ran */
 {
     if constexpr (ND) { /* (the else branch is discarded: an ND shape has no siblings that read d unless another launch names them) */
         hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
@@ -102,15 +102,16 @@ static void launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s)
         if constexpr (NW == 8 && ((RJ == 4 && PF == 1) || (RJ == 2 && PF >= 2))) {
             if (a.dz) {
                 hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
-                return;
+                return true;
             }
         }
         hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
     }
+    return false;
 }
 
 template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1, bool ND = false>
-static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s)
+static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s, SweepTaken *t)
 {
     using Sh = SweepShape<S, RES>;
     constexpr int VJ = NW * RJ - 2 * Sh::HJ;
@@ -135,12 +136,17 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
     const int nout = a.i_hi - a.i_lo;
     const int ncu = device_cus();
     const long long T = (long long)a.ntj * a.ntk;
+    /* the record of the launch taken (SweepLaunch::taken), written where the kernel is launched */
+    auto record = [&](bool dz, long long blocks) {
+        if (t)
+            *t = SweepTaken{S, RES, RJ, NW, PF, (int)ND, (int)dz, a.CI, (int)blocks, a.xcd_remap, a.ntj, a.ntk, (int)PRO, (int)RST, DP, TAP, g.N};
+    };
     if (a.edge > 0) { /* the two end windows of the range as two chunks of one launch (see SweepArgs::edge) */
         if (2 * a.edge > nout || (a.partials && 2 * T > max_partials))
             return -1;
         a.CI = a.edge;
         a.xcd_remap = 2 * T < 64 ? 0 : 2 * T <= ncu ? 1 : 2;
-        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)(2 * T), s);
+        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)(2 * T), s), 2 * T);
         return (int)(2 * T);
     }
     const int ovh = Sh::HI + Sh::ST + (RES == 2 ? 2 : 0) + 1;
@@ -211,7 +217,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
         static_assert(C1K < 0 || !PRO || C1K == 0, "PRO launches are post-smoothers");
         if (C1K >= 0 && a.c1 != C1K)
             return;
-        launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)nb, s);
+        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)nb, s), nb);
     };
     /* Measured choice.  The model above ranks chunk lengths by steps; what a step costs depends on how many CUs stream
      * at once and on how well the chunks keep in lock-step, which it does not know.  The first launch of a shape on a
@@ -310,34 +316,34 @@ static SweepCfg opt_cfg(const mg3d_options &o, SweepCfg dflt)
 /* the first shape listed is the default; a request that names no compiled shape falls back to it */
 #define TRY(S_, RES_, RJ_, NW_, PF_)                                              \
     if (c.rj == RJ_ && c.nw == NW_ && c.pf == PF_)                                \
-        return launch_sweep<S_, RES_, RJ_, NW_, PF_>(o, a, max_partials, s);
-#define DFLT(S_, RES_, RJ_, NW_, PF_) return launch_sweep<S_, RES_, RJ_, NW_, PF_>(o, a, max_partials, s);
+        return launch_sweep<S_, RES_, RJ_, NW_, PF_>(o, a, max_partials, s, t);
+#define DFLT(S_, RES_, RJ_, NW_, PF_) return launch_sweep<S_, RES_, RJ_, NW_, PF_>(o, a, max_partials, s, t);
 
-template <int S, int RES> static int dispatch(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s);
+template <int S, int RES> static int dispatch(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t);
 
-template <> int dispatch<4, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<4, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(4, 1, 6, 4, 1) TRY(4, 1, 6, 4, 2) TRY(4, 1, 4, 4, 2) TRY(4, 1, 4, 8, 1) TRY(4, 1, 2, 8, 2)
     DFLT(4, 1, 6, 4, 2)
 }
-template <> int dispatch<4, 0>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<4, 0>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(4, 0, 8, 4, 1) TRY(4, 0, 6, 4, 2) TRY(4, 0, 6, 4, 3) TRY(4, 0, 4, 8, 1) TRY(4, 0, 4, 8, 2)
     TRY(4, 0, 2, 8, 2) TRY(4, 0, 2, 8, 4) TRY(4, 0, 2, 16, 1)
     DFLT(4, 0, 4, 8, 1)
 }
-template <> int dispatch<2, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<2, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(2, 1, 4, 8, 1) TRY(2, 1, 8, 4, 2) TRY(2, 1, 6, 4, 2) TRY(2, 1, 2, 16, 1) TRY(2, 1, 6, 8, 1)
     DFLT(2, 1, 4, 8, 1)
 }
-template <> int dispatch<2, 0>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<2, 0>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(2, 0, 6, 8, 1) TRY(2, 0, 8, 4, 2) TRY(2, 0, 4, 8, 1) TRY(2, 0, 4, 8, 2) TRY(2, 0, 4, 8, 3)
     TRY(2, 0, 2, 8, 4) TRY(2, 0, 2, 16, 1)
     DFLT(2, 0, 4, 8, 1)
 }
-template <> int dispatch<0, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<0, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(0, 1, 4, 8, 1) TRY(0, 1, 8, 4, 2) TRY(0, 1, 4, 8, 2) TRY(0, 1, 4, 8, 3) TRY(0, 1, 2, 8, 4) TRY(0, 1, 2, 16, 1)
     DFLT(0, 1, 4, 8, 1)
@@ -345,12 +351,12 @@ template <> int dispatch<0, 1>(const mg3d_options &o, SweepArgs &a, SweepCfg c, 
 
 /* S colour passes starting with colour c1, optional residual.  Returns the number of
  * partial sums written (0 when no norm was requested), -1 if the shape is unsupported. */
-template <> int dispatch<0, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<0, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(0, 2, 4, 8, 1) TRY(0, 2, 4, 8, 2) TRY(0, 2, 2, 8, 2) TRY(0, 2, 2, 8, 4) TRY(0, 2, 2, 16, 1) TRY(0, 2, 6, 8, 1)
     DFLT(0, 2, 4, 8, 1)
 }
-template <> int dispatch<4, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<4, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     /* the whole down-leg of a level in ONE launch.  The six-stage window only fits two rows per thread (16-row tiles
      * with a halo of 6: four owned rows): a quarter of the rows it computes are kept -- for the levels where a launch
@@ -358,19 +364,19 @@ template <> int dispatch<4, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, 
     TRY(4, 2, 2, 8, 1) TRY(4, 2, 2, 8, 2)
     DFLT(4, 2, 2, 8, 2)
 }
-template <> int dispatch<2, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<2, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(2, 2, 4, 8, 1)
     DFLT(2, 2, 4, 8, 1)
 }
-template <> int dispatch<1, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<1, 2>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     /* the LAST pre-smoothing pass + residual + restriction: the down-leg's only launch on the top level of a cycle whose
      * first three pre-smoothing passes rode on the previous cycle's last launch (SWEEP_TAP) */
     TRY(1, 2, 4, 8, 1) TRY(1, 2, 4, 8, 2)
     DFLT(1, 2, 4, 8, 1)
 }
-template <> int dispatch<4, 3>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s)
+template <> int dispatch<4, 3>(const mg3d_options &o, SweepArgs &a, SweepCfg c, int max_partials, hipStream_t s, SweepTaken *t)
 {
     TRY(4, 3, 4, 8, 1)
     DFLT(4, 3, 4, 8, 1)
@@ -425,7 +431,7 @@ static bool fill_args(SweepArgs &a, const SweepLaunch &w)
 }
 
 /* SWEEP_PASSES, SWEEP_PASSES_RES, SWEEP_TAP: the compiled shape by (S, residual, restriction, prolongation) and level size */
-static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
+static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s, SweepTaken *t)
 {
     const Geom &g = *w.g;
     const bool tap = w.kind == SWEEP_TAP, residual = w.kind == SWEEP_PASSES_RES;
@@ -440,16 +446,16 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
     if (tap) { /* four passes, the residual norm of the state after the second one into partials */
         if (S != 4 || dc || ec || r || !partials || residual)
             return -1;
-        return dispatch<4, 3>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s);
+        return dispatch<4, 3>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
     }
     if (ec) { /* prolongation fused into the input: 4- and 2-pass smoothing launches */
         if (dc || residual || (g.nj & 1) == 0 || c1 != 0) /* (c1: the kernel derives the plane parity from it, see PRO) */
             return -1;
         if (S == 4) /* small levels: two rows per thread (no spills, 8 owned rows of 16); else the opt-in four-row shape */
-            return g.N <= o.v[MG3D_OPT_SMALL_MAX] ? launch_sweep<4, 0, 2, 8, 2, true>(o, a, max_partials, s)
-                                              : launch_sweep<4, 0, 4, 8, 1, true>(o, a, max_partials, s);
+            return g.N <= o.v[MG3D_OPT_SMALL_MAX] ? launch_sweep<4, 0, 2, 8, 2, true>(o, a, max_partials, s, t)
+                                              : launch_sweep<4, 0, 4, 8, 1, true>(o, a, max_partials, s, t);
         if (S == 2)
-            return launch_sweep<2, 0, 4, 8, 1, true>(o, a, max_partials, s);
+            return launch_sweep<2, 0, 4, 8, 1, true>(o, a, max_partials, s, t);
         return -1;
     }
     /* Levels of at most 65^3 points: a step costs a global-load latency (~1.4 us with one plane in flight), not
@@ -457,37 +463,37 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
      * (33^3: four passes 20 -> 13 us, residual + restriction 15 -> 12 us; at 257^3 the same shapes are 40 % slower). */
     const bool small = g.N <= o.v[MG3D_OPT_SMALL_MAX];
     if (dc && S == 0 && residual)
-        return dispatch<0, 2>(o, a, opt_cfg(o, small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s);
+        return dispatch<0, 2>(o, a, opt_cfg(o, small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s, t);
     if (dc && S == 2 && residual)
-        return dispatch<2, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s);
+        return dispatch<2, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
     if (dc && S == 1 && residual)
-        return dispatch<1, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s);
+        return dispatch<1, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
     if (dc && S == 4 && residual)
-        return dispatch<4, 2>(o, a, opt_cfg(o, {2, 8, 2}), max_partials, s);
+        return dispatch<4, 2>(o, a, opt_cfg(o, {2, 8, 2}), max_partials, s, t);
     if (dc)
         return -1;
     if (S == 4 && residual)
-        return dispatch<4, 1>(o, a, opt_cfg(o, {6, 4, 2}), max_partials, s);
+        return dispatch<4, 1>(o, a, opt_cfg(o, {6, 4, 2}), max_partials, s, t);
     if (S == 4 && !residual) {
         /* from the zero guess on the levels between 66 and 300 points per side (129^3, 257^3: a step is paid in latency, the
          * launch has a CU per block and little else): two rows a thread, SIXTEEN waves -- the same 32-row tile at four waves
          * per SIMD (128 VGPRs, no scratch): 257^3 80 -> 71-74 us, 129^3 25 -> 22 us; 65^3 and below 11.5 -> 14 (the eight-wave
          * two-row shape stays), 513^3 425 -> 420 (the four-row shape stays); kernel trace, round 4 */
         const bool mid = vin == nullptr && g.N > 65 && g.N <= 300;
-        return dispatch<4, 0>(o, a, opt_cfg(o, mid ? SweepCfg{2, 16, 1} : small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s);
+        return dispatch<4, 0>(o, a, opt_cfg(o, mid ? SweepCfg{2, 16, 1} : small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s, t);
     }
     if (S == 2 && residual) {
         /* the norm alone (the top level's second post-smoothing launch): a shape without the code that assembles r */
         const SweepCfg c = opt_cfg(o, {4, 8, 1});
         if (!r && c.rj == 4 && c.nw == 8 && (c.pf == 1 || c.pf == 2))
-            return c.pf == 1 ? launch_sweep<2, 1, 4, 8, 1, false, false>(o, a, max_partials, s)
-                             : launch_sweep<2, 1, 4, 8, 2, false, false>(o, a, max_partials, s);
-        return dispatch<2, 1>(o, a, c, max_partials, s);
+            return c.pf == 1 ? launch_sweep<2, 1, 4, 8, 1, false, false>(o, a, max_partials, s, t)
+                             : launch_sweep<2, 1, 4, 8, 2, false, false>(o, a, max_partials, s, t);
+        return dispatch<2, 1>(o, a, c, max_partials, s, t);
     }
     if (S == 2 && !residual)
-        return dispatch<2, 0>(o, a, opt_cfg(o, small ? SweepCfg{2, 8, 4} : SweepCfg{4, 8, 1}), max_partials, s);
+        return dispatch<2, 0>(o, a, opt_cfg(o, small ? SweepCfg{2, 8, 4} : SweepCfg{4, 8, 1}), max_partials, s, t);
     if (S == 0 && residual)
-        return dispatch<0, 1>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s);
+        return dispatch<0, 1>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
     return -1;
 }
 
@@ -554,7 +560,7 @@ static mg3d_options leg_options(const mg3d_options &o)
     return q;
 }
 
-static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
+static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s, SweepTaken *t)
 {
     if (!w.dc || w.ec || w.r || w.edge)
         return -1;
@@ -564,27 +570,27 @@ static int sweep_leg_down(const mg3d_options &o, SweepArgs &a, const SweepLaunch
     if (a.d_none && S == 3 && a.vin) { /* d is +0.0 at every interior point: the kernels without a d window, nothing parked (DP = 0) */
         constexpr int PFD = MG3D_LEG_ND_PF_DOWN, PFA = 3 - PFD;
         if (o.v[MG3D_OPT_SWEEP_PF] == PFA) /* the other candidate of the choice (measurement only) */
-            return w.partials ? launch_sweep<3, 2, 4, 8, PFA, false, true, 0, 0, -1, true>(oq, a, max_partials, s)
-                              : launch_sweep<3, 2, 4, 8, PFA, false, true, 0, -1, -1, true>(oq, a, max_partials, s);
-        return w.partials ? launch_sweep<3, 2, 4, 8, PFD, false, true, 0, 0, -1, true>(oq, a, max_partials, s)
-                          : launch_sweep<3, 2, 4, 8, PFD, false, true, 0, -1, -1, true>(oq, a, max_partials, s);
+            return w.partials ? launch_sweep<3, 2, 4, 8, PFA, false, true, 0, 0, -1, true>(oq, a, max_partials, s, t)
+                              : launch_sweep<3, 2, 4, 8, PFA, false, true, 0, -1, -1, true>(oq, a, max_partials, s, t);
+        return w.partials ? launch_sweep<3, 2, 4, 8, PFD, false, true, 0, 0, -1, true>(oq, a, max_partials, s, t)
+                          : launch_sweep<3, 2, 4, 8, PFD, false, true, 0, -1, -1, true>(oq, a, max_partials, s, t);
     }
     a.d_none = 0; /* no such kernel for this request: d is read through its map as before */
 #if MG3D_LEG_DOWN_RJ == 4
     if (S == 3 && w.partials)
-        return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s);
+        return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s, t);
     if (S == 3)
-        return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s);
+        return launch_sweep<3, 2, 4, 8, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s, t);
 #else
     if (S == 3 && w.partials)
-        return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s);
+        return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, 0>(oq, a, max_partials, s, t);
     if (S == 3)
-        return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s);
+        return launch_sweep<3, 2, 8, 4, 1, false, true, MG3D_LEG_DP_DOWN3, -1>(oq, a, max_partials, s, t);
 #endif
     return -1;
 }
 
-static int sweep_leg_up(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s)
+static int sweep_leg_up(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s, SweepTaken *t)
 {
     if (!w.ec || w.dc || w.r)
         return -1;
@@ -594,20 +600,43 @@ static int sweep_leg_up(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
     if (a.d_none) {
         constexpr int PFU = MG3D_LEG_ND_PF_UP, PFA = 3 - PFU;
         if (o.v[MG3D_OPT_SWEEP_PF] == PFA)
-            return w.partials ? launch_sweep<4, 0, 4, 8, PFA, true, true, 0, 4, -1, true>(oq, a, max_partials, s)
-                              : launch_sweep<4, 0, 4, 8, PFA, true, true, 0, -1, -1, true>(oq, a, max_partials, s);
-        return w.partials ? launch_sweep<4, 0, 4, 8, PFU, true, true, 0, 4, -1, true>(oq, a, max_partials, s)
-                          : launch_sweep<4, 0, 4, 8, PFU, true, true, 0, -1, -1, true>(oq, a, max_partials, s);
+            return w.partials ? launch_sweep<4, 0, 4, 8, PFA, true, true, 0, 4, -1, true>(oq, a, max_partials, s, t)
+                              : launch_sweep<4, 0, 4, 8, PFA, true, true, 0, -1, -1, true>(oq, a, max_partials, s, t);
+        return w.partials ? launch_sweep<4, 0, 4, 8, PFU, true, true, 0, 4, -1, true>(oq, a, max_partials, s, t)
+                          : launch_sweep<4, 0, 4, 8, PFU, true, true, 0, -1, -1, true>(oq, a, max_partials, s, t);
     }
 #if MG3D_LEG_UP_RJ == 4
     if (w.partials)
-        return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s);
-    return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s);
+        return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s, t);
+    return launch_sweep<4, 0, 4, 8, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s, t);
 #else
     if (w.partials)
-        return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s);
-    return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s);
+        return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, 4>(oq, a, max_partials, s, t);
+    return launch_sweep<4, 0, 8, 4, 1, true, true, MG3D_LEG_DP_UP, -1>(oq, a, max_partials, s, t);
 #endif
+}
+
+/* one more launch of `kind` in the log: its record moves to the front of the kind's distinct ones (SweepTakenLog) */
+static void sweep_taken_log(SweepTakenLog &log, SweepKind kind, const SweepTaken &rec)
+{
+    static_assert(SWEEP_LEG_UP + 1 == MG3D_SWEEP_KINDS, "one list per SweepKind");
+    SweepTakenLog::Entry *const e = log.e[kind];
+    int &n = log.n[kind];
+    int at = 0;
+    while (at < n && memcmp(&e[at].t, &rec, sizeof rec) != 0)
+        at++;
+    unsigned long long count = 1;
+    if (at < n)
+        count += e[at].count;
+    else if (n < MG3D_SWEEP_TAKEN_KEEP)
+        at = n++;
+    else
+        at = n - 1; /* full: the record used longest ago goes */
+    for (; at > 0; at--)
+        e[at] = e[at - 1];
+    e[0].t = rec;
+    e[0].count = count;
+    log.launches[kind]++;
 }
 
 int k_sweep(const mg3d_options &o, const SweepLaunch &w, hipStream_t s)
@@ -617,20 +646,25 @@ int k_sweep(const mg3d_options &o, const SweepLaunch &w, hipStream_t s)
     SweepArgs a;
     if (!fill_args(a, w))
         return 0;
+    SweepTaken rec = {};
+    SweepTaken *const t = w.taken ? &rec : nullptr;
     int n;
     switch (w.kind) {
     case SWEEP_LEG_DOWN:
-        n = sweep_leg_down(o, a, w, s);
+        n = sweep_leg_down(o, a, w, s, t);
         break;
     case SWEEP_LEG_UP:
-        n = sweep_leg_up(o, a, w, s);
+        n = sweep_leg_up(o, a, w, s, t);
         break;
     default:
         a.d_none = 0; /* only the legs have kernels without d */
-        return sweep_passes(o, a, w, s);
+        n = sweep_passes(o, a, w, s, t);
+        break;
     }
     if (n >= 0 && a.d_none && w.d_none_taken)
         ++*w.d_none_taken;
+    if (n >= 0 && t && rec.blocks > 0)
+        sweep_taken_log(*w.taken, w.kind, rec);
     return n;
 }
 

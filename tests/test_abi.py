@@ -30,6 +30,28 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert sorted(SIGNATURES) == names
 
 
+def test_sweep_taken_getter_is_declared_bound_and_refuses_bad_arguments():
+    """mg3d_ctx_sweep_taken: the binding's field and kind names are the header's enumerators in the header's order (a record
+    is read by position), and the export refuses a NULL context or record without touching anything (no GPU needed)."""
+    from multigrid_parallel_amd.binding import SWEEP_KINDS, SWEEP_TAKEN_FIELDS
+    assert "mg3d_ctx_sweep_taken" in declared_symbols() and "mg3d_ctx_sweep_taken" in SIGNATURES
+    hdr = open(os.path.join(ROOT, "include", "mg3d.h")).read()
+    decl = hdr[hdr.index("enum { MG3D_SWEEP_KIND_PASSES = 0"):hdr.index("int mg3d_ctx_sweep_taken(")]
+    kinds = re.findall(r"\bMG3D_SWEEP_KIND_([A-Z_]+)", decl)
+    assert [k.lower() for k in kinds] == sorted(SWEEP_KINDS, key=SWEEP_KINDS.get)
+    assert sorted(SWEEP_KINDS.values()) == list(range(len(kinds))) and len(kinds) == 5
+    fields = re.findall(r"\bMG3D_SWEEP_TAKEN_([A-Z_]+)", decl)
+    assert fields[-1] == "FIELDS" and [f.lower() for f in fields[:-1]] == [f.lower() for f in SWEEP_TAKEN_FIELDS]
+    for name in ("S", "RES", "RJ", "NW", "PF", "ND", "DZ", "CI", "blocks", "xcd_remap", "ntj", "ntk"):
+        assert name in SWEEP_TAKEN_FIELDS
+    L = M.lib()
+    out = (C.c_int * len(SWEEP_TAKEN_FIELDS))(*([7] * len(SWEEP_TAKEN_FIELDS)))
+    count, launches = C.c_ulonglong(7), C.c_ulonglong(7)
+    assert L.mg3d_ctx_sweep_taken(None, 0, 0, out, C.byref(count), C.byref(launches)) == 1  # MG3D_ERR_ARG
+    assert b"mg3d_ctx_sweep_taken" in L.mg3d_last_error()
+    assert list(out) == [7] * len(SWEEP_TAKEN_FIELDS) and count.value == 7 and launches.value == 7
+
+
 def test_no_oracle_in_product():
     """The product must not link, load or reference anything under oracle/."""
     import subprocess
