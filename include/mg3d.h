@@ -180,7 +180,8 @@ int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces);
  * on the unknowns: the cycle remains a symmetric preconditioner.
  * Injection loses a body thinner than the coarse spacing -- a one-point plate on an odd plane is gone from every coarse
  * level -- and plain cycles then converge slowly or GROW: mg3d_vcycle(s) are for bodies that survive on the coarse grids,
- * mg3d_pcg_solve / mg3d_wpcg_solve are the solvers for thin ones ("Embedded conductors").
+ * mg3d_pcg_solve / mg3d_wpcg_solve are the solvers for thin ones ("Embedded conductors") -- or the
+ * hierarchy keeps them: mg3d_ctx_set_mask_coarsening(MG3D_MASK_KEEP) below, under which plain cycles contract on thin bodies.
  * Singular cases: the pin of unknown (0,0,0) of level 0 applies iff the condition of mg3d_ctx_set_neumann holds AND level
  * 0's mask has no fixed unknown; mg3d_wpcg_solve projects iff that condition holds and the FINEST mask has no fixed
  * unknown (a fixed unknown removes the constants from the kernel).
@@ -189,17 +190,50 @@ int mg3d_ctx_get_neumann(const mg3d_ctx *ctx, int *faces);
  * context without a mask, bit for bit and with its fused schedules; an all-zero mask is a mask: every grid value and norm
  * is that of the context without one on the unfused kernels.  With a mask the fused, carried, per-leg and
  * single-workgroup schedules do not apply (option values kept).  Refused with MG3D_ERR_STATE, nothing changed, on a context
- * with a mask: mg3d_es_*, mg3d_fmg_initialize, mg3d_fmg_solve, mg3d_fmg_interpolate (full multigrid would need a
- * mask-aware restriction of d and interpolation).  mg3d_step_advance works as it is: fixed points are Dirichlet values
+ * with a mask: mg3d_es_*, mg3d_fmg_initialize, and -- while the mask is coarsened by injection, under which a thin body is
+ * absent from the levels full multigrid starts on -- mg3d_fmg_solve, mg3d_fmg_interpolate (accepted under
+ * MG3D_MASK_KEEP, mg3d_ctx_set_mask_coarsening).  mg3d_step_advance works as it is: fixed points are Dirichlet values
  * constant in time, d there is unspecified.  The slab, fp32 and mg3d_host_* forms and the drop-in header have no mask.
  * mg3d_ctx_set_mask_device: the same from a device array (mg3d_array below) of dtype MG3D_U8 -- nothing else --, any
  * element strides >= 0; the pointer is checked and the streams joined as for mg3d_ctx_set_coefficient_device.  Every byte
  * value is valid, so nothing is checked on the device; the call synchronises with the host once, to read back level 0's
  * mask for the coarse matrix and the numbers of fixed unknowns.  NULL: no mask.
- * mg3d_ctx_get_mask: the injected mask of a level, dense n^3 (periodic duplicates hold their sources' bytes). */
+ * mg3d_ctx_get_mask: the mask a level holds, under either coarsening rule, dense n^3 (periodic duplicates hold their
+ * sources' bytes). */
 int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask); /* finest level, dense N^3 host array; NULL: no mask */
 int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on);
-int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host); /* the injected mask, dense n^3; MG3D_ERR_STATE without one */
+int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host); /* the level's mask, dense n^3; MG3D_ERR_STATE without one */
+/* How the coarser levels take the mask.  MG3D_MASK_INJECT, the default: injection as above, every byte, count and grid value
+ * what it is without this call.  MG3D_MASK_KEEP: a fixed point that injection would lose fixes ONE coarse point, so a body
+ * thinner than the coarse spacing stays on every level without growing thicker level by level.  Level l -> l-1 (fine side N,
+ * coarse side Nc), on the stored bytes of the fine level, whose periodic duplicates hold their sources' bytes; raw bytes, no
+ * boundary word, nothing outside the array is read.  For the coarse point C = (I, J, K):
+ *   1. m_f[2C] != 0: m_c[C] = m_f[2C], the injection.
+ *   2. otherwise the fine points F = 2C + (a, b, c), a, b, c in {0, 1} not all zero, are looked at in the order (0,0,1),
+ *      (0,1,0), (0,1,1), (1,0,0), (1,0,1), (1,1,0), (1,1,1); an F with an index > N-1 is skipped (only where a coarse index is
+ *      Nc-1).  F is LOST when m_f[F] != 0 and m_f[2P] == 0 for every parent P = C + (a*al, b*be, c*ga), al, be, ga in {0, 1},
+ *      of F.  m_c[C] is the byte of the first lost F, or 0 when there is none.
+ *   3. the coarse level's periodic duplicates take their sources' bytes (a duplicate plane Nc-1 sees fewer F than its source).
+ * So every fixed fine point has a fixed parent on the next level: an injected one, or its lower parent floor(F/2).  A body
+ * that injection represents already is left exactly as injection has it (a ball of radius 0.2 at 33^3 or 65^3: the same
+ * hierarchy).  Effects: BIAS -- a lost body moves by up to one fine spacing towards the LOW index on each level, since the
+ * lower parent is taken; the rule is not mirror-symmetric, the price of not thickening the body.  LABELS -- a coarse byte is
+ * the byte of the point it stands for.  The cycle stays a SYMMETRIC preconditioner for any coarse mask (the restriction
+ * reads the zeros the residual stores at fine fixed points, coarse fixed points hold zero error, the prolongation skips
+ * fine fixed points), so mg3d_pcg_solve, mg3d_wpcg_solve and mg3d_step_advance work unchanged.  The SINGULAR-case rules
+ * read the same counts: under MG3D_MASK_KEEP a thin body reaches level 0, so the pin is lifted where injection would have kept
+ * it.  Plain cycles that GROW on thin bodies under injection (factor 1.6 to 4.7 per cycle at 33^3 and 65^3) contract under
+ * MG3D_MASK_KEEP (0.42 to 0.54; INTEGRATION.md, "Embedded conductors", has the table).
+ * Operator state, not a launch option (grid values depend on it): it may be set before or after the mask and every other
+ * setter, in every order.  A rule that is neither of the two, or a NULL pointer: MG3D_ERR_ARG, nothing changed.  Without a
+ * mask the rule is stored for the next mg3d_ctx_set_mask(_device).  With one, a call that CHANGES the rule finishes a cycle
+ * that has run ahead, takes levels L-2 .. 0 again from the finest level's stored bytes, recounts the fixed unknowns and
+ * reads back level 0 (one host synchronisation), and rebuilds or drops the coarse factor as every setter does; the same rule
+ * again changes nothing.  When the periodic mask changes, the finest duplicates are rewritten for good as above and, under
+ * MG3D_MASK_KEEP, the lower levels are coarsened again from the finest one. */
+enum { MG3D_MASK_INJECT = 0, MG3D_MASK_KEEP = 1 };
+int mg3d_ctx_set_mask_coarsening(mg3d_ctx *ctx, int rule);
+int mg3d_ctx_get_mask_coarsening(const mg3d_ctx *ctx, int *rule);
 /* (mg3d_ctx_set_mask_device is declared with the other device-array calls, behind mg3d_array) */
 
 /* Screening field: sigma per grid point.  s is one double per point of the finest level, a dense N^3 host array, every entry
@@ -573,9 +607,10 @@ int mg3d_fmg_initialize(mg3d_ctx *ctx);
 /* Full multigrid for the CALLER's problem: the finest level's d and Dirichlet values, on every operator the context
  * supports (constant, sigma, eps, any periodic mask, any Neumann mask).  mg3d_fmg_initialize above stays what the reference
  * is -- one analytic test problem, Dirichlet faces only, and its interpolated guess is discarded below the finest level.
- *   in : u of the finest level as uploaded -- only its Dirichlet points are read, whatever else it holds is ignored; d of
- *        the finest level; the coarse factor set as for mg3d_vcycle; cycles >= 1, otherwise MG3D_ERR_ARG and nothing
- *        changes.  A cycle that has run ahead is finished first.
+ *   in : u of the finest level as uploaded -- only its Dirichlet points AND its fixed points (mg3d_ctx_set_mask under
+ *        MG3D_MASK_KEEP) are read, whatever else it holds is ignored; d of the finest level (never read at a fixed point: it
+ *        may hold anything there, NaN included); the coarse factor set as for mg3d_vcycle; cycles >= 1, otherwise
+ *        MG3D_ERR_ARG and nothing changes.  A cycle that has run ahead is finished first.
  *   1. for l = L-1 .. 1: d[l-1] = the context's own restriction of d[l] (full weighting of the unknowns; Dirichlet points
  *      are injected and never enter a weighted sum, so the caller need not define d there), u[l-1] = injection of u[l]
  *      (u[l-1][I,J,K] = u[l][2I,2J,2K]: the Dirichlet values); then d[0] = u[0] at every Dirichlet point of level 0, the
@@ -583,7 +618,13 @@ int mg3d_fmg_initialize(mg3d_ctx *ctx);
  *   2. level 0: the direct solve, duplicates and the pinned row as in a cycle
  *   3. for l = 1 .. L-1: mg3d_fmg_interpolate(l), then `cycles` V-cycles from level l that keep u[l] as their guess (the
  *      levels below l start from zero as in every cycle); on l = L-1 they are mg3d_vcycles(cycles), schedules included
- *   out: u of the finest level holds the result, its Dirichlet points the caller's bit for bit, its periodic duplicates
+ *   With fixed points: in 1. d[l] counts as 0. at the fixed unknowns of level l (the bits of restricting a copy with zeros
+ *      stored there), and a coarse point C that is a fixed unknown of level l-1 while m_l[2C] == 0 -- it stands for a lost fine
+ *      point F, step 2 of mg3d_ctx_set_mask_coarsening -- takes u[l][F] instead of u[l][2C], so each level's body carries its
+ *      conductor's potential; in 2. the identity rows of level 0's fixed unknowns take u[0] there, as the Dirichlet points
+ *      do; in 3. the interpolation does not write a fixed unknown of the fine level and reads coarse fixed points like any
+ *      other value.
+ *   out: u of the finest level holds the result, its Dirichlet points and fixed points the caller's bit for bit, its periodic duplicates
  *        equal to their sources; d of the finest level is the caller's bit for bit; *norm (may be NULL) is the residual
  *        norm after the last finest-level cycle, the value mg3d_vcycles returns.  u and d of the lower levels and r are
  *        unspecified.  The context is usable as before: mg3d_vcycles(1) from the returned u gives, bit for bit, what a
@@ -592,7 +633,8 @@ int mg3d_fmg_initialize(mg3d_ctx *ctx);
  * multigrid start"): what six or seven cycles from a zero guess do.  The singular case has mg3d_vcycle's caveat: nothing
  * is projected, d must be compatible, u is fixed by the pin.
  * mg3d_fmg_interpolate: u[level] at every unknown (and its periodic duplicates) is OVERWRITTEN with the interpolant of
- * u[level-1]; Dirichlet points of u[level] are never written, those of u[level-1] are read like any other point.  Per
+ * u[level-1]; Dirichlet points and fixed points of u[level] are never written, those of u[level-1] are read like any other
+ * point.  Per
  * axis (coarse side Nc): an even fine index 2I copies coarse I; an odd one, 2I+1, takes coarse I-1, I, I+1, I+2 with
  * -1/16, 9/16, 9/16, -1/16 -- an index outside the unique range wrapped modulo Nc-1 on a periodic axis, reflected at a
  * Neumann face (-1 -> 1, Nc -> Nc-2); next to a Dirichlet face the one-sided cubic over the four points nearest the face
@@ -600,7 +642,8 @@ int mg3d_fmg_initialize(mg3d_ctx *ctx);
  * Nc < 4 coarse I, I+1 with 1/2, 1/2.  The value is the tensor product sum_i(wi * sum_j(wj * sum_k(wk * u))), each sum
  * left to right in the order given, uncontracted (tests/_fmg_ref.py restates it bit for bit).  1 <= level < L, otherwise
  * MG3D_ERR_ARG.
- * Both return MG3D_ERR_STATE, nothing changed, on a context without a coarse factor or after mg3d_es_setup.  The slab,
+ * Both return MG3D_ERR_STATE, nothing changed, on a context without a coarse factor, after mg3d_es_setup, or with a mask
+ * coarsened by injection (MG3D_MASK_INJECT, the default; the message names mg3d_ctx_set_mask_coarsening).  The slab,
  * fp32 and mg3d_host_* forms have no such entry points. */
 int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level);
 int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm /* may be NULL */);

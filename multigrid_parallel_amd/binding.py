@@ -94,6 +94,8 @@ SIGNATURES = {
     "mg3d_ctx_set_mask_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
     "mg3d_ctx_has_mask": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mg3d_ctx_get_mask": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte)]),
+    "mg3d_ctx_set_mask_coarsening": (C.c_int, [C.c_void_p, C.c_int]),
+    "mg3d_ctx_get_mask_coarsening": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mg3d_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mg3d_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "mg3d_smooth_residual": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, dp]),
@@ -229,6 +231,7 @@ SIGNATURES = {
 
 
 NEUMANN_FACES = ("ilo", "ihi", "jlo", "jhi", "klo", "khi")  # bit f of the MG3D_NEUMANN_* mask
+MASK_COARSENING = {"inject": 0, "keep": 1}  # MG3D_MASK_INJECT, MG3D_MASK_KEEP
 
 
 class PcgInfo(C.Structure):
@@ -513,8 +516,10 @@ class Solver:
     def set_mask(self, mask):
         """mg3d_ctx_set_mask: fixed points inside the domain (embedded conductors).  mask is bool or uint8, (N, N, N) or
         flat, nonzero = fixed: u there keeps what was uploaded and acts as a Dirichlet value, like a point on a Dirichlet
-        face; coarser levels take the mask by injection.  None: no mask again.  Plain cycles are for bodies that survive on
-        the coarse grids; pcg_solve / wpcg_solve are the solvers for thin ones.  Rebuilds a coarse factor of get_details();
+        face; coarser levels take the mask by injection unless set_mask_coarsening("keep") says otherwise.  None: no mask
+        again.  Under injection plain cycles are for bodies that survive on the coarse grids, and pcg_solve / wpcg_solve are
+        the solvers for thin ones; under "keep" thin bodies stay on every level, plain cycles contract on them and
+        fmg_solve accepts the mask.  Rebuilds a coarse factor of get_details();
         drops one given to set_lu.  The bytes are kept as given: a uint8 value 1..255 is a label of its body, which
         field_flux(label) asks for."""
         if mask is None:
@@ -534,12 +539,30 @@ class Solver:
         return bool(on.value)
 
     def get_mask(self, level=None):
-        """the injected mask of a level as the kernels use it, (n, n, n) uint8"""
+        """the mask of a level as the kernels use it (under either coarsening rule), (n, n, n) uint8"""
         level = self.num_levels - 1 if level is None else level
         n = self.level_n(level)
         out = np.empty(n ** 3, dtype=np.uint8)
         check(self.L.mg3d_ctx_get_mask(self._h, level, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out.reshape(n, n, n)
+
+    def set_mask_coarsening(self, rule):
+        """mg3d_ctx_set_mask_coarsening: how the coarser levels take the mask -- "inject" (MG3D_MASK_INJECT = 0, the
+        default: m[I,J,K] = m_fine[2I,2J,2K]) or "keep" (MG3D_MASK_KEEP = 1: a fixed point that injection would lose fixes
+        its lower parent, so a body thinner than the coarse spacing stays on every level without thickening; it moves by up
+        to one fine spacing towards the low index per level).  Operator state: set it before or after the mask, in any order
+        with the other setters; a change under a mask rebuilds the coarser masks and the coarse factor of get_details()."""
+        if isinstance(rule, str):
+            if rule not in MASK_COARSENING:
+                raise ValueError(f"set_mask_coarsening: need one of {sorted(MASK_COARSENING)} or the enum value, got {rule!r}")
+            rule = MASK_COARSENING[rule]
+        check(self.L.mg3d_ctx_set_mask_coarsening(self._h, int(rule)))
+
+    def get_mask_coarsening(self):
+        """mg3d_ctx_get_mask_coarsening: the rule by its name, "inject" or "keep", as set_mask_coarsening takes it"""
+        rule = C.c_int(0)
+        check(self.L.mg3d_ctx_get_mask_coarsening(self._h, C.byref(rule)))
+        return {v: k for k, v in MASK_COARSENING.items()}[rule.value]
 
     def set_shift_field(self, s):
         """mg3d_ctx_set_shift_field: solve  div(eps grad u) - (sigma + s)*u = d  with s >= 0 given at every point of the
@@ -955,14 +978,18 @@ class Solver:
 
     def fmg_interpolate(self, level):
         """mg3d_fmg_interpolate: every unknown of u[level] overwritten with the cubic interpolant of u[level - 1]
-        (1 <= level < num_levels); Dirichlet points stay."""
+        (1 <= level < num_levels); Dirichlet points stay, and so do the fixed points of a mask (accepted under
+        set_mask_coarsening("keep") only)."""
         check(self.L.mg3d_fmg_interpolate(self._h, int(level)))
 
     def fmg_solve(self, cycles=1):
         """mg3d_fmg_solve: full multigrid from the uploaded d and the Dirichlet points of the uploaded u of the finest
         level (its interior is ignored) -- d restricted down the hierarchy, a direct solve, then per level the cubic
         interpolant as the guess of `cycles` V-cycles that keep it.  With V(2,2) one cycle per level leaves an algebraic
-        error below the discretisation error.  Returns the residual norm after the last finest-level cycle."""
+        error below the discretisation error.  With a mask (under set_mask_coarsening("keep") only; under "inject" the
+        call raises MG3D_ERR_STATE) the fixed points of the uploaded u are read as the Dirichlet points are, and every
+        level's body carries its conductor's potential; d at fixed points is never read.  Returns the residual norm after
+        the last finest-level cycle."""
         nrm = C.c_double(0)
         check(self.L.mg3d_fmg_solve(self._h, int(cycles), C.byref(nrm)))
         return nrm.value

@@ -60,9 +60,13 @@ struct mg3d_ctx {
      * layout (not set: the constant-coefficient operator) and level 0's, dense, for the coarse matrix; no counts */
     OperatorField<double> eps;
     /* fixed points (mg3d_ctx_set_mask): one byte per point of every level in the padded layout, the finest level's as given
-     * and the others' by injection (not set: no mask); level 0's, dense, for the coarse matrix; and how many fixed UNKNOWNS
+     * and the others' by the context's coarsening rule (mask_rule below; not set: no mask); level 0's, dense, for the coarse matrix; and how many fixed UNKNOWNS
      * level 0 and the finest level have under the present boundary masks (recounted when those change) */
     OperatorField<unsigned char> mask;
+    /* how the levels below the finest take the mask (mg3d_ctx_set_mask_coarsening): MG3D_MASK_INJECT as above, or
+     * MG3D_MASK_KEEP, under which a fixed fine point that injection loses fixes its lower parent.  Operator state: kept while
+     * there is no mask, for the next one */
+    int mask_rule = MG3D_MASK_INJECT;
     /* the screening field of div(eps grad u) - (sigma + s) u (mg3d_ctx_set_shift_field): s of every level in the padded
      * layout, the finest level's as given and each coarser one's by the context's own restriction (not set: no field); level
      * 0's, dense, for the coarse matrix; how many UNKNOWNS of level 0 and of the finest level have s > 0 under the present

@@ -1021,7 +1021,8 @@ static void enqueue_prolong(mg3d_ctx *ctx, int level)
  * rows' values in place (k_coarse_rhs: 0; a one-level context has no cycle above the solve, its fixed points keep u's own
  * values); the duplicates of x are then copied from their sources.  Otherwise (Dirichlet faces, Neumann faces without the
  * pin) b is d itself, and there is no duplicate to refresh */
-static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* NULL: d of level 0 */)
+static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* NULL: d of level 0 */,
+                                 bool own_values = false /* the fixed points keep u's values (mg3d_fmg_solve: the solve of the problem itself) */)
 {
     Level &l0 = ctx->lv[0];
     if (!rhs)
@@ -1029,7 +1030,7 @@ static void enqueue_coarse_solve(mg3d_ctx *ctx, const double *rhs = nullptr /* N
     const int bc = mg3d_ctx_bc(ctx), pin = mg3d_ctx_pinned(ctx);
     const unsigned char *m = mg3d_level_operator(ctx, 0).m;
     if (m || ctx->periodic || (ctx->neumann && pin)) {
-        k_coarse_rhs(l0.g, rhs, ctx->per_b, bc, pin, m, ctx->L == 1 ? l0.f[MG3D_U] : nullptr, ctx->stream);
+        k_coarse_rhs(l0.g, rhs, ctx->per_b, bc, pin, m, (ctx->L == 1 || own_values) ? l0.f[MG3D_U] : nullptr, ctx->stream);
         rhs = ctx->per_b;
     }
     k_lu_solve(ctx->lu, ctx->lu_in, l0.g, rhs, l0.f[MG3D_U], ctx->lu_work, ctx->stream);
@@ -1661,8 +1662,12 @@ extern "C" int mg3d_fmg_initialize(mg3d_ctx *ctx)
  * that keep the interpolated guess (keep_guess of mg3d_enqueue_vcycle). */
 static int fmg_check(mg3d_ctx *ctx, const char *who)
 {
-    if (ctx->mask.set()) /* (full multigrid would need a mask-aware restriction of d and interpolation) */
-        return fail(MG3D_ERR_STATE, "%s: the context has fixed points (mg3d_ctx_set_mask); set the mask to NULL", who);
+    /* (under injection a thin body is absent from the levels full multigrid starts on) */
+    if (ctx->mask.set() && ctx->mask_rule == MG3D_MASK_INJECT)
+        return fail(MG3D_ERR_STATE,
+                    "%s: the context has fixed points coarsened by injection (mg3d_ctx_set_mask); call "
+                    "mg3d_ctx_set_mask_coarsening(MG3D_MASK_KEEP), or set the mask to NULL",
+                    who);
     if (!ctx->have_lu)
         return fail(MG3D_ERR_STATE, "%s: no coarse LU set (mg3d_ctx_build_coarse / mg3d_ctx_set_lu)", who);
     if (ctx->have_es)
@@ -1677,7 +1682,7 @@ extern "C" int mg3d_fmg_interpolate(mg3d_ctx *ctx, int level)
     CHK(fmg_check(ctx, "mg3d_fmg_interpolate"));
     CHK(mg3d_drop_carry(ctx));
     const Level &lev = ctx->lv[level], &lc = ctx->lv[level - 1];
-    k_fmg_interp(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream);
+    k_fmg_interp(lc.g, lc.f[MG3D_U], lev.g, lev.f[MG3D_U], mg3d_ctx_bc(ctx), ctx->stream, ctx->mask.at(level));
     return mg3d_launch_ok("mg3d_fmg_interpolate");
 }
 
@@ -1689,15 +1694,21 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
     CHK(mg3d_drop_carry(ctx));
     const int L = ctx->L, bc = mg3d_ctx_bc(ctx);
     hipStream_t s = ctx->stream;
-    /* 1. the right-hand side down the hierarchy by the context's own restriction, u by injection: the Dirichlet values */
+    /* 1. the right-hand side down the hierarchy by the context's own restriction, u by injection: the Dirichlet values.
+     * With fixed points (MG3D_MASK_KEEP): d counts as 0. at the fixed unknowns, where it is never read, and a coarse fixed
+     * point that stands for a lost fine one takes that one's u, so every level's body carries its conductor's potential */
     for (int l = L - 1; l >= 1; l--) {
         const Level &lev = ctx->lv[l], &lc = ctx->lv[l - 1];
-        k_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], bc, s);
-        k_coef_inject(lev.g, lev.f[MG3D_U], lc.g, lc.f[MG3D_U], s);
+        const unsigned char *mf = ctx->mask.at(l);
+        k_restrict(lev.g, lev.f[MG3D_D], lc.g, lc.f[MG3D_D], bc, s, -1, -1, false, mf);
+        if (mf)
+            k_fmg_inject(lev.g, lev.f[MG3D_U], mf, lc.g, lc.f[MG3D_U], bc, s);
+        else
+            k_coef_inject(lev.g, lev.f[MG3D_U], lc.g, lc.f[MG3D_U], s);
         mg3d_ctx_touched(ctx, MG3D_D, l - 1); /* its faces are no injection of r any more: the cycles inject them again */
     }
-    /* 2. the direct solve, its identity rows taking the Dirichlet values (a one-level context keeps its d: the
-     * right-hand side is put together in r) */
+    /* 2. the direct solve, its identity rows taking the Dirichlet values, those of the fixed unknowns included (a one-level
+     * context keeps its d: the right-hand side is put together in r) */
     Level &l0 = ctx->lv[0];
     double *rhs = l0.f[MG3D_D];
     if (L == 1) {
@@ -1705,7 +1716,7 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
         HIPCHK(hipMemcpyAsync(rhs, l0.f[MG3D_D], l0.elems * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     k_dirichlet_rhs(l0.g, l0.f[MG3D_U], rhs, bc, s);
-    enqueue_coarse_solve(ctx, rhs);
+    enqueue_coarse_solve(ctx, rhs, true);
     CHK(mg3d_launch_ok("mg3d_fmg_solve"));
     if (L == 1) {
         if (norm)
@@ -1715,11 +1726,12 @@ extern "C" int mg3d_fmg_solve(mg3d_ctx *ctx, int cycles, double *norm)
     /* 3. up: the cubic interpolant as the guess, `cycles` V-cycles that keep it; d of level l and the Dirichlet points of
      * u of level l are still those of step 1 -- a cycle from below writes d below l and u at or below l - 1 only */
     for (int l = 1; l < L - 1; l++) {
-        k_fmg_interp(ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_U], ctx->lv[l].g, ctx->lv[l].f[MG3D_U], bc, s);
+        k_fmg_interp(ctx->lv[l - 1].g, ctx->lv[l - 1].f[MG3D_U], ctx->lv[l].g, ctx->lv[l].f[MG3D_U], bc, s, ctx->mask.at(l));
         for (int c = 0; c < cycles; c++)
             CHK(mg3d_enqueue_vcycle(ctx, l, ctx->sumsq_slots - 1, 0, true));
     }
-    k_fmg_interp(ctx->lv[L - 2].g, ctx->lv[L - 2].f[MG3D_U], ctx->lv[L - 1].g, ctx->lv[L - 1].f[MG3D_U], bc, s);
+    k_fmg_interp(ctx->lv[L - 2].g, ctx->lv[L - 2].f[MG3D_U], ctx->lv[L - 1].g, ctx->lv[L - 1].f[MG3D_U], bc, s,
+                 ctx->mask.at(L - 1));
     CHK(mg3d_launch_ok("mg3d_fmg_solve"));
     std::vector<double> norms((size_t)cycles);
     CHK(mg3d_vcycles(ctx, cycles, norms.data())); /* the finest level: its schedules, its guard */

@@ -166,7 +166,8 @@ int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOp
  * a slab halo.  bc = mg3d_bc(periodic, neumann) != 0 (single-domain levels): every plane, full weighting on periodic and
  * Neumann faces too, duplicates written with their sources; the window and faces_only are not looked at */
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s, int ic_lo = -1,
-                int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */);
+                int ic_hi = -1, bool faces_only = false /* injection on the coarse faces only */,
+                const unsigned char *mf = nullptr /* the fine level's fixed points (single-domain levels, any bc): 0. in place of r there */);
 void k_prolong(const Geom &gc, const double *ec, const Geom &gf, double *ef, int bc, hipStream_t s, int if_lo = -1,
                int if_hi = -1, const unsigned char *mf = nullptr /* the fine level's fixed points: the point form, skipping them */);
 /* BCFunc(i*h, j*h, k*h) = x*x - 2*y*y + z*z on the six faces of a field (mg_3d.h:89-90, 1147-1239) */
@@ -384,11 +385,18 @@ void k_per_refresh(const Geom &g, double *v, int bc, hipStream_t s, const unsign
 void k_mask_pack(const Geom &g, unsigned char *m, const mg3d_array &a, int bc, hipStream_t s);
 void k_mask_inject(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s);
 void k_mask_refresh(const Geom &g, unsigned char *m, int bc, hipStream_t s);
+/* MG3D_MASK_KEEP: the coarser level's bytes by injection where the coarse point's own fine point is fixed, else the byte of
+ * the first lost fine point it is the lower parent of (mg3d_kernels.hip); the caller refreshes the coarse duplicates */
+void k_mask_keep(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s);
 void k_mask_count(const Geom &g, const unsigned char *m, int bc, unsigned long long *out, hipStream_t s);
 /* full multigrid (mg3d_fmg_solve): every unknown of the fine level (and its periodic duplicates) overwritten with the
  * tensor-product cubic interpolant of the coarse u -- never a Dirichlet point; and d = u at the Dirichlet points of a level,
- * the right-hand side of the direct solve's identity rows.  Single-domain levels, bc the boundary word */
-void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s);
+ * the right-hand side of the direct solve's identity rows.  Single-domain levels, bc the boundary word.  mf: the fine level's
+ * fixed points, which the interpolation does not write either.  k_fmg_inject: u of the coarser level under MG3D_MASK_KEEP --
+ * injection, a coarse fixed unknown that stands for a lost fine point taking that point's u */
+void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s,
+                  const unsigned char *mf = nullptr);
+void k_fmg_inject(const Geom &gf, const double *uf, const unsigned char *mf, const Geom &gc, double *uc, int bc, hipStream_t s);
 void k_dirichlet_rhs(const Geom &g, const double *u, double *d, int bc, hipStream_t s);
 /* zeros on the faces of a single-domain level given as a MG3D_NEUMANN_* mask */
 void k_zero_faces(const Geom &g, double *v, int faces, hipStream_t s);

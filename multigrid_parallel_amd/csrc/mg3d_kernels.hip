@@ -1150,10 +1150,15 @@ void k_dzero_fill(const Geom &g, unsigned *map, hipStream_t s)
  *     weighting, whose -1 / +1 taps are the neighbours the stencil has at the fine point (2i, 2j, 2k) -- nb_lo / nb_hi:
  *     fine index -1 wrapped to Nf-2 on a periodic axis (2I+1 <= Nf-2 never wraps) and reflected to 1 at a Neumann low
  *     face, fine index Nf reflected to Nf-2 at a Neumann high face.  A duplicate is written as a copy by the thread of
- *     its source. */
-template <int BC>
+ *     its source.
+ *   With the fine level's fixed-point bytes (the pack M, one trailing argument; mg3d_fmg_solve's restriction of d) a weighted
+ *     tap at a fixed point counts as 0. whatever r holds there, NaN included: the bits of restricting a copy with zeros
+ *     stored at the fixed unknowns.  Every weighted tap is an unknown (never a Dirichlet face point or a duplicate), so the
+ *     raw byte decides; an injected face point is no unknown and is copied as ever.  The instantiations without the
+ *     pack have neither the argument nor the test. */
+template <int BC, class... M>
 __global__ void __launch_bounds__(256) restrict_kernel(Geom gf, const double *__restrict__ r, Geom gc,
-                                                       double *__restrict__ dc, int bc, int ic_lo, int ic_hi)
+                                                       double *__restrict__ dc, int bc, int ic_lo, int ic_hi, M... fixed)
 {
     const bool pi = BC && (bc & 1), pj = BC && (bc & 2), pk = BC && (bc & 4);
     const bool ril = BC && bc_ref_lo(bc, 0), rih = BC && bc_ref_hi(bc, 0), rjl = BC && bc_ref_lo(bc, 1),
@@ -1188,7 +1193,8 @@ __global__ void __launch_bounds__(256) restrict_kernel(Geom gf, const double *__
 #pragma unroll
                 for (int tk = 0; tk < 3; tk++) {
                     const double w = (ti != 1 ? 0.25 : 0.5) * (tj != 1 ? 0.25 : 0.5) * (tk != 1 ? 0.25 : 0.5);
-                    val += r[pf + oi[ti] + oj[tj] + ok[tk]] * w;
+                    const long long q = pf + oi[ti] + oj[tj] + ok[tk];
+                    val += (mask_fixed(q, fixed...) ? 0. : r[q]) * w;
                 }
     }
     store_dup(gc, dc, gidx(gc, ic, jc, kc), val, pi && icg == 0, pj && jc == 0, pk && kc == 0);
@@ -1226,9 +1232,14 @@ __global__ void __launch_bounds__(256) restrict_faces_kernel(Geom gf, const doub
 }
 
 void k_restrict(const Geom &gf, const double *r, const Geom &gc, double *dc, int bc, hipStream_t s, int ic_lo, int ic_hi,
-                bool faces_only)
+                bool faces_only, const unsigned char *mf)
 {
     const dim3 block(WAVE, 4, 1);
+    if (mf) { /* a single-domain level, any boundary word (0 too: the Dirichlet faces' injection and plain offsets) */
+        const dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
+        hipLaunchKernelGGL((restrict_kernel<BC_WRAP, MaskPtr>), grid, block, 0, s, gf, r, gc, dc, bc, 0, gc.N, mf);
+        return;
+    }
     if (bc) { /* a single-domain level: every plane, never faces only -- periodic and Neumann faces are fully weighted */
         const dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
         hipLaunchKernelGGL(restrict_kernel<BC_WRAP>, grid, block, 0, s, gf, r, gc, dc, bc, 0, gc.N);
@@ -1273,6 +1284,87 @@ void k_mask_inject(const Geom &gf, const unsigned char *mf, const Geom &gc, unsi
 {
     dim3 grid((gc.nk + WAVE - 1) / WAVE, (gc.nj + 3) / 4, gc.ni);
     hipLaunchKernelGGL(coef_inject_kernel<unsigned char>, grid, dim3(WAVE, 4, 1), 0, s, gf, mf, gc, mc);
+}
+
+/* MG3D_MASK_KEEP (include/mg3d.h): the coarse point C = (I, J, K) whose own fine point 2C is not fixed stands for the first
+ * LOST fine point among F = 2C + (a, b, c), (a, b, c) = (0,0,1), (0,1,0), (0,1,1), (1,0,0) ... (1,1,1): one with a nonzero
+ * byte none of whose parents C + (a*al, b*be, c*ga), al, be, ga in {0, 1}, has a nonzero byte at its own fine point.  Raw
+ * bytes of the fine level, its duplicates holding their sources'; an F past index N-1 is skipped, and then every parent
+ * lies inside: 2I + 1 <= N-1 gives 2(I + 1) <= N-1.  At most 15 bytes read.  Returns the offset of that F, or -1 */
+__device__ __forceinline__ long long keep_lost(const Geom &gf, const unsigned char *__restrict__ mf, int I, int J, int K)
+{
+    const int N = gf.N;
+    const long long p0 = gidx(gf, 2 * I, 2 * J, 2 * K);
+    for (int t = 1; t < 8; t++) {
+        const int a = t >> 2, b = (t >> 1) & 1, c = t & 1;
+        if (2 * I + a > N - 1 || 2 * J + b > N - 1 || 2 * K + c > N - 1)
+            continue;
+        const long long pF = p0 + a * gf.plane + b * (long long)gf.pitch + c;
+        if (!mf[pF])
+            continue;
+        bool lost = true;
+        for (int q = 0; q < 8; q++)
+            if (!(q & ~t)) /* the parents: the subsets of (a, b, c) */
+                lost = lost && mf[p0 + 2 * ((q >> 2) * gf.plane + ((q >> 1) & 1) * (long long)gf.pitch + (q & 1))] == 0;
+        if (lost)
+            return pF;
+    }
+    return -1;
+}
+
+/* one thread per coarse point, set-up time only; the caller refreshes the coarse duplicates behind it (k_mask_refresh) */
+__global__ void __launch_bounds__(256) mask_keep_kernel(Geom gf, const unsigned char *__restrict__ mf, Geom gc,
+                                                        unsigned char *__restrict__ mc)
+{
+    const int kc = blockIdx.x * WAVE + threadIdx.x;
+    const int jc = blockIdx.y * 4 + threadIdx.y;
+    const int ic = blockIdx.z;
+    if (kc >= gc.N || jc >= gc.N)
+        return;
+    unsigned char b = mf[gidx(gf, 2 * ic, 2 * jc, 2 * kc)];
+    if (!b) {
+        const long long p = keep_lost(gf, mf, ic, jc, kc);
+        if (p >= 0)
+            b = mf[p];
+    }
+    mc[gidx(gc, ic, jc, kc)] = b;
+}
+
+void k_mask_keep(const Geom &gf, const unsigned char *mf, const Geom &gc, unsigned char *mc, hipStream_t s)
+{
+    assert(gf.N == 2 * gc.N - 1); /* (every hierarchy meets it, as for k_prolong: operator state is never left unwritten) */
+    dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
+    hipLaunchKernelGGL(mask_keep_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, mf, gc, mc);
+}
+
+/* u of the coarse level for mg3d_fmg_solve under MG3D_MASK_KEEP: the injection uc[C] = uf[2C], except that a fixed unknown
+ * of the coarse level whose own fine point is not fixed -- it stands for a lost fine point -- takes u of that fine point,
+ * the conductor's potential.  A periodic duplicate asks at its source, so it holds its source's value. */
+__global__ void __launch_bounds__(256) fmg_inject_kernel(Geom gf, const double *__restrict__ uf,
+                                                         const unsigned char *__restrict__ mf, Geom gc,
+                                                         double *__restrict__ uc, int bc)
+{
+    const int k = blockIdx.x * WAVE + threadIdx.x;
+    const int j = blockIdx.y * 4 + threadIdx.y;
+    const int i = blockIdx.z;
+    const int N = gc.N;
+    if (k >= N || j >= N)
+        return;
+    const int si = ((bc & 1) && i == N - 1) ? 0 : i, sj = ((bc & 2) && j == N - 1) ? 0 : j, sk = ((bc & 4) && k == N - 1) ? 0 : k;
+    long long q = gidx(gf, 2 * i, 2 * j, 2 * k);
+    if (bc_unknown(bc, N, si, sj, sk) && !mf[gidx(gf, 2 * si, 2 * sj, 2 * sk)]) {
+        const long long p = keep_lost(gf, mf, si, sj, sk);
+        if (p >= 0)
+            q = p;
+    }
+    uc[gidx(gc, i, j, k)] = uf[q];
+}
+
+void k_fmg_inject(const Geom &gf, const double *uf, const unsigned char *mf, const Geom &gc, double *uc, int bc, hipStream_t s)
+{
+    assert(gf.N == 2 * gc.N - 1);
+    dim3 grid((gc.N + WAVE - 1) / WAVE, (gc.N + 3) / 4, gc.N);
+    hipLaunchKernelGGL(fmg_inject_kernel, grid, dim3(WAVE, 4, 1), 0, s, gf, uf, mf, gc, uc, bc);
 }
 
 /* -------------------------------------------------------------- prolongation
@@ -1563,9 +1655,11 @@ __device__ __forceinline__ double fmg_sum(const FmgTaps &t, double x0, double x1
 #define FMG_TJ 8  /* fine rows of a tile */
 #define FMG_CJ 7  /* coarse rows its j pass reads: logical Jc0-1 .. Jc0+5 */
 
-template <int BC>
+/* With fixed points (the pack M: the fine level's bytes, one trailing argument) a fixed unknown of the fine level is not
+ * written; every store goes to an unknown, so the raw byte decides.  Without the pack: the kernel as it was */
+template <int BC, class... M>
 __global__ void __launch_bounds__(256) fmg_interp_kernel(Geom gc, const double *__restrict__ uc, Geom gf,
-                                                         double *__restrict__ uf, int bc, int chunk)
+                                                         double *__restrict__ uf, int bc, int chunk, M... fixed)
 {
     __shared__ double T1[2][FMG_CJ][WAVE];
     const int Nc = gc.N, Nf = gf.N;
@@ -1619,7 +1713,7 @@ __global__ void __launch_bounds__(256) fmg_interp_kernel(Geom gc, const double *
         o1 = fmg_sum(tj[1], T[r[1][0]][tx], T[r[1][1]][tx], T[r[1][2]][tx], T[r[1][3]][tx]);
     };
     auto store = [&](int i, int m, double x) {
-        if (ok[m])
+        if (ok[m] && !mask_fixed(gidx(gf, i, j[m], k), fixed...))
             store_dup(gf, uf, gidx(gf, i, j[m], k), x, ai.per && i == 0, aj.per && j[m] == 0, dk);
     };
 
@@ -1661,7 +1755,7 @@ __global__ void __launch_bounds__(256) fmg_interp_kernel(Geom gc, const double *
     }
 }
 
-void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s)
+void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, int bc, hipStream_t s, const unsigned char *mf)
 {
     if (gf.N != 2 * gc.N - 1 || gc.N < 3)
         return;
@@ -1671,7 +1765,14 @@ void k_fmg_interp(const Geom &gc, const double *uc, const Geom &gf, double *uf, 
         chunk /= 2;
     const dim3 grid(gx, gy, (gc.N + chunk - 1) / chunk), block(WAVE, 4, 1);
     const int mode = bc_mode(bc);
-    if (mode == BC_REFLECT)
+    if (mf) {
+        if (mode == BC_REFLECT)
+            hipLaunchKernelGGL((fmg_interp_kernel<BC_REFLECT, MaskPtr>), grid, block, 0, s, gc, uc, gf, uf, bc, chunk, mf);
+        else if (mode == BC_WRAP)
+            hipLaunchKernelGGL((fmg_interp_kernel<BC_WRAP, MaskPtr>), grid, block, 0, s, gc, uc, gf, uf, bc, chunk, mf);
+        else
+            hipLaunchKernelGGL((fmg_interp_kernel<BC_PLAIN, MaskPtr>), grid, block, 0, s, gc, uc, gf, uf, bc, chunk, mf);
+    } else if (mode == BC_REFLECT)
         hipLaunchKernelGGL(fmg_interp_kernel<BC_REFLECT>, grid, block, 0, s, gc, uc, gf, uf, bc, chunk);
     else if (mode == BC_WRAP)
         hipLaunchKernelGGL(fmg_interp_kernel<BC_WRAP>, grid, block, 0, s, gc, uc, gf, uf, bc, chunk);

@@ -379,9 +379,25 @@ extern "C" int mg3d_ctx_get_coefficient(mg3d_ctx *ctx, int level, double *host)
 
 /* ------------------------------------------------------------------------------------------------ fixed points */
 
+/* Levels L-2 .. 0 of the mask from the finest level's stored bytes (its duplicates hold their sources') by the context's
+ * rule: injection, or MG3D_MASK_KEEP (k_mask_keep), behind which each coarse level's duplicates take their sources' bytes
+ * before the next level reads them -- a duplicate plane sees fewer fine points than its source does.  Enqueued only */
+static void mask_coarsen(mg3d_ctx *ctx)
+{
+    const int bc = mg3d_ctx_bc(ctx);
+    for (int l = ctx->L - 1; l >= 1; l--) {
+        if (ctx->mask_rule == MG3D_MASK_KEEP) {
+            k_mask_keep(ctx->lv[l].g, ctx->mask.lv[l], ctx->lv[l - 1].g, ctx->mask.lv[l - 1], ctx->stream);
+            k_mask_refresh(ctx->lv[l - 1].g, ctx->mask.lv[l - 1], bc, ctx->stream);
+        } else {
+            k_mask_inject(ctx->lv[l].g, ctx->mask.lv[l], ctx->lv[l - 1].g, ctx->mask.lv[l - 1], ctx->stream);
+        }
+    }
+}
+
 /* the mask from a checked device array: the cycle that has run ahead, then everything that can fail for want of memory
- * (nothing has changed when it does), the pack into the finest level (duplicates from their sources), the injections, the
- * counts and level 0's bytes for the coarse matrix, the coarse factor */
+ * (nothing has changed when it does), the pack into the finest level (duplicates from their sources), the coarser levels
+ * by the context's rule, the counts and level 0's bytes for the coarse matrix, the coarse factor */
 static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
 {
     const int L = ctx->L;
@@ -393,16 +409,15 @@ static int mask_install(mg3d_ctx *ctx, const mg3d_array &a, const char *who)
         StageScope kt(ctx, L - 1, MG3D_K_PACK, true);
         k_mask_pack(ctx->lv[L - 1].g, ctx->mask.lv[L - 1], a, mg3d_ctx_bc(ctx), ctx->stream);
     }
-    for (int l = L - 1; l >= 1; l--)
-        k_mask_inject(ctx->lv[l].g, ctx->mask.lv[l], ctx->lv[l - 1].g, ctx->mask.lv[l - 1], ctx->stream);
+    mask_coarsen(ctx);
     const int rc = field_to_host(ctx, ctx->mask, who);
     if (rc != MG3D_OK)
         return field_abandon(ctx, ctx->mask, rc);
     return operator_changed(ctx);
 }
 
-/* Fixed points (mg3d_kernels.hip): one byte per point of every level, the finest level's as given, the others' by injection.
- * NULL: no mask again. */
+/* Fixed points (mg3d_kernels.hip): one byte per point of every level, the finest level's as given, the others' by the
+ * context's coarsening rule (injection unless mg3d_ctx_set_mask_coarsening said otherwise).  NULL: no mask again. */
 extern "C" int mg3d_ctx_set_mask(mg3d_ctx *ctx, const unsigned char *mask)
 {
     static const char who[] = "mg3d_ctx_set_mask";
@@ -446,6 +461,41 @@ extern "C" int mg3d_ctx_has_mask(const mg3d_ctx *ctx, int *on) { return field_ha
 extern "C" int mg3d_ctx_get_mask(mg3d_ctx *ctx, int level, unsigned char *host)
 {
     return field_get(ctx, &mg3d_ctx::mask, level, host, "mg3d_ctx_get_mask", "mask");
+}
+
+/* How the levels below the finest take the mask: operator state, for grid values depend on it -- no launch option.  The
+ * argument is checked before anything changes.  Without a mask the rule is kept for the next one.  With one, a rule that
+ * differs from the present one: a cycle that has run ahead is finished with the hierarchy it started with, levels L-2 .. 0
+ * are taken again from the finest level's stored bytes, the fixed unknowns counted and level 0 read back (one host
+ * synchronisation), the coarse factor rebuilt or dropped.  The same rule again changes nothing. */
+extern "C" int mg3d_ctx_set_mask_coarsening(mg3d_ctx *ctx, int rule)
+{
+    static const char who[] = "mg3d_ctx_set_mask_coarsening";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (rule != MG3D_MASK_INJECT && rule != MG3D_MASK_KEEP)
+        return fail(MG3D_ERR_ARG, "%s: rule = %d (MG3D_MASK_INJECT or MG3D_MASK_KEEP)", who, rule);
+    if (rule == ctx->mask_rule)
+        return MG3D_OK;
+    if (!ctx->mask.set()) {
+        ctx->mask_rule = rule;
+        return MG3D_OK;
+    }
+    CHK(mg3d_drop_carry(ctx));
+    ctx->mask_rule = rule;
+    mask_coarsen(ctx);
+    const int rc = field_to_host(ctx, ctx->mask, who);
+    if (rc != MG3D_OK)
+        return field_abandon(ctx, ctx->mask, rc);
+    return operator_changed(ctx);
+}
+
+extern "C" int mg3d_ctx_get_mask_coarsening(const mg3d_ctx *ctx, int *rule)
+{
+    if (!ctx || !rule)
+        return fail(MG3D_ERR_ARG, "mg3d_ctx_get_mask_coarsening: NULL argument");
+    *rule = ctx->mask_rule;
+    return MG3D_OK;
 }
 
 /* ------------------------------------------------------------------------------------------ the screening field */
@@ -532,16 +582,22 @@ extern "C" int mg3d_ctx_get_shift_field(mg3d_ctx *ctx, int level, double *host)
 /* the boundary masks changed.  Under a screening field: the finest level's duplicates of a periodic axis take their
  * sources' values, and the coarser levels and the counts are taken again, for the restriction is the boundary word's.  Under
  * a mask: the duplicates take their sources' bytes -- for good: the caller's bytes there are not kept, an axis that stops
- * being periodic finds its plane N-1 with plane 0's bytes -- and which fixed points are unknowns is counted again.  Then the
- * coarse factor, as for every change of the operator */
+ * being periodic finds its plane N-1 with plane 0's bytes -- and which fixed points are unknowns is counted again; under
+ * MG3D_MASK_KEEP the lower levels are coarsened again from the finest one (re-injection alone would not do: which lost point a
+ * coarse point stands for depends on the duplicates' bytes).  Then the coarse factor, as for every change of the operator */
 static int boundaries_changed(mg3d_ctx *ctx, const char *who)
 {
     if (ctx->sfield.set())
         CHK(sfield_rebuild(ctx, who));
     if (!ctx->mask.set())
         return operator_changed(ctx);
-    for (int l = 0; l < ctx->L; l++)
-        k_mask_refresh(ctx->lv[l].g, ctx->mask.lv[l], mg3d_ctx_bc(ctx), ctx->stream);
+    if (ctx->mask_rule == MG3D_MASK_KEEP) {
+        k_mask_refresh(ctx->lv[ctx->L - 1].g, ctx->mask.lv[ctx->L - 1], mg3d_ctx_bc(ctx), ctx->stream);
+        mask_coarsen(ctx);
+    } else {
+        for (int l = 0; l < ctx->L; l++)
+            k_mask_refresh(ctx->lv[l].g, ctx->mask.lv[l], mg3d_ctx_bc(ctx), ctx->stream);
+    }
     const int rc = field_to_host(ctx, ctx->mask, who);
     if (rc != MG3D_OK)
         return field_abandon(ctx, ctx->mask, rc);
