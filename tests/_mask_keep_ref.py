@@ -84,7 +84,7 @@ class Hierarchy(MR.Hierarchy):
     """_mask_ref.Hierarchy with the coarser masks taken under `rule` (KEEP by default; INJECT: the parent class itself)"""
 
     def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, grid_length=1.0, rule=KEEP):
-        MR.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, mask, grid_length)
+        MR.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, mask, grid_length, lu=rule != KEEP)
         self.rule = rule
         self.origin = [None] * L
         if rule == KEEP:
@@ -96,7 +96,7 @@ class FieldHierarchy(SF.Hierarchy):
     """_shift_field_ref.Hierarchy (a mask and a screening field s) with the coarser masks taken under KEEP"""
 
     def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, s, grid_length=1.0):
-        SF.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, mask, s, grid_length)
+        SF.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, mask, s, grid_length, lu=False)
         self.mask, self.origin = keep(self.mask[-1], L, axes, origins=True)
         self.LU = SF.coarse_lu(c, self.h * (1 << (L - 1)), self.e(0), sigma, axes, faces, self.mask[0], self.sf(0))
 
@@ -218,5 +218,51 @@ def thin_mask(N, seed=3):
         for g in _images(F, N):
             m[g] = byte
     return m
+
+
+SEAM = (125, 127, 129, 131)  # fine indices around coarse index 64: its lower parents are coarse 62 .. 65
+
+
+def seam_points(N):
+    """the planted lost points of seam_mask: [((i, j, k), byte), ...], the bytes all different.  All three indices odd: k
+    in SEAM (those below N-1) with i and j in {1, N//2|1, N-2}, then the same with j and k exchanged; a named point of
+    thin_mask is left to it"""
+    q = (N // 2) | 1
+    side = (1, q, N - 2)
+    seam = [x for x in SEAM if x <= N - 2]
+    pts = [(i, j, k) for i in side for j in side for k in seam]
+    pts += [(i, k, j) for i, j, k in pts if (i, k, j) not in pts]
+    named = {F for F, _ in thin_points(N).values()}  # (129: the high corner is one of thin_mask's)
+    pts = [p for p in pts if p not in named]
+    assert len(pts) < 200
+    return [(p, 32 + n) for n, p in enumerate(pts)]
+
+
+def seam_mask(N, seed=3):
+    """thin_mask with lost points planted where the threads of a kernel that runs one thread per COARSE point pass from
+    their first block of 64 lanes in k into the second (N >= 129: coarse side >= 65), and the same pattern along j.  Each
+    planted point F is made lost as thin_mask makes its named points lost: the fine points 2P of its eight parents and the
+    other children of its lower parent C = floor(F/2) are cleared with their images, so that origin[C] = F under every
+    periodic mask (no planted point lies on a face).  Its byte is its own (seam_points): a coarse byte taken from the wrong
+    fine point is a wrong byte."""
+    m = thin_mask(N, seed)
+    pts = seam_points(N)
+    for F, _ in pts:
+        for t in range(8):
+            a, b, c = t >> 2, (t >> 1) & 1, t & 1
+            for p in ((F[0] - 1 + a, F[1] - 1 + b, F[2] - 1 + c),  # 2C and the children of C
+                      (F[0] - 1 + 2 * a, F[1] - 1 + 2 * b, F[2] - 1 + 2 * c)):  # the parents' fine points
+                for g in _images(p, N):
+                    m[g] = 0
+    for F, byte in pts:
+        m[F] = byte
+    return m
+
+
+def second_block_counts(origin_level, Nc):
+    """(lost points whose coarse point has 64 <= K <= Nc-2, those with K == Nc-1) of one level's origin array: what a
+    kernel with one thread per coarse point reaches only in its second block of 64 lanes"""
+    lost = origin_level >= 0
+    return int(lost[:, :, 64:Nc - 1].sum()), int(lost[:, :, Nc - 1].sum())
 
 

@@ -197,11 +197,12 @@ def coarse_solve(LU, d0, u0, axes, faces, sigma, mask0, one_level=False):
 class Hierarchy(NR.Problem):
     """_neumann_ref.Problem with fixed points: `mask` is the finest level's, (N, N, N) bytes or bool"""
 
-    def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, grid_length=1.0):
-        NR.Problem.__init__(self, c, L, nu, sigma, eps, axes, faces, grid_length)
+    def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, grid_length=1.0, lu=True):
+        NR.Problem.__init__(self, c, L, nu, sigma, eps, axes, faces, grid_length, lu=False)
         top = stored(np.asarray(mask).reshape((self.N[-1],) * 3), axes)
         self.mask = inject(top, L)
-        self.LU = coarse_lu(c, self.h * (1 << (L - 1)), self.e(0), sigma, axes, faces, self.mask[0])
+        if lu:
+            self.LU = coarse_lu(c, self.h * (1 << (L - 1)), self.e(0), sigma, axes, faces, self.mask[0])
 
     def fixed(self, l=-1):
         return fixed(self.mask[l], self.axes, self.faces)

@@ -311,7 +311,7 @@ class Problem:
     sigma and eps (the finest level's, or None).  blocks: the stencils of levels of more than `blocks` points per side
     run in their block forms."""
 
-    def __init__(self, c, L, nu, sigma, eps, axes, faces, grid_length=1.0, blocks=200):
+    def __init__(self, c, L, nu, sigma, eps, axes, faces, grid_length=1.0, blocks=200, lu=True):
         assert valid(axes, faces)
         self.c, self.L, self.nu, self.sigma, self.axes, self.faces, self.blocks = c, L, nu, sigma, axes, faces, blocks
         self.N = O.level_sizes(c, L)
@@ -324,7 +324,9 @@ class Problem:
             top = np.array(eps, dtype=np.float64).reshape((self.N[-1],) * 3)
             refresh(top, axes)
             self.eps = CR.inject(top, L)
-        self.LU = coarse_lu(c, self.h * (1 << (L - 1)), None if eps is None else self.eps[0], sigma, axes, faces)
+        self.LU = None  # (lu = False: a subclass factors its own coarse matrix)
+        if lu:
+            self.LU = coarse_lu(c, self.h * (1 << (L - 1)), None if eps is None else self.eps[0], sigma, axes, faces)
 
     def e(self, l):
         return None if self.eps is None else self.eps[l]

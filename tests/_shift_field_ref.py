@@ -201,14 +201,15 @@ class Hierarchy(MR.Hierarchy):
     """_mask_ref.Hierarchy with a screening field: `s` is the finest level's, (N, N, N), or None; `mask` may be None.
     rule: "restrict" (the library's) or "inject" (for the measurement of the two rules)"""
 
-    def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, s, grid_length=1.0, rule="restrict"):
+    def __init__(self, c, L, nu, sigma, eps, axes, faces, mask, s, grid_length=1.0, rule="restrict", lu=True):
         N = O.level_sizes(c, L)[-1]
-        MR.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, _mask(mask, N), grid_length)
+        MR.Hierarchy.__init__(self, c, L, nu, sigma, eps, axes, faces, _mask(mask, N), grid_length, lu=lu and s is None)
         self.s = None
         if s is not None:
             top = np.asarray(s, dtype=np.float64).reshape(N, N, N)
             self.s = restrict_field(top, L, axes, faces) if rule == "restrict" else inject_field(top, L, axes)
-            self.LU = coarse_lu(c, self.h * (1 << (L - 1)), self.e(0), sigma, axes, faces, self.mask[0], self.s[0])
+            if lu:
+                self.LU = coarse_lu(c, self.h * (1 << (L - 1)), self.e(0), sigma, axes, faces, self.mask[0], self.s[0])
 
     def sf(self, l):
         return None if self.s is None else self.s[l]

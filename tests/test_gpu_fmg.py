@@ -43,7 +43,8 @@ def _solver(c, L, nu, sigma=0.0, eps=None, axes=0, faces=0):
 # fine side -> (c, L) with the interpolation into the top level: 5 (Nc = 3, the two-term form), 9 (Nc = 5: both one-sided
 # rows touch the central ones), 17, 33, 65 and 73 / 81 (past the 64-lane row by 1, 9 and 17 columns; 67 is no side of a
 # hierarchy with a coarse grid small enough to factor, 73 none with the even c - 1 a periodic axis needs), 129 (several
-# tiles in j and chunks in i)
+# tiles in j, and the most chunks in i at the shortest chunk: k_fmg_interp marches 2 coarse planes a block at every side
+# up to 129; the chunk lengths 4, 8 and 16 are held in tests/test_gpu_mask_keep_shapes.py at 145 .. 257)
 _SHAPES = {5: (3, 2), 9: (5, 2), 17: (5, 3), 33: (5, 4), 65: (5, 5), 73: (10, 4), 81: (11, 4), 129: (5, 6)}
 # (periodic axes, Neumann faces): none; each periodic axis, all three; each Neumann face; both faces of j; periodic k with
 # Neumann i-low and Dirichlet j

@@ -123,7 +123,9 @@ def test_hierarchy(c, L, axes, faces):
 
 @pytest.mark.parametrize("axes,faces", [(0, 0), (7, 0), (2, 1 | 2 | 16)])
 def test_hierarchy_at_65(axes, faces):
-    """65^3: rows of more than one block of 64 lanes on the two finest levels"""
+    """65^3: the fine level's rows of bytes are longer than one block of 64 lanes.  mask_keep_kernel runs one thread per
+    COARSE point and the coarse side is 33 here, so its threads stay in one k-block; the second block of threads, with
+    lost points behind coarse column 63, is reached in tests/test_gpu_mask_keep_shapes.py (145^3 .. 193^3)"""
     c, L, N = 5, 5, 65
     mask = MK.thin_mask(N)
     for p in itertools.product((61, 63), (1, 63), (62, 63, 64)):  # lost points around the lane-block boundary

@@ -82,6 +82,44 @@ def test_the_named_points_of_the_test_mask_are_lost(N, axes):
     assert 0.08 < (m != 0).mean() < 0.2
 
 
+# (c, L, periodic axes): the shapes and periodic words of tests/test_gpu_mask_keep_shapes.py past coarse column 64
+SEAM_CASES = [(10, 5, 0), (6, 6, 0), (11, 5, 7), (11, 5, 4), (11, 5, 2)]
+
+
+@pytest.mark.parametrize("c,L,axes", SEAM_CASES)
+def test_the_seam_mask_reaches_past_coarse_column_64(c, L, axes):
+    """seam_mask at 145^3 and 161^3, what tests/test_gpu_mask_keep_shapes.py relies on: every planted point (and every named
+    point of thin_mask under it) is lost by the stated rule and is the point its lower parent stands for, with its own
+    byte; on the level below the finest at least 1000 lost points have a coarse column 64 <= K <= Nc-2 and at least one
+    has K == Nc-1; the invariant holds on every level.  Measured: 16146 and 1041 at 145^3; 39755 and 1315 at 161^3
+    without a periodic axis, 40240 and 2454 with all three"""
+    N = _n(c, L)
+    assert N in (145, 161)
+    Nc = (N + 1) // 2
+    m = MR.stored(MK.seam_mask(N), axes)
+    levels, origins = MK.keep(m, L, axes, origins=True)
+    mc, origin = levels[L - 2], origins[L - 2]
+    idx = np.arange(N ** 3).reshape(N, N, N)
+    planted = MK.seam_points(N)
+    assert len({F for F, _ in planted}) == len({b for _, b in planted}) == len(planted) == 72
+    assert {F[2] for F, _ in planted} >= set(MK.SEAM) and {F[1] for F, _ in planted} >= set(MK.SEAM)
+    for F, byte in planted + list(MK.thin_points(N).values()):
+        C = tuple(x // 2 for x in F)
+        assert m[F] == byte, F
+        parents = {(C[0] + al * (F[0] & 1), C[1] + be * (F[1] & 1), C[2] + ga * (F[2] & 1))
+                   for al, be, ga in itertools.product((0, 1), repeat=3)}
+        assert all(m[2 * P[0], 2 * P[1], 2 * P[2]] == 0 for P in parents), f"{F}: a parent's own fine point is fixed"
+        src = tuple(0 if MR.PER.per(axes, ax) and F[ax] == N - 1 else F[ax] for ax in range(3))
+        assert mc[C] == byte and origin[C] == idx[src], F
+    assert {F[2] // 2 for F, _ in planted} >= {62, 63, 64, 65}  # both sides of the boundary between the k-blocks
+    inside, last = MK.second_block_counts(origin, Nc)
+    print(N, axes, "lost points with 64 <= K <= Nc-2:", inside, "with K == Nc-1:", last)
+    assert inside >= 1000 and last >= 1
+    for l in range(1, L):
+        assert MK.parents_fixed(levels[l], levels[l - 1]).all(), l
+    assert 0.08 < (m != 0).mean() < 0.2
+
+
 @pytest.mark.parametrize("c,L", SHAPES)
 @pytest.mark.parametrize("axes", AXES)
 def test_every_fixed_point_has_a_fixed_parent_on_every_level(c, L, axes):
