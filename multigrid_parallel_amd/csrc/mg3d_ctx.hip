@@ -247,6 +247,7 @@ static const OptionRow kOptionTable[MG3D_OPT_COUNT] = {
     {"sweep_nw", nullptr, 0, 0},
     {"sweep_pf", nullptr, 0, 0},
     {"d_zero_skip", "MG3D_D_ZERO_SKIP", 0, 1},
+    {"zero_front", "MG3D_ZERO_FRONT", 0, 1},
 };
 
 void mg3d_options_init(mg3d_options *o)

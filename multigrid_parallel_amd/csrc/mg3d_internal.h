@@ -89,6 +89,7 @@ enum {
     MG3D_OPT_SWEEP_NW,     /*      fall back to the default */
     MG3D_OPT_SWEEP_PF,
     MG3D_OPT_D_ZERO_SKIP,  /* the planes of the top level's d that are +0.0 at every interior point are not read (the zero map, mg3d_ctx.h): 0 off, 1 the map and, when it is full, the leg kernels without d (default), 2 the map only */
+    MG3D_OPT_ZERO_FRONT,   /* the four-pass launch from the zero guess (a coarse level's pre-smoother) forms its first pass from d as the plane arrives and runs a three-pass kernel (ZF, mg3d_sweep_kernel.h): 1 (default), 0 the four-pass kernel on an input that is not read */
     MG3D_OPT_COUNT
 };
 struct mg3d_options {

@@ -93,10 +93,12 @@ static int device_cus() /* of the CURRENT device (a process may drive several: m
  * the levels below the top one, a dense d, the slab path -- runs a kernel with no trace of it.  Compiled for the tile shapes
  * the default schedules use; the shapes only the options sweep_rj / nw / pf reach read every plane.
  * ND: the launcher has chosen the kernel without d (SweepArgs::d_none, the leg launches): neither a.d nor a.dz is looked at. */
-template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND>
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND, int ZF>
 static bool launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s) /* true: the instantiation with the zero map ran */
 {
-    if constexpr (ND) { /* (the else branch is discarded: an ND shape has no siblings that read d unless another launch names them) */
+    if constexpr (ZF != 0) { /* the zero front (sweep_passes): every plane of d is read, no sibling with a map */
+        hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false, false, ZF>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
+    } else if constexpr (ND) { /* (the else branch is discarded: an ND shape has no siblings that read d unless another launch names them) */
         hipLaunchKernelGGL((sweep_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, false, true>), dim3(blocks), dim3(NW * WAVE), 0, s, a);
     } else {
         if constexpr (NW == 8 && ((RJ == 4 && PF == 1) || (RJ == 2 && PF >= 2))) {
@@ -110,12 +112,15 @@ static bool launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s) /*
     return false;
 }
 
-template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1, bool ND = false>
+template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1, bool ND = false, int ZF = 0>
 static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s, SweepTaken *t)
 {
     using Sh = SweepShape<S, RES>;
     constexpr int VJ = NW * RJ - 2 * Sh::HJ;
     const Geom &g = a.g;
+    /* no input: only the front, which reads none, and the shapes whose plane load tests for it */
+    if (a.vin == nullptr && ZF != ZF_FRONT && !sweep_tests_input<S, RES, RJ, NW, PF, PRO, RES == 3 ? S / 2 : TAP, ZF>())
+        return -1;
     a.ntj = (g.nj + VJ - 1) / VJ;
     /* k-tiling: tiles of 128 columns starting at multiples of vk = 128 - 2*hk, hk >= HK.  The first and the last
      * tile own their columns up to the global boundary (no halo needed there), so T tiles cover vk*(T-1) + 128
@@ -146,7 +151,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
             return -1;
         a.CI = a.edge;
         a.xcd_remap = 2 * T < 64 ? 0 : 2 * T <= ncu ? 1 : 2;
-        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)(2 * T), s), 2 * T);
+        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND, ZF>(a, (unsigned)(2 * T), s), 2 * T);
         return (int)(2 * T);
     }
     const int ovh = Sh::HI + Sh::ST + (RES == 2 ? 2 : 0) + 1;
@@ -217,7 +222,7 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
         static_assert(C1K < 0 || !PRO || C1K == 0, "PRO launches are post-smoothers");
         if (C1K >= 0 && a.c1 != C1K)
             return;
-        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND>(a, (unsigned)nb, s), nb);
+        record(launch_kernel<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND, ZF>(a, (unsigned)nb, s), nb);
     };
     /* Measured choice.  The model above ranks chunk lengths by steps; what a step costs depends on how many CUs stream
      * at once and on how well the chunks keep in lock-step, which it does not know.  The first launch of a shape on a
@@ -229,11 +234,11 @@ static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, h
      * into per-block partial sums, and a timing-dependent choice would make it differ from run to run */
     if (!forced && tune_on && !a.partials && T * nout >= 1024) {
         struct Key {
-            int v[15];
+            int v[16];
             bool operator<(const Key &o) const { return memcmp(v, o.v, sizeof v) < 0; }
         };
         const Key key = {{g.ni, g.nj, g.nk, g.N, g.ig0 & 1, a.i_lo, a.i_hi, a.vin != nullptr, a.partials != nullptr,
-                          a.r != nullptr, a.vk, max_partials, current_device(), a.dz != nullptr, (int)ND}};
+                          a.r != nullptr, a.vk, max_partials, current_device(), a.dz != nullptr, (int)ND, ZF}};
         static std::mutex mu;
         static std::map<Key, int> tuned; /* chunk length */
         std::lock_guard<std::mutex> lock(mu);
@@ -478,9 +483,33 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
         /* from the zero guess on the levels between 66 and 300 points per side (129^3, 257^3: a step is paid in latency, the
          * launch has a CU per block and little else): two rows a thread, SIXTEEN waves -- the same 32-row tile at four waves
          * per SIMD (128 VGPRs, no scratch): 257^3 80 -> 71-74 us, 129^3 25 -> 22 us; 65^3 and below 11.5 -> 14 (the eight-wave
-         * two-row shape stays), 513^3 425 -> 420 (the four-row shape stays); kernel trace, round 4 */
+         * two-row shape stays), 513^3 425 -> 420 (the four-row shape stays); kernel trace, round 4.  Measured on the four-pass
+         * kernels; the zero front below, which has taken their place from the zero guess, keeps the rule for its three shapes */
         const bool mid = vin == nullptr && g.N > 65 && g.N <= 300;
-        return dispatch<4, 0>(o, a, opt_cfg(o, mid ? SweepCfg{2, 16, 1} : small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s, t);
+        /* The zero front (option zero_front, ZF in the kernel): from the zero guess the first of the four passes is pointwise
+         * in d, so the launch runs the THREE-pass kernel of the other colour on an input formed from d as the plane arrives --
+         * a halo of 3 instead of 4 (26 owned rows of 32 instead of 24), one warm-up and one drain plane fewer per chunk, a
+         * quarter fewer stencil evaluations a step and no test for the absent input.  The same tile shapes by level size
+         * (sweep_rj / nw / pf choose among the three, anything else runs the level's default); its record says S = 3, which
+         * no other launch of kind PASSES does.  Not where d is known to be +0.0 (d_none) or comes with its zero map: those
+         * launches keep the four-pass kernels */
+        if (vin == nullptr && !w.d_none && !a.dz && o.v[MG3D_OPT_ZERO_FRONT] != 0) {
+            const SweepCfg dflt = mid ? SweepCfg{2, 16, 1} : small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1};
+            SweepCfg c = opt_cfg(o, dflt);
+            if (!((c.rj == 2 && c.nw == 16 && c.pf == 1) || (c.rj == 2 && c.nw == 8 && c.pf == 2) || (c.rj == 4 && c.nw == 8 && c.pf == 1)))
+                c = dflt;
+            a.c1 = 1 - c1; /* the front is the pass of colour c1 */
+            if (c.nw == 16)
+                return launch_sweep<3, 0, 2, 16, 1, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+            if (c.rj == 2)
+                return launch_sweep<3, 0, 2, 8, 2, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+            return launch_sweep<3, 0, 4, 8, 1, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+        }
+        /* without the front the zero guess takes the one four-pass kernel whose plane load still tests for an absent input
+         * (ZF_MAYBE: the sixteen-wave shape, on every level); the shapes of dispatch<4, 0> are launched with an input only */
+        if (vin == nullptr)
+            return launch_sweep<4, 0, 2, 16, 1, false, true, 0, -1, -1, false, ZF_MAYBE>(o, a, max_partials, s, t);
+        return dispatch<4, 0>(o, a, opt_cfg(o, small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, 1}), max_partials, s, t);
     }
     if (S == 2 && residual) {
         /* the norm alone (the top level's second post-smoothing launch): a shape without the code that assembles r */

@@ -179,7 +179,29 @@ __device__ unsigned long long g_dbg_bt[8][1024];
 /* ND: the launch's d is +0.0 at every interior point (SweepArgs::d_none).  No d window, no aging of it, nothing parked: the
  * update is sixth * sum -- hSq is positive and finite, hSq * (+0.0) is +0.0 and sum - (+0.0) is sum, bit for bit, for every
  * sum -- and the residual stays the SUBTRACTION 0. - invHsq * (...): 0 - (+0) is +0 where a negation would give -0. */
-template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false, bool ND = false>
+/* ZF, the zero front: the launch that begins a coarse level's pre-smoother from the zero guess (four passes, red first,
+ * vin == NULL).  Its first pass is pointwise in d -- every updatable red point becomes sixth * (0 - hSq * d), black points and
+ * faces stay +0.0 -- so it is no stage of the window: the kernel runs S = 3 passes black first (c1 = 0) on an input it forms
+ * from d when the plane arrives, and reads no u.  d then travels WITH its plane, not one behind (DLAG = 0): one more slot of
+ * the d window and one stage fewer.  The launcher names the launch's remaining three passes as S (sweep_passes).
+ * The slot has three values: ZF_FRONT the kernel above; ZF_OFF no front, and the launch has an input wherever
+ * sweep_tests_input says so; ZF_MAYBE no front and the input may be absent -- the four-pass kernel option zero_front = 0 runs
+ * from the zero guess. */
+enum { ZF_OFF = 0, ZF_FRONT = 1, ZF_MAYBE = 2 };
+/* Does the plane load test for an absent input (vin == NULL: identically zero, not read)?  Only where a zero guess can still
+ * arrive: two passes without a prolongation (the first launch of a V(1,1) pre-smoother), the whole down-leg in one launch
+ * <4, 2> (option fuse_leg_max) and ZF_MAYBE.  Every other shape is launched with an input or not at all (launch_sweep returns
+ * -1): prolonging, tapped, zero-, one- and three-pass shapes, and four passes without the front.  The test is a branch around
+ * the loads at the top of every step behind 64-bit moves that zero their destinations, and the loads of the next plane wait
+ * for both (profiles/dnone_down_ab.txt, section 2) */
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, int TAPQ, int ZFM> constexpr bool sweep_tests_input()
+{
+    /* (<4, 0, 4, 8, 2>, a shape only the options reach, keeps its test: without it the shape, at 256 VGPRs, takes 8 bytes of
+     * scratch -- profiles/zero_front_resources.txt) */
+    constexpr bool at_limit = S == 4 && RES == 0 && RJ == 4 && NW == 8 && PF == 2;
+    return ZFM == ZF_MAYBE || (ZFM == ZF_OFF && !PRO && TAPQ < 0 && (S == 2 || (S == 4 && RES == 2) || at_limit));
+}
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false, bool ND = false, int ZFM = ZF_OFF>
 __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepArgs a)
 {
     using Sh = SweepShape<S, RES>;
@@ -191,15 +213,20 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
     static_assert(TAPQ <= S, "tap behind the last pass");
     static_assert(!ND || DP == 0, "no d window: nothing to park");
     static_assert(!ND || !DZ, "no d window: no map to test");
+    constexpr bool ZF = ZFM == ZF_FRONT;
+    static_assert(ZFM == ZF_OFF || (S == (ZF ? 3 : 4) && RES == 0), "the launch from the zero guess: three passes behind the front, or four");
+    static_assert(ZFM == ZF_OFF || (!PRO && !ND && RES == 0 && TAP < 0), "the zero front: plain colour passes on a d that is read");
+    static_assert(ZFM == ZF_OFF || (!DZ && DP == 0 && C1K < 0), "the zero front: every plane of d is read, nothing parked, c1 from the launcher");
     constexpr int KV = ST - DP; /* slots of the d window kept in VGPRs */
     constexpr int TJ = NW * RJ, VJ = TJ - 2 * HJ;
     static_assert(RJ % 2 == 0, "RJ must be even (row parity of a wave's first row)");
     static_assert(VJ > 0 && ST >= 1, "tile too small");
     constexpr int STX = ST > 0 ? ST : 1;
     /* NDR: the restricting shape without d (the down-leg of the one-launch-per-leg schedule on a source-free problem).  The d
-     * window it does not hold leaves it 30-odd VGPRs below the limit the restricting shapes were written against, so three of
+     * window it does not hold leaves it 30-odd VGPRs below the limit the restricting shapes were written against, so two of
      * their economies are off in it: the r pairs stay in registers (RPARK), the update and the tap test lane masks formed once a
-     * step, and the plane load carries no test for an absent input (load_plane).  profiles/dnone_down_ab.txt */
+     * step.  (It was also the first shape whose plane load lost the test for an absent input: now sweep_tests_input's rule for
+     * every shape.)  profiles/dnone_down_ab.txt */
     constexpr bool NDR = ND && RES == 2;
 
     /* edge rows exchanged between waves: [parity][wave][top/bottom][stage][lane].  Two copies, written at the end of a step
@@ -341,7 +368,7 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
 #define MG3D_ADDR32 3 /* same bits: 32-bit per-lane offsets instead of 64-bit ones */
 #endif
     constexpr int SHAPE_BIT = (S == 4 && (RES == 0 || RES == 3)) ? 0 : 1;
-    constexpr int DLAG = (MG3D_DLAG >> SHAPE_BIT) & 1;
+    constexpr int DLAG = ZF ? 0 : (MG3D_DLAG >> SHAPE_BIT) & 1; /* (ZF: the plane's input is made of its own d) */
     static_assert(DP == 0 || DLAG == 1, "the parked d window assumes d trails u by one plane");
     constexpr bool A32 = ((MG3D_ADDR32 >> SHAPE_BIT) & 1) != 0;
     /* a row's offset = a wave-uniform part (row, scalar registers) + ONE per-lane part (column) for all rows: RJ - 1 VGPRs
@@ -437,29 +464,39 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         const int iu = i < 0 ? 0 : (i >= g.ni ? g.ni - 1 : i), id = i - DLAG < 0 ? 0 : (i - DLAG >= g.ni ? g.ni - 1 : i - DLAG);
 #endif
         /* plane bases in bytes, uniform: one scalar 64-bit product per plane, not one re-materialised per row */
-        long long pbase = (long long)((unsigned long long)plane_bytes * (unsigned)iu), pbase_d = ND ? 0ll : (long long)((unsigned long long)plane_bytes * (unsigned)id);
+        long long pbase = ZF ? 0ll : (long long)((unsigned long long)plane_bytes * (unsigned)iu), pbase_d = ND ? 0ll : (long long)((unsigned long long)plane_bytes * (unsigned)id);
         if constexpr (ND)
             asm volatile("" : "+s"(pbase));
+        else if constexpr (ZF)
+            asm volatile("" : "+s"(pbase_d));
         else
             asm volatile("" : "+s"(pbase), "+s"(pbase_d));
         /* the plane's base ADDRESS opaque, not only its offset: otherwise `field + plane offset + row offset` is
          * re-associated into a loop-invariant 64-bit `field + row offset` per row and field (2 VGPRs each, kept across the
          * plane loop) plus a 64-bit vector add per access, instead of the saddr form `SGPR base + 32-bit lane offset` */
-        unsigned long long ub_ = reinterpret_cast<unsigned long long>(a.vin) + (unsigned long long)pbase, db_ = 0ull;
+        unsigned long long ub_ = ZF ? 0ull : reinterpret_cast<unsigned long long>(a.vin) + (unsigned long long)pbase, db_ = 0ull;
         if constexpr (ND) {
             asm volatile("" : "+s"(ub_));
+        } else if constexpr (ZF) {
+            db_ = reinterpret_cast<unsigned long long>(a.d) + (unsigned long long)pbase_d;
+            asm volatile("" : "+s"(db_));
         } else {
             db_ = reinterpret_cast<unsigned long long>(a.d) + (unsigned long long)pbase_d;
             asm volatile("" : "+s"(ub_), "+s"(db_));
         }
         const gcbytes ubase = reinterpret_cast<gcbytes>(ub_), dbase = reinterpret_cast<gcbytes>(db_);
         /* vin == NULL: the input field is identically zero (a coarse level's initial guess, mg_3d.h:1258-1259) --
-         * neither zeroed in memory beforehand nor read.  NDR: the launcher passes an input (sweep_leg_down), no test: the test
-         * is a branch around the loads at the top of every step and eight 64-bit moves that zero their destinations in front
-         * of it, and the loads cannot be issued before either (513^3: 0.563 -> 0.511 ms) */
-        const bool have_u = NDR ? true : a.vin != nullptr; /* uniform */
+         * neither zeroed in memory beforehand nor read.  Tested only in the shapes a zero guess can reach
+         * (sweep_tests_input): the test is a branch around the loads at the top of every step and eight 64-bit moves that
+         * zero their destinations in front of it, and the loads cannot be issued before either (the restricting down-leg
+         * without d at 513^3: 0.563 -> 0.511 ms) */
+        const bool have_u = sweep_tests_input<S, RES, RJ, NW, PF, PRO, TAPQ, ZFM>() ? a.vin != nullptr : true; /* uniform */
         /* (one uniform test for the whole plane, not one per row: the rows' loads stay a straight line) */
-        if (have_u) {
+        if constexpr (ZF) { /* no u: the step forms the plane's input from dd, vv stays untouched (nothing reads it) */
+            (void)ubase;
+            (void)vv;
+            (void)have_u;
+        } else if (have_u) {
 #pragma unroll
             for (int rr = 0; rr < RJ; rr++) {
                 const gcbytes pu = ubase + row_base[rr] + lane_off(col_off);
@@ -632,7 +669,8 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
              * the queue a "second plane in flight" was never in flight for more than one step */
 #pragma unroll
             for (int rr = 0; rr < RJ; rr++) {
-                cur_v[rr] = nxt_v[PAR][rr];
+                if constexpr (!ZF)
+                    cur_v[rr] = nxt_v[PAR][rr];
                 if constexpr (!ND) {
                     dring[rr][0][0] = nxt_d[PAR][rr].x;
                     dring[rr][0][1] = nxt_d[PAR][rr].y;
@@ -642,19 +680,37 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
         } else {
 #pragma unroll
             for (int rr = 0; rr < RJ; rr++) {
-                cur_v[rr] = nxt_v[0][rr];
+                if constexpr (!ZF)
+                    cur_v[rr] = nxt_v[0][rr];
                 if constexpr (!ND) {
                     dring[rr][0][0] = nxt_d[0][rr].x;
                     dring[rr][0][1] = nxt_d[0][rr].y;
                 }
 #pragma unroll
                 for (int f = 0; f + 1 < PF; f++) {
-                    nxt_v[f][rr] = nxt_v[f + 1][rr];
+                    if constexpr (!ZF)
+                        nxt_v[f][rr] = nxt_v[f + 1][rr];
                     if constexpr (!ND)
                         nxt_d[f][rr] = nxt_d[f + 1][rr];
                 }
             }
             load_plane(i + PF, nxt_v[PF - 1], nxt_d[PF - 1]);
+        }
+        if constexpr (ZF) {
+            /* The zero front: plane i as the red pass leaves the zero guess.  The column active at this step holds the
+             * plane's red points (it is the one stage 1, a black pass, reads as its neighbours): the update's own expression
+             * with the neighbour sum the literal 0. where the update's masks hold -- a product subtracted from +0.0 is rounded
+             * once either way, and +0.0 - (+-0.0) is +0.0 --, +0.0 everywhere else, whatever d holds there: faces, rows,
+             * columns and planes outside the updatable range (a warm-up plane outside the level included), and the black column */
+            const bool pl_front = (unsigned)(i - upd_lo) <= upd_span;
+#pragma unroll
+            for (int rr = 0; rr < RJ; rr++) {
+                constexpr int X0 = PAR & 1; /* rows alternate: X = (PAR + rr) & 1 */
+                const int X = (X0 + rr) & 1;
+                const double dd = dring[rr][0][X];
+                const double f = ((row_upd[rr] & pl_front) & upd_col[X]) ? a.sixth * (0. - a.hSq * dd) : 0.;
+                cur_v[rr] = X ? make_double2(0., f) : make_double2(f, 0.);
+            }
         }
         double cbuf[CPT];
         bool stage_new = false;
@@ -833,7 +889,8 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
                         } else {
                             dd = dring[rr][s - DLAG][X];
                         }
-                        const double center = (s == 1) ? in_prev[rr][X] : last[rr][s - 2][X];
+                        /* (ZF: stage 1 updates the black points of a plane that came from the zero front: +0.0) */
+                        const double center = (s == 1) ? (ZF ? 0. : in_prev[rr][X]) : last[rr][s - 2][X];
                         double sum = up + dn;
                         sum = sum + jm;
                         sum = sum + jp;
