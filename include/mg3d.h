@@ -489,6 +489,75 @@ int mg3d_field_sample(mg3d_ctx *ctx, long long count, const double *xyz /* count
                       double *grad /* count x 3; NULL: not wanted */);
 int mg3d_deposit(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 */, const double *q /* count */, double scale);
 
+/* The MOVE between gather and scatter: one kick-and-drift step of `count` particles with the context's own boundary word and
+ * mask -- periodic axes wrap, Neumann faces reflect (the operator's mirror), Dirichlet faces and labelled conductors
+ * retire a particle and count it.  The sampled field never leaves registers.  tests/_push_ref.py restates it bit for bit.
+ *
+ * Vectors (mg3d_vec, checked as above; overlap between them is the caller's business):
+ *     pos[a]  MG3D_F64 only, stride >= 1, updated in place.  (A float position rounded on store can land outside a
+ *             reflecting wall: positions stay in double.)
+ *     vel[a]  MG3D_F64 or MG3D_F32 (rounded to nearest even on store), stride >= 1, updated in place
+ *     qm      MG3D_F64 or MG3D_F32, stride >= 0 (0: one charge-to-mass ratio for all)
+ *     fate    MG3D_I32 -- a dtype this vector alone takes, every other call keeps refusing it --, stride >= 1, read and
+ *             written: MG3D_FATE_ALIVE (0), a conductor's label 1..255, MG3D_FATE_FACE + f for face f = 0..5 (ilo, ihi,
+ *             jlo, jhi, klo, khi), MG3D_FATE_INVALID.
+ * Host constants, formed in this order (N, h of the finest level):
+ *     cs = scale*(0.5/h);  gdt[a] = dt*accel[a];  inv = 1.0/(1.0 + drag*dt);  n1 = (double)(N-1);  xper = n1*h;
+ *     xhi = xper; while (xhi/h > n1) xhi = nextafter(xhi, 0)      (the largest coordinate known to locate inside; division
+ *                                                                   is monotone, so every x <= xhi does)
+ * Per particle m whose fate[m] == 0 on entry (any other value: the particle is dead, nothing of it is read further and
+ * nothing is written), every operation uncontracted:
+ *   1 locate x0 as the sample does.  Not inside: the fate is set, pos and vel are not written, the particle is done.  The
+ *     fate is MG3D_FATE_INVALID if a coordinate or its quotient t is not finite; otherwise MG3D_FATE_FACE + 2a (t < 0) or
+ *     + 2a+1 (t > N-1) for the first axis a, in i, j, k order, on which the point is outside.
+ *   2 gather: E_a = the bits of grad_out[a] of mg3d_field_sample_device at x0 with this `scale` (cs above).
+ *   3 kick and drift:  k = qm_m*dt;  v1_a = (v0_a + ((k*E_a) + gdt[a])) * inv;  x1_a = x0_a + (dt*v1_a)
+ *     -- dv/dt = (q/m) E + accel - drag*v with the drag taken implicitly.  If k, a v1_a or an x1_a is not finite the fate is
+ *     MG3D_FATE_INVALID and nothing else is written.
+ *   4 walls, per axis a = 0, 1, 2 independently, tt = x1_a/h:
+ *       periodic axis          : tt < 0: x1_a = x1_a + xper;  tt >= n1: x1_a = x1_a - xper   (one wrap; the locator wraps the rest)
+ *       tt < 0,  Neumann face  : x1_a = -x1_a, v1_a = -v1_a          Dirichlet face: exit through face 2a
+ *       tt > n1, Neumann face  : x1_a = xhi - (x1_a - xhi), v1_a = -v1_a    Dirichlet face: exit through face 2a+1
+ *     The fate is MG3D_FATE_FACE + f of the first exit in axis order; wraps and reflections on the other axes still apply to
+ *     what is stored.  One reflection per axis and step: a particle that moves more than a box length is retired by
+ *     step 1 of the next push.  Keeping |v|*dt < h is the caller's job -- a body thinner than the step can be tunnelled.
+ *   5 conductors, on a context with a mask and only while the fate is still 0: x1 is located as in step 1 (a point that
+ *     is not inside skips this step); the nearest node is n_a = c_a + (w1_a >= 0.5), on a periodic axis N-1 becomes 0; b
+ *     is the byte mg3d_ctx_get_mask(finest) returns at that node; b != 0 makes the fate b.
+ *   6 stores: the final x1, v1 and -- where it changed -- the fate, also for particles retired in steps 4 and 5: the caller
+ *     sees where they hit.  Every transition from 0 to a fate f adds 1 to slot f of a table of MG3D_FATE_SLOTS 64-bit
+ *     counters on the device (an integer atomic add: the counts have the same bits in every run and for every order of
+ *     the particles), allocated and zeroed with the first push and freed with the context (MG3D_ERR_ALLOC, nothing
+ *     changed, when it does not fit).
+ * Read-only in the sense of "Field output": a cycle that has run ahead is finished as the sample finishes it, and no field,
+ * option, factor or flag changes; sigma, eps and the screening field play no part.  ONE launch per call (the sample's
+ * shape: 256 threads, at most MG3D_PARTICLE_MAX_BLOCKS blocks, striding on), counted under MG3D_K_PACK; the two-event
+ * stream ordering of "Device arrays", no host synchronisation.  count == 0: MG3D_OK, nothing launched or allocated.
+ * MG3D_ERR_ARG, nothing changed: a NULL context, pos, vel, vector or params; count < 0 or > 2^40; dt not finite or <= 0; scale
+ * or an accel not finite; drag negative or not finite; a bad dtype or stride; a foreign pointer.
+ * mg3d_particle_push: the same on host arrays -- xyz and vxyz count x 3, qm count doubles, fate count ints --, staged
+ *   like mg3d_field_sample: one device buffer for the call, one synchronisation, the bits of the device form.
+ * mg3d_particle_counts: synchronises once and copies the cumulative table; slot 0 is always 0 and the table is all zero
+ *   before the first push; reset != 0 zeroes the table behind the copy.
+ * Out of scope: magnetic fields (Boris); charge-weighted tallies (the caller's bincount of fate weighted by q);
+ * compaction or sorting; the slab and fp32 forms. */
+enum { MG3D_I32 = 3 };   /* beside MG3D_F64/F32/U8: the fate vector of the push only; every other call keeps refusing it */
+enum { MG3D_FATE_ALIVE = 0,        /* 1..255: absorbed by the conductor whose mask byte is this label */
+       MG3D_FATE_FACE = 256,       /* + f, f = 0..5 (ilo, ihi, jlo, jhi, klo, khi): left the box through / lies beyond face f */
+       MG3D_FATE_INVALID = 262,    /* a coordinate, velocity, q/m or field value that is not finite */
+       MG3D_FATE_SLOTS = 263 };
+typedef struct mg3d_push_params {
+    double dt;        /* > 0 */
+    double scale;     /* the force field is scale * grad u, exactly mg3d_field_sample's grad_out; -1: E = -grad u */
+    double accel[3];  /* a constant acceleration (gravity), along i, j, k */
+    double drag;      /* gamma >= 0: dv/dt = (q/m) E + accel - gamma v, the drag taken implicitly */
+} mg3d_push_params;
+int mg3d_particle_push_device(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3], const mg3d_vec *const vel[3],
+                              const mg3d_vec *qm, const mg3d_vec *fate, const mg3d_push_params *p, void *stream);
+int mg3d_particle_push(mg3d_ctx *ctx, long long count, double *xyz, double *vxyz, const double *qm, int *fate,
+                       const mg3d_push_params *p);           /* host arrays, count x 3; staged like mg3d_field_sample */
+int mg3d_particle_counts(mg3d_ctx *ctx, unsigned long long out[MG3D_FATE_SLOTS], int reset);
+
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)
  *                   postSmoother (post=1, mg_3d.h:711-781: iters x black,red)

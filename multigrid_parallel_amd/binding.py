@@ -34,6 +34,10 @@ def lib_path():
 _lib = None
 
 MG3D_F64, MG3D_F32, MG3D_U8 = 0, 1, 2  # mg3d_array.dtype (MG3D_U8: mg3d_ctx_set_mask_device only)
+MG3D_I32 = 3  # mg3d_vec.dtype of the fate vector of mg3d_particle_push_device, and of nothing else
+# the fates of mg3d_particle_push: 0 alive, 1..255 the label of the conductor that absorbed the particle, MG3D_FATE_FACE + f
+# for face f = 0..5 (ilo, ihi, jlo, jhi, klo, khi), MG3D_FATE_INVALID; MG3D_FATE_SLOTS counters (mg3d_particle_counts)
+MG3D_FATE_ALIVE, MG3D_FATE_FACE, MG3D_FATE_INVALID, MG3D_FATE_SLOTS = 0, 256, 262, 263
 
 
 class mg3d_array(C.Structure):
@@ -52,6 +56,12 @@ class mg3d_vec(C.Structure):
 
 
 _vp = C.POINTER(mg3d_vec)
+
+
+class mg3d_push_params(C.Structure):
+    """mg3d_push_params: the step dt, the scale of the force field (scale * grad u), a constant acceleration, the drag."""
+    _fields_ = [("dt", C.c_double), ("scale", C.c_double), ("accel", C.c_double * 3), ("drag", C.c_double)]
+
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/mg3d.h
 SIGNATURES = {
@@ -123,6 +133,11 @@ SIGNATURES = {
                                            C.c_void_p]),
     "mg3d_deposit": (C.c_int, [C.c_void_p, C.c_longlong, dp, dp, C.c_double]),
     "mg3d_deposit_device": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(_vp), _vp, C.c_double, C.c_void_p]),
+    "mg3d_particle_push_device": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp,
+                                            C.POINTER(mg3d_push_params), C.c_void_p]),
+    "mg3d_particle_push": (C.c_int, [C.c_void_p, C.c_longlong, dp, dp, dp, C.POINTER(C.c_int),
+                                     C.POINTER(mg3d_push_params)]),
+    "mg3d_particle_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -325,15 +340,20 @@ def _device_args(t, who, shape, writable=False):
     return a, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def vec_desc(t, writable=False, count=None):
+def vec_desc(t, writable=False, count=None, fate=False):
     """The mg3d_vec of a 1-D float64 / float32 torch tensor: data_ptr(), the dtype code and stride(0) in elements -- any
     view is described as it is, nothing is copied.  TypeError for anything else; ValueError for a length other than
-    `count` (when given) and, with writable=True, for a zero stride.  The tensor must stay alive until the call that takes
-    the descriptor has returned."""
+    `count` (when given) and, with writable=True, for a zero stride.  fate=True: the fate vector of push_tensor, int32
+    and nothing else (MG3D_I32), always written.  The tensor must stay alive until the call that takes the descriptor has
+    returned."""
     import torch
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"vec_desc: need a torch.Tensor, got {type(t).__name__}")
-    if t.dtype not in (torch.float64, torch.float32):
+    if fate:
+        if t.dtype != torch.int32:
+            raise TypeError(f"vec_desc: a fate vector is int32, got {t.dtype}")
+        writable = True
+    elif t.dtype not in (torch.float64, torch.float32):
         raise TypeError(f"vec_desc: need float64 or float32, got {t.dtype}")
     if t.dim() != 1:
         raise TypeError(f"vec_desc: need a 1-D tensor, got {t.dim()} dimensions")
@@ -342,6 +362,8 @@ def vec_desc(t, writable=False, count=None):
     st = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), 1)
     if writable and st == 0:
         raise ValueError("vec_desc: a tensor that is written needs a stride >= 1, got 0")
+    if fate:
+        return mg3d_vec(t.data_ptr(), MG3D_I32, st)
     return mg3d_vec(t.data_ptr(), MG3D_F64 if t.dtype == torch.float64 else MG3D_F32, st)
 
 
@@ -349,7 +371,7 @@ def _vec_ptrs(descs):
     return (_vp * 3)(*[C.pointer(d) if d is not None else _vp() for d in descs])
 
 
-def _position_args(pos, who):
+def _position_args(pos, who, writable=False):
     """the three position vectors of an (M, 3) tensor (any view) or of a sequence of three 1-D tensors of one length, all on
     one GPU: (descriptors, M, device, stream handle)"""
     import torch
@@ -371,7 +393,7 @@ def _position_args(pos, who):
     if any(t.dim() != 1 for t in parts):
         raise ValueError(f"{who}: each coordinate vector must be 1-D")
     M = parts[0].shape[0]
-    descs = [vec_desc(t, count=M) for t in parts]
+    descs = [vec_desc(t, writable=writable, count=M) for t in parts]
     return descs, M, parts[0].device, C.c_void_p(torch.cuda.current_stream(parts[0].device).cuda_stream)
 
 
@@ -906,6 +928,66 @@ class Solver:
             raise ValueError(f"deposit_tensor: q needs shape ({M},), got {tuple(q.shape)}")
         dq = vec_desc(q, count=M)
         check(self.L.mg3d_deposit_device(self._h, M, _vec_ptrs(descs), C.byref(dq), float(scale), stream))
+
+    @staticmethod
+    def _push_params(dt, scale, accel, drag):
+        accel = tuple(float(a) for a in accel)
+        if len(accel) != 3:
+            raise ValueError(f"push: accel needs three components, got {len(accel)}")
+        return mg3d_push_params(float(dt), float(scale), (C.c_double * 3)(*accel), float(drag))
+
+    def push_tensor(self, pos, vel, qm, dt, fate, scale=-1.0, accel=(0., 0., 0.), drag=0.0):
+        """mg3d_particle_push_device: one kick-and-drift step, in place, of the particles whose fate is 0 --
+        v = (v + (qm*dt)*E + dt*accel) / (1 + drag*dt), x += dt*v with E = scale * grad u gathered as sample_tensor
+        gathers it -- with the context's walls (periodic axes wrap, Neumann faces reflect, Dirichlet faces retire) and
+        conductors (a nonzero mask byte at the nearest node retires with that label).  pos (float64) and vel (float64 or
+        float32) are each an (M, 3) tensor (any view) or three 1-D tensors; qm an (M,) tensor or a Python float (one value
+        for all); fate an (M,) torch.int32 tensor of MG3D_FATE_* values.  One launch on the current stream, no host
+        synchronisation; push_counts() has the running totals."""
+        import torch
+        dpos, M, dev, stream = _position_args(pos, "push_tensor", writable=True)
+        dvel, Mv, devv, _ = _position_args(vel, "push_tensor", writable=True)
+        if Mv != M or devv != dev:
+            raise ValueError(f"push_tensor: {M} positions on {dev}, {Mv} velocities on {devv}")
+        if any(d.dtype != MG3D_F64 for d in dpos):
+            raise TypeError("push_tensor: positions need float64")
+        if not isinstance(qm, torch.Tensor):
+            qm = torch.tensor([float(qm)], dtype=torch.float64, device=dev).expand(M)
+        if not (qm.is_cuda and qm.device == dev):
+            raise ValueError(f"push_tensor: qm must be a tensor on {dev}")
+        if tuple(qm.shape) != (M,):
+            raise ValueError(f"push_tensor: qm needs shape ({M},), got {tuple(qm.shape)}")
+        if not (isinstance(fate, torch.Tensor) and fate.is_cuda and fate.device == dev):
+            raise ValueError(f"push_tensor: fate must be a tensor on {dev}")
+        dq = vec_desc(qm, count=M)
+        df = vec_desc(fate, count=M, fate=True)
+        pp = self._push_params(dt, scale, accel, drag)
+        check(self.L.mg3d_particle_push_device(self._h, M, _vec_ptrs(dpos), _vec_ptrs(dvel), C.byref(dq), C.byref(df),
+                                               C.byref(pp), stream))
+
+    def push(self, xyz, vel, qm, dt, fate=None, scale=-1.0, accel=(0., 0., 0.), drag=0.0):
+        """mg3d_particle_push: push_tensor on numpy arrays -- xyz and vel (M, 3), qm (M,) or a float, fate (M,) int32 or
+        None (all alive).  Returns new arrays (xyz, vel, fate)."""
+        xyz = np.array(xyz, dtype=np.float64, order="C")
+        vel = np.array(vel, dtype=np.float64, order="C")
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or vel.shape != xyz.shape:
+            raise ValueError(f"push: positions and velocities need one shape (M, 3), got {xyz.shape} and {vel.shape}")
+        M = xyz.shape[0]
+        qm = np.ascontiguousarray(np.broadcast_to(np.asarray(qm, dtype=np.float64), (M,)))
+        fate = np.zeros(M, dtype=np.int32) if fate is None else np.array(fate, dtype=np.int32, order="C")
+        if fate.shape != (M,):
+            raise ValueError(f"push: fate needs shape ({M},), got {fate.shape}")
+        pp = self._push_params(dt, scale, accel, drag)
+        check(self.L.mg3d_particle_push(self._h, M, P(xyz.reshape(-1)), P(vel.reshape(-1)), P(qm),
+                                        fate.ctypes.data_as(C.POINTER(C.c_int)), C.byref(pp)))
+        return xyz, vel, fate
+
+    def push_counts(self, reset=False):
+        """mg3d_particle_counts: how many particles each fate has taken since the context was made (or since the last
+        reset), a (MG3D_FATE_SLOTS,) uint64 array indexed by fate; one host synchronisation."""
+        out = np.zeros(MG3D_FATE_SLOTS, dtype=np.uint64)
+        check(self.L.mg3d_particle_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(bool(reset))))
+        return out
 
     # -- operators
     def smooth(self, level, post, iters):

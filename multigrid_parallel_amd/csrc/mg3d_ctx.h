@@ -130,6 +130,9 @@ struct mg3d_ctx {
      * layout, and the word that takes max |q|; allocated on the first deposit, freed with the context */
     long long *dep_acc = nullptr;
     unsigned long long *dep_max = nullptr;
+    /* mg3d_particle_push(_device): the MG3D_FATE_SLOTS cumulative 64-bit counters of the fates, on the device; allocated and
+     * zeroed with the first push, freed with the context */
+    unsigned long long *push_table = nullptr;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     /* The zero map of d of the top level (k_dzero_scan: bit i = plane i is +0.0 at every interior point), which the fused
      * sweep launches of that level take so as not to read those planes (mg3d_level_sweep).  Every writer of that d says

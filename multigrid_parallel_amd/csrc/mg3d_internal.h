@@ -433,6 +433,9 @@ int k_field_energy(const Geom &g, const double *u, const LevelOperator &A, doubl
  * past that a thread strides on to further points.  pos, q: the caller's vectors, checked by the entry point.
  * k_part_sample: u and the nodal gradient (cs = scale * (0.5 / h)) interpolated to the points, NaN for a point outside,
  *   into u_out / grad_out[0..2] (NULL: not wanted), one launch.
+ * k_part_push: one step of mg3d_particle_push_device for the particles whose fate is 0 -- the host constants are formed
+ *   here from pp and h --, mask the level's fixed-point bytes in the padded layout (NULL: no mask), table the
+ *   MG3D_FATE_SLOTS 64-bit counters; pos, vel, qm and fate the caller's vectors (fate of MG3D_I32), one launch.
  * The deposit, K the smallest integer with count <= 2^K, amax one 64-bit word and acc one long long per element of the
  * level's layout, both zeroed by the caller:
  *   k_part_scan       : *amax = the largest bit pattern of |q| over the points inside with a finite q
@@ -442,6 +445,9 @@ int k_field_energy(const Geom &g, const double *u, const LevelOperator &A, doubl
 #define MG3D_PARTICLE_MAX_BLOCKS 2048
 int k_part_sample(const Geom &g, const double *u, int bc, double h, double cs, long long count, const mg3d_vec *const pos[3],
                   const mg3d_vec *u_out, const mg3d_vec *const grad_out[3], hipStream_t s);
+int k_part_push(const Geom &g, const double *u, const unsigned char *mask, int bc, double h, long long count,
+                const mg3d_vec *const pos[3], const mg3d_vec *const vel[3], const mg3d_vec *qm, const mg3d_vec *fate,
+                const mg3d_push_params &pp, unsigned long long *table, hipStream_t s);
 int k_part_scan(const Geom &g, int bc, double h, long long count, const mg3d_vec *const pos[3], const mg3d_vec *q,
                 unsigned long long *amax, hipStream_t s);
 int k_part_accumulate(const Geom &g, int bc, double h, long long count, int K, const mg3d_vec *const pos[3],

@@ -2308,15 +2308,55 @@ __device__ __forceinline__ double part_trilinear(const PartCell (&cell)[3], F va
     return (cell[0].w0 * mid[0]) + (cell[0].w1 * mid[1]);
 }
 
-/* The sample.  The eight corners of the cell are taken to their sources and loaded once; the nodal gradient at a corner is
- * grad_value of grad_axis's taps, as gradient_kernel forms it.  Of a corner's two taps along an axis one is, away from the
- * boundary forms, the cell's other corner on that axis and comes from its register: 8 + 24 loads of u per point. */
+/* The gather of the sample and of the push at a located point.  The eight corners of the cell are taken to their sources and
+ * loaded once; the nodal gradient at a corner is grad_value of grad_axis's taps, as gradient_kernel forms it.  Of a corner's
+ * two taps along an axis one is, away from the boundary forms, the cell's other corner on that axis and comes from its
+ * register: 8 + 24 loads of u per point.  want(t) says whether value t (0: u, 1 + d: component d of the gradient) is
+ * asked for, emit(t, x) takes it. */
+template <int BC, class W, class E>
+__device__ __forceinline__ void part_gather(const Geom &g, const double *__restrict__ u, int bc, double cs,
+                                            const PartCell (&cell)[3], W want, E emit)
+{
+    const int N = g.N;
+    GradAxis ga[3][2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        ga[0][e] = grad_axis<BC>(bc, 0, cell[0].c + e, N, g.plane);
+        ga[1][e] = grad_axis<BC>(bc, 1, cell[1].c + e, N, g.pitch);
+        ga[2][e] = grad_axis<BC>(bc, 2, cell[2].c + e, N, 1);
+    }
+    long long p[8];
+    double v[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        p[t] = g.plane * ga[0][t >> 2].src + (long long)g.pitch * ga[1][(t >> 1) & 1].src + ga[2][t & 1].src;
+        v[t] = u[p[t]];
+    }
+    if (want(0))
+        emit(0, part_trilinear(cell, [&](int t) { return v[t]; }));
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        if (!want(1 + d))
+            continue;
+        const int bit = 4 >> d;
+        const double gd = part_trilinear(cell, [&](int t) {
+            const GradAxis &A = ga[d][(t & bit) ? 1 : 0];
+            const long long po = p[t ^ bit], qa = p[t] + A.oa, qb = p[t] + A.ob;
+            const double ta = qa == po ? v[t ^ bit] : u[qa];
+            const double tb = qb == po ? v[t ^ bit] : u[qb];
+            return grad_value(A.kind, ta, tb, v[t], cs);
+        });
+        emit(1 + d, gd);
+    }
+}
+
+/* The sample: the gather into the caller's wanted outputs, NaN for a point outside. */
 template <int BC>
 __global__ void __launch_bounds__(256) part_sample_kernel(Geom g, const double *__restrict__ u, PartPos pos, long long count,
                                                           double h, double cs, int bc, PartOut o)
 {
     const int N = g.N;
-    const bool want_grad[3] = {o.v[1].p != nullptr, o.v[2].p != nullptr, o.v[3].p != nullptr};
+    const bool wanted[4] = {o.v[0].p != nullptr, o.v[1].p != nullptr, o.v[2].p != nullptr, o.v[3].p != nullptr};
     for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
         PartCell cell[3];
         if (!part_locate3<BC>(bc, pos, m, h, N, cell)) {
@@ -2326,35 +2366,118 @@ __global__ void __launch_bounds__(256) part_sample_kernel(Geom g, const double *
                 part_store(o.v[t], m, nan);
             continue;
         }
-        GradAxis ga[3][2];
+        part_gather<BC>(g, u, bc, cs, cell, [&](int t) { return wanted[t]; },
+                        [&](int t, double x) { part_store(o.v[t], m, x); });
+    }
+}
+
+/* The push (include/mg3d.h "Particles", mg3d_particle_push_device): locate, gather E, kick and drift, the walls of the
+ * context's boundary word, the conductors of its mask, then the stores and one count per particle that changes its fate.
+ * Every floating-point operation is spelled as the header spells it. */
+struct PartPush {
+    double dt, cs, gdt[3], inv, xper, xhi; /* the host's constants */
+    PartPos vel;
+    PartVec qm;
+    int *fate;
+    long long fate_stride;
+};
+template <int BC>
+__global__ void __launch_bounds__(256) part_push_kernel(Geom g, const double *__restrict__ u,
+                                                        const unsigned char *__restrict__ mask, PartPos pos, long long count,
+                                                        double h, int bc, PartPush a, unsigned long long *__restrict__ table)
+{
+    const int N = g.N;
+    const double n1 = (double)(N - 1);
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        int *const fp = a.fate + a.fate_stride * m;
+        if (*fp != MG3D_FATE_ALIVE)
+            continue;
+        /* 1: locate x0; a point that is not inside only changes its fate */
+        double x[3];
+        PartCell cell[3];
+        bool in = true, finite = true;
+        int face = -1;
 #pragma unroll
-        for (int e = 0; e < 2; e++) {
-            ga[0][e] = grad_axis<BC>(bc, 0, cell[0].c + e, N, g.plane);
-            ga[1][e] = grad_axis<BC>(bc, 1, cell[1].c + e, N, g.pitch);
-            ga[2][e] = grad_axis<BC>(bc, 2, cell[2].c + e, N, 1);
+        for (int ax = 0; ax < 3; ax++) {
+            x[ax] = part_load(pos.x[ax], m);
+            const double t = x[ax] / h;
+            const bool here = part_locate<BC>(bc, ax, x[ax], h, N, cell[ax]);
+            in = in && here;
+            finite = finite && isfinite(x[ax]) && isfinite(t);
+            if (!here && face < 0)
+                face = 2 * ax + (t < 0.0 ? 0 : 1);
         }
-        long long p[8];
-        double v[8];
+        int f = MG3D_FATE_ALIVE;
+        if (!in) {
+            f = finite ? MG3D_FATE_FACE + face : MG3D_FATE_INVALID;
+        } else {
+            /* 2: E, the sample's gradient with cs */
+            double E[3];
+            part_gather<BC>(g, u, bc, a.cs, cell, [](int t) { return t != 0; }, [&](int t, double e) { E[t - 1] = e; });
+            /* 3: kick and drift */
+            const double k = part_load(a.qm, m) * a.dt;
+            double v[3];
+            bool ok = isfinite(k);
 #pragma unroll
-        for (int t = 0; t < 8; t++) {
-            p[t] = g.plane * ga[0][t >> 2].src + (long long)g.pitch * ga[1][(t >> 1) & 1].src + ga[2][t & 1].src;
-            v[t] = u[p[t]];
+            for (int ax = 0; ax < 3; ax++) {
+                v[ax] = (part_load(a.vel.x[ax], m) + ((k * E[ax]) + a.gdt[ax])) * a.inv;
+                x[ax] = x[ax] + (a.dt * v[ax]);
+                ok = ok && isfinite(v[ax]) && isfinite(x[ax]);
+            }
+            if (!ok) {
+                f = MG3D_FATE_INVALID;
+            } else {
+                /* 4: walls, each axis on its own; the first exit in axis order is the fate */
+#pragma unroll
+                for (int ax = 0; ax < 3; ax++) {
+                    const double tt = x[ax] / h;
+                    if (BC && (bc >> ax & 1)) {
+                        if (tt < 0.0)
+                            x[ax] = x[ax] + a.xper;
+                        else if (tt >= n1)
+                            x[ax] = x[ax] - a.xper;
+                    } else if (tt < 0.0) {
+                        if (BC == BC_REFLECT && bc_ref_lo(bc, ax)) {
+                            x[ax] = -x[ax];
+                            v[ax] = -v[ax];
+                        } else if (f == MG3D_FATE_ALIVE) {
+                            f = MG3D_FATE_FACE + 2 * ax;
+                        }
+                    } else if (tt > n1) {
+                        if (BC == BC_REFLECT && bc_ref_hi(bc, ax)) {
+                            x[ax] = a.xhi - (x[ax] - a.xhi);
+                            v[ax] = -v[ax];
+                        } else if (f == MG3D_FATE_ALIVE) {
+                            f = MG3D_FATE_FACE + 2 * ax + 1;
+                        }
+                    }
+                }
+                /* 5: conductors: the mask byte of the node nearest to the final position, where that is inside */
+                if (mask && f == MG3D_FATE_ALIVE) {
+                    int n[3];
+                    bool there = true;
+#pragma unroll
+                    for (int ax = 0; ax < 3; ax++) {
+                        PartCell c = {0, 0., 0.};
+                        there = part_locate<BC>(bc, ax, x[ax], h, N, c) && there;
+                        n[ax] = c.c + (c.w1 >= 0.5 ? 1 : 0);
+                        if (BC && (bc >> ax & 1) && n[ax] == N - 1)
+                            n[ax] = 0;
+                    }
+                    if (there)
+                        f = mask[gidx(g, n[0], n[1], n[2])];
+                }
+                /* 6: the position and velocity of survivors and of what steps 4 and 5 retired */
+#pragma unroll
+                for (int ax = 0; ax < 3; ax++) {
+                    part_store(pos.x[ax], m, x[ax]);
+                    part_store(a.vel.x[ax], m, v[ax]);
+                }
+            }
         }
-        if (o.v[0].p)
-            part_store(o.v[0], m, part_trilinear(cell, [&](int t) { return v[t]; }));
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            if (!want_grad[d])
-                continue;
-            const int bit = 4 >> d;
-            const double gd = part_trilinear(cell, [&](int t) {
-                const GradAxis &A = ga[d][(t & bit) ? 1 : 0];
-                const long long po = p[t ^ bit], qa = p[t] + A.oa, qb = p[t] + A.ob;
-                const double ta = qa == po ? v[t ^ bit] : u[qa];
-                const double tb = qb == po ? v[t ^ bit] : u[qb];
-                return grad_value(A.kind, ta, tb, v[t], cs);
-            });
-            part_store(o.v[1 + d], m, gd);
+        if (f != MG3D_FATE_ALIVE) {
+            *fp = f;
+            atomicAdd(table + f, 1ULL);
         }
     }
 }
@@ -2393,6 +2516,42 @@ int k_part_sample(const Geom &g, const double *u, int bc, double h, double cs, l
         break;
     default:
         hipLaunchKernelGGL(part_sample_kernel<BC_PLAIN>, grid, block, 0, s, g, u, p, count, h, cs, bc, o);
+    }
+    return 0;
+}
+
+int k_part_push(const Geom &g, const double *u, const unsigned char *mask, int bc, double h, long long count,
+                const mg3d_vec *const pos[3], const mg3d_vec *const vel[3], const mg3d_vec *qm, const mg3d_vec *fate,
+                const mg3d_push_params &pp, unsigned long long *table, hipStream_t s)
+{
+    if (!part_level_ok(g) || count <= 0)
+        return -1;
+    PartPush a;
+    a.dt = pp.dt;
+    a.cs = pp.scale * (0.5 / h);
+    for (int ax = 0; ax < 3; ax++)
+        a.gdt[ax] = pp.dt * pp.accel[ax];
+    a.inv = 1.0 / (1.0 + pp.drag * pp.dt);
+    const double n1 = (double)(g.N - 1);
+    a.xper = n1 * h;
+    a.xhi = a.xper;
+    while (a.xhi / h > n1) /* the largest coordinate known to locate inside */
+        a.xhi = nextafter(a.xhi, 0.0);
+    a.vel = part_pos(vel);
+    a.qm = part_vec(qm);
+    a.fate = (int *)fate->ptr;
+    a.fate_stride = fate->stride;
+    const PartPos p = part_pos(pos);
+    const dim3 grid = part_grid(count), block(256, 1, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(part_push_kernel<BC_REFLECT>, grid, block, 0, s, g, u, mask, p, count, h, bc, a, table);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(part_push_kernel<BC_WRAP>, grid, block, 0, s, g, u, mask, p, count, h, bc, a, table);
+        break;
+    default:
+        hipLaunchKernelGGL(part_push_kernel<BC_PLAIN>, grid, block, 0, s, g, u, mask, p, count, h, bc, a, table);
     }
     return 0;
 }

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The particle gather and scatter against a plain torch restatement: python tools/particle_bench.py [c,L ...]
-(default 9,7 and 9,6: 513^3 and 257^3, constant operator, Dirichlet faces, random u; POINTS=1000000,10000000).
+"""The particle gather, scatter and push against a plain torch restatement: python tools/particle_bench.py [c,L ...]
+(default 9,7 and 9,6: 513^3 and 257^3, constant operator, Dirichlet faces, random u; POINTS=1000000,10000000;
+ROWS=sample,deposit,push).
 
 Per size and number of points, for points uniformly random in the box and for the same points sorted by cell, in one
 process, the median (min .. max) of RUNS runs after a warm-up, each run one call between two events on the current stream:
@@ -9,6 +10,9 @@ process, the median (min .. max) of RUNS runs after a warm-up, each run one call
   torch    the same in torch on the same GPU: index arithmetic, then for the sample eight gathers of u and of a
            gradient_tensor() made beforehand (its launch is NOT in the time), for the deposit eight index_add_ -- floating
            point atomics, so neither reproducible nor independent of the order of the points
+  push     push_tensor(pos, vel, qm, dt, fate): one launch; speeds up to half a spacing per step, kicks up to a hundredth.
+           Its torch column is the composition it replaces: sample_tensor(want_u=False), then the kick, the drift and the
+           fates of Dirichlet faces in torch (the first exit in axis order, INVALID for what is not finite; no table)
 Nothing is gated; the numbers go into INTEGRATION.md ("Particles")."""
 import os
 import statistics
@@ -21,6 +25,7 @@ import multigrid_parallel_amd as M
 from multigrid_parallel_amd.binding import MG3D_D, MG3D_U
 
 RUNS = int(os.environ.get("RUNS", "5"))
+ROWS = os.environ.get("ROWS", "sample,deposit,push").split(",")
 POINTS = [int(v) for v in os.environ.get("POINTS", "1000000,10000000").split(",")]
 
 
@@ -77,6 +82,22 @@ def torch_deposit(d, pos, q, h, N, scale):
                 df.index_add_(0, base + ((a * N + b) * N + cc), qs * w)
 
 
+def torch_push(s, pos, vel, qm, fate, dt, h, N, og):
+    s.sample_tensor(pos, want_u=False, scale=-1.0, out_grad=og)  # (NaN for a point outside)
+    alive = fate == 0
+    v1 = vel + (qm * dt)[:, None] * og
+    x1 = pos + dt * v1
+    t = x1 / h
+    face = 2 * torch.arange(3, device=pos.device)
+    code = torch.where(t < 0, 256 + face, torch.where(t > N - 1, 257 + face, torch.zeros_like(face)))
+    first = torch.where(code[:, 0] != 0, code[:, 0], torch.where(code[:, 1] != 0, code[:, 1], code[:, 2]))
+    f = torch.where(torch.isfinite(x1).all(dim=1), first, torch.full_like(first, 262)).to(torch.int32)
+    moved = (alive & (f != 262))[:, None]
+    pos.copy_(torch.where(moved, x1, pos))
+    vel.copy_(torch.where(moved, v1, vel))
+    fate.copy_(torch.where(alive, f, fate))
+
+
 def main():
     cases = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]] or [(9, 7), (9, 6)]
     dev = dict(dtype=torch.float64, device="cuda")
@@ -97,15 +118,29 @@ def main():
                 ou, og = torch.empty(count, **dev), torch.empty(count, 3, **dev)
                 print(f"{N}^3, {count} points, Dirichlet faces, float64, median of {RUNS} runs:")
                 for name, p, qq in (("random", pos, q), ("sorted by cell", pos[order].contiguous(), q[order].contiguous())):
-                    ts = timed(lambda: s.sample_tensor(p, scale=-1.0, out_u=ou, out_grad=og))
-                    tt = timed(lambda: torch_sample(u, g, p, h, N))
-                    ds = timed(lambda: s.deposit_tensor(p, qq, scale=-1.0))
-                    dt = timed(lambda: torch_deposit(d, p, qq, h, N, -1.0))
-                    ms, mt = statistics.median(ts), statistics.median(tt)
-                    md, mdt = statistics.median(ds), statistics.median(dt)
-                    print(f"  {name:15s} sample   library {spread(ts)}   torch {spread(tt)}   library / torch = {ms / mt:.2f}")
-                    print(f"  {name:15s} deposit  library {spread(ds)}   torch {spread(dt)}   library / torch = {md / mdt:.2f}",
-                          flush=True)
+                    if "sample" in ROWS:
+                        ts = timed(lambda: s.sample_tensor(p, scale=-1.0, out_u=ou, out_grad=og))
+                        tt = timed(lambda: torch_sample(u, g, p, h, N))
+                        ms, mt = statistics.median(ts), statistics.median(tt)
+                        print(f"  {name:15s} sample   library {spread(ts)}   torch {spread(tt)}   library / torch = {ms / mt:.2f}")
+                    if "deposit" in ROWS:
+                        ds = timed(lambda: s.deposit_tensor(p, qq, scale=-1.0))
+                        dt = timed(lambda: torch_deposit(d, p, qq, h, N, -1.0))
+                        md, mdt = statistics.median(ds), statistics.median(dt)
+                        print(f"  {name:15s} deposit  library {spread(ds)}   torch {spread(dt)}   library / torch = {md / mdt:.2f}")
+                    if "push" in ROWS:
+                        step = 1.0
+                        vel = (torch.rand(count, 3, generator=gen, **dev) * 2 - 1) * (0.5 * h / step)
+                        qm = qq * (0.01 * h * h / (step * step))
+                        pa, va, fa = p.clone(), vel.clone(), torch.zeros(count, dtype=torch.int32, device="cuda")
+                        pb, vb, fb = p.clone(), vel.clone(), torch.zeros(count, dtype=torch.int32, device="cuda")
+                        ps = timed(lambda: s.push_tensor(pa, va, qm, step, fa))
+                        pt = timed(lambda: torch_push(s, pb, vb, qm, fb, step, h, N, og))
+                        mp, mpt = statistics.median(ps), statistics.median(pt)
+                        print(f"  {name:15s} push     library {spread(ps)}   torch {spread(pt)}   library / torch = {mp / mpt:.2f}"
+                              f"   (alive after {RUNS + 1} steps: {int((fa == 0).sum())} / {int((fb == 0).sum())})")
+                        del vel, qm, pa, va, fa, pb, vb, fb
+                    sys.stdout.flush()
                 s.zero(MG3D_D, top)
                 d.zero_()
                 del pos, q, order, ou, og
