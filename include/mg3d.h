@@ -473,8 +473,8 @@ int mg3d_field_energy(mg3d_ctx *ctx, double *energy);
  *   q hold count doubles, grad count x 3; u or grad may be NULL (not wanted).  They stage through device buffers allocated
  *   for the call (MG3D_ERR_ALLOC, nothing changed, when they do not fit), run the same launches and synchronise once;
  *   the results have the bits of the device forms.
- * Out of scope: the slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms; higher-order shapes (TSC); sorting the
- * points; a count of the points that were outside. */
+ * Out of scope: the slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms; higher-order shapes (TSC); a count of the
+ * points that were outside (mg3d_particle_sort_device below gives one). */
 typedef struct mg3d_vec {
     void *ptr;        /* element 0, device memory of the context's device */
     int dtype;        /* MG3D_F64 / MG3D_F32 */
@@ -498,7 +498,8 @@ int mg3d_deposit(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 
  *             reflecting wall: positions stay in double.)
  *     vel[a]  MG3D_F64 or MG3D_F32 (rounded to nearest even on store), stride >= 1, updated in place
  *     qm      MG3D_F64 or MG3D_F32, stride >= 0 (0: one charge-to-mass ratio for all)
- *     fate    MG3D_I32 -- a dtype this vector alone takes, every other call keeps refusing it --, stride >= 1, read and
+ *     fate    MG3D_I32 -- a dtype that this vector and the vectors of the reorder below take, every other call keeps
+ *             refusing it --, stride >= 1, read and
  *             written: MG3D_FATE_ALIVE (0), a conductor's label 1..255, MG3D_FATE_FACE + f for face f = 0..5 (ilo, ihi,
  *             jlo, jhi, klo, khi), MG3D_FATE_INVALID.
  * Host constants, formed in this order (N, h of the finest level):
@@ -540,8 +541,8 @@ int mg3d_deposit(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 
  * mg3d_particle_counts: synchronises once and copies the cumulative table; slot 0 is always 0 and the table is all zero
  *   before the first push; reset != 0 zeroes the table behind the copy.
  * Out of scope: magnetic fields (Boris); charge-weighted tallies (the caller's bincount of fate weighted by q);
- * compaction or sorting; the slab and fp32 forms. */
-enum { MG3D_I32 = 3 };   /* beside MG3D_F64/F32/U8: the fate vector of the push only; every other call keeps refusing it */
+ * compaction (mg3d_particle_sort_device below puts the dead last); the slab and fp32 forms. */
+enum { MG3D_I32 = 3 };   /* beside MG3D_F64/F32/U8: the fate vector of the push, the fate, perm and data vectors of the reorder; every other call keeps refusing it */
 enum { MG3D_FATE_ALIVE = 0,        /* 1..255: absorbed by the conductor whose mask byte is this label */
        MG3D_FATE_FACE = 256,       /* + f, f = 0..5 (ilo, ihi, jlo, jhi, klo, khi): left the box through / lies beyond face f */
        MG3D_FATE_INVALID = 262,    /* a coordinate, velocity, q/m or field value that is not finite */
@@ -557,6 +558,54 @@ int mg3d_particle_push_device(mg3d_ctx *ctx, long long count, const mg3d_vec *co
 int mg3d_particle_push(mg3d_ctx *ctx, long long count, double *xyz, double *vxyz, const double *qm, int *fate,
                        const mg3d_push_params *p);           /* host arrays, count x 3; staged like mg3d_field_sample */
 int mg3d_particle_counts(mg3d_ctx *ctx, unsigned long long out[MG3D_FATE_SLOTS], int reset);
+
+/* The REORDER: particles sorted by cell with the library's own locator, the lost and the dead moved behind the living, and
+ * every attribute moved in one launch.  The grid kernels above are much faster on points in cell order, and a cloud that
+ * starts sorted does not stay so.  tests/_sort_ref.py restates both calls bit for bit.
+ *
+ * mg3d_particle_sort_device writes into perm the STABLE permutation that sorts the particles by the key K below: perm[m] is
+ *   the old index of the particle that belongs at place m.  With N and h of the finest level, c_a the cell index of
+ *   "Locating a point" on axis a (periodic wraps included), b_a = c_a >> shift, nb = ((N-2) >> shift) + 1, KMAX = nb*nb*nb:
+ *     fate given and fate[m] != 0                           : K = KMAX + 1   (dead; its position is not read)
+ *     otherwise, the point is OUTSIDE (not finite included) : K = KMAX       (lost)
+ *     otherwise                                             : K = (b_0*nb + b_1)*nb + b_2   (the device layout's order, k fastest)
+ *   Equal keys keep the order of their old indices, so the result is unique and has the same bits in every run: the living in
+ *   cell order, then the lost, then the dead, the last two groups in their original order.  shift (0 .. 8) sorts by blocks of
+ *   2^shift cells per side: fewer key bits, nearly the same locality.  KMAX + 1 must fit 32 bits (nb <= 1625), else MG3D_ERR_ARG.
+ *   counts_dev (device memory, checked as every device pointer, or NULL): counts_dev[0] = the particles with K < KMAX,
+ *   counts_dev[1] = those with K == KMAX.
+ *   Vectors: pos[a] MG3D_F64 or MG3D_F32 (widened exactly), stride >= 0; fate MG3D_I32, stride >= 0, read only, NULL: all alive;
+ *   perm MG3D_I32, stride >= 1, written.  0 <= count <= 2^31 - 1; count == 0: MG3D_OK, nothing launched, counts_dev not written.
+ *   State: reads the geometry (N, h, the boundary word) and no field; a cycle that has run ahead is NOT finished, the next
+ *   mg3d_vcycle gives the bits it would have given.  The two-event stream ordering of "Device arrays", no host
+ *   synchronisation: the number of passes depends on KMAX + 2 alone, no launch decision on device data.
+ *   The sort: a key launch, then a least-significant-digit radix sort with 8-bit digits, P = ceil(B / 8) passes for the B bits
+ *   of KMAX + 1, three launches a pass (digit counts per tile of 2048 elements -- a constant, whatever the grid --, an
+ *   exclusive scan of the [digit][tile] table, a stable scatter whose places are prefix + rank, the ranks from wave ballots
+ *   and per-wave counts in LDS; no atomic decides a place): 1 + 3*P launches under MG3D_K_PACK (4, 7, 10 or 13).
+ *   Scratch: two key and two index buffers and the digit tables, 16*count + 1024*(ceil(count/2048) + 1) bytes, allocated on
+ *   first use, re-allocated when count grows (the one moment the call may wait for the device), freed with the context;
+ *   MG3D_ERR_ALLOC, nothing changed, when they do not fit.
+ *   MG3D_ERR_ARG, nothing written or launched: a NULL context, pos or perm; count out of range; shift outside 0 .. 8; keys
+ *   past 32 bits; a bad dtype or stride; a foreign pointer.
+ * mg3d_particle_permute_device: dst[v][m] = src[v][perm[m]] for every v < nvec (1 .. MG3D_PERMUTE_MAX_VECS) and m < count, ONE
+ *   launch under MG3D_K_PACK that reads perm once.  Each pair (src[v], dst[v]) has one dtype out of MG3D_F64, MG3D_F32,
+ *   MG3D_I32; the bytes are copied as they are (-0.0 and NaN payloads survive).  src stride >= 0, dst stride >= 1; out of
+ *   place, overlap is the caller's business.  A perm[m] outside 0 .. count-1 writes nothing for that m and reads nothing out
+ *   of bounds.  Stream ordering as above; count == 0 launches nothing.  MG3D_ERR_ARG, nothing written: a NULL argument, a
+ *   bad nvec, a dtype mismatch in a pair, a bad stride, a foreign pointer, count < 0 or > 2^31 - 1.
+ * mg3d_particle_sort: the sort on host arrays -- xyz count x 3, fate count ints or NULL, perm count ints, counts 2 entries
+ *   or NULL --, staged like mg3d_field_sample: one synchronisation, the bits of the device form.
+ * Out of scope: sorting in place; 64-bit permutations; the sorted keys or per-cell ranges; the slab and fp32 forms. */
+enum { MG3D_PERMUTE_MAX_VECS = 16 };
+int mg3d_particle_sort_device(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3],
+                              const mg3d_vec *fate /* MG3D_I32, read only; NULL: all alive */, int shift,
+                              const mg3d_vec *perm /* MG3D_I32, stride >= 1, written */,
+                              long long *counts_dev /* 2 entries in device memory, or NULL */, void *stream);
+int mg3d_particle_permute_device(mg3d_ctx *ctx, long long count, const mg3d_vec *perm /* MG3D_I32 */, int nvec,
+                                 const mg3d_vec *const *src, const mg3d_vec *const *dst, void *stream);
+int mg3d_particle_sort(mg3d_ctx *ctx, long long count, const double *xyz /* count x 3 */, const int *fate /* or NULL */,
+                       int shift, int *perm /* count */, long long *counts /* 2, or NULL */);
 
 /* ------------------------------------------------ operators on device levels
  * mg3d_smooth     : preSmoother (post=0, mg_3d.h:640-709: iters x red,black)

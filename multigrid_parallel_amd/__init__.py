@@ -8,4 +8,4 @@ This Python package is only the thin ctypes mirror used by the tests and by benc
 from .binding import Solver, Solver32, DistSolver, DistSolver32, EsParams, Mg3dError, lib, lib_path  # noqa: F401
 from .binding import MG3D_F32, MG3D_F64, array_desc, mg3d_array, mg3d_vec, vec_desc  # noqa: F401  (device arrays; torch is imported on use only)
 from .binding import (MG3D_FATE_ALIVE, MG3D_FATE_FACE, MG3D_FATE_INVALID, MG3D_FATE_SLOTS, MG3D_I32,  # noqa: F401
-                      mg3d_push_params)  # the particle push
+                      MG3D_PERMUTE_MAX_VECS, mg3d_push_params)  # the particle push and the reorder

@@ -34,7 +34,8 @@ def lib_path():
 _lib = None
 
 MG3D_F64, MG3D_F32, MG3D_U8 = 0, 1, 2  # mg3d_array.dtype (MG3D_U8: mg3d_ctx_set_mask_device only)
-MG3D_I32 = 3  # mg3d_vec.dtype of the fate vector of mg3d_particle_push_device, and of nothing else
+MG3D_I32 = 3  # mg3d_vec.dtype of the fate vector of mg3d_particle_push_device and of the vectors of the reorder
+MG3D_PERMUTE_MAX_VECS = 16  # vectors per launch of mg3d_particle_permute_device
 # the fates of mg3d_particle_push: 0 alive, 1..255 the label of the conductor that absorbed the particle, MG3D_FATE_FACE + f
 # for face f = 0..5 (ilo, ihi, jlo, jhi, klo, khi), MG3D_FATE_INVALID; MG3D_FATE_SLOTS counters (mg3d_particle_counts)
 MG3D_FATE_ALIVE, MG3D_FATE_FACE, MG3D_FATE_INVALID, MG3D_FATE_SLOTS = 0, 256, 262, 263
@@ -138,6 +139,12 @@ SIGNATURES = {
     "mg3d_particle_push": (C.c_int, [C.c_void_p, C.c_longlong, dp, dp, dp, C.POINTER(C.c_int),
                                      C.POINTER(mg3d_push_params)]),
     "mg3d_particle_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]),
+    "mg3d_particle_sort_device": (C.c_int, [C.c_void_p, C.c_longlong, C.POINTER(_vp), _vp, C.c_int, _vp, C.c_void_p,
+                                            C.c_void_p]),
+    "mg3d_particle_permute_device": (C.c_int, [C.c_void_p, C.c_longlong, _vp, C.c_int, C.POINTER(_vp), C.POINTER(_vp),
+                                               C.c_void_p]),
+    "mg3d_particle_sort": (C.c_int, [C.c_void_p, C.c_longlong, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_longlong)]),
     "mg3d_fill_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mg3d_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mg3d_timing_reset": (C.c_int, [C.c_void_p]),
@@ -365,6 +372,25 @@ def vec_desc(t, writable=False, count=None, fate=False):
     if fate:
         return mg3d_vec(t.data_ptr(), MG3D_I32, st)
     return mg3d_vec(t.data_ptr(), MG3D_F64 if t.dtype == torch.float64 else MG3D_F32, st)
+
+
+def _data_vec(t, who, writable=False, count=None):
+    """The mg3d_vec of a 1-D float64 / float32 / int32 torch tensor, any view: the vectors of the reorder (sort_tensor,
+    permute_tensors), which take MG3D_I32 beside the two float types."""
+    import torch
+    codes = {torch.float64: MG3D_F64, torch.float32: MG3D_F32, torch.int32: MG3D_I32}
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: need a torch.Tensor, got {type(t).__name__}")
+    if t.dtype not in codes:
+        raise TypeError(f"{who}: need float64, float32 or int32, got {t.dtype}")
+    if t.dim() != 1:
+        raise TypeError(f"{who}: need a 1-D tensor, got {t.dim()} dimensions")
+    if count is not None and t.shape[0] != count:
+        raise ValueError(f"{who}: need {count} elements, got {t.shape[0]}")
+    st = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), 1)
+    if writable and st == 0:
+        raise ValueError(f"{who}: a tensor that is written needs a stride >= 1, got 0")
+    return mg3d_vec(t.data_ptr(), codes[t.dtype], st)
 
 
 def _vec_ptrs(descs):
@@ -988,6 +1014,84 @@ class Solver:
         out = np.zeros(MG3D_FATE_SLOTS, dtype=np.uint64)
         check(self.L.mg3d_particle_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), int(bool(reset))))
         return out
+
+    def sort_tensor(self, pos, fate=None, shift=0, out=None):
+        """mg3d_particle_sort_device: the stable permutation that puts the particles in cell order (blocks of 2**shift
+        cells per side), the lost behind the living and the dead (fate != 0) last.  pos as in sample_tensor, fate an (M,)
+        torch.int32 tensor (any view) or None: all alive.  Returns (perm, counts): perm an (M,) int32 tensor -- `out` when
+        given, any view of stride >= 1 -- with perm[m] the old index of the particle that belongs at place m, counts a
+        (2,) int64 tensor (inside, lost), both on the GPU.  Ordered on the current stream, no host synchronisation."""
+        import torch
+        descs, M, dev, stream = _position_args(pos, "sort_tensor")
+        df = None
+        if fate is not None:
+            if not (isinstance(fate, torch.Tensor) and fate.is_cuda and fate.device == dev):
+                raise ValueError(f"sort_tensor: fate must be a tensor on {dev}")
+            if fate.dtype != torch.int32:
+                raise TypeError(f"sort_tensor: fate is int32, got {fate.dtype}")
+            df = _data_vec(fate, "sort_tensor", count=M)
+        if out is None:
+            out = torch.empty((M,), dtype=torch.int32, device=dev)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev):
+            raise ValueError(f"sort_tensor: out must be a tensor on {dev}")
+        if out.dtype != torch.int32:
+            raise TypeError(f"sort_tensor: the permutation is int32, got {out.dtype}")
+        dp_ = _data_vec(out, "sort_tensor", writable=True, count=M)
+        counts = torch.zeros((2,), dtype=torch.int64, device=dev)
+        check(self.L.mg3d_particle_sort_device(self._h, M, _vec_ptrs(descs), C.byref(df) if df is not None else None,
+                                               int(shift), C.byref(dp_), C.c_void_p(counts.data_ptr()), stream))
+        return out, counts
+
+    def permute_tensors(self, perm, *tensors):
+        """mg3d_particle_permute_device: new tensors t[perm] for every t of `tensors` -- each (M,) or (M, 3), float64,
+        float32 or int32, any view; an (M, 3) tensor counts as three vectors -- with up to MG3D_PERMUTE_MAX_VECS vectors
+        per launch, the bytes copied as they are.  perm: an (M,) int32 tensor.  An entry of perm outside 0..M-1 leaves its
+        element of the outputs unwritten.  Ordered on the current stream, no host synchronisation."""
+        import torch
+        if not (isinstance(perm, torch.Tensor) and perm.is_cuda):
+            raise ValueError("permute_tensors: perm must be a tensor on the GPU")
+        if perm.dtype != torch.int32:
+            raise TypeError(f"permute_tensors: the permutation is int32, got {perm.dtype}")
+        dev = perm.device
+        dperm = _data_vec(perm, "permute_tensors")
+        M = perm.shape[0]
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        outs, src, dst = [], [], []
+        for t in tensors:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev):
+                raise ValueError(f"permute_tensors: every tensor must be on {dev}")
+            if not (tuple(t.shape) == (M,) or tuple(t.shape) == (M, 3)):
+                raise ValueError(f"permute_tensors: need shape ({M},) or ({M}, 3), got {tuple(t.shape)}")
+            o = torch.empty(t.shape, dtype=t.dtype, device=dev)
+            outs.append(o)
+            for a, b in ([(t, o)] if t.dim() == 1 else [(t[:, k], o[:, k]) for k in range(3)]):
+                src.append(_data_vec(a, "permute_tensors", count=M))
+                dst.append(_data_vec(b, "permute_tensors", writable=True, count=M))
+        for lo in range(0, len(src), MG3D_PERMUTE_MAX_VECS):
+            n = min(MG3D_PERMUTE_MAX_VECS, len(src) - lo)
+            ps = (_vp * n)(*[C.pointer(d) for d in src[lo:lo + n]])
+            pd = (_vp * n)(*[C.pointer(d) for d in dst[lo:lo + n]])
+            check(self.L.mg3d_particle_permute_device(self._h, M, C.byref(dperm), n, ps, pd, stream))
+        return tuple(outs)
+
+    def sort(self, xyz, fate=None, shift=0):
+        """mg3d_particle_sort: sort_tensor on numpy arrays -- xyz (M, 3), fate (M,) int32 or None.  Returns
+        (perm (M,) int32, (n_inside, n_lost)); one host synchronisation."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"sort: positions need shape (M, 3), got {xyz.shape}")
+        M = xyz.shape[0]
+        pf = None
+        if fate is not None:
+            fate = np.ascontiguousarray(fate, dtype=np.int32)
+            if fate.shape != (M,):
+                raise ValueError(f"sort: fate needs shape ({M},), got {fate.shape}")
+            pf = fate.ctypes.data_as(C.POINTER(C.c_int))
+        perm = np.empty(M, dtype=np.int32)
+        counts = (C.c_longlong * 2)(0, 0)
+        check(self.L.mg3d_particle_sort(self._h, M, P(xyz.reshape(-1)), pf, int(shift),
+                                        perm.ctypes.data_as(C.POINTER(C.c_int)), counts))
+        return perm, (int(counts[0]), int(counts[1]))
 
     # -- operators
     def smooth(self, level, post, iters):

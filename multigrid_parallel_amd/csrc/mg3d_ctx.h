@@ -133,6 +133,11 @@ struct mg3d_ctx {
     /* mg3d_particle_push(_device): the MG3D_FATE_SLOTS cumulative 64-bit counters of the fates, on the device; allocated and
      * zeroed with the first push, freed with the context */
     unsigned long long *push_table = nullptr;
+    /* mg3d_particle_sort(_device): one allocation for sort_cap particles -- two key and two index buffers of sort_cap words,
+     * the digit table and the row sums (mg3d_particle.hip: sort_bytes) --; made on first use, grown when count grows, freed
+     * with the context */
+    unsigned *sort_buf = nullptr;
+    long long sort_cap = 0;
     bool raw_top; /* a raw device pointer to u or d of the top level was handed out (mg3d_device_view) */
     /* The zero map of d of the top level (k_dzero_scan: bit i = plane i is +0.0 at every interior point), which the fused
      * sweep launches of that level take so as not to read those planes (mg3d_level_sweep).  Every writer of that d says

@@ -203,6 +203,8 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
         (void)hipFree(ctx->dep_max);
     if (ctx->push_table)
         (void)hipFree(ctx->push_table);
+    if (ctx->sort_buf)
+        (void)hipFree(ctx->sort_buf);
     for (hipEvent_t e : ctx->io_ev)
         if (e)
             (void)hipEventDestroy(e);

@@ -454,6 +454,25 @@ int k_part_accumulate(const Geom &g, int bc, double h, long long count, int K, c
                       const mg3d_vec *q, const unsigned long long *amax, long long *acc, hipStream_t s);
 int k_part_apply(const Geom &g, int bc, double f0, int K, const unsigned long long *amax, const long long *acc, double *d,
                  hipStream_t s);
+/* The reorder (mg3d_particle_sort_device, mg3d_particle_permute_device), ntiles = ceil(count / MG3D_SORT_TILE):
+ *   k_sort_keys    : keys[m] = the key of particle m (fate NULL: all alive; nb^3 + 1 must fit 32 bits, the entry point
+ *                    checks); counts (NULL: not wanted; two 64-bit words zeroed by the caller) += the inside and the lost.
+ *                    -1 when the level has no launch shape.
+ *   k_sort_hist    : table[digit * ntiles + tile] = the tile's keys whose bits sh .. sh+7 are `digit` (256 * ntiles words)
+ *   k_sort_rowscan : every row of the table scanned in place, exclusive; tot[digit] = the row's sum (256 words)
+ *   k_sort_scatter : the stable scatter of (kin, iin) by that digit into (kout, iout[iout_stride * .]); iin NULL: the old
+ *                    index of element e is e; kout NULL: the keys are not written (the last pass)
+ *   k_part_permute : dst[v][m] = src[v][perm[m]], v < nvec <= MG3D_PERMUTE_MAX_VECS, one launch; the entry point has
+ *                    checked the vectors (a pair of one dtype, MG3D_F64 eight bytes an element, the others four) */
+#define MG3D_SORT_TILE 2048
+int k_sort_keys(const Geom &g, int bc, double h, long long count, const mg3d_vec *const pos[3], const mg3d_vec *fate,
+                int shift, unsigned *keys, unsigned long long *counts, hipStream_t s);
+void k_sort_hist(const unsigned *keys, long long count, int sh, unsigned *table, hipStream_t s);
+void k_sort_rowscan(long long count, unsigned *table, unsigned *tot, hipStream_t s);
+void k_sort_scatter(const unsigned *kin, const int *iin, unsigned *kout, int *iout, long long iout_stride, long long count,
+                    int sh, const unsigned *table, const unsigned *tot, hipStream_t s);
+int k_part_permute(long long count, const mg3d_vec *perm, int nvec, const mg3d_vec *const *src, const mg3d_vec *const *dst,
+                   hipStream_t s);
 /* b and x are level-0 grids in the padded layout g0; work holds 2n doubles */
 /* steps per chunk of the streamed solve for n unknowns and rot_r = R on the current device, 0 if it cannot run */
 int mg3d_lu_stream_chunk(int n, int R);

@@ -68,6 +68,7 @@
 
 #include <assert.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <map>
 #include <mutex>
@@ -2694,6 +2695,289 @@ int k_part_apply(const Geom &g, int bc, double f0, int K, const unsigned long lo
         return -1;
     const dim3 grid((g.N + WAVE - 1) / WAVE, (g.N + 3) / 4, g.N);
     hipLaunchKernelGGL(part_apply_kernel, grid, dim3(WAVE, 4, 1), 0, s, g, bc, f0, K, amax, acc, d);
+    return 0;
+}
+
+/* The reorder (include/mg3d.h "Particles", mg3d_particle_sort_device): a key per particle from the sample's locator, then a
+ * least-significant-digit radix sort of (key, old index) with 8-bit digits.  A pass is three launches over tiles of
+ * MG3D_SORT_TILE consecutive elements -- a constant, so the order cannot depend on a launch shape:
+ *   hist    : table[digit][tile] = how many keys of the tile have that digit
+ *   rowscan : each row of the table scanned in place (exclusive) by one block, the row's sum into tot[digit]
+ *   scatter : element e of tile T with digit d goes to  (sum of tot[< d]) + table[d][T] + (its rank among the tile's
+ *             elements of digit d in index order).
+ * The rank: wave w of the block owns elements w*512 .. w*512+511 of the tile, lane l takes w*512 + 64*r + l in round r;
+ * a round's rank is the number of lower lanes with the same digit (eight ballots give the lanes that match) plus the wave's
+ * count of that digit from its earlier rounds, kept in LDS and advanced by the lowest matching lane; the waves' counts are
+ * then turned into offsets in wave order.  Sums and ranks only: no atomic whose arrival order could decide a place, so the
+ * sort is stable and has the same bits in every run.  The first pass takes the index of an element for its old index, the
+ * last one writes no keys and stores the indices into the caller's perm. */
+template <int BC>
+__global__ void __launch_bounds__(256) sort_key_kernel(PartPos pos, PartVec fate, long long count, double h, int N, int bc,
+                                                       int shift, unsigned nb, unsigned *__restrict__ keys,
+                                                       unsigned long long *__restrict__ counts)
+{
+    const unsigned kmax = nb * nb * nb;
+    unsigned n_in = 0, n_lost = 0;
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        unsigned K = kmax + 1u; /* dead */
+        if (!fate.p || ((const int *)fate.p)[fate.s * m] == 0) {
+            PartCell cell[3];
+            if (part_locate3<BC>(bc, pos, m, h, N, cell)) {
+                K = (((unsigned)cell[0].c >> shift) * nb + ((unsigned)cell[1].c >> shift)) * nb + ((unsigned)cell[2].c >> shift);
+                n_in++;
+            } else {
+                K = kmax; /* lost */
+                n_lost++;
+            }
+        }
+        keys[m] = K;
+    }
+    if (!counts)
+        return;
+    /* integer sums: a thread's own, the wave's by shuffles, one atomic add per wave */
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        n_in += __shfl_down(n_in, o, WAVE);
+        n_lost += __shfl_down(n_lost, o, WAVE);
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        if (n_in)
+            atomicAdd(counts, (unsigned long long)n_in);
+        if (n_lost)
+            atomicAdd(counts + 1, (unsigned long long)n_lost);
+    }
+}
+
+/* the lanes of the wave that are valid and hold the digit d of this lane */
+__device__ __forceinline__ unsigned long long sort_match(unsigned d, bool valid)
+{
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long bal = __ballot(bit);
+        m &= bit ? bal : ~bal;
+    }
+    return m;
+}
+/* the exclusive prefix of v over the 256 threads of the block and the block's sum; ws: four words of LDS, free again on
+ * return */
+__device__ __forceinline__ unsigned sort_block_scan(unsigned v, unsigned *ws, unsigned &total)
+{
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    unsigned inc = v;
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const unsigned t = __shfl_up(inc, o, WAVE);
+        if (lane >= o)
+            inc += t;
+    }
+    if (lane == WAVE - 1)
+        ws[w] = inc;
+    __syncthreads();
+    unsigned pre = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const unsigned t = ws[i];
+        pre += i < w ? t : 0u;
+        tot += t;
+    }
+    __syncthreads();
+    total = tot;
+    return pre + (inc - v);
+}
+
+__global__ void __launch_bounds__(256) sort_hist_kernel(const unsigned *__restrict__ keys, long long count, int sh,
+                                                        unsigned ntiles, unsigned *__restrict__ table)
+{
+    __shared__ unsigned hist[256];
+    const int tid = threadIdx.x;
+    const unsigned long long lt = (1ULL << (tid & (WAVE - 1))) - 1ULL;
+    hist[tid] = 0;
+    __syncthreads();
+    const long long e0 = (long long)blockIdx.x * MG3D_SORT_TILE + tid;
+#pragma unroll
+    for (int r = 0; r < MG3D_SORT_TILE / 256; r++) {
+        const long long e = e0 + 256LL * r;
+        const bool valid = e < count;
+        const unsigned d = valid ? (keys[e] >> sh) & 255u : 0u;
+        const unsigned long long m = sort_match(d, valid);
+        if (valid && (m & lt) == 0) /* the lowest matching lane adds for all of them (an integer sum in LDS) */
+            atomicAdd(&hist[d], (unsigned)__popcll(m));
+    }
+    __syncthreads();
+    table[(size_t)tid * ntiles + blockIdx.x] = hist[tid];
+}
+
+__global__ void __launch_bounds__(256) sort_rowscan_kernel(unsigned *__restrict__ table, unsigned ntiles,
+                                                           unsigned *__restrict__ tot)
+{
+    __shared__ unsigned ws[4];
+    unsigned *const row = table + (size_t)blockIdx.x * ntiles;
+    unsigned carry = 0;
+    for (unsigned c0 = 0; c0 < ntiles; c0 += 1024u) {
+        const unsigned i0 = c0 + 4u * threadIdx.x;
+        unsigned v[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            v[j] = i0 + j < ntiles ? row[i0 + j] : 0u;
+            sum += v[j];
+        }
+        unsigned total;
+        unsigned run = carry + sort_block_scan(sum, ws, total);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (i0 + j < ntiles)
+                row[i0 + j] = run;
+            run += v[j];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0)
+        tot[blockIdx.x] = carry;
+}
+
+__global__ void __launch_bounds__(256) sort_scatter_kernel(const unsigned *__restrict__ kin, const int *__restrict__ iin,
+                                                           unsigned *__restrict__ kout, int *__restrict__ iout,
+                                                           long long iout_stride, long long count, int sh, unsigned ntiles,
+                                                           const unsigned *__restrict__ table,
+                                                           const unsigned *__restrict__ tot)
+{
+    constexpr int ROUNDS = MG3D_SORT_TILE / 256;
+    __shared__ unsigned wcnt[4][256];
+    __shared__ unsigned ws[4];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+    const unsigned long long lt = (1ULL << lane) - 1ULL;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        wcnt[i][tid] = 0;
+    /* thread tid speaks for digit tid: where the tile's elements of that digit begin */
+    unsigned total;
+    const unsigned first = sort_block_scan(tot[tid], ws, total) + table[(size_t)tid * ntiles + blockIdx.x];
+    /* (the scan's barriers stand between the zeroes above and the rounds below) */
+    volatile unsigned *const mine = wcnt[w];
+    const long long e0 = (long long)blockIdx.x * MG3D_SORT_TILE + (long long)w * (WAVE * ROUNDS) + lane;
+    unsigned key[ROUNDS], rank[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; r++) {
+        const long long e = e0 + (long long)WAVE * r;
+        const bool valid = e < count;
+        key[r] = valid ? kin[e] : 0u;
+        const unsigned d = (key[r] >> sh) & 255u;
+        const unsigned long long m = sort_match(d, valid);
+        const unsigned prev = mine[d];
+        rank[r] = prev + (unsigned)__popcll(m & lt);
+        __builtin_amdgcn_wave_barrier();
+        if (valid && (m & lt) == 0)
+            mine[d] = prev + (unsigned)__popcll(m);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    unsigned run = first;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const unsigned c = wcnt[i][tid];
+        wcnt[i][tid] = run;
+        run += c;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < ROUNDS; r++) {
+        const long long e = e0 + (long long)WAVE * r;
+        if (e >= count)
+            continue;
+        const long long dst = (long long)wcnt[w][(key[r] >> sh) & 255u] + rank[r];
+        if (dst >= count)
+            continue;
+        if (kout)
+            kout[dst] = key[r];
+        iout[iout_stride * dst] = iin ? iin[e] : (int)e;
+    }
+}
+
+int k_sort_keys(const Geom &g, int bc, double h, long long count, const mg3d_vec *const pos[3], const mg3d_vec *fate,
+                int shift, unsigned *keys, unsigned long long *counts, hipStream_t s)
+{
+    if (!part_level_ok(g) || count <= 0)
+        return -1;
+    const PartPos p = part_pos(pos);
+    const PartVec f = part_vec(fate);
+    const unsigned nb = ((unsigned)(g.N - 2) >> shift) + 1u;
+    const dim3 grid = part_grid(count), block(256, 1, 1);
+    if (bc & 7)
+        hipLaunchKernelGGL(sort_key_kernel<BC_WRAP>, grid, block, 0, s, p, f, count, h, g.N, bc, shift, nb, keys, counts);
+    else
+        hipLaunchKernelGGL(sort_key_kernel<BC_PLAIN>, grid, block, 0, s, p, f, count, h, g.N, bc, shift, nb, keys, counts);
+    return 0;
+}
+
+void k_sort_hist(const unsigned *keys, long long count, int sh, unsigned *table, hipStream_t s)
+{
+    const unsigned ntiles = (unsigned)((count + MG3D_SORT_TILE - 1) / MG3D_SORT_TILE);
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(ntiles, 1, 1), dim3(256, 1, 1), 0, s, keys, count, sh, ntiles, table);
+}
+
+void k_sort_rowscan(long long count, unsigned *table, unsigned *tot, hipStream_t s)
+{
+    const unsigned ntiles = (unsigned)((count + MG3D_SORT_TILE - 1) / MG3D_SORT_TILE);
+    hipLaunchKernelGGL(sort_rowscan_kernel, dim3(256, 1, 1), dim3(256, 1, 1), 0, s, table, ntiles, tot);
+}
+
+void k_sort_scatter(const unsigned *kin, const int *iin, unsigned *kout, int *iout, long long iout_stride, long long count,
+                    int sh, const unsigned *table, const unsigned *tot, hipStream_t s)
+{
+    const unsigned ntiles = (unsigned)((count + MG3D_SORT_TILE - 1) / MG3D_SORT_TILE);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(ntiles, 1, 1), dim3(256, 1, 1), 0, s, kin, iin, kout, iout, iout_stride,
+                       count, sh, ntiles, table, tot);
+}
+
+/* The permute (mg3d_particle_permute_device): dst[v][m] = src[v][perm[m]] for up to MG3D_PERMUTE_MAX_VECS vectors, four or
+ * eight bytes an element copied as they are; a perm[m] outside 0 .. count-1 reads and writes nothing.  The loop over the
+ * vectors is unrolled with constant indices: the descriptors stay in the kernel's arguments. */
+struct PermVecs {
+    const void *src[MG3D_PERMUTE_MAX_VECS];
+    void *dst[MG3D_PERMUTE_MAX_VECS];
+    long long ss[MG3D_PERMUTE_MAX_VECS], ds[MG3D_PERMUTE_MAX_VECS];
+    int wide[MG3D_PERMUTE_MAX_VECS]; /* eight bytes an element */
+    int n;
+};
+__global__ void __launch_bounds__(256) part_permute_kernel(const int *__restrict__ perm, long long ps, long long count,
+                                                           PermVecs a)
+{
+    for (long long m = blockIdx.x * 256LL + threadIdx.x; m < count; m += 256LL * gridDim.x) {
+        const long long p = perm[ps * m];
+        if (p < 0 || p >= count)
+            continue;
+#pragma unroll
+        for (int v = 0; v < MG3D_PERMUTE_MAX_VECS; v++) {
+            if (v >= a.n)
+                break;
+            if (a.wide[v])
+                ((unsigned long long *)a.dst[v])[a.ds[v] * m] = ((const unsigned long long *)a.src[v])[a.ss[v] * p];
+            else
+                ((unsigned *)a.dst[v])[a.ds[v] * m] = ((const unsigned *)a.src[v])[a.ss[v] * p];
+        }
+    }
+}
+
+int k_part_permute(long long count, const mg3d_vec *perm, int nvec, const mg3d_vec *const *src, const mg3d_vec *const *dst,
+                   hipStream_t s)
+{
+    if (count <= 0 || nvec < 1 || nvec > MG3D_PERMUTE_MAX_VECS)
+        return -1;
+    PermVecs a;
+    memset(&a, 0, sizeof a);
+    a.n = nvec;
+    for (int v = 0; v < nvec; v++) {
+        a.src[v] = src[v]->ptr;
+        a.dst[v] = dst[v]->ptr;
+        a.ss[v] = src[v]->stride;
+        a.ds[v] = dst[v]->stride;
+        a.wide[v] = src[v]->dtype == MG3D_F64;
+    }
+    hipLaunchKernelGGL(part_permute_kernel, part_grid(count), dim3(256, 1, 1), 0, s, (const int *)perm->ptr, perm->stride,
+                       count, a);
     return 0;
 }
 

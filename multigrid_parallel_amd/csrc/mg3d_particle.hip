@@ -13,6 +13,11 @@
  *   push    : mg3d_particle_push(_device), mg3d_particle_counts: one kick-and-drift step of the particles whose fate is 0
  *             with the context's walls and conductors.  Reads the context only, as the sample; one launch under
  *             MG3D_K_PACK; the fates are counted in a table of 64-bit integers on the device (integer adds again).
+ *   reorder : mg3d_particle_sort(_device), mg3d_particle_permute_device: the stable permutation that puts the particles in
+ *             cell order (the lost behind the living, the dead last) by a radix sort of (key, old index), 1 + 3 launches a
+ *             pass under MG3D_K_PACK, and the gather of up to 16 attribute vectors in one launch.  Reads the geometry and
+ *             no field: a cycle that has run ahead is left as it is.  The scratch belongs to the context and grows with
+ *             the count.
  * The device forms do not synchronise with the host.  The host forms stage through buffers allocated for the call, run
  * the same launches and synchronise once.
  */
@@ -314,6 +319,183 @@ extern "C" int mg3d_particle_counts(mg3d_ctx *ctx, unsigned long long out[MG3D_F
     return MG3D_OK;
 }
 
+/* ---------------------------------------------------------------------------------------------------------- reorder */
+#define SORT_MAX_COUNT 2147483647LL
+#define SORT_MAX_SHIFT 8
+
+/* a vector of MG3D_I32 (the sort's fate and perm, the permute's perm); four-byte elements, checked as the push's fate is */
+static int i32_check(const mg3d_ctx *ctx, const mg3d_vec *v, long long count, bool writable, const char *who, const char *what)
+{
+    if (!v)
+        return fail(MG3D_ERR_ARG, "%s: NULL %s vector", who, what);
+    if (v->dtype != MG3D_I32)
+        return fail(MG3D_ERR_ARG, "%s: the %s vector has dtype %d (MG3D_I32)", who, what, v->dtype);
+    const mg3d_vec as_f32 = {v->ptr, MG3D_F32, v->stride};
+    return vec_check(ctx, &as_f32, count, writable, who);
+}
+
+/* the sort's own arguments; *passes = the 8-bit digits of KMAX + 1 */
+static int sort_args(const mg3d_ctx *ctx, long long count, int shift, int *passes, const char *who)
+{
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (count < 0 || count > SORT_MAX_COUNT)
+        return fail(MG3D_ERR_ARG, "%s: count = %lld (0 .. 2^31 - 1)", who, count);
+    if (shift < 0 || shift > SORT_MAX_SHIFT)
+        return fail(MG3D_ERR_ARG, "%s: shift = %d (0 .. %d)", who, shift, SORT_MAX_SHIFT);
+    const int rc = mg3d_field_level(ctx, who);
+    if (rc != MG3D_OK)
+        return rc;
+    const unsigned long long nb = (unsigned long long)((ctx->lv[ctx->L - 1].g.N - 2) >> shift) + 1ULL;
+    const unsigned long long top = nb * nb * nb + 1ULL; /* the largest key */
+    if (top > 0xFFFFFFFFULL)
+        return fail(MG3D_ERR_ARG, "%s: %llu^3 + 2 keys do not fit 32 bits: a larger shift is needed", who, nb);
+    int bits = 0;
+    while (top >> bits)
+        bits++;
+    *passes = (bits + 7) / 8;
+    return MG3D_OK;
+}
+
+static long long sort_tiles(long long count) { return (count + MG3D_SORT_TILE - 1) / MG3D_SORT_TILE; }
+static size_t sort_bytes(long long count) { return 4 * (4 * (size_t)count + 256 * (size_t)(sort_tiles(count) + 1)); }
+
+/* the scratch for `count` particles; a larger one replaces a smaller one only once it exists */
+static int sort_alloc(mg3d_ctx *ctx, long long count, const char *who)
+{
+    if (count <= ctx->sort_cap)
+        return MG3D_OK;
+    unsigned *buf = nullptr;
+    const int rc = mg3d_device_alloc((void **)&buf, sort_bytes(count), who);
+    if (rc != MG3D_OK)
+        return rc;
+    if (ctx->sort_buf)
+        (void)hipFree(ctx->sort_buf);
+    ctx->sort_buf = buf;
+    ctx->sort_cap = count;
+    return MG3D_OK;
+}
+
+/* the sort's launches on the context's stream: 1 + 3 * passes of them.  Reads the geometry and no field: a cycle that has
+ * run ahead stays as it is. */
+static int sort_enqueue(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3], const mg3d_vec *fate, int shift,
+                        int passes, const mg3d_vec *perm, long long *counts_dev, const char *who)
+{
+    const int q = ctx->L - 1;
+    const Level &top = ctx->lv[q];
+    const size_t cap = (size_t)ctx->sort_cap;
+    unsigned *kin = ctx->sort_buf, *kout = ctx->sort_buf + cap;
+    int *iin = (int *)(ctx->sort_buf + 2 * cap), *iout = (int *)(ctx->sort_buf + 3 * cap);
+    unsigned *const tot = ctx->sort_buf + 4 * cap, *const table = tot + 256;
+    if (counts_dev) {
+        const hipError_t e = hipMemsetAsync(counts_dev, 0, 2 * sizeof(long long), ctx->stream);
+        if (e != hipSuccess)
+            return fail(MG3D_ERR_HIP, "%s: clearing the counts: %s", who, hipGetErrorString(e));
+    }
+    {
+        StageScope kt(ctx, q, MG3D_K_PACK, true);
+        if (k_sort_keys(top.g, mg3d_ctx_bc(ctx), top.h, count, pos, fate, shift, kin, (unsigned long long *)counts_dev,
+                        ctx->stream) < 0)
+            return fail(MG3D_ERR_STATE, "%s: the level has no launch shape", who);
+    }
+    for (int p = 0; p < passes; p++) {
+        const bool last = p == passes - 1;
+        {
+            StageScope kt(ctx, q, MG3D_K_PACK, true);
+            k_sort_hist(kin, count, 8 * p, table, ctx->stream);
+        }
+        {
+            StageScope kt(ctx, q, MG3D_K_PACK, true);
+            k_sort_rowscan(count, table, tot, ctx->stream);
+        }
+        {
+            StageScope kt(ctx, q, MG3D_K_PACK, true);
+            k_sort_scatter(kin, p == 0 ? nullptr : iin, last ? nullptr : kout, last ? (int *)perm->ptr : iout,
+                           last ? perm->stride : 1, count, 8 * p, table, tot, ctx->stream);
+        }
+        unsigned *const tk = kin;
+        kin = kout;
+        kout = tk;
+        int *const ti = iin;
+        iin = iout;
+        iout = ti;
+    }
+    return part_launch_ok(who);
+}
+
+extern "C" int mg3d_particle_sort_device(mg3d_ctx *ctx, long long count, const mg3d_vec *const pos[3], const mg3d_vec *fate,
+                                         int shift, const mg3d_vec *perm, long long *counts_dev, void *stream)
+{
+    static const char who[] = "mg3d_particle_sort_device";
+    int passes = 0;
+    int rc = sort_args(ctx, count, shift, &passes, who);
+    if (rc == MG3D_OK)
+        rc = pos_check(ctx, count, pos, who);
+    if (rc == MG3D_OK && fate)
+        rc = i32_check(ctx, fate, count, false, who, "fate");
+    if (rc == MG3D_OK)
+        rc = i32_check(ctx, perm, count, true, who, "perm");
+    if (rc == MG3D_OK && counts_dev) {
+        const mg3d_vec c = {counts_dev, MG3D_F64, 1};
+        rc = vec_check(ctx, &c, 2, true, who);
+    }
+    if (rc != MG3D_OK || count == 0)
+        return rc;
+    rc = sort_alloc(ctx, count, who);
+    if (rc == MG3D_OK)
+        rc = mg3d_stream_join(ctx, (hipStream_t)stream, false, who);
+    if (rc == MG3D_OK)
+        rc = sort_enqueue(ctx, count, pos, fate, shift, passes, perm, counts_dev, who);
+    if (rc != MG3D_OK)
+        return rc;
+    return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
+}
+
+extern "C" int mg3d_particle_permute_device(mg3d_ctx *ctx, long long count, const mg3d_vec *perm, int nvec,
+                                            const mg3d_vec *const *src, const mg3d_vec *const *dst, void *stream)
+{
+    static const char who[] = "mg3d_particle_permute_device";
+    if (!ctx)
+        return fail(MG3D_ERR_ARG, "%s: NULL context", who);
+    if (count < 0 || count > SORT_MAX_COUNT)
+        return fail(MG3D_ERR_ARG, "%s: count = %lld (0 .. 2^31 - 1)", who, count);
+    if (nvec < 1 || nvec > MG3D_PERMUTE_MAX_VECS)
+        return fail(MG3D_ERR_ARG, "%s: nvec = %d (1 .. %d)", who, nvec, MG3D_PERMUTE_MAX_VECS);
+    if (!src || !dst)
+        return fail(MG3D_ERR_ARG, "%s: NULL %s", who, src ? "destinations" : "sources");
+    int rc = i32_check(ctx, perm, count, false, who, "perm");
+    for (int v = 0; v < nvec && rc == MG3D_OK; v++) {
+        if (!src[v] || !dst[v])
+            return fail(MG3D_ERR_ARG, "%s: NULL vector (%s[%d])", who, src[v] ? "dst" : "src", v);
+        if (src[v]->dtype != dst[v]->dtype)
+            return fail(MG3D_ERR_ARG, "%s: src[%d] has dtype %d, dst[%d] has dtype %d", who, v, src[v]->dtype, v,
+                        dst[v]->dtype);
+        if (src[v]->dtype == MG3D_I32) {
+            rc = i32_check(ctx, src[v], count, false, who, "source");
+            if (rc == MG3D_OK)
+                rc = i32_check(ctx, dst[v], count, true, who, "destination");
+        } else {
+            rc = vec_check(ctx, src[v], count, false, who);
+            if (rc == MG3D_OK)
+                rc = vec_check(ctx, dst[v], count, true, who);
+        }
+    }
+    if (rc != MG3D_OK || count == 0)
+        return rc;
+    rc = mg3d_stream_join(ctx, (hipStream_t)stream, false, who);
+    if (rc != MG3D_OK)
+        return rc;
+    {
+        StageScope kt(ctx, ctx->L - 1, MG3D_K_PACK, true);
+        if (k_part_permute(count, perm, nvec, src, dst, ctx->stream) < 0)
+            return fail(MG3D_ERR_STATE, "%s: nothing to launch", who);
+    }
+    rc = part_launch_ok(who);
+    if (rc != MG3D_OK)
+        return rc;
+    return mg3d_stream_join(ctx, (hipStream_t)stream, true, who);
+}
+
 /* ------------------------------------------------------------------------------------------------------ host forms */
 /* `doubles` doubles of device memory for one call of a host form */
 struct Staging {
@@ -455,6 +637,49 @@ extern "C" int mg3d_particle_push(mg3d_ctx *ctx, long long count, double *xyz, d
         e = hipMemcpyAsync(vxyz, dv, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (rc == MG3D_OK && e == hipSuccess)
         e = hipMemcpyAsync(fate, df, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream); /* (also before the buffer goes) */
+    if (rc == MG3D_OK && (e != hipSuccess || es != hipSuccess))
+        rc = fail(MG3D_ERR_HIP, "%s: copy to the host: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    return rc;
+}
+
+extern "C" int mg3d_particle_sort(mg3d_ctx *ctx, long long count, const double *xyz, const int *fate, int shift, int *perm,
+                                  long long *counts)
+{
+    static const char who[] = "mg3d_particle_sort";
+    int passes = 0;
+    int rc = sort_args(ctx, count, shift, &passes, who);
+    if (rc != MG3D_OK)
+        return rc;
+    if (!xyz || !perm)
+        return fail(MG3D_ERR_ARG, "%s: NULL %s", who, xyz ? "permutation" : "positions");
+    if (count == 0)
+        return MG3D_OK;
+    /* one buffer: the positions (3 per particle), the two counts, then the fates and the permutation as ints */
+    const size_t n = (size_t)count;
+    Staging buf;
+    rc = buf.alloc(3 * n + 2 + n + 1, who);
+    if (rc == MG3D_OK)
+        rc = sort_alloc(ctx, count, who);
+    if (rc != MG3D_OK)
+        return rc;
+    double *const dx = buf.p;
+    long long *const dc = (long long *)(buf.p + 3 * n);
+    int *const df = (int *)(buf.p + 3 * n + 2), *const dp = df + n;
+    const mg3d_vec px = {dx, MG3D_F64, 3}, py = {dx + 1, MG3D_F64, 3}, pz = {dx + 2, MG3D_F64, 3};
+    const mg3d_vec vf = {df, MG3D_I32, 1}, vp = {dp, MG3D_I32, 1};
+    const mg3d_vec *const pos[3] = {&px, &py, &pz};
+    hipError_t e = hipMemcpyAsync(dx, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && fate)
+        e = hipMemcpyAsync(df, fate, n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess)
+        rc = fail(MG3D_ERR_HIP, "%s: copy to the device: %s", who, hipGetErrorString(e));
+    if (rc == MG3D_OK)
+        rc = sort_enqueue(ctx, count, pos, fate ? &vf : nullptr, shift, passes, &vp, counts ? dc : nullptr, who);
+    if (rc == MG3D_OK)
+        e = hipMemcpyAsync(perm, dp, n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    if (rc == MG3D_OK && e == hipSuccess && counts)
+        e = hipMemcpyAsync(counts, dc, 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream);
     const hipError_t es = hipStreamSynchronize(ctx->stream); /* (also before the buffer goes) */
     if (rc == MG3D_OK && (e != hipSuccess || es != hipSuccess))
         rc = fail(MG3D_ERR_HIP, "%s: copy to the host: %s", who, hipGetErrorString(e != hipSuccess ? e : es));

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The particle gather, scatter and push against a plain torch restatement: python tools/particle_bench.py [c,L ...]
 (default 9,7 and 9,6: 513^3 and 257^3, constant operator, Dirichlet faces, random u; POINTS=1000000,10000000;
-ROWS=sample,deposit,push).
+ROWS=sample,deposit,push; ROWS=sort for the reorder alone, see below).
 
 Per size and number of points, for points uniformly random in the box and for the same points sorted by cell, in one
 process, the median (min .. max) of RUNS runs after a warm-up, each run one call between two events on the current stream:
@@ -13,6 +13,12 @@ process, the median (min .. max) of RUNS runs after a warm-up, each run one call
   push     push_tensor(pos, vel, qm, dt, fate): one launch; speeds up to half a spacing per step, kicks up to a hundredth.
            Its torch column is the composition it replaces: sample_tensor(want_u=False), then the kick, the drift and the
            fates of Dirichlet faces in torch (the first exit in axis order, INVALID for what is not finite; no table)
+  sort     (ROWS=sort) points that start sorted by cell and then drift: DRIFT (50) pushes at up to half a spacing per step.
+           (a) the cost of one reorder: sort_tensor(pos, fate) plus one permute_tensors of pos, vel, q, qm and fate (nine
+           vectors, 1 + 3 passes + 1 launches) against what it replaces in torch on the same GPU: the keys of cells()
+           above (no periodic wrap; the dead put last), torch.sort(stable=True), one index_select per tensor.  The two
+           sides alternate run by run.  (b) the gain: push_tensor plus deposit_tensor on the drifted points against the same
+           on the re-sorted points, alternating, and how many steps repay one reorder.
 Nothing is gated; the numbers go into INTEGRATION.md ("Particles")."""
 import os
 import statistics
@@ -41,6 +47,23 @@ def timed(call):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b))
+    return out
+
+
+def timed_pair(first, second):
+    """timed() for two calls that alternate run by run: (milliseconds of first, of second)"""
+    first()
+    second()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(RUNS):
+        for call, ts in zip((first, second), out):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            call()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b))
     return out
 
 
@@ -98,6 +121,58 @@ def torch_push(s, pos, vel, qm, fate, dt, h, N, og):
     fate.copy_(torch.where(alive, f, fate))
 
 
+def torch_reorder(tensors, pos, fate, h, N):
+    """what the library's reorder replaces: the tool's own keys, a stable sort, one index_select per tensor"""
+    cell, _ = cells(pos, h, N)
+    key = (cell[:, 0] * N + cell[:, 1]) * N + cell[:, 2]
+    key = torch.where(fate != 0, torch.full_like(key, N ** 3), key)
+    order = torch.sort(key, stable=True)[1]
+    return [t.index_select(0, order) for t in tensors]
+
+
+def sort_rows(s, gen, count, N, h):
+    dev = dict(dtype=torch.float64, device="cuda")
+    drift, step = int(os.environ.get("DRIFT", "50")), 1.0
+    pos = torch.rand(count, 3, generator=gen, **dev) * ((N - 1) * h)
+    cell, _ = cells(pos, h, N)
+    pos = pos[torch.argsort((cell[:, 0] * N + cell[:, 1]) * N + cell[:, 2])].contiguous()
+    del cell
+    vel = (torch.rand(count, 3, generator=gen, **dev) * 2 - 1) * (0.5 * h / step)
+    q = torch.rand(count, generator=gen, **dev) * 2 - 1
+    qm = q * (0.01 * h * h / (step * step))
+    fate = torch.zeros(count, dtype=torch.int32, device="cuda")
+    for _ in range(drift):
+        s.push_tensor(pos, vel, qm, step, fate)
+    tensors = [pos, vel, q, qm, fate]
+
+    def library():
+        perm, _ = s.sort_tensor(pos, fate)
+        return s.permute_tensors(perm, *tensors)
+
+    tl, tt = timed_pair(library, lambda: torch_reorder(tensors, pos, fate, h, N))
+    ts = timed(lambda: s.sort_tensor(pos, fate))
+    ml, mt = statistics.median(tl), statistics.median(tt)
+    verdict = "faster" if max(tl) < min(tt) else ("slower" if min(tl) > max(tt) else "the ranges overlap")
+    alive = int((fate == 0).sum())
+    print(f"  after {drift} pushes ({alive} alive)")
+    print(f"  reorder  library {spread(tl)}   torch {spread(tt)}   library / torch = {ml / mt:.2f} ({verdict})")
+    print(f"           of which sort_tensor {spread(ts)}")
+    # the gain: one step on the drifted points and on the re-sorted ones (clones: a step moves them)
+    a = [t.clone() for t in tensors]
+    b = [t.clone() for t in library()]
+    del tensors, pos, vel, q, qm, fate
+
+    def one_step(t):
+        s.push_tensor(t[0], t[1], t[3], step, t[4])
+        s.deposit_tensor(t[0], t[2], scale=-1.0)
+
+    td, tr = timed_pair(lambda: one_step(a), lambda: one_step(b))
+    md, mr = statistics.median(td), statistics.median(tr)
+    even = f"{ml / (md - mr):.1f} steps repay one reorder" if md > mr else "a reorder is not repaid"
+    print(f"  push + deposit  drifted {spread(td)}   re-sorted {spread(tr)}   gain {md - mr:.3f} ms a step: {even}")
+    sys.stdout.flush()
+
+
 def main():
     cases = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]] or [(9, 7), (9, 6)]
     dev = dict(dtype=torch.float64, device="cuda")
@@ -110,6 +185,13 @@ def main():
             g = s.gradient_tensor(scale=-1.0)
             d = torch.zeros(N, N, N, **dev)
             for count in POINTS:
+                if "sort" in ROWS:
+                    print(f"{N}^3, {count} points that drift away from cell order, Dirichlet faces, float64, median of {RUNS} runs:")
+                    sort_rows(s, gen, count, N, h)
+                    s.zero(MG3D_D, top)
+                    torch.cuda.empty_cache()
+                if not set(ROWS) & {"sample", "deposit", "push"}:
+                    continue
                 pos = torch.rand(count, 3, generator=gen, **dev) * ((N - 1) * h)
                 q = torch.rand(count, generator=gen, **dev) * 2 - 1
                 cell, _ = cells(pos, h, N)
