@@ -852,6 +852,9 @@ int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
  *   zero_front      1        MG3D_ZERO_FRONT           the four-pass launch that starts a coarse level from the zero guess
  *                                                      forms its first pass from d as a plane arrives and runs a three-pass
  *                                                      kernel; 0: the four-pass kernel on an input that is not read
+ *   fuse_down_min   130      MG3D_FUSE_DOWN_MIN        smallest level side whose V(2,2) down-leg from the zero guess is ONE
+ *                                                      launch: the zero front, three passes, the residual and its
+ *                                                      restriction (needs zero_front; levels above fuse_leg_max only); 0: never
  * mg3d_option_name(i) enumerates the keys (NULL past the end).  mg3d_dist_set_option forwards to every local rank (carry /
  * carry_min of a multi-rank job are agreed at creation and refuse to change); mg3d32_set_option knows "pairs", "fuse",
  * "carry" (MG3D_F32_NO_PAIRS / _NO_FUSE / _NO_CARRY at creation).  A context with a variable coefficient

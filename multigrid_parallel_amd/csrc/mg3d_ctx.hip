@@ -252,6 +252,7 @@ static const OptionRow kOptionTable[MG3D_OPT_COUNT] = {
     {"sweep_pf", nullptr, 0, 0},
     {"d_zero_skip", "MG3D_D_ZERO_SKIP", 0, 1},
     {"zero_front", "MG3D_ZERO_FRONT", 0, 1},
+    {"fuse_down_min", "MG3D_FUSE_DOWN_MIN", 0, 130},
 };
 
 void mg3d_options_init(mg3d_options *o)
@@ -917,10 +918,11 @@ static int read_norm(mg3d_ctx *ctx, int slot, double *norm)
 
 /* what mg3d_stage_plan is asked about a stage on a level of this context */
 static StageAsk stage_ask(const mg3d_ctx *ctx, int level, int post, int iters, int want_res, bool has_coarse, bool need_norm,
-                          bool pro_offered)
+                          bool pro_offered, bool zero_in = false)
 {
     const Geom &g = ctx->lv[level].g;
-    return StageAsk{g.N, g.nj, post != 0, iters, want_res, has_coarse, need_norm, pro_offered, /* leg4_form */ true};
+    return StageAsk{g.N, g.nj, post != 0, iters, want_res, has_coarse, need_norm, pro_offered, /* leg4_form */ true, zero_in,
+                    /* down_form */ true};
 }
 
 /* One launch of a stage's list on a single-domain level (fused sweep): u -> alt, swapped behind a launch with passes; the
@@ -983,7 +985,7 @@ static int enqueue_smooth_residual(mg3d_ctx *ctx, int level, int post, int iters
     hipStream_t s = ctx->stream;
     if (mg3d_fused(ctx)) {
         const StagePlan plan = mg3d_stage_plan(ctx->opt, stage_ask(ctx, level, post, iters, want_res, coarse != nullptr, need_norm,
-                                                                   pro != nullptr));
+                                                                   pro != nullptr, zero_in));
         for (int k = 0; mg3d_stage_launch(plan, k); k++)
             CHK(enqueue_stage_step(ctx, level, post, *mg3d_stage_launch(plan, k), k == 0, want_res, slot, coarse, pro, zero_in, need_norm));
         return MG3D_OK;

@@ -1063,7 +1063,8 @@ static StagePlan dist_stage_plan(mg3d_dist *D, int l, int post, int want_res, bo
 {
     const Geom &g = SL(D, D->rs[0], l).lv.g;
     return mg3d_stage_plan(D->rs[0].coarse->opt,
-                           StageAsk{g.N, g.nj, post != 0, D->nu, want_res, has_coarse, want_res == 1, pro_offered, /* leg4_form */ false});
+                           StageAsk{g.N, g.nj, post != 0, D->nu, want_res, has_coarse, want_res == 1, pro_offered, /* leg4_form */ false, /* zero_in */ false,
+                                    /* down_form */ false});
 }
 
 /* a sweep launch on rank ri's slab of level l, u -> alt, over the owned planes; the norm counts the owned planes */

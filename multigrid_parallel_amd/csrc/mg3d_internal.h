@@ -90,6 +90,7 @@ enum {
     MG3D_OPT_SWEEP_PF,
     MG3D_OPT_D_ZERO_SKIP,  /* the planes of the top level's d that are +0.0 at every interior point are not read (the zero map, mg3d_ctx.h): 0 off, 1 the map and, when it is full, the leg kernels without d (default), 2 the map only */
     MG3D_OPT_ZERO_FRONT,   /* the four-pass launch from the zero guess (a coarse level's pre-smoother) forms its first pass from d as the plane arrives and runs a three-pass kernel (ZF, mg3d_sweep_kernel.h): 1 (default), 0 the four-pass kernel on an input that is not read */
+    MG3D_OPT_FUSE_DOWN_MIN, /* smallest level side whose V(2,2) pre-smoother from the zero guess, residual and restriction run as ONE launch behind the zero front (130; 0 never; needs zero_front, never at or below fuse_leg_max) */
     MG3D_OPT_COUNT
 };
 struct mg3d_options {
@@ -275,6 +276,8 @@ struct StageAsk {
     bool need_norm;   /* the norm of the residual is wanted */
     bool pro_offered; /* a prolongation source is offered: the first launch may take u + P(e) as its input */
     bool leg4_form;   /* the single domain has the whole down-leg as one two-row launch (option fuse_leg_max); the slab path does not */
+    bool zero_in;     /* the stage starts from the zero guess: its first launch has no input */
+    bool down_form;   /* the single domain has the zero-guess down-leg as one launch behind the zero front (option fuse_down_min); the slab path keeps its launches */
 };
 struct StageStep {
     int S;      /* colour passes of the launch: 4, 2 or 0 (the residual alone) */
@@ -321,7 +324,13 @@ static inline StagePlan mg3d_stage_plan(const mg3d_options &o, const StageAsk &q
          * against 0.85 + 0.76 ms split on a 513^3 level) */
         /* two passes + residual + restriction (the down-leg of V(1,1), the tail of V(3,3)'s): one launch from 130
          * points per side up, two below (k_sweep_fuse_rst2) */
-        const bool res = last && q.want_res != 0 && (S != 4 || leg4) && !(S == 2 && q.has_coarse && !k_sweep_fuse_rst2(o, q.N));
+        /* larger levels (>= fuse_down_min points per side) from the zero guess: the front forms the first red pass from d, three
+         * passes, residual and restriction ride behind it in the four-row shape -- d is read once, u and the coarse d written
+         * once, where four passes and then residual + restriction read d twice and u once more (k_sweep: S = 3, RES = 2) */
+        const bool down = q.down_form && q.zero_in && !q.post && 2 * q.iters == 4 && passes == 4 && q.has_coarse && !q.need_norm &&
+                          q.want_res != 0 && o.v[MG3D_OPT_ZERO_FRONT] != 0 && o.v[MG3D_OPT_FUSE_DOWN_MIN] > 0 &&
+                          q.N >= o.v[MG3D_OPT_FUSE_DOWN_MIN] && q.N > o.v[MG3D_OPT_FUSE_LEG_MAX];
+        const bool res = last && q.want_res != 0 && (S != 4 || leg4 || down) && !(S == 2 && q.has_coarse && !k_sweep_fuse_rst2(o, q.N));
         const StageStep st = {S, 1, res, res && q.has_coarse, pro && passes == 2 * q.iters, last};
         StageStep *prev = p.n ? &p.step[p.n - 1] : nullptr;
         if (prev && prev->S == S && !prev->res && !res && !prev->pro && prev->last == last)

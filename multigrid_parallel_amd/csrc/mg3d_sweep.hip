@@ -112,8 +112,21 @@ static bool launch_kernel(const SweepArgs &a, unsigned blocks, hipStream_t s) /*
     return false;
 }
 
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND, int ZF>
+static int launch_sweep_paired(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s, SweepTaken *t);
+
+/* (a ZF slot with an (S, RES) it does not go with -- sweep_front_pairing -- has no kernel: -1, nothing instantiated or launched) */
 template <int S, int RES, int RJ, int NW, int PF, bool PRO = false, bool RST = true, int DP = 0, int TAP = -1, int C1K = -1, bool ND = false, int ZF = 0>
 static int launch_sweep(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s, SweepTaken *t)
+{
+    if constexpr (sweep_front_pairing<S, RES, ZF>())
+        return launch_sweep_paired<S, RES, RJ, NW, PF, PRO, RST, DP, TAP, C1K, ND, ZF>(o, a, max_partials, s, t);
+    else
+        return -1;
+}
+
+template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K, bool ND, int ZF>
+static int launch_sweep_paired(const mg3d_options &o, SweepArgs &a, int max_partials, hipStream_t s, SweepTaken *t)
 {
     using Sh = SweepShape<S, RES>;
     constexpr int VJ = NW * RJ - 2 * Sh::HJ;
@@ -435,6 +448,14 @@ static bool fill_args(SweepArgs &a, const SweepLaunch &w)
     return a.i_hi > a.i_lo;
 }
 
+/* planes of d in flight in the four-row zero-guess down-leg behind the front (sweep_passes): both are compiled, 236 and 252
+ * VGPRs, no scratch (profiles/fused_down_resources.txt).  The 257^3 level of the 513^3 problem, kernel trace, median of 20
+ * cycles: 107.4 us with one plane, 108.1 with two, against 61.2 + 66.7 as two launches (profiles/fused_down_timeline.txt):
+ * the step is not waiting for its loads, one plane stays */
+#ifndef MG3D_FUSED_DOWN_PF
+#define MG3D_FUSED_DOWN_PF 1
+#endif
+
 /* SWEEP_PASSES, SWEEP_PASSES_RES, SWEEP_TAP: the compiled shape by (S, residual, restriction, prolongation) and level size */
 static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &w, hipStream_t s, SweepTaken *t)
 {
@@ -473,8 +494,28 @@ static int sweep_passes(const mg3d_options &o, SweepArgs &a, const SweepLaunch &
         return dispatch<2, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
     if (dc && S == 1 && residual)
         return dispatch<1, 2>(o, a, opt_cfg(o, {4, 8, 1}), max_partials, s, t);
-    if (dc && S == 4 && residual)
+    if (dc && S == 4 && residual) {
+        /* The down-leg of a coarse level from the zero guess behind the zero front (option fuse_down_min, mg3d_stage_plan): the
+         * front forms the first red pass from d, the kernel runs black, red, black, the residual and its restriction -- the
+         * run of the finest level's leg launch <3, 2> on an input made of d.  One read of d, one write of u and of the coarse
+         * d, where four passes and residual + restriction as two launches read d twice and u once more.  Four rows a thread,
+         * one or two planes of d in flight (MG3D_FUSED_DOWN_PF the default, option sweep_pf the other); two rows on the small
+         * levels and under sweep_rj / nw / pf.  Its record says S = 3 and RES = 2, which no other launch of kind PASSES_RES
+         * does.  At or below fuse_leg_max the level keeps that option's form <4, 2>, as without the front */
+        if (vin == nullptr && !w.d_none && !a.dz && o.v[MG3D_OPT_ZERO_FRONT] != 0 && g.N > o.v[MG3D_OPT_FUSE_LEG_MAX]) {
+            const SweepCfg dflt = small ? SweepCfg{2, 8, 2} : SweepCfg{4, 8, MG3D_FUSED_DOWN_PF};
+            SweepCfg c = opt_cfg(o, dflt);
+            if (!((c.rj == 2 && c.nw == 8 && c.pf == 2) || (c.rj == 4 && c.nw == 8 && (c.pf == 1 || c.pf == 2))))
+                c = dflt;
+            a.c1 = 1 - c1; /* the front is the pass of colour c1 */
+            if (c.rj == 2)
+                return launch_sweep<3, 2, 2, 8, 2, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+            if (c.pf == 2)
+                return launch_sweep<3, 2, 4, 8, 2, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+            return launch_sweep<3, 2, 4, 8, 1, false, true, 0, -1, -1, false, ZF_FRONT>(o, a, max_partials, s, t);
+        }
         return dispatch<4, 2>(o, a, opt_cfg(o, {2, 8, 2}), max_partials, s, t);
+    }
     if (dc)
         return -1;
     if (S == 4 && residual)

@@ -201,6 +201,12 @@ template <int S, int RES, int RJ, int NW, int PF, bool PRO, int TAPQ, int ZFM> c
     constexpr bool at_limit = S == 4 && RES == 0 && RJ == 4 && NW == 8 && PF == 2;
     return ZFM == ZF_MAYBE || (ZFM == ZF_OFF && !PRO && TAPQ < 0 && (S == 2 || (S == 4 && RES == 2) || at_limit));
 }
+/* the (S, RES) a ZF slot goes with: the front with three passes, alone or with residual + restriction; ZF_MAYBE with four
+ * passes alone.  launch_sweep launches nothing for any other pairing */
+template <int S, int RES, int ZFM> constexpr bool sweep_front_pairing()
+{
+    return ZFM == ZF_OFF || (ZFM == ZF_FRONT && S == 3 && (RES == 0 || RES == 2)) || (ZFM == ZF_MAYBE && S == 4 && RES == 0);
+}
 template <int S, int RES, int RJ, int NW, int PF, bool PRO, bool RST, int DP, int TAP, int C1K = -1, bool DZ = false, bool ND = false, int ZFM = ZF_OFF>
 __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepArgs a)
 {
@@ -214,8 +220,13 @@ __global__ void __launch_bounds__(NW *WAVE) MG3D_KERNEL_ATTR sweep_kernel(SweepA
     static_assert(!ND || DP == 0, "no d window: nothing to park");
     static_assert(!ND || !DZ, "no d window: no map to test");
     constexpr bool ZF = ZFM == ZF_FRONT;
-    static_assert(ZFM == ZF_OFF || (S == (ZF ? 3 : 4) && RES == 0), "the launch from the zero guess: three passes behind the front, or four");
-    static_assert(ZFM == ZF_OFF || (!PRO && !ND && RES == 0 && TAP < 0), "the zero front: plain colour passes on a d that is read");
+    /* The front with RES == 2 is the whole down-leg of a coarse level in one launch: front, black, red, black, the residual and
+     * its restriction (option fuse_down_min).  Nothing of the restricting path looks at where stage 1's input came from: the r
+     * pairs (rlag / rpark, rkeep), the coarse row parity CO and the coarse plane a step completes are counted from ST = 4 and
+     * HJ = 5 as in the leg launch <3, 2> behind a finished cycle, and the residual stages read slot s of the d window like the
+     * passes (DLAG = 0: the window's ST + 1 slots in registers, none parked) */
+    static_assert(sweep_front_pairing<S, RES, ZFM>(), "the launch from the zero guess: three passes behind the front (alone or with residual + restriction), or four");
+    static_assert(ZFM == ZF_OFF || (!PRO && !ND && TAP < 0), "the zero front: plain colour passes on a d that is read");
     static_assert(ZFM == ZF_OFF || (!DZ && DP == 0 && C1K < 0), "the zero front: every plane of d is read, nothing parked, c1 from the launcher");
     constexpr int KV = ST - DP; /* slots of the d window kept in VGPRs */
     constexpr int TJ = NW * RJ, VJ = TJ - 2 * HJ;
