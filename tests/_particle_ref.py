@@ -167,7 +167,9 @@ def box_points(N, h, count, seed):
 
 def edge_points(N, h, axes):
     """points that lie on nodes, on both ends of every axis, on cell boundaries, far outside on periodic axes and outside /
-    not finite on the others: (M, 3).  h a power of two makes index*h exact."""
+    not finite on the others: (M, 3).  index*h is exact only for a dyadic h: for any other h the point meant for node i is
+    the double nearest to i*h, and (i*h)/h may round to just below i, which puts it into cell i-1 with w1 one ulp below 1
+    (node_points() holds every node of an axis; tests/test_particle_length_host.py counts the nodes that do)."""
     length = (N - 1) * h
     nodes = [0.0, -0.0, h, (N - 2) * h, length, (N // 2) * h, 0.5 * h, length - 0.25 * h]
     pts = [(a, b, c) for a in nodes for b in (0.0, length, 1.5 * h) for c in (0.0, length, (N - 2) * h + 0.75 * h)]
@@ -182,3 +184,36 @@ def edge_points(N, h, axes):
             p[ax] = v
             pts.append(tuple(p))
     return np.array(pts, dtype=np.float64)
+
+
+NODE_OFF = (0.3717, 0.6143)  # the other two coordinates of a node point, as fractions of the box: off the nodes, inside
+
+
+def node_points(N, h, step=0):
+    """for each axis all N coordinates i*h, formed as np.float64(i) * h, the other two coordinates at the fixed positions
+    NODE_OFF inside the box: (3 N, 3), axis after axis, node after node.  step = +1 / -1: every node coordinate moved one
+    ulp up / down with np.nextafter (below node 0 and above node N-1 that is outside on an axis that is not periodic)"""
+    h = np.float64(h)
+    x = np.array([np.float64(i) * h for i in range(N)], dtype=np.float64)
+    if step:
+        x = np.nextafter(x, np.float64(np.inf if step > 0 else -np.inf))
+    length = np.float64(N - 1) * h
+    pts = np.empty((3, N, 3), dtype=np.float64)
+    for ax in range(3):
+        pts[ax, :, (ax + 1) % 3] = NODE_OFF[0] * length
+        pts[ax, :, (ax + 2) % 3] = NODE_OFF[1] * length
+        pts[ax, :, ax] = x
+    return pts.reshape(3 * N, 3)
+
+
+def node_points_all(N, h):
+    """the nodes, then the doubles one ulp above them, then those one ulp below: (9 N, 3)"""
+    return np.concatenate([node_points(N, h, 0), node_points(N, h, 1), node_points(N, h, -1)])
+
+
+def low_nodes(N, h):
+    """(the i with floor((i*h)/h) == i - 1, the i with (i*h)/h > i), in float64 as the locator divides"""
+    h = np.float64(h)
+    t = np.array([(np.float64(i) * h) / h for i in range(N)])
+    i = np.arange(N)
+    return np.flatnonzero(np.floor(t) == i - 1), np.flatnonzero(t > i)

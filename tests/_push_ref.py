@@ -140,9 +140,9 @@ CASES = ([(5, bc, 257, n % 2 == 0, 20) for n, bc in enumerate(BCS)] + [(17, bc, 
             (65, "per7", 4099, True, 20), (17, "per4_f15", PAST_CAP_COUNT, True, 3)])
 
 
-def spacing(N):
-    """h of a unit box, as the library forms it"""
-    return 1.0 / (N - 1)
+def spacing(N, grid_length=1.0):
+    """h of a box of side grid_length, as the library forms it"""
+    return grid_length / (N - 1)
 
 
 def bodies(N):
@@ -155,15 +155,16 @@ def bodies(N):
     return m
 
 
-def particles(N, h, axes, count, seed):
+def particles(N, h, axes, count, seed, nodes=False):
     """(xyz, vel, qm) of a case: `count` seeded points inside the box and then the edge points of the sample's tests (a
     count of 1: the one point alone), speeds up to 1.5 h per step on each axis -- a quarter of the particles fifty times
     slower, so that some stay --, q/m for kicks of up to a hundredth of a spacing against a field of size 1/h; one velocity
-    and one q/m that are not finite"""
+    and one q/m that are not finite.  Everything is written in units of h (the box's own: h carries the grid length) and
+    DT.  nodes: PR.node_points_all(N, h) behind the edge points"""
     rng = np.random.default_rng(seed)
     xyz = PR.box_points(N, h, count, seed)
     if count > 1:
-        xyz = np.concatenate([xyz, PR.edge_points(N, h, axes)])
+        xyz = np.concatenate([xyz, PR.edge_points(N, h, axes)] + ([PR.node_points_all(N, h)] if nodes else []))
     M = xyz.shape[0]
     vel = rng.uniform(-1.5, 1.5, (M, 3)) * (h / DT)
     vel[rng.uniform(size=M) < 0.25] *= 0.02
@@ -179,24 +180,28 @@ def field(N, seed):
     return np.random.default_rng(seed).uniform(-1, 1, (N, N, N))
 
 
-def case_data(N, bc, count, with_mask):
-    """(u, mask or None, xyz, vel, qm, accel, drag) of a case of CASES"""
+def case_data(N, bc, count, with_mask, grid_length=1.0, nodes=False):
+    """(u, mask or None, xyz, vel, qm, accel, drag) of a case of CASES, on a box of side grid_length (velocities, q/m and
+    accel are in units of h and DT: they carry over)"""
     axes, faces = BCS[bc]
-    h = spacing(N)
+    h = spacing(N, grid_length)
     u = field(N, 1000 * N + axes * 64 + faces)
-    xyz, vel, qm = particles(N, h, axes, count, 7 * N + count + axes + faces)
+    xyz, vel, qm = particles(N, h, axes, count, 7 * N + count + axes + faces, nodes)
     accel = (0.0, 0.0, -0.002 * h / (DT * DT))
     return u, (bodies(N) if with_mask else None), xyz, vel, qm, accel, 0.25
 
 
-def run_case(N, bc, count, with_mask, pushes, events=None):
+def run_case(N, bc, count, with_mask, pushes, events=None, grid_length=1.0, nodes=False, vel_dtype=np.float64):
     """the restatement's states after each push: [(xyz, vel, fate, table copy)]"""
     axes, faces = BCS[bc]
-    u, mask, xyz, vel, qm, accel, drag = case_data(N, bc, count, with_mask)
+    u, mask, xyz, vel, qm, accel, drag = case_data(N, bc, count, with_mask, grid_length, nodes)
+    with np.errstate(over="ignore", invalid="ignore"):
+        vel = vel.astype(vel_dtype)
     fate = np.zeros(xyz.shape[0], dtype=np.int32)
     table = new_table()
     out = []
+    h = spacing(N, grid_length)
     for _ in range(pushes):
-        xyz, vel, fate = push(u, mask, xyz, vel, qm, fate, spacing(N), axes, faces, DT, -1.0, accel, drag, table, events)
+        xyz, vel, fate = push(u, mask, xyz, vel, qm, fate, h, axes, faces, DT, -1.0, accel, drag, table, events)
         out.append((xyz, vel, fate, table.copy()))
     return out

@@ -78,17 +78,19 @@ SMALL_CASES = [(N, bc) for N in (5, 17, 37, 65, 161, 321) for bc in boundary_set
 LARGE_CASES = [(5, "dirichlet"), (17, "per7"), (37, "per4_f15"), (65, "f63"), (161, "f22"), (321, "f25")]
 
 
-def spacing(N):
-    return QR.spacing(N)
+def spacing(N, grid_length=1.0):
+    return QR.spacing(N, grid_length)
 
 
 @functools.lru_cache(maxsize=4)
-def _particles(N, bc, count):
+def _particles(N, bc, count, grid_length=1.0, nodes=False):
     axes, _ = QR.BCS[bc]
-    h = spacing(N)
+    h = spacing(N, grid_length)
     length = (N - 1) * h
     rng = np.random.default_rng(100003 * N + 17 * count + axes)
     edge = PR.edge_points(N, h, axes) if count > 1 else np.zeros((0, 3))
+    if nodes and count > 1:
+        edge = np.concatenate([edge, PR.node_points_all(N, h)])
     xyz = np.concatenate([edge, PR.box_points(N, h, count, 11 * N + count)])[:count]
     fresh = np.arange(count) >= edge.shape[0]
     for ax in range(3):
@@ -110,12 +112,12 @@ def _particles(N, bc, count):
     return xyz, fate
 
 
-def particles(N, bc, count):
+def particles(N, bc, count, grid_length=1.0, nodes=False):
     """(xyz (count, 3) float64, fate (count,) int32) of a case, read only: the edge points of the sample's tests first (a
-    count of 1: one seeded point), seeded points inside, a tenth per axis moved whole periods away on a periodic axis and
-    beyond a face on another, an eighth dead with the fates a push gives; past 3 * FAR particles one cell is held by three
-    living particles at both ends and in the middle"""
-    return _particles(N, bc, count)
+    count of 1: one seeded point; nodes: PR.node_points_all behind them), seeded points inside, a tenth per axis moved whole
+    periods away on a periodic axis and beyond a face on another, an eighth dead with the fates a push gives; past 3 * FAR
+    particles one cell is held by three living particles at both ends and in the middle.  On a box of side grid_length"""
+    return _particles(N, bc, count, grid_length, nodes)
 
 
 def classes(K, top):

@@ -23,9 +23,19 @@ C  the scaling identity between GPU runs, where the fused and distributed paths 
    4^-m times, PCG iterates and counts the same, the gradient 2^-m times, flux and energy 2^m times (include/mg3d.h:
    *flux = h * sum, *energy = 0.5 * h * sum, the sums of unscaled terms).  No CPU reference of the cycle is needed; the
    unit-length runs at these shapes are pinned to the oracle by tests/test_gpu_legs.py, tests/test_gpu_parity.py and
-   tests/test_gpu_screened_variants.py.  The identity cannot see a spacing that is wrong by the same factor in both runs
-   (another level's h): the base run's coarsest level is therefore solved again on the CPU with the factor of the
-   coarsest spacing, 2^(L-1) * grid_length / (N - 1), and the gradient is compared with _field_ref.gradient."""
+   tests/test_gpu_screened_variants.py (the bases at 3e-4 by the identity from them).  The identity cannot see a spacing
+   that is wrong by the same factor in both runs (another level's h): the base run's coarsest level is therefore solved
+   again on the CPU with the factor of the coarsest spacing, 2^(L-1) * grid_length / (N - 1), and the gradient is
+   compared with _field_ref.gradient.
+
+The features merged after this file have siblings of their own, with these lengths, data and tolerances:
+   tests/test_gpu_length_fields.py    the screening field (mg3d_ctx_set_shift_field), the KEEP coarsening rule and masked
+                                      full multigrid, PCG / WPCG over both: parts B and C; its identity runs are pinned
+                                      by its own part B at the smaller sizes
+   tests/test_gpu_particle_length.py  sample, deposit, push, sort and permute at 21, 37, 41 and 65 points per side, where a
+                                      coordinate i*h locates in cell i - 1; its identity runs at 41^3 are pinned to the
+                                      restatements in the same test
+   tests/test_particle_length_host.py the coverage of those particle cases and the identity on their restatements"""
 import numpy as np
 import pytest
 import torch  # noqa: F401  (before the package, as bench.py does: the HIP runtime is torch's)
