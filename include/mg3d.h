@@ -819,6 +819,80 @@ int mg3d_step_setup(mg3d_ctx *ctx, double dt, double theta, double kappa);
 int mg3d_step_set_source(mg3d_ctx *ctx, const double *s /* finest level, dense N^3 host; NULL: no source */);
 int mg3d_step_advance(mg3d_ctx *ctx, int nsteps, int method, int cycles, double rtol,
                       double *norms /* NULL or nsteps entries */, mg3d_step_info *info /* may be NULL */);
+
+/* ------------------------------------------------------------ nonlinear solves
+ * Damped Newton-multigrid on the device for
+ *     A u - g0 * g(x) * phi(beta*(u - uref)) = d
+ * with A the context's linear operator and boundaries as set (constant or eps, sigma, periodic axes, Neumann faces, mask),
+ * phi = exp (MG3D_NL_EXP: Boltzmann electrons, div(eps grad u) - g exp(beta (u - uref)) = -rho_i/eps0) or phi = sinh
+ * (MG3D_NL_SINH: Poisson-Boltzmann, Delta u - kappa^2 sinh u = f), g0 >= 0, beta > 0 and uref finite scalars, g >= 0 an
+ * optional weight per point (none: 1).  d and the Dirichlet values of u are the caller's, as for every solve; a prescribed
+ * Neumann flux is folded into d (mg3d_neumann_fold_flux).  Finest level of a single-domain fp64 context.
+ * The evaluation, one launch on the residual's column walk; per unknown, uncontracted and in this order:
+ *     w   = beta*(u[p] - uref)
+ *     ph  = exp(w), dph = ph      or      ph = sinh(w), dph = cosh(w)      (the device library's double functions)
+ *     gp  = g0*g[p]                                                        (no weight: gp = g0)
+ *     lin = d[p] - invHsq*(S - dg*u[p])      mg3d_residual's expression for the operator at sigma WITHOUT a screening field
+ *     F   = lin + gp*ph                      the nonlinear residual
+ *     s   = (gp*beta)*dph                    the screening field of the linearisation, A - s
+ * F and s are 0. at fixed points.  tests/_nl_ref.py restates it in numpy.
+ * mg3d_nl_setup: kind MG3D_NL_EXP or MG3D_NL_SINH, g0 >= 0, beta > 0, all three finite; otherwise MG3D_ERR_ARG and nothing
+ *   changes.  Stores the four; call it again for other values.  Touches neither fields nor the factor.
+ * mg3d_nl_set_weight: g of the finest level, a dense N^3 host array, every entry finite and >= 0, checked as
+ *   mg3d_ctx_set_shift_field checks its own (periodic duplicates skipped; MG3D_ERR_ARG names the lowest bad index), uploaded
+ *   into a field of the library's own that is allocated on the first call and freed with the context (MG3D_ERR_ALLOC, nothing
+ *   changed, when it does not fit); NULL drops the weight.  Values at Dirichlet points and duplicates are never used.
+ * mg3d_nl_set_weight_device: the same from a device array, MG3D_F64 or MG3D_F32, any strides >= 0, checked on the device
+ *   (one host synchronisation), packed on the context's stream behind what the caller's stream did to the array.
+ * mg3d_nl_residual: F at every unknown of the finest level from u and d as they stand; *norm (may be NULL) = sqrt of the sum
+ *   of F^2, per-block partial sums folded in a fixed order as mg3d_residual's; store != 0: F goes into r of the finest level,
+ *   duplicates written, Dirichlet and fixed points keep / get 0. as under mg3d_residual.  With g0 = 0 it is mg3d_residual of a
+ *   context without a screening field, bit for bit.  A screening field on the context (mg3d_nl_solve leaves one) is NOT part of
+ *   A here.  Read-only otherwise (a cycle that has run ahead is finished first).  MG3D_ERR_STATE without mg3d_nl_setup.
+ * mg3d_nl_solve: inexact Newton in correction form with backtracking on ||F||, from u of the finest level:
+ *     x := u, f := d                        (fields of the library's own, allocated before the first write)
+ *     evaluate at x -> F into d, s into the screening field's finest level, n := ||F||; norm0 := n
+ *     repeat up to max_newton times, stopping when n <= max(atol, rtol*norm0):
+ *         install s: restrict it down the hierarchy and rebuild the coarse factor, what mg3d_ctx_set_shift_field_device does
+ *                    behind its pack
+ *         u := 0 everywhere; solve (A - s) delta = F by
+ *             MG3D_STEP_VCYCLES  mg3d_vcycles(cycles)                   (rtol_lin ignored)
+ *             MG3D_STEP_WPCG     mg3d_wpcg_solve(rtol_lin, 0, cycles)
+ *         lambda := 1; up to max_halvings + 1 trials:
+ *             t := x + lambda*delta at the unknowns (Dirichlet and fixed points of x copied, duplicates written)
+ *             evaluate at t -> F, s, n_t
+ *             accept if n_t and every s are finite and n_t < (1 - 1e-4*lambda)*n; else lambda := lambda/2
+ *         accepted: x := t, n := n_t;   none accepted: evaluate at x again, stop, converged = 0
+ *     on every exit: s(x) installed on all levels; u := x; d := f bit for bit; the lower levels and r are unspecified
+ *   norms, if not NULL, has max_newton + 1 entries: norms[0] = norm0, norms[k] = n behind Newton step k.  info (may be NULL):
+ *   the counts below.  One host synchronisation per evaluation (the norm and the count of non-finite s) beside those of the
+ *   install and of the linear solve.
+ *   After the call the context is the linearisation at the solution: mg3d_ctx_has_shift_field reports 1, a cycle solves
+ *   (A - s) v = d; mg3d_ctx_set_shift_field(ctx, NULL) drops the field and returns to the context as it was.  A screening
+ *   field the CALLER installed is refused (MG3D_ERR_STATE, nothing changed): folding it in is not offered; one left by an
+ *   earlier mg3d_nl_solve is overwritten.  max_newton = 0 evaluates, installs s(x) and returns.
+ *   MG3D_ERR_ARG, nothing changed: max_newton < 0, a method that is neither, cycles < 1, max_halvings < 0, rtol or atol (or,
+ *   with MG3D_STEP_WPCG, rtol_lin) negative or not finite.  MG3D_ERR_STATE, nothing changed: mg3d_nl_setup never called; a
+ *   caller's screening field; no coarse factor, or one that mg3d_ctx_build_coarse did not build (every install rebuilds it);
+ *   a context after mg3d_es_setup; a linearisation that would be singular -- every axis closed (periodic or Neumann on both
+ *   faces), sigma = 0, no fixed unknown and g0*g > 0 at no unknown.  A HIP or allocation error is returned as it is, u and d
+ *   put back where that is still possible; info says how far the solve got.
+ * The slab (mg3d_dist_*), fp32 (mg3d32_*) and mg3d_host_* forms have no nonlinear solve: single domain, fp64 only. */
+enum { MG3D_NL_EXP = 0, MG3D_NL_SINH = 1 };
+typedef struct mg3d_nl_info {
+    int iterations;        /* Newton steps accepted */
+    int converged;         /* 1 when n <= max(atol, rtol*norm0) was reached */
+    int halvings;          /* halvings of lambda over all steps */
+    int linear_iterations; /* V-cycles (MG3D_STEP_VCYCLES) or CG iterations (MG3D_STEP_WPCG) over all steps */
+    double last_lambda;    /* lambda of the last accepted step (0: none) */
+    double norm0, norm;    /* ||F|| at the caller's u and at the returned u */
+} mg3d_nl_info;
+int mg3d_nl_setup(mg3d_ctx *ctx, int kind, double g0, double beta, double uref);
+int mg3d_nl_set_weight(mg3d_ctx *ctx, const double *g /* finest level, dense N^3 host; NULL: no weight */);
+int mg3d_nl_set_weight_device(mg3d_ctx *ctx, const mg3d_array *g /* NULL: no weight */, void *stream);
+int mg3d_nl_residual(mg3d_ctx *ctx, int store, double *norm /* may be NULL */);
+int mg3d_nl_solve(mg3d_ctx *ctx, int max_newton, int method, int cycles, double rtol_lin, double rtol, double atol,
+                  int max_halvings, double *norms /* NULL or max_newton + 1 entries */, mg3d_nl_info *info /* may be NULL */);
 /* setupBoundaryConditions (mg_3d.h:1147-1239) on a device-resident field */
 int mg3d_fill_boundary(mg3d_ctx *ctx, int field, int level);
 

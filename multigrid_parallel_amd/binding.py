@@ -125,6 +125,12 @@ SIGNATURES = {
     "mg3d_step_setup": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
     "mg3d_step_set_source": (C.c_int, [C.c_void_p, dp]),
     "mg3d_step_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_void_p]),
+    "mg3d_nl_setup": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "mg3d_nl_set_weight": (C.c_int, [C.c_void_p, dp]),
+    "mg3d_nl_set_weight_device": (C.c_int, [C.c_void_p, _ap, C.c_void_p]),
+    "mg3d_nl_residual": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "mg3d_nl_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, dp,
+                                C.c_void_p]),
     "mg3d_field_gradient": (C.c_int, [C.c_void_p, C.c_double, dp, dp, dp]),
     "mg3d_field_gradient_device": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(_ap), C.c_void_p]),
     "mg3d_field_flux": (C.c_int, [C.c_void_p, C.c_int, dp]),
@@ -273,6 +279,15 @@ class StepInfo(C.Structure):
 
 
 STEP_METHODS = {"vcycles": 0, "wpcg": 1}  # MG3D_STEP_VCYCLES, MG3D_STEP_WPCG
+
+
+class NlInfo(C.Structure):
+    """mg3d_nl_info: what mg3d_nl_solve reports"""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("halvings", C.c_int), ("linear_iterations", C.c_int),
+                ("last_lambda", C.c_double), ("norm0", C.c_double), ("norm", C.c_double)]
+
+
+NL_KINDS = {"exp": 0, "sinh": 1}  # MG3D_NL_EXP, MG3D_NL_SINH
 
 
 class EsParams(C.Structure):
@@ -1212,6 +1227,60 @@ class Solver:
                                        C.byref(info)))
         return norms, {"steps": info.steps, "iterations": info.iterations, "converged": bool(info.converged),
                        "time": info.time}
+
+    # -- nonlinear solves, csrc/mg3d_nl.hip
+    def nl_setup(self, kind, g0=1.0, beta=1.0, uref=0.0):
+        """mg3d_nl_setup: the nonlinear term of  A u - g0*g*phi(beta*(u - uref)) = d,  phi = exp (kind "exp", Boltzmann
+        electrons) or sinh (kind "sinh", Poisson-Boltzmann); g0 >= 0, beta > 0."""
+        if kind not in NL_KINDS:
+            raise ValueError(f"nl_setup: kind {kind!r} (need one of {', '.join(NL_KINDS)})")
+        check(self.L.mg3d_nl_setup(self._h, NL_KINDS[kind], float(g0), float(beta), float(uref)))
+
+    def nl_set_weight(self, g):
+        """mg3d_nl_set_weight: the weight g >= 0 of the finest level ((N, N, N) or flat float64), kept on the device;
+        None drops it (g = 1 everywhere)."""
+        if g is None:
+            check(self.L.mg3d_nl_set_weight(self._h, None))
+            return
+        g = np.asarray(g)
+        if g.dtype != np.float64:
+            raise TypeError(f"nl_set_weight: need float64, got {g.dtype}")
+        if g.size != self.N ** 3 or g.shape not in ((self.N ** 3,), (self.N, self.N, self.N)):
+            raise ValueError(f"nl_set_weight: need shape ({self.N},)*3 or ({self.N ** 3},), got {g.shape}")
+        check(self.L.mg3d_nl_set_weight(self._h, P(np.ascontiguousarray(g).reshape(-1))))
+
+    def nl_set_weight_tensor(self, t):
+        """mg3d_nl_set_weight_device: nl_set_weight from an (N, N, N) float64 or float32 tensor on the GPU, any view, no
+        host copy.  None drops the weight."""
+        if t is None:
+            check(self.L.mg3d_nl_set_weight_device(self._h, None, None))
+            return
+        a, stream = _device_args(t, "nl_set_weight_tensor", (self.N,) * 3)
+        check(self.L.mg3d_nl_set_weight_device(self._h, C.byref(a), stream))
+
+    def nl_residual(self, store=False):
+        """mg3d_nl_residual: ||F||, F = d - (A u - g0*g*phi(beta*(u - uref))) at the unknowns of the finest level; with
+        store, F goes into r of that level."""
+        nrm = C.c_double()
+        check(self.L.mg3d_nl_residual(self._h, int(bool(store)), C.byref(nrm)))
+        return nrm.value
+
+    def nl_solve(self, max_newton=20, cycles=2, method="vcycles", rtol_lin=1e-2, rtol=1e-8, atol=0.0, max_halvings=10):
+        """mg3d_nl_solve: damped Newton-multigrid from u of the finest level, entirely on the device: each step evaluates
+        the residual and the linearisation in one launch, installs it as the screening field, solves the correction with
+        `cycles` V-cycles (method "vcycles") or wpcg_solve(rtol_lin, max_iters=cycles) (method "wpcg") and backtracks on
+        ||F||.  Returns (norms[0 .. iterations], info dict: iterations, converged, halvings, linear_iterations,
+        last_lambda, norm0, norm).  Afterwards the context holds the linearisation at u (has_shift_field() is True;
+        set_shift_field(None) drops it)."""
+        if method not in STEP_METHODS:
+            raise ValueError(f"nl_solve: method {method!r} (need one of {', '.join(STEP_METHODS)})")
+        norms = np.zeros(max(int(max_newton), 0) + 1)
+        info = NlInfo()
+        check(self.L.mg3d_nl_solve(self._h, int(max_newton), STEP_METHODS[method], int(cycles), float(rtol_lin), float(rtol),
+                                   float(atol), int(max_halvings), P(norms), C.byref(info)))
+        return norms[:info.iterations + 1], {"iterations": info.iterations, "converged": bool(info.converged),
+                                             "halvings": info.halvings, "linear_iterations": info.linear_iterations,
+                                             "last_lambda": info.last_lambda, "norm0": info.norm0, "norm": info.norm}
 
     # -- the mixed-boundary ("electrospray") problem, csrc/mg3d_es.hip
     def es_setup(self, params=None):

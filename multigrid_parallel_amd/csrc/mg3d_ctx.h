@@ -120,6 +120,17 @@ struct mg3d_ctx {
     double step_dt = 0., step_theta = 0., step_kappa = 0., step_sigma = 0.;
     double *step_src = nullptr;
     bool step_has_src = false;
+    /* the nonlinear term (mg3d_nl.hip): kind, g0, beta, uref of mg3d_nl_setup; the weight g of the finest level in its
+     * padded layout (nl_has_g: in use); the solve's own fields of that level -- nl_v[0] the iterate x, [1] the trial t,
+     * [2] the caller's d --, all allocated on first use, kept and freed with the context.  sfield_nl: the screening field the
+     * context has was left by mg3d_nl_solve (the next solve overwrites it; the public field setters clear the flag) */
+    bool nl_set = false;
+    int nl_kind = 0;
+    double nl_g0 = 0., nl_beta = 0., nl_uref = 0.;
+    double *nl_g = nullptr;
+    bool nl_has_g = false;
+    double *nl_v[3] = {nullptr, nullptr, nullptr};
+    bool sfield_nl = false;
     /* device arrays (mg3d_*_device): the device that was current when the context was created -- a caller's array must
      * live there --, the two events of the stream join (io_ev[0] recorded on the caller's stream, io_ev[1] on the
      * context's; created on first use, freed with the context) and the two 64-bit results of k_coef_check on the device */
@@ -294,5 +305,17 @@ int mg3d_stream_join(mg3d_ctx *ctx, hipStream_t caller, bool out, const char *wh
 /* the finest level of a context as the field output and the particle calls need it (mg3d_field.hip): MG3D_ERR_STATE unless
  * it is a single-domain level of at least three points per side */
 int mg3d_field_level(const mg3d_ctx *ctx, const char *who);
+/* the install path of the screening field (mg3d_operator.hip) for mg3d_nl_solve, which writes the finest level's field with
+ * a kernel of its own -- the kernel counts the entries that are not finite, there is no host check of s here:
+ * mg3d_sfield_prepare everything that can fail for want of memory (the field of every level, eps = 1 for a context without
+ * eps, the two device words io_chk), nothing has changed when it does; mg3d_sfield_rebuild the finest level's duplicates,
+ * the restrictions, the counts and level 0's field (one host synchronisation; a HIP error leaves the context without a
+ * field); mg3d_operator_changed the coarse factor rebuilt or dropped.  mg3d_check_weight_*: the value check of the field
+ * setters (finite and >= 0), on a host or a device array, under another name */
+int mg3d_sfield_prepare(mg3d_ctx *ctx, const char *who);
+int mg3d_sfield_rebuild(mg3d_ctx *ctx, const char *who);
+int mg3d_operator_changed(mg3d_ctx *ctx);
+int mg3d_check_weight_host(const mg3d_ctx *ctx, const double *a, const char *name, const char *who);
+int mg3d_check_weight_device(mg3d_ctx *ctx, const mg3d_array &a, const char *name, const char *who);
 
 #endif

@@ -195,6 +195,11 @@ extern "C" int mg3d_ctx_destroy(mg3d_ctx *ctx)
             (void)hipFree(v);
     if (ctx->step_src)
         (void)hipFree(ctx->step_src);
+    if (ctx->nl_g)
+        (void)hipFree(ctx->nl_g);
+    for (double *v : ctx->nl_v)
+        if (v)
+            (void)hipFree(v);
     if (ctx->io_chk)
         (void)hipFree(ctx->io_chk);
     if (ctx->dep_acc)

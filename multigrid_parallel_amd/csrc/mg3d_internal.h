@@ -164,6 +164,20 @@ double k_wpcg_weight_sum(const Geom &g, int bc);
  * Return value: 0, or -1 when the level has no launch shape (nothing launched) */
 int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOperator &A, double a, double c1, double b,
                bool backward_euler, double *d, hipStream_t s);
+/* The nonlinear term of mg3d_nl_residual / mg3d_nl_solve on a single-domain level (formulas at the kernels):
+ *   k_nl_eval  : F = d - (A v - gp*phi(w)) and sf = gp*beta*phi'(w) at the unknowns, w = beta*(v - uref), gp = g0*gw[p] or g0
+ *                (gw NULL), phi by kind (MG3D_NL_EXP, MG3D_NL_SINH); A is the operator WITHOUT a screening field (A.s NULL).
+ *                F (NULL: not stored) also at the duplicates, sf (NULL: not wanted) at the unknowns only, both 0. at fixed
+ *                points; *sumsq_out = the sum of F^2 through partials and k_fold, residual_kernel's order; with sf,
+ *                *bad += the number of sf that are not finite (the caller zeroes it).  Return value: the number of partials
+ *                (0: no unknowns, *sumsq_out = 0), -1 when the level has no launch shape or A has a field: nothing launched
+ *   k_nl_trial : t = x + lambda*dl at the unknowns and their duplicates, t = x at the fixed points of m (NULL: no mask);
+ *                Dirichlet points of t are not written.  0, or -1: no launch shape */
+int k_nl_eval(const Geom &g, const double *v, const double *d, const LevelOperator &A, int kind, const double *gw, double g0,
+              double beta, double uref, double *F, double *sf, double *partials, double *sumsq_out, unsigned long long *bad,
+              hipStream_t s);
+int k_nl_trial(const Geom &g, int bc, const double *x, const double *dl, double lambda, double *t, const unsigned char *m,
+               hipStream_t s);
 /* The grid transfers.  bc = 0: ic_lo/ic_hi, if_lo/if_hi: local plane range to produce; -1 = every local plane that is not
  * a slab halo.  bc = mg3d_bc(periodic, neumann) != 0 (single-domain levels): every plane, full weighting on periodic and
  * Neumann faces too, duplicates written with their sources; the window and faces_only are not looked at */

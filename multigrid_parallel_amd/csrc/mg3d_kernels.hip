@@ -1054,6 +1054,158 @@ int k_step_rhs(const Geom &g, const double *u0, const double *src, const LevelOp
     return 0;
 }
 
+/* ------------------------------------------------------------- the nonlinear term
+ * mg3d_nl_residual and mg3d_nl_solve (mg3d_nl.hip, include/mg3d.h):  A u - g0*g(x)*phi(beta*(u - uref)) = d  with A the
+ * level's operator WITHOUT a screening field.  The evaluation: residual_kernel's walk, neighbour offsets and operand order for
+ * the linear part, then per unknown, uncontracted and in this order
+ *     w   = beta*(v[p] - uref)
+ *     ph  = exp(w), dph = ph              (KIND = MG3D_NL_EXP)     ph = sinh(w), dph = cosh(w)     (MG3D_NL_SINH)
+ *     gp  = g0*gw[p]                      (WEIGHT; else gp = g0)
+ *     lin = d[p] - invHsq*(s - dg*v[p])   residual_kernel's diff
+ *     F   = lin + gp*ph                   the nonlinear residual d - (A u - gp*ph)
+ *     sf  = (gp*beta)*dph                 the screening field of the linearisation A - sf
+ * F (optional) is stored at the unknowns and their duplicates, sf (optional) at the unknowns (the install path refreshes the
+ * field's duplicates); a fixed point has F = 0. and sf = 0., neither d nor gw is read there.  partials: one sum of F^2 per
+ * block, residual_kernel's order; with sf, *bad += the block's count of sf that are not finite -- an integer, so the order of
+ * the atomics does not matter.  exp, sinh and cosh are the device library's double functions: sinh keeps its relative
+ * accuracy at small |w|, which a difference of exponentials would lose. */
+struct NlTerm {
+    double g0, beta, uref;
+};
+template <bool COEF, int BC, int KIND, bool WEIGHT, bool MASK, class... M>
+__global__ void __launch_bounds__(256) nl_eval_kernel(Geom g, const double *__restrict__ v, const double *__restrict__ e,
+                                                      const double *__restrict__ d, const double *__restrict__ gw,
+                                                      double invHsq, double dg0, NlTerm nl, double *__restrict__ F,
+                                                      double *__restrict__ sf, double *__restrict__ partials,
+                                                      unsigned long long *__restrict__ bad, int bc, int chunk, int i_lo,
+                                                      int i_hi, M... fixed)
+{
+    static_assert(sizeof...(M) == (MASK ? 1 : 0), "MASK: the mask trails");
+    __shared__ double lds4[4];
+    double acc = 0.;
+    int nbad = 0;
+    Column c;
+    if (column<BC>(g, bc, chunk, i_lo, i_hi, c)) {
+        walk_column<COEF>(g, c, v, e, [&](const ColumnPoint<COEF> &pt) {
+            double s, dg;
+            pt.sum(dg0, s, dg);
+            double diff = 0., sv = 0.;
+            if (!(MASK && mask_fixed(pt.p, fixed...))) {
+                const double w = nl.beta * (pt.vh - nl.uref);
+                double ph, dph;
+                if constexpr (KIND == MG3D_NL_EXP) {
+                    ph = exp(w);
+                    dph = ph;
+                } else {
+                    ph = sinh(w);
+                    dph = cosh(w);
+                }
+                double gp = nl.g0;
+                if constexpr (WEIGHT)
+                    gp = nl.g0 * gw[pt.p];
+                const double lin = d[pt.p] - invHsq * (s - dg * pt.vh);
+                diff = lin + gp * ph;
+                sv = (gp * nl.beta) * dph;
+            }
+            if (F)
+                store_dup(g, F, pt.p, diff, pt.di(), c.dj, c.dk);
+            if (sf) {
+                sf[pt.p] = sv;
+                nbad += !(fabs(sv) <= 1.7976931348623157e308);
+            }
+            acc += diff * diff;
+        });
+    }
+    const double tot = block_sum_256(acc, lds4);
+    const bool first = threadIdx.x == 0 && threadIdx.y == 0;
+    if (first)
+        partials[(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
+    if (sf) { /* (uniform: a kernel argument) */
+        __syncthreads();
+        const double nb = block_sum_256((double)nbad, lds4); /* at most 256 * chunk: exact */
+        if (first && nb > 0.)
+            atomicAdd(bad, (unsigned long long)nb);
+    }
+}
+
+int k_nl_eval(const Geom &g, const double *v, const double *d, const LevelOperator &A, int kind, const double *gw, double g0,
+              double beta, double uref, double *F, double *sf, double *partials, double *sumsq_out, unsigned long long *bad,
+              hipStream_t s)
+{
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N || A.s)
+        return -1;
+    int i_lo = -1, i_hi = -1;
+    if (!stencil_window(g, A.bc, i_lo, i_hi)) {
+        (void)hipMemsetAsync(sumsq_out, 0, sizeof(double), s);
+        return 0;
+    }
+    int chunk;
+    const dim3 grid = column_grid(g, A.bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    const NlTerm nl = {g0, beta, uref};
+    dispatch_op(A.e, A.bc, A.m, [&](auto coef, auto mode, auto mask) {
+        const auto go = [&](auto kd, auto wt) {
+            launch_op(mask, OP_KERNELS(nl_eval_kernel, coef(), mode(), kd(), wt()), grid, block, s, A.m, g, v, A.e, d, gw,
+                      A.op.invHsq, op_dg0(A), nl, F, sf, partials, bad, A.bc, chunk, i_lo, i_hi);
+        };
+        const auto with_kind = [&](auto wt) {
+            if (kind == MG3D_NL_SINH)
+                go(std::integral_constant<int, MG3D_NL_SINH>(), wt);
+            else
+                go(std::integral_constant<int, MG3D_NL_EXP>(), wt);
+        };
+        if (gw)
+            with_kind(std::true_type());
+        else
+            with_kind(std::false_type());
+    });
+    const int np = (int)(grid.x * grid.y * grid.z);
+    k_fold(partials, np, sumsq_out, s);
+    return np;
+}
+
+/* The trial point of the line search, t = x + lambda*dl at the unknowns (their duplicates written with them); a fixed point
+ * of m (NULL: no mask) takes x as it is.  Dirichlet points of t are not written: the caller copied them from x once.  The
+ * column grid, one (j, k) column of `chunk` planes a thread, no stencil */
+template <int BC>
+__global__ void __launch_bounds__(256) nl_trial_kernel(Geom g, const double *__restrict__ x, const double *__restrict__ dl,
+                                                       double lambda, double *__restrict__ t,
+                                                       const unsigned char *__restrict__ m, int bc, int chunk, int i_lo,
+                                                       int i_hi)
+{
+    Column c;
+    if (!column<BC>(g, bc, chunk, i_lo, i_hi, c))
+        return;
+    long long p = gidx(g, c.i0, c.j, c.k);
+    for (int i = c.i0; i < c.i1; i++, p += g.plane) {
+        const double xv = x[p];
+        const double tv = (m && m[p] != 0) ? xv : xv + lambda * dl[p];
+        store_dup(g, t, p, tv, c.pi && i == 0, c.dj, c.dk);
+    }
+}
+
+int k_nl_trial(const Geom &g, int bc, const double *x, const double *dl, double lambda, double *t, const unsigned char *m,
+               hipStream_t s)
+{
+    if (g.N < 3 || g.ni != g.N || g.nj != g.N || g.nk != g.N)
+        return -1;
+    int i_lo = -1, i_hi = -1;
+    if (!stencil_window(g, bc, i_lo, i_hi))
+        return 0;
+    int chunk;
+    const dim3 grid = column_grid(g, bc, i_hi - i_lo, chunk), block(WAVE, 4, 1);
+    switch (bc_mode(bc)) {
+    case BC_REFLECT:
+        hipLaunchKernelGGL(nl_trial_kernel<BC_REFLECT>, grid, block, 0, s, g, x, dl, lambda, t, m, bc, chunk, i_lo, i_hi);
+        break;
+    case BC_WRAP:
+        hipLaunchKernelGGL(nl_trial_kernel<BC_WRAP>, grid, block, 0, s, g, x, dl, lambda, t, m, bc, chunk, i_lo, i_hi);
+        break;
+    default:
+        hipLaunchKernelGGL(nl_trial_kernel<BC_PLAIN>, grid, block, 0, s, g, x, dl, lambda, t, m, bc, chunk, i_lo, i_hi);
+    }
+    return 0;
+}
+
 /* GetL2NormOfVector (mg_3d.h:783-792) over every point of a level, boundary included */
 __global__ void __launch_bounds__(256) sumsq_kernel(Geom g, const double *__restrict__ a,
                                                     double *__restrict__ partials)

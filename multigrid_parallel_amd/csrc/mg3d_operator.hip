@@ -536,11 +536,14 @@ extern "C" int mg3d_ctx_set_shift_field(mg3d_ctx *ctx, const double *s)
     static const char who[] = "mg3d_ctx_set_shift_field";
     if (!ctx)
         return fail(MG3D_ERR_ARG, "%s: NULL context", who);
-    if (!s)
+    if (!s) {
+        ctx->sfield_nl = false; /* (whatever the context keeps is not mg3d_nl_solve's any more) */
         return field_clear(ctx, ctx->sfield);
+    }
     CHK(check_host<true>(ctx, s, "s", who));
     CHK(mg3d_drop_carry(ctx));
     CHK(sfield_prepare(ctx, who));
+    ctx->sfield_nl = false; /* the caller's field from here on */
     CHK(top_from_host(ctx, ctx->sfield, s));
     CHK(sfield_rebuild(ctx, who)); /* (the host array may go once the call returns) */
     return operator_changed(ctx);
@@ -555,16 +558,31 @@ extern "C" int mg3d_ctx_set_shift_field_device(mg3d_ctx *ctx, const mg3d_array *
     if (!ctx)
         return fail(MG3D_ERR_ARG, "%s: NULL context", who);
     if (!s)
-        return field_clear(ctx, ctx->sfield);
+        return mg3d_ctx_set_shift_field(ctx, nullptr);
     CHK(mg3d_array_check(ctx, s, false, who));
     CHK(ensure_io_chk(ctx, who));
     CHK(mg3d_stream_join(ctx, (hipStream_t)stream, false, who));
     CHK(check_device(ctx, *s, true, "s", who));
     CHK(mg3d_drop_carry(ctx));
     CHK(sfield_prepare(ctx, who));
+    ctx->sfield_nl = false; /* the caller's field from here on */
     top_from_device(ctx, ctx->sfield, *s);
     CHK(sfield_rebuild(ctx, who));
     return operator_changed(ctx);
+}
+
+/* the install path for mg3d_nl.hip (mg3d_ctx.h) */
+int mg3d_sfield_prepare(mg3d_ctx *ctx, const char *who) { return sfield_prepare(ctx, who); }
+int mg3d_sfield_rebuild(mg3d_ctx *ctx, const char *who) { return sfield_rebuild(ctx, who); }
+int mg3d_operator_changed(mg3d_ctx *ctx) { return operator_changed(ctx); }
+int mg3d_check_weight_host(const mg3d_ctx *ctx, const double *a, const char *name, const char *who)
+{
+    return check_host<true>(ctx, a, name, who);
+}
+int mg3d_check_weight_device(mg3d_ctx *ctx, const mg3d_array &a, const char *name, const char *who)
+{
+    CHK(ensure_io_chk(ctx, who));
+    return check_device(ctx, a, true, name, who);
 }
 
 extern "C" int mg3d_ctx_has_shift_field(const mg3d_ctx *ctx, int *on)
